@@ -23,12 +23,13 @@ The roofline object prices the fused encode+MLP kernel with HIP events recorded 
 inside the timed region. Default arithmetic ("f16x2"): every fp32 operand is carried exactly as two fp16
 halves and every product costs three v_mfma_f32_32x32x16_f16, so the algorithmic FLOP rate is priced
 against one third of the dense fp16 MFMA peak (2516.6 / 3 = 838.9 TFLOP/s, MI355X_MICROARCH.md);
-`--precision f32` runs the v_mfma_f32_32x32x2_f32 kernel, priced against 157.3 TFLOP/s. After the timed region (N=1):
-the other mode renders five timed frames of the same rays (`other_precision`); a short training run reports it/s of
-the reference's loop body (`train`); the `parity` object compares the HIP render of the 4096 fixture rays of this frame
-with the REFERENCE's own fp32 render of them (tests/golden/bench_frame.npz, oracle/parity.py); the `cpu_baseline` object
-times the CPU oracle (oracle/nerf_oracle.py) on a bounded sample of the same rays with the thread count that maximises
-it. These legs are reported next to the GPU number, never used by it.
+`--precision f32` runs the v_mfma_f32_32x32x2_f32 kernel, priced against 157.3 TFLOP/s. `--dump-outputs DIR` writes the
+frame of the last timed step as DIR/<map>.npy. A plain run stops there and prints the line. With `--full`, after the
+timed region (N=1): the other mode renders five timed frames of the same rays (`other_precision`); a short training run
+reports it/s of the reference's loop body (`train`); the `parity` object compares the HIP render of the 4096 fixture
+rays of this frame with the REFERENCE's own fp32 render of them (tests/golden/bench_frame.npz, oracle/parity.py); the
+`cpu_baseline` object times the CPU oracle (oracle/nerf_oracle.py) on a bounded sample of the same rays with the
+thread count that maximises it. These legs are reported next to the GPU number, never used by it.
 """
 import argparse
 import json
@@ -64,11 +65,16 @@ def parse():
     p.add_argument("--chunk", type=int, default=32768)
     p.add_argument("--precision", default=None, choices=["f16x2", "f32"],
                    help="arithmetic of the fused MLP kernel (default: the library's, f16x2)")
-    p.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the oracle sample")
-    p.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (cpu_baseline and parity)")
-    p.add_argument("--no-train", action="store_true", help="skip the short training-throughput leg")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the legs reported next to the result (other_precision, train, "
+                        "parity, cpu_baseline); a plain run times the steps and prints the line only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's frame (rgb_map, disp_map, acc_map) as float32 DIR/<name>.npy")
+    p.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the oracle sample (--full)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (cpu_baseline and parity; --full)")
+    p.add_argument("--no-train", action="store_true", help="skip the short training-throughput leg (--full)")
     p.add_argument("--no-other-precision", action="store_true",
-                   help="skip the short run in the other arithmetic mode that is reported next to the result")
+                   help="skip the short run in the other arithmetic mode that is reported next to the result (--full)")
     p.add_argument("--force-collective", action="store_true",
                    help="under torch.distributed.run with one rank: still create the RCCL group and gather")
     return p.parse_args()
@@ -375,6 +381,15 @@ def train_leg(N, synthetic, iters=30, warmup=5, n_rand=1024, Sc=64, Si=128):
             "reference_stored_run": "5.6-7.4 it/s (ship 96+192, unknown CUDA GPU; BASELINE.md section 1)"}
 
 
+def dump_outputs(frame, directory):
+    """The frame the last timed step returned, as its caller receives it (one row per ray), one float32 .npy per map:
+    rgb_map [n, 3], disp_map [n], acc_map [n]; 12.8 MB for the 800x800 frame. Inputs are seeded, so two builds'
+    dumps of the same command compare element for element."""
+    os.makedirs(directory, exist_ok=True)
+    for name, t in frame.items():
+        np.save(os.path.join(directory, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def pmc_traffic(precision):
     """HBM bytes per launch of the dominant kernel from the committed rocprofv3 --pmc passes of this
     same command (profiles/rNN_pmc_summary.json for f16x2, rNN_pmc_summary_f32.json for --precision f32,
@@ -481,6 +496,8 @@ def main():
     dt = time.perf_counter() - t0
     ctx.profile_enable(False)
     mlp_ms, mlp_launches, mlp_points = ctx.profile_read(reset=True)
+    if args.dump_outputs and frame is not None:          # rank 0 holds the gathered frame, the other ranks None
+        dump_outputs(frame, args.dump_outputs)
     gather_ms = sum(a.elapsed_time(b) for a, b in gather_events) / max(len(gather_events), 1)
     t = torch.tensor([dt, mlp_ms, float(mlp_points), float(mlp_launches)], device="cuda", dtype=torch.float64)
     per_rank = None
@@ -505,7 +522,7 @@ def main():
     # the other arithmetic mode on the same rays, outside the timed region above: 1 warm-up + 5 timed frames,
     # reported in `other_precision` so that both kernels' numbers come from one run
     other = None
-    if not args.no_other_precision:
+    if args.full and not args.no_other_precision:
         alt = "f32" if precision.startswith("f16x2") else "f16x2"
         ctx.set_precision(alt)
         step()
@@ -584,9 +601,9 @@ def main():
         if other is not None:
             out["other_precision"] = other
         out["precision_status"] = int(ctx.precision_status())      # layers whose a-priori scale bound was loose (0 = none)
-        if world == 1 and not args.no_train and not use_dist:
+        if args.full and world == 1 and not args.no_train and not use_dist:
             out["train"] = train_leg(N, synthetic)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.workload == "lego_800x800_64c+128f":
                 out["parity"] = reference_parity(N, net_c, net_f, query)
             # same rays, spread over the whole frame so empty, grazing and opaque rays are all present

@@ -12,10 +12,10 @@ PMC_SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INS
 PMC_L2="GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum"
 pmc() { timeout -k 10 240 rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $O/$2 -- $3 > $O/$2.log 2>&1; }
 if [ $PART = bench ] || [ $PART = all ]; then
-timeout -k 10 400 python3 $R/bench.py > $O/bench_n1.json 2> $O/bench_n1.err && echo bench ok &&
-timeout -k 10 300 python3 $R/bench.py --precision f32 --no-cpu-baseline > $O/bench_n1_f32.json 2>> $O/bench_n1.err && echo f32 ok &&
-timeout -k 10 300 python3 $R/bench.py --workload lego_400x400_64c --steps 10 > $O/bench_c1.json 2>> $O/bench_n1.err && echo c1 ok &&
-timeout -k 10 300 python3 $R/bench.py --workload fern_1008x756_ndc_64c+128f --no-cpu-baseline > $O/bench_c4.json 2>> $O/bench_n1.err && echo c4 ok &&
+timeout -k 10 400 python3 $R/bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err && echo bench ok &&
+timeout -k 10 300 python3 $R/bench.py --full --precision f32 --no-cpu-baseline > $O/bench_n1_f32.json 2>> $O/bench_n1.err && echo f32 ok &&
+timeout -k 10 300 python3 $R/bench.py --full --workload lego_400x400_64c --steps 10 > $O/bench_c1.json 2>> $O/bench_n1.err && echo c1 ok &&
+timeout -k 10 300 python3 $R/bench.py --full --workload fern_1008x756_ndc_64c+128f --no-cpu-baseline > $O/bench_c4.json 2>> $O/bench_n1.err && echo c4 ok &&
 timeout -k 10 300 python3 $R/bench.py --gpus 1 --force-collective --steps 3 --no-cpu-baseline --no-other-precision > $O/bench_n1_rccl_group.json 2>> $O/bench_n1.err && echo rccl-group ok &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-precision --no-train > $O/stats.log 2>&1 && echo stats ok &&
 timeout -k 10 400 python3 $R/profiles/shard_projection.py > $O/shard_projection.log 2>&1 && echo shards ok || exit 1

@@ -145,3 +145,27 @@ def test_whole_host_cpu_baseline_runs_worker_processes(bench):
     # one process already covering the host: nothing to add
     one = bench.cpu_baseline_all_cores(g["rays"][:64], 8, 8, True, threads=8, ncpu=8, single_pool_rate=5.0, target_s=1.0)
     assert one["processes"] == 1 and one["value_all_cores"] == 5.0
+
+
+def test_plain_run_leaves_the_extra_legs_to_full(bench, monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the steps and prints the line; the legs reported next to it
+    (other_precision, train, parity, cpu_baseline) run only with --full, where the --no-* switches still apply."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-train", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.no_train and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_arrays(bench, tmp_path):
+    """--dump-outputs: one float32 .npy per map of the frame, rows as the caller received them."""
+    import numpy as np
+    import torch
+    frame = {"rgb_map": torch.rand(10, 3), "disp_map": torch.rand(10, dtype=torch.float64), "acc_map": torch.rand(10)}
+    bench.dump_outputs(frame, str(tmp_path / "d"))
+    assert sorted(os.listdir(tmp_path / "d")) == ["acc_map.npy", "disp_map.npy", "rgb_map.npy"]
+    for k, v in frame.items():
+        got = np.load(tmp_path / "d" / (k + ".npy"))
+        assert got.dtype == np.float32 and got.shape == tuple(v.shape)
+        np.testing.assert_array_equal(got, v.to(torch.float32).numpy())
