@@ -409,6 +409,65 @@ int nerf_profile_read_train(nerf_ctx* ctx, double* ms /*[host] [4]*/, int64_t* l
 /* Bytes of device workspace currently held by the context. */
 int64_t nerf_workspace_bytes(nerf_ctx* ctx);
 
+/* Mesh extraction -------------------------------------------------------------------------------
+ * gen_mesh.marching_cubes (plenoctree/nerf_sh/gen_mesh.py:88-129) on the device, in two calls.
+ *
+ * nerf_density_grid: sigma = relu(raw[..., 3]) (nerf.ipynb:291) of network `slot` on the regular lattice of
+ * reso[0] x reso[1] x reso[2] nodes spanning [c1, c2] (gen_mesh.py:104-119). Node (i, j, k) is point
+ * n = (i * reso[1] + j) * reso[2] + k of sigma [dev] [X, Y, Z] (C order, x slowest); its coordinate on axis a is
+ * np.linspace(c1[a], c2[a], reso[a], dtype=np.float32)[i]: fp64 i * ((c2 - c1) / (reso - 1)) + c1 with two roundings (no
+ * fma), the last node exactly c2, then rounded to fp32. The fused encode+MLP kernel evaluates the lattice in place of a
+ * point buffer (no point is read, no view direction: sigma does not depend on it) and writes one float per node (NaN
+ * propagates as through F.relu). The result equals relu(nerf_run_network(...)[..., 3]) on the same points in the same
+ * order, bit for bit, in either arithmetic (nerf_set_render_precision). precision_guard as for nerf_render_frame:
+ * NERF_GUARD_FALLBACK evaluates the lattice again with the fp32 kernel when the fp16-pair kernel's scale bound was loose.
+ * reso[a] must be in [2, 1024], c2[a] > c1[a], both finite.
+ *
+ * nerf_marching_cubes: the isosurface v = iso of any device volume [X, Y, Z] of fp32 (mcubes.marching_cubes,
+ * gen_mesh.py:124), every axis in [2, 1024]. Conventions:
+ *   - a node is INSIDE iff v >= iso (NaN is outside).
+ *   - one vertex per lattice edge whose ends classify differently (welded: shared by every triangle that uses the edge).
+ *     With a the value at the edge's lower-index end and b at the other, t = (iso - a) / (b - a) in fp32 (0.5 when t is
+ *     not finite: a NaN or infinite end); the vertex is (i, j, k) with t added (fp32) on the edge's axis, in INDEX
+ *     coordinates as mcubes returns them.
+ *   - vertex order: by edge key 3 * ((i * Y + j) * Z + k) + axis (axis 0, 1, 2 = x, y, z); triangles: by cell (C order over
+ *     [X-1, Y-1, Z-1]), then in table order within the cell. No atomics on the output path: two calls return identical
+ *     arrays.
+ *   - winding: the right-hand normal of every triangle points OUT of the region v >= iso, so a closed surface around an
+ *     inside region has positive signed volume. Ambiguous faces separate the inside corners; the two cells that share a
+ *     face draw the same segments on it, so a surface that stays inside the lattice is closed and every edge has exactly
+ *     two triangles.
+ *   - vertices [dev] [V, 3] fp32, triangles [dev] [T, 3] int64 vertex ids. With both output pointers NULL the call only
+ *     counts: *n_vertices, *n_triangles are exact. If a capacity is too small nothing is written, the call returns
+ *     NERF_E_INVALID and *n_vertices / *n_triangles report what is needed.
+ *   - the call synchronises `stream` (the counts decide the writes); its scratch is the context's workspace
+ *     (nerf_workspace_bytes includes it: 2 bytes per node and a few per 2048 nodes). */
+typedef struct nerf_grid_args {
+    double c1[3], c2[3];        /* lattice corners (the Python floats gen_mesh passes)                           */
+    int32_t reso[3];            /* nodes per axis                                                                */
+    int32_t slot;               /* network (coarse or fine, gen_mesh's --coarse)                                 */
+    float* sigma;               /* [dev] [X, Y, Z]                                                               */
+    void* stream;
+    int32_t precision_guard;    /* NERF_GUARD_*                                                                  */
+} nerf_grid_args;
+
+int nerf_density_grid(nerf_ctx* ctx, const nerf_grid_args* args);
+
+typedef struct nerf_mc_args {
+    const float* volume;        /* [dev] [X, Y, Z]                                                               */
+    int32_t reso[3];            /* X, Y, Z                                                                       */
+    float iso;
+    float* vertices;            /* [dev] [vertex_capacity, 3] or NULL (count only)                               */
+    int64_t vertex_capacity;
+    int64_t* triangles;         /* [dev] [triangle_capacity, 3] or NULL (count only)                             */
+    int64_t triangle_capacity;
+    int64_t* n_vertices;        /* [host] out                                                                    */
+    int64_t* n_triangles;       /* [host] out                                                                    */
+    void* stream;
+} nerf_mc_args;
+
+int nerf_marching_cubes(nerf_ctx* ctx, const nerf_mc_args* args);
+
 #ifdef __cplusplus
 }
 #endif

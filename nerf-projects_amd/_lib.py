@@ -21,7 +21,7 @@ EXPORTS = (
     "nerf_get_precision", "nerf_precision_status", "nerf_get_adam_state", "nerf_set_adam_state",
     "nerf_shard_bounds", "nerf_render_shard", "nerf_precision_peek", "nerf_precision_check",
     "nerf_precision_detail", "nerf_profile_read_train", "nerf_set_render_precision",
-    "nerf_pack_rays",
+    "nerf_pack_rays", "nerf_density_grid", "nerf_marching_cubes",
 )
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
 NERF_GUARD_OFF, NERF_GUARD_REPORT, NERF_GUARD_FALLBACK = 0, 1, 2
@@ -70,6 +70,17 @@ class FrameArgs(C.Structure):
                 ("slot_fine", C.c_int32), ("lindisp", C.c_int32), ("white_bkgd", C.c_int32), ("rgb_map", _FP),
                 ("disp_map", _FP), ("acc_map", _FP), ("rgb0", _FP), ("disp0", _FP), ("acc0", _FP), ("z_std", _FP),
                 ("stream", C.c_void_p), ("precision_guard", C.c_int32)]
+
+
+class GridArgs(C.Structure):
+    _fields_ = [("c1", C.c_double * 3), ("c2", C.c_double * 3), ("reso", C.c_int32 * 3), ("slot", C.c_int32),
+                ("sigma", _FP), ("stream", C.c_void_p), ("precision_guard", C.c_int32)]
+
+
+class McArgs(C.Structure):
+    _fields_ = [("volume", _FP), ("reso", C.c_int32 * 3), ("iso", C.c_float), ("vertices", _FP),
+                ("vertex_capacity", C.c_int64), ("triangles", _FP), ("triangle_capacity", C.c_int64),
+                ("n_vertices", C.POINTER(C.c_int64)), ("n_triangles", C.POINTER(C.c_int64)), ("stream", C.c_void_p)]
 
 
 _lib = None
@@ -164,6 +175,10 @@ def load():
     lib.nerf_precision_peek.argtypes = [vp, C.POINTER(i64)]
     lib.nerf_precision_check.restype = i32
     lib.nerf_precision_check.argtypes = [vp, vp, C.POINTER(i64)]
+    lib.nerf_density_grid.restype = i32
+    lib.nerf_density_grid.argtypes = [vp, C.POINTER(GridArgs)]
+    lib.nerf_marching_cubes.restype = i32
+    lib.nerf_marching_cubes.argtypes = [vp, C.POINTER(McArgs)]
     _lib = lib
     return lib
 

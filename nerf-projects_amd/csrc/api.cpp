@@ -1,6 +1,7 @@
 // C ABI of libnerf_mi355x.so (declared in include/nerf_mi355x.h): context, weights,
 // workspace, the stage entry points and the render_rays pipeline. Host code only; every
 // device function lives in mlp_kernel.hip / ray_kernels.hip.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1013,6 +1014,106 @@ int nerf_precision_check(nerf_ctx* c, void* stream, int64_t* new_events) {
     HIP_TRY(mirror_loose(c, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     *new_events = (int64_t)take_new_loose(c);
+    return NERF_OK;
+}
+
+// ---- mesh extraction ----------------------------------------------------------------------------------------------
+
+int nerf_density_grid(nerf_ctx* c, const nerf_grid_args* g) {
+    if (!c || !g || !g->sigma) {
+        set_error("nerf_density_grid: invalid argument (NULL context, arguments or sigma)");
+        return NERF_E_INVALID;
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (g->reso[a] < 2 || g->reso[a] > 1024) {
+            set_error("nerf_density_grid: reso[%d] = %d outside [2, 1024]", a, g->reso[a]);
+            return NERF_E_INVALID;
+        }
+        if (!(std::isfinite(g->c1[a]) && std::isfinite(g->c2[a]) && g->c2[a] > g->c1[a])) {
+            set_error("nerf_density_grid: axis %d: c2 = %g must be finite and greater than c1 = %g", a, g->c2[a], g->c1[a]);
+            return NERF_E_INVALID;
+        }
+    }
+    if (g->precision_guard != NERF_GUARD_OFF && g->precision_guard != NERF_GUARD_REPORT &&
+        g->precision_guard != NERF_GUARD_FALLBACK) {
+        set_error("nerf_density_grid: precision_guard %d is not a NERF_GUARD_* value", g->precision_guard);
+        return NERF_E_INVALID;
+    }
+    const PackedNet* net = get_net(c, g->slot);
+    if (!net) return NERF_E_STATE;
+    if (net->out_ch < 4) {
+        set_error("nerf_density_grid: the network has %d output channels; sigma is channel 3", net->out_ch);
+        return NERF_E_INVALID;
+    }
+    DeviceGuard dg(c->device);
+    hipStream_t s = (hipStream_t)g->stream;
+    MlpLaunch a{};
+    a.n_points = (int64_t)g->reso[0] * g->reso[1] * g->reso[2];
+    a.samples_per_ray = 1;
+    a.out = g->sigma;
+    for (int k = 0; k < 3; ++k) {
+        a.lat_lo[k] = g->c1[k];
+        a.lat_hi[k] = g->c2[k];
+        a.lat_step[k] = (g->c2[k] - g->c1[k]) / (double)(g->reso[k] - 1);      // numpy: delta / div, in fp64
+        a.lat_n[k] = g->reso[k];
+    }
+    int rc = run_mlp(c, a, *net, kInputLattice, s);
+    if (rc != NERF_OK) return rc;
+    HIP_TRY(mirror_loose(c, s));
+    if (g->precision_guard == NERF_GUARD_OFF || c->precision != NERF_PRECISION_F16X2) return NERF_OK;
+    // the guard, as nerf_render_frame's: wait for the lattice, look at the counter mirrored behind it
+    HIP_TRY(hipStreamSynchronize(s));
+    const unsigned n_new = take_new_loose(c);
+    if (n_new == 0) return NERF_OK;
+    if (g->precision_guard == NERF_GUARD_REPORT) {
+        set_error("nerf_density_grid: the fp16-pair kernel's output-scale bound was loose in %u (wavefront, layer) cases "
+                  "of this lattice: some activations kept fewer than 24 bits with these weights (NERF_PRECISION_F32 "
+                  "evaluates them as the reference does)", n_new);
+        return NERF_W_PRECISION;
+    }
+    c->precision = NERF_PRECISION_F32;
+    rc = run_mlp(c, a, *net, kInputLattice, s);
+    c->precision = NERF_PRECISION_F16X2;
+    if (rc != NERF_OK) return rc;
+    set_error("nerf_density_grid: the fp16-pair kernel's output-scale bound was loose in %u (wavefront, layer) cases of "
+              "this lattice; it was evaluated again with the fp32 kernel", n_new);
+    return NERF_W_PRECISION_FALLBACK;
+}
+
+int nerf_marching_cubes(nerf_ctx* c, const nerf_mc_args* m) {
+    if (!c || !m || !m->volume || !m->n_vertices || !m->n_triangles) {
+        set_error("nerf_marching_cubes: invalid argument (NULL context, arguments, volume or count pointers)");
+        return NERF_E_INVALID;
+    }
+    for (int a = 0; a < 3; ++a)
+        if (m->reso[a] < 2 || m->reso[a] > 1024) {
+            set_error("nerf_marching_cubes: reso[%d] = %d outside [2, 1024]", a, m->reso[a]);
+            return NERF_E_INVALID;
+        }
+    const bool count_only = !m->vertices && !m->triangles;
+    if (!count_only && (!m->vertices || !m->triangles)) {
+        set_error("nerf_marching_cubes: vertices and triangles must both be given, or both be NULL (count only)");
+        return NERF_E_INVALID;
+    }
+    DeviceGuard dg(c->device);
+    hipStream_t s = (hipStream_t)m->stream;
+    ScratchScope scope(c, s);
+    HIP_TRY(scope.status);
+    int rc = ensure_workspace(c, mc_scratch_bytes(m->reso));
+    if (rc != NERF_OK) return rc;
+    McArgs a{m->volume, {m->reso[0], m->reso[1], m->reso[2]}, m->iso, m->vertices, m->triangles};
+    int64_t totals[2] = {0, 0};
+    HIP_TRY(launch_mc_count(a, c->ws, totals, s));
+    *m->n_vertices = totals[0];
+    *m->n_triangles = totals[1];
+    if (count_only) return NERF_OK;
+    if (totals[0] > m->vertex_capacity || totals[1] > m->triangle_capacity) {
+        set_error("nerf_marching_cubes: the mesh has %lld vertices and %lld triangles; capacities %lld and %lld (nothing "
+                  "was written)", (long long)totals[0], (long long)totals[1], (long long)m->vertex_capacity,
+                  (long long)m->triangle_capacity);
+        return NERF_E_INVALID;
+    }
+    HIP_TRY(launch_mc_emit(a, c->ws, s));
     return NERF_OK;
 }
 

@@ -72,6 +72,15 @@ __device__ __forceinline__ void encode_point(const float (&p)[3], const float (&
 constexpr unsigned kBadXyz = 1u, kBadDir = 2u;
 __device__ __forceinline__ bool nonfinite(float v) { return !(fabsf(v) <= 3.4028234663852886e38f); }
 
+// np.linspace(lo, hi, n, dtype=np.float32)[i]: numpy evaluates i * step + lo in fp64 (step = (hi - lo) / (n - 1)), sets the
+// last element to hi and only then rounds to fp32. Two separate roundings here (no fma), as numpy's multiply and add.
+__device__ __forceinline__ float lattice_coord(int64_t i, int64_t n, double lo, double hi, double step) {
+    return (float)(i == n - 1 ? hi : __dadd_rn(__dmul_rn((double)i, step), lo));
+}
+
+// relu(sigma) as F.relu computes it: NaN propagates (v_max_f32 would drop it)
+__device__ __forceinline__ float relu_keep_nan(float v) { return v > 0.0f ? v : (v == v ? 0.0f : v); }
+
 // WANT_XYZ / WANT_DIR: which tiles the caller uses (the other is left untouched). dir_max: largest |component| of the
 // direction (an upper bound of |gamma(dir)| together with 1), or of the encoded direction columns in embedded mode.
 // bad: kBadXyz | kBadDir of this point's raw inputs (both halves of a point get the same value).
@@ -109,6 +118,19 @@ __device__ __forceinline__ void load_inputs(const MlpLaunch& a, int64_t pt, int 
         return;
     }
     float p[3], d[3] = {0.0f, 0.0f, 0.0f};
+    if (MODE == kInputLattice) {
+        // node (i, j, k) of the lattice, x slowest (gen_mesh.py:104-111: meshgrid(indexing="ij") of three linspaces); no
+        // view direction is read (sigma does not depend on it): d = 0
+        const int64_t k = pt % a.lat_n[2], ij = pt / a.lat_n[2];
+        const int64_t j = ij % a.lat_n[1], i = ij / a.lat_n[1];
+        p[0] = lattice_coord(i, a.lat_n[0], a.lat_lo[0], a.lat_hi[0], a.lat_step[0]);
+        p[1] = lattice_coord(j, a.lat_n[1], a.lat_lo[1], a.lat_hi[1], a.lat_step[1]);
+        p[2] = lattice_coord(k, a.lat_n[2], a.lat_lo[2], a.lat_hi[2], a.lat_step[2]);
+        if (dir_max) *dir_max = 1.0f;
+        if (bad) *bad = (nonfinite(p[0]) || nonfinite(p[1]) || nonfinite(p[2])) ? kBadXyz : 0u;
+        encode_point<WANT_XYZ, WANT_DIR>(p, d, h, a.use_viewdirs != 0, x0, x1, dd);
+        return;
+    }
     const int64_t ray = pt / a.samples_per_ray;
     if (MODE == kInputPoints) {
         p[0] = a.pts[pt * 3 + 0];

@@ -439,7 +439,10 @@ void nerf_mlp_kernel(const MlpLaunch a) {
         const float r0 = row_dot<4>(hid, bias_lds, 8 * a.D + 22, h) + rb[0];
         const float r1 = row_dot<4>(hid, bias_lds, 8 * a.D + 26, h) + rb[1];
         const float r2 = row_dot<4>(hid, bias_lds, 8 * a.D + 30, h) + rb[2];
-        if (live && h == 0) {
+        if (MODE == kInputLattice) {
+            // the density lattice keeps sigma alone: relu(raw[..., 3]) (nerf.ipynb:291)
+            if (live && h == 0) a.out[pt] = relu_keep_nan((bad & kBadXyz) ? __builtin_nanf("") : sigma);
+        } else if (live && h == 0) {
             // outputs = cat[rgb, alpha] (nerf.py:106)
             f32x4 o = {r0, r1, r2, sigma};
             if (bad || poisoned) {      // (poisoned: the trunk or feature_linear overflowed; sigma has its own mark above)
@@ -456,7 +459,12 @@ void nerf_mlp_kernel(const MlpLaunch a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (row < a.out_ch) a.out[pt * a.out_ch + row] = ((bad & kBadXyz) || poisoned) ? __builtin_nanf("") : o[r];
+                const float v = ((bad & kBadXyz) || poisoned) ? __builtin_nanf("") : o[r];
+                if (MODE == kInputLattice) {
+                    if (row == 3) a.out[pt] = relu_keep_nan(v);      // sigma alone (nerf.ipynb:291)
+                } else if (row < a.out_ch) {
+                    a.out[pt * a.out_ch + row] = v;
+                }
             }
         }
     }
@@ -751,8 +759,8 @@ hipError_t launch_mlp(const MlpLaunch& a, int mode, hipStream_t s) {
     }
     const dim3 grid((unsigned)(tiles < n_cu[dev] ? tiles : n_cu[dev])), block(256);
     const size_t lds = kBiasLdsBytes + kRing * kChunkBytes;
-    static bool raised[64][4] = {};
-    if (mode < 0 || mode > 2) return hipErrorInvalidValue;
+    static bool raised[64][5] = {};
+    if (mode < 0 || mode > 3) return hipErrorInvalidValue;
     if (a.store && (mode != kInputRays || a.n_points > (int64_t)1 << 22)) return hipErrorInvalidValue;   // training forward: ray records; 32-bit element offsets in store_tiles
     if (a.store) {   // the hooks inside the chunk loop are unconditional 16-byte stores (RowRef)
         bool rows_ok = !a.use_viewdirs || (training_rows_ok(a.st.feat, a.st.feat_ld) && training_rows_ok(a.st.hv, a.st.hv_ld));
@@ -760,10 +768,11 @@ hipError_t launch_mlp(const MlpLaunch& a, int mode, hipStream_t s) {
         if (!rows_ok) return hipErrorInvalidValue;
     }
     typedef void (*kernel_t)(const MlpLaunch);
-    static const kernel_t table[4] = {nerf_mlp_kernel<kInputEmbedded>, nerf_mlp_kernel<kInputPoints>,
-                                      nerf_mlp_kernel<kInputRays>, nerf_mlp_kernel<kInputRays, true>};
-    static_assert(kInputEmbedded == 0 && kInputPoints == 1 && kInputRays == 2, "kernel table order");
-    const int which = a.store ? 3 : mode;
+    static const kernel_t table[5] = {nerf_mlp_kernel<kInputEmbedded>, nerf_mlp_kernel<kInputPoints>,
+                                      nerf_mlp_kernel<kInputRays>, nerf_mlp_kernel<kInputRays, true>,
+                                      nerf_mlp_kernel<kInputLattice>};
+    static_assert(kInputEmbedded == 0 && kInputPoints == 1 && kInputRays == 2 && kInputLattice == 3, "kernel table order");
+    const int which = a.store ? 3 : mode == kInputLattice ? 4 : mode;
     // 112 KiB of dynamic LDS is above the 64 KiB default cap: raise it once per device and kernel
     if (!raised[dev][which]) {
         e = hipFuncSetAttribute((const void*)table[which], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -593,7 +593,10 @@ void nerf_mlp_h2_kernel(const MlpLaunch a) {
             const float r0 = row_dot4(y, bias0 + 128 * (8 * a.D + 22)) + lds_scalar(rb);
             const float r1 = row_dot4(y, bias0 + 128 * (8 * a.D + 26)) + lds_scalar(rb + 1);
             const float r2 = row_dot4(y, bias0 + 128 * (8 * a.D + 30)) + lds_scalar(rb + 2);
-            if (live && h == 0) {
+            if (MODE == kInputLattice) {
+                // the density lattice keeps sigma alone: relu(raw[..., 3]) (nerf.ipynb:291)
+                if (live && h == 0) a.out[pt] = relu_keep_nan((bad & kBadXyz) ? __builtin_nanf("") : sigma);
+            } else if (live && h == 0) {
                 f32x4 o = {r0, r1, r2, sigma};   // outputs = cat[rgb, alpha] (nerf.py:106)
                 if (bad || rgb_poisoned) {       // NaN / Inf inputs propagate as through F.relu (see kBadXyz)
                     const float qnan = __builtin_nanf("");
@@ -631,8 +634,12 @@ void nerf_mlp_h2_kernel(const MlpLaunch a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (row < a.out_ch)
-                        a.out[pt * a.out_ch + row] = ((bad & kBadXyz) || poisoned) ? __builtin_nanf("") : fmaf(o[r], c, b.q[r >> 2][r & 3]);
+                    const float v = ((bad & kBadXyz) || poisoned) ? __builtin_nanf("") : fmaf(o[r], c, b.q[r >> 2][r & 3]);
+                    if (MODE == kInputLattice) {
+                        if (row == 3) a.out[pt] = relu_keep_nan(v);      // sigma alone (nerf.ipynb:291)
+                    } else if (row < a.out_ch) {
+                        a.out[pt * a.out_ch + row] = v;
+                    }
                 }
             }
         }
@@ -664,8 +671,8 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
     }
     const dim3 grid((unsigned)(tiles < n_cu[dev] ? tiles : n_cu[dev])), block(256);
     const size_t lds = kRingH * kChunkBytes;   // + 20.5 KiB static (bias block, layer scales)
-    static bool raised[64][3] = {};
-    if (mode < 0 || mode > 2) return hipErrorInvalidValue;
+    static bool raised[64][4] = {};
+    if (mode < 0 || mode > 3) return hipErrorInvalidValue;
     if (a.store) {
         // training forward: ray records, a view-dependent network, buffers the one-instruction stores can address
         // (16-byte aligned rows, byte offsets below 2^32)
@@ -696,7 +703,8 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
     if (!raised[dev][mode]) {
         const void* fn = mode == kInputEmbedded ? (const void*)nerf_mlp_h2_kernel<kInputEmbedded>
                          : mode == kInputPoints ? (const void*)nerf_mlp_h2_kernel<kInputPoints>
-                                                : (const void*)nerf_mlp_h2_kernel<kInputRays>;
+                         : mode == kInputLattice ? (const void*)nerf_mlp_h2_kernel<kInputLattice>
+                                                 : (const void*)nerf_mlp_h2_kernel<kInputRays>;
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         raised[dev][mode] = true;
@@ -707,6 +715,9 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
             break;
         case kInputPoints:
             hipLaunchKernelGGL(nerf_mlp_h2_kernel<kInputPoints>, grid, block, lds, s, a);
+            break;
+        case kInputLattice:
+            hipLaunchKernelGGL(nerf_mlp_h2_kernel<kInputLattice>, grid, block, lds, s, a);
             break;
         default:
             hipLaunchKernelGGL(nerf_mlp_h2_kernel<kInputRays>, grid, block, lds, s, a);

@@ -126,7 +126,9 @@ constexpr int kLooseTrain = kLooseRecord;
 constexpr int kLooseBwdGuard = 1000;    // overshoot (in binades) from which a backward event would also count for the guard:
                                         // never (nerf_mi355x.h, nerf_precision_detail, says why)
 
-enum MlpInputMode { kInputEmbedded = 0, kInputPoints = 1, kInputRays = 2 };
+// kInputLattice: point n is node (i, j, k) = C order over [X, Y, Z] of a regular lattice (nerf_density_grid); the kernels write
+// one float per point, relu(sigma), instead of the [n, out_ch] rows
+enum MlpInputMode { kInputEmbedded = 0, kInputPoints = 1, kInputRays = 2, kInputLattice = 3 };
 
 // Training forward pass through the fused fp32 kernel: where the activations autograd would keep are written
 // (row-major [points, channels], any row stride; nullptr = not kept). See train_api.cpp forward_pass.
@@ -185,6 +187,10 @@ struct MlpLaunch {
     float* out;
     int store;               // 1: also write the activations named in `st` (fp32 kernel only)
     MlpStore st;
+    // kInputLattice: coordinate i of axis a is np.linspace(lo, hi, n, dtype=np.float32)[i] - fp64 i * step + lo with two
+    // roundings, the last node exactly hi, then rounded to fp32 (lattice_coord in mlp_inputs.h); `out` is [X, Y, Z]
+    double lat_lo[3], lat_hi[3], lat_step[3];
+    int64_t lat_n[3];
 };
 
 // Fused backward-data pass (nerf_mlp_bwd_kernel): from d raw to the gradient at every pre-activation, one launch.
@@ -453,6 +459,29 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, 
                        int step, hipStream_t s);
 hipError_t launch_transpose(const float* src, int rows, int cols, float* dst, hipStream_t s);
 hipError_t launch_gather(const float* params, const int* table, int64_t n, float* out, hipStream_t s);
+
+// ---- marching cubes (mesh_kernels.hip) ---------------------------------------------------------------
+struct McArgs {
+    const float* volume;     // [X, Y, Z]
+    int32_t reso[3];
+    float iso;
+    float* vertices;         // [V, 3] (launch_mc_emit)
+    int64_t* triangles;      // [T, 3]
+};
+struct McScratch {           // carved from the context's workspace (mc_scratch_bytes)
+    uint16_t* rec;           // per lattice point: tile-local prefix of crossing edges << 3 | crossing mask
+    int* vcount;             // per tile of points: crossing edges
+    int* tcount;             // per tile of cells: triangles
+    int64_t* voff;           // exclusive offsets of the two
+    int64_t* toff;
+    int64_t* totals;         // [2]: vertices, triangles
+};
+size_t mc_scratch_bytes(const int32_t reso[3]);
+McScratch mc_scratch(const int32_t reso[3], char* base);
+// the counting passes and the scan; copies the totals to totals_host and synchronises the stream
+hipError_t launch_mc_count(const McArgs& m, char* scratch, int64_t* totals_host, hipStream_t s);
+// the emitting passes (after launch_mc_count on the same scratch)
+hipError_t launch_mc_emit(const McArgs& m, char* scratch, hipStream_t s);
 
 void set_error(const char* fmt, ...);
 
