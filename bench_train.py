@@ -6,7 +6,11 @@ The reference's stored run trains at 5.6-7.4 it/s with N_rand = 1024 rays per it
 (nerf.ipynb:1258-1282: render with the training kwargs, two MSE losses, backward, Adam, lr decay)
 on one MI355X with synthetic rays/targets and seeded weights.
 
-    python bench_train.py [--iters 50] [--n-rand 1024] [--samples 64 --importance 128]
+    python bench_train.py [--iters 50] [--n-rand 1024] [--samples 64 --importance 128] [--autograd]
+
+--autograd also times the reference's loop body written out - render(..., retraw=True), optimizer.zero_grad(), two
+img2mse, loss.backward(), optimizer.step() - through taped renders (NeRF.requires_grad_()), in the same process, and
+reports it next to train_on_batch's rate as "autograd".
 """
 import argparse
 import json
@@ -30,9 +34,15 @@ def main():
     p.add_argument("--importance", type=int, default=128)
     p.add_argument("--no-viewdirs", action="store_true", help="networks without view directions (use_viewdirs=False, 5-channel head)")
     p.add_argument("--only", action="store_true", help="no second, short run of create_nerf's other branch (train_noviewdirs)")
+    p.add_argument("--autograd", action="store_true", help="also time the loop body through loss.backward() (taped renders)")
     a = p.parse_args()
     torch.cuda.set_device(0)
     res = run(a, a.no_viewdirs, a.iters, a.warmup, True)
+    if a.autograd:
+        ag = run(a, a.no_viewdirs, a.iters, a.warmup, False, autograd=True)
+        res["autograd"] = {"value": ag["value"], "unit": "it/s", "ms_per_iter": ag["ms_per_iter"],
+                           "ratio_to_train_on_batch": ag["value"] / res["value"], "final_loss": ag["final_loss"],
+                           "loop": "render(retraw=True), zero_grad, img2mse x2, loss.backward(), step"}
     if not a.no_viewdirs and not a.only:      # create_nerf's other branch (nerf.ipynb:885-896), 20 iterations of it
         nv = run(a, True, 20, 3, False)
         res["train_noviewdirs"] = {"value": nv["value"], "unit": "it/s", "ms_per_iter": nv["ms_per_iter"], "iters": 20,
@@ -40,7 +50,7 @@ def main():
     print(json.dumps(res))
 
 
-def run(a, no_viewdirs, iters, warmup, spans_wanted):
+def run(a, no_viewdirs, iters, warmup, spans_wanted, autograd=False):
     import nerf_projects_amd as N
     from nerf_projects_amd import synthetic
     sd_c, sd_f = synthetic.synthetic_pair(0)
@@ -56,6 +66,11 @@ def run(a, no_viewdirs, iters, warmup, spans_wanted):
               perturb=1.0, raw_noise_std=1.0, ndc=False, use_viewdirs=not no_viewdirs, near=near, far=far)
     torch.manual_seed(0)
     lrate, lrate_decay = 5e-4, 500
+    if autograd:
+        net_c.requires_grad_()
+        net_f.requires_grad_()
+        kw["network_query_fn"] = N.make_network_query_fn(N.get_embedder(10, 0)[0],
+                                                         None if no_viewdirs else N.get_embedder(4, 0)[0])
 
     # The batches: the reference's use_batching mode (nerf.ipynb:1209-1230) - all rays shuffled once, consecutive windows of
     # N_rand, a new shuffle after an epoch - so that the step, not the sampler, is what is timed (a fresh permutation of the
@@ -70,7 +85,15 @@ def run(a, no_viewdirs, iters, warmup, spans_wanted):
         state["i_batch"] += a.n_rand
         r = packed[idx]
         target = torch.rand((a.n_rand, 3), device="cuda")
-        out = N.train_on_batch(800, 800, K, (r[:, 0:3], r[:, 3:6]), target, opt, **kw)
+        if autograd:      # nerf.ipynb:1258-1275 as written
+            rgb, disp, acc, extras = N.render(800, 800, K, chunk=1024 * 32, rays=(r[:, 0:3], r[:, 3:6]), retraw=True, **kw)
+            opt.zero_grad()
+            loss = N.img2mse(rgb, target) + N.img2mse(extras['rgb0'], target)
+            loss.backward()
+            opt.step()
+            out = {"loss": loss.detach()}
+        else:
+            out = N.train_on_batch(800, 800, K, (r[:, 0:3], r[:, 3:6]), target, opt, **kw)
         opt.param_groups[0]['lr'] = lrate * (0.1 ** (i / (lrate_decay * 1000)))     # nerf.ipynb:1278-1282
         return out
 

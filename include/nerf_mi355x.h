@@ -348,9 +348,9 @@ int nerf_image_metrics(nerf_ctx* ctx, const float* img1 /*[dev] [H,W,3]*/, const
  * on the master fp32 copy of the weights that nerf_load_weights keeps on the device. Afterwards the
  * inference entry points see the updated weights. The caller owns the RNG (t_rand, u_rand, noise*, as in
  * nerf_render_args), the ray batching and the learning-rate schedule (nerf.ipynb:1278-1282).
- * Arithmetic: the forward pass and the hidden-width weight gradients follow nerf_set_precision (NERF_PRECISION_F16X2:
- * fp16-pair arithmetic, whose error is the fp32 kernels'; NERF_TRAIN_FORWARD=f32 / NERF_TRAIN_DW=f32 in the environment
- * keep fp32); backward-data, the other weight gradients, Adam and the master weights are fp32 always.
+ * Arithmetic: the forward pass, backward-data and the weight gradients follow nerf_set_precision (NERF_PRECISION_F16X2:
+ * fp16-pair arithmetic, whose error is the fp32 kernels'; NERF_TRAIN_FORWARD=f32 / NERF_TRAIN_BWD=f32 / NERF_TRAIN_DW=f32 in
+ * the environment keep fp32 for that stage); compositing, its backward, Adam and the master weights are fp32.
  */
 typedef struct nerf_train_args {
     const float* rays;          /* [dev] [N, 8|11] as render() packs them                       */
@@ -358,7 +358,8 @@ typedef struct nerf_train_args {
     int64_t n_rays;
     int32_t ray_stride;
     int32_t N_samples, N_importance;
-    int32_t slot_coarse, slot_fine;     /* a distinct fine network is required when N_importance > 0 */
+    int32_t slot_coarse, slot_fine;     /* slot_fine < 0 with N_importance > 0: both passes through slot_coarse (network_fine=None,
+                                           nerf.ipynb:471); its gradient is the sum over the passes */
     int32_t lindisp, white_bkgd, perturb;
     const float* t_rand;        /* [dev] [N,S_c]      */
     const float* u_rand;        /* [dev] [N,S_i]      */
@@ -391,6 +392,64 @@ int nerf_get_adam_state(nerf_ctx* ctx, int slot, float* const* exp_avg /*[host]*
                         int n_tensors);
 int nerf_set_adam_state(nerf_ctx* ctx, int slot, const float* const* exp_avg /*[host]*/,
                         const float* const* exp_avg_sq /*[host]*/, int n_tensors);
+
+/* Differentiable rendering: loss.backward() through the training kernels ---------------------------------------------
+ * nerf_train_step with the loss left to the caller. nerf_train_forward renders a batch as render(rays, retraw=True,
+ * **render_kwargs_train) does (the same kernels and random numbers as nerf_train_step) and keeps a TAPE: the activations,
+ * ReLU masks and maxima of both passes, their depths and the inputs the backward pass re-reads, in an arena the context owns
+ * (grow-only, apart from the render workspace). nerf_train_backward takes the caller's gradients on the outputs (NULL =
+ * zero), runs raw2outputs' backward of both passes and the backward pass of nerf_train_step, and ADDS the weight gradients
+ * into those nerf_get_gradients reads (nerf_zero_grad clears them): loss.backward() with .grad accumulating. It consumes
+ * the tape. One tape is current per context; it stops being current after another nerf_train_forward, nerf_train_step,
+ * nerf_adam_step or nerf_load_weights, and a backward on it then returns NERF_E_STATE. With only d_rgb / d_rgb0 given the
+ * gradients are nerf_train_step's for the same upstream values, bit for bit. nerf_adam_step is nerf_train_step's update
+ * (and refresh of the derived weight copies) on its own. The precision guard acts in nerf_train_forward as it does in
+ * nerf_train_step. Both argument structs start with struct_size = sizeof(the struct), which the library checks. */
+typedef struct nerf_train_forward_args {
+    size_t struct_size;         /* sizeof(nerf_train_forward_args)                                           */
+    const float* rays;          /* [dev] [N, 8|11] as render() packs them                                    */
+    int64_t n_rays;
+    int32_t ray_stride;
+    int32_t N_samples, N_importance;
+    int32_t slot_coarse, slot_fine;     /* as nerf_train_args                                                 */
+    int32_t lindisp, white_bkgd, perturb;
+    const float* t_rand;        /* [dev] [N,S_c]      (the caller's RNG, as nerf_train_args)                 */
+    const float* u_rand;        /* [dev] [N,S_i]      */
+    const float* noise0;        /* [dev] [N,S_c]      */
+    const float* noise;         /* [dev] [N,S_c+S_i]  */
+    const float* z_vals_fine_in;/* [dev] [N,S_c+S_i] optional, as nerf_train_args                             */
+    float* rgb_map;             /* [dev] [N,3] outputs of the last pass, each optional                        */
+    float* disp_map;            /* [dev] [N]   */
+    float* acc_map;             /* [dev] [N]   */
+    float* rgb0;                /* [dev] [N,3] outputs of the coarse pass (N_importance > 0), optional        */
+    float* disp0;               /* [dev] [N]   */
+    float* acc0;                /* [dev] [N]   */
+    float* raw;                 /* [dev] [N, S_last, C_last] optional: the last pass's network output (retraw) */
+    void* stream;
+    uint64_t* tape;             /* [host] out: the tape's id                                                  */
+} nerf_train_forward_args;
+
+typedef struct nerf_train_backward_args {
+    size_t struct_size;         /* sizeof(nerf_train_backward_args)                                          */
+    uint64_t tape;              /* what nerf_train_forward returned                                          */
+    const float* d_rgb;         /* [dev] [N,3] dL/d rgb_map; every gradient is optional (NULL = zero)        */
+    const float* d_disp;        /* [dev] [N]   */
+    const float* d_acc;         /* [dev] [N]   */
+    const float* d_rgb0;        /* [dev] [N,3] */
+    const float* d_disp0;       /* [dev] [N]   */
+    const float* d_acc0;        /* [dev] [N]   */
+    const float* d_raw;         /* [dev] [N, S_last, C_last] dL/d raw of the last pass                       */
+    void* stream;
+} nerf_train_backward_args;
+
+int nerf_train_forward(nerf_ctx* ctx, const nerf_train_forward_args* args);
+int nerf_train_backward(nerf_ctx* ctx, const nerf_train_backward_args* args);
+/* Zeroes a slot's gradients (optimizer.zero_grad()). */
+int nerf_zero_grad(nerf_ctx* ctx, int slot, void* stream);
+/* optimizer.step(): torch.optim.Adam over the n (1 or 2, distinct) slots, as nerf_train_step applies it after its backward
+ * pass; step is the 1-based step count. */
+int nerf_adam_step(nerf_ctx* ctx, const int32_t* slots /*[host] [n]*/, int n, float lr, float beta1, float beta2, float eps,
+                   int step, void* stream);
 
 /* Measurement hooks ------------------------------------------------------------------
  * Accumulated device time of the dominant kernel (the fused encode+MLP kernel),

@@ -21,7 +21,8 @@ EXPORTS = (
     "nerf_get_precision", "nerf_precision_status", "nerf_get_adam_state", "nerf_set_adam_state",
     "nerf_shard_bounds", "nerf_render_shard", "nerf_precision_peek", "nerf_precision_check",
     "nerf_precision_detail", "nerf_profile_read_train", "nerf_set_render_precision",
-    "nerf_pack_rays", "nerf_density_grid", "nerf_marching_cubes",
+    "nerf_pack_rays", "nerf_density_grid", "nerf_marching_cubes", "nerf_train_forward", "nerf_train_backward",
+    "nerf_zero_grad", "nerf_adam_step",
 )
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
 NERF_GUARD_OFF, NERF_GUARD_REPORT, NERF_GUARD_FALLBACK = 0, 1, 2
@@ -55,6 +56,28 @@ class TrainArgs(C.Structure):
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int32),
                 ("apply_update", C.c_int32), ("loss", _FP), ("rgb_map", _FP), ("rgb0", _FP), ("stream", C.c_void_p),
                 ("z_vals_fine_in", _FP), ("stats", _FP)]
+
+
+class TrainForwardArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("rays", _FP), ("n_rays", C.c_int64), ("ray_stride", C.c_int32),
+                ("N_samples", C.c_int32), ("N_importance", C.c_int32), ("slot_coarse", C.c_int32),
+                ("slot_fine", C.c_int32), ("lindisp", C.c_int32), ("white_bkgd", C.c_int32), ("perturb", C.c_int32),
+                ("t_rand", _FP), ("u_rand", _FP), ("noise0", _FP), ("noise", _FP), ("z_vals_fine_in", _FP),
+                ("rgb_map", _FP), ("disp_map", _FP), ("acc_map", _FP), ("rgb0", _FP), ("disp0", _FP), ("acc0", _FP),
+                ("raw", _FP), ("stream", C.c_void_p), ("tape", C.POINTER(C.c_uint64))]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(self)
+
+
+class TrainBackwardArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("tape", C.c_uint64), ("d_rgb", _FP), ("d_disp", _FP), ("d_acc", _FP),
+                ("d_rgb0", _FP), ("d_disp0", _FP), ("d_acc0", _FP), ("d_raw", _FP), ("stream", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(self)
 
 
 class Camera(C.Structure):
@@ -139,6 +162,14 @@ def load():
     lib.nerf_image_metrics.argtypes = [vp, vp, vp, i32, i32, C.c_float, vp, vp]
     lib.nerf_train_step.restype = i32
     lib.nerf_train_step.argtypes = [vp, C.POINTER(TrainArgs)]
+    lib.nerf_train_forward.restype = i32
+    lib.nerf_train_forward.argtypes = [vp, C.POINTER(TrainForwardArgs)]
+    lib.nerf_train_backward.restype = i32
+    lib.nerf_train_backward.argtypes = [vp, C.POINTER(TrainBackwardArgs)]
+    lib.nerf_zero_grad.restype = i32
+    lib.nerf_zero_grad.argtypes = [vp, i32, vp]
+    lib.nerf_adam_step.restype = i32
+    lib.nerf_adam_step.argtypes = [vp, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp]
     lib.nerf_get_weights.restype = i32
     lib.nerf_get_weights.argtypes = [vp, i32, C.POINTER(vp), i32]
     lib.nerf_get_gradients.restype = i32

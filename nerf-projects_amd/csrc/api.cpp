@@ -330,6 +330,7 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     (void)hipDeviceSynchronize();
     for (auto& n : c->nets) free_net(n);
     if (c->ws) (void)hipFree(c->ws);
+    if (c->tape_mem) (void)hipFree(c->tape_mem);
     if (c->frame_rays) (void)hipFree(c->frame_rays);
     if (c->d_loose) (void)hipFree(c->d_loose);
     if (c->h_loose) (void)hipHostFree(c->h_loose);
@@ -384,6 +385,7 @@ int nerf_load_weights(nerf_ctx* c, int slot, const nerf_arch* arch, const float*
     int rc = pack_weights(*arch, tensors, n_tensors, &hs, &nc, &hb, &nbt, &mask, &out_ch);
     if (rc != NERF_OK) return rc;
     PackedNet& net = c->nets[slot];
+    c->tape_live = false;      // (a tape of nerf_train_forward holds activations of the weights being replaced)
     // the previous stream of this slot may still be in use by enqueued work
     hipError_t e = hipDeviceSynchronize();
     free_net(net);

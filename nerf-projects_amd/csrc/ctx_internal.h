@@ -2,6 +2,7 @@
 #pragma once
 #include <cstddef>
 #include <initializer_list>
+#include <memory>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -62,6 +63,15 @@ struct nerf_ctx {
     std::vector<TrainSpan> train_spans;
     double train_ms[4] = {};
     int64_t train_points[4] = {}, train_launches[4] = {};
+    // The tape of nerf_train_forward (train_api.cpp): a grow-only arena apart from `ws` (renders reuse that between the
+    // forward and the backward call), what the backward needs to find in it, and which tape is current. A tape stops being
+    // current (tape_live = false) after its backward, another taped forward, nerf_train_step, nerf_adam_step or
+    // nerf_load_weights.
+    char* tape_mem = nullptr;
+    size_t tape_bytes = 0;
+    std::shared_ptr<void> tape_state;
+    uint64_t tape_id = 0;
+    bool tape_live = false;
 };
 
 namespace nerf {

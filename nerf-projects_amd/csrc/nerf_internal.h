@@ -76,6 +76,8 @@ struct TrainState {
     int* d_chunk_layer_bwd = nullptr;
     float* d_chunk_max_bwd = nullptr;
     bool grads_valid = false;
+    bool eq_units = false;           // the last taped forward (nerf_train_forward) ran this slot in the equalised network's
+                                     // units: nerf_adam_step then refreshes the derived copies at once, as nerf_train_step does
 };
 
 struct PackedNet {
@@ -431,7 +433,8 @@ hipError_t launch_train_prologue(const float* rays, int ray_ld, int64_t N, int S
                                  unsigned* zero, int n_zero, hipStream_t s, int pad = 0);
 hipError_t launch_train_mid(const float* raw, int C, const float* z_c, const float* rays_d, int d_ld, const float* noise,
                             int white_bkgd, int64_t N, int S, float* rgb_c, float* w_c, const float* u, int n_samples,
-                            float* z_f, hipStream_t s);
+                            float* z_f, hipStream_t s, float* disp_c = nullptr,
+                            float* acc_c = nullptr);      // (optional outputs of the taped forward, nerf_train_forward)
 struct TrainEpilogue {
     const float* rays_d; int d_ld;
     const float* target;
@@ -451,6 +454,29 @@ struct TrainEpilogue {
     float* out_stats;        // [5] optional (nerf_train_args::stats)
 };
 hipError_t launch_train_epilogue(const TrainEpilogue& e, hipStream_t s);
+// The taped forward / backward (nerf_train_forward / nerf_train_backward) split the epilogue above at the loss: the forward one
+// composites the last pass for the caller, the backward one runs raw2outputs' backward of both passes from the caller's
+// gradients (nullptr = zero).
+struct TrainFwdEpilogue {
+    const float* rays_d; int d_ld;
+    int64_t N;
+    int white_bkgd;
+    const float* raw_l; int C_l; const float* z_l; const float* noise_l; int S_l;   // the last pass
+    const float* rgb_c;      // [N,3] the coarse colours of the mid launch (nullptr: one pass)
+    float *out_rgb, *out_disp, *out_acc, *out_rgb0;      // optional
+};
+struct TrainBwdEpilogue {
+    const float* rays_d; int d_ld;
+    int64_t N;
+    int white_bkgd;
+    const float* raw_l; int C_l; const float* z_l; const float* noise_l; int S_l; float* d_raw_l; int dC_l;
+    const float *g_rgb_l, *g_disp_l, *g_acc_l;      // [N,3], [N], [N]
+    const float* g_raw_l;                            // [N, S_l, C_l]: the caller's gradient on the returned raw
+    const float* raw_c; int C_c; const float* z_c; const float* noise_c; int S_c; float* d_raw_c; int dC_c;   // raw_c = nullptr: one pass
+    const float *g_rgb_c, *g_disp_c, *g_acc_c;
+};
+hipError_t launch_train_fwd_epilogue(const TrainFwdEpilogue& e, hipStream_t s);
+hipError_t launch_train_bwd_epilogue(const TrainBwdEpilogue& e, hipStream_t s);
 hipError_t launch_train_stats(const float* loss, bool two, float* stats, hipStream_t s);
 hipError_t launch_composite_bwd(const float* raw, int C, const float* z, const float* rays_d, int d_ld,
                                 const float* noise, int white_bkgd, int64_t N, int S, const float* g_rgb,

@@ -240,16 +240,27 @@ __device__ __forceinline__ void sample_pdf_ray(int64_t ray, int lane, char* smem
 // ---- backward of raw2outputs (training step) ------------------------------------------------
 // Backward of raw2outputs for ONE ray by a 64-thread workgroup; Tsh: S floats of LDS (the exclusive transmittance of every
 // sample); (g0, g1, g2) = dL/d rgb_map of this ray.
+// GEN (the taped backward, nerf_train_backward): also dL/d disp_map (g_disp) and dL/d acc_map (g_acc) of this ray, and the
+// caller's dL/d raw (add_raw: [N, S, add_C], nullptr = zero) added to the rows written here. raw2outputs (nerf.ipynb:329-347)
+//   depth = sum_i w_i z_i,  acc = sum_i w_i,  denom = max(1e-10, acc),  disp = 1 / clamp(depth / denom, min=1e-10)
+// so dL/dw_i = g.c_i - gbg + g_acc' + g_depth' z_i with gbg = sum(g) under white_bkgd, and g_acc' / g_depth' the gradients
+// that reach acc (directly and through denom) and depth. At the kinks PyTorch's conventions: clamp(min=) passes the gradient
+// where its input is >= min; binary max sends it to the larger side and halves it on a tie. acc and depth are summed
+// exactly as composite_ray sums them (the same T, w and order). GEN = false is the rgb-only function, operation for operation.
+template <bool GEN = false>
 __device__ __forceinline__ void composite_bwd_ray(int64_t ray, int lane, float* Tsh, const float* __restrict__ raw, int C,
                                                   const float* __restrict__ z_vals, const float* __restrict__ rays_d, int d_ld,
                                                   const float* __restrict__ noise, int white_bkgd, int S, float g0, float g1,
-                                                  float g2, float* __restrict__ d_raw, int dC) {      // dC: row stride of d_raw (>= C; the rest zeroed)
+                                                  float g2, float* __restrict__ d_raw, int dC,      // dC: row stride of d_raw (>= C; the rest zeroed)
+                                                  float g_disp = 0.0f, float g_acc = 0.0f,
+                                                  const float* __restrict__ add_raw = nullptr, int add_C = 0) {
     const float* d = rays_d + ray * d_ld;
     const float norm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
     const float* z = z_vals + ray * S;
     const float* rw = raw + ray * (int64_t)S * C;
     float* dr = d_raw + ray * (int64_t)S * dC;
-    const float gbg = white_bkgd ? (g0 + g1 + g2) : 0.0f;
+    float gbg = white_bkgd ? (g0 + g1 + g2) : 0.0f;
+    float sa = 0.0f, sd = 0.0f;      // (GEN) acc and depth, summed as composite_ray sums them
 
     auto alpha_at = [&](int i, float& dist, float& sig) {
         dist = __fmul_rn(i < S - 1 ? __fsub_rn(z[i + 1], z[i]) : 1e10f, norm);
@@ -272,11 +283,32 @@ __device__ __forceinline__ void composite_bwd_ray(int64_t ray, int lane, float* 
         double excl = __shfl_up(v, 1);
         if (lane == 0) excl = 1.0;
         if (i < S) Tsh[i] = (float)(carry_t * excl);
+        if constexpr (GEN) {
+            if (i < S) {
+                const float w = __fmul_rn(alpha, (float)(carry_t * excl));
+                sd += __fmul_rn(w, z[i]);
+                sa += w;
+            }
+        }
         carry_t *= __shfl(v, 63);
     }
     __syncthreads();
+    float g_dep = 0.0f;      // (GEN) dL/d depth
+    if constexpr (GEN) {
+        sa = wave_sum(sa);      // (every lane holds the sum)
+        sd = wave_sum(sd);
+        const float denom = fmaxf(1e-10f, sa);                                  // :339
+        const float q = __fdiv_rn(sd, denom);                                   // :340
+        const float disp = __fdiv_rn(1.0f, fmaxf(q, 1e-10f));
+        const float gq = q >= 1e-10f ? -g_disp * (disp * disp) : 0.0f;          // reciprocal, then clamp(min=1e-10)
+        g_dep = gq / denom;                                                     // depth / denom
+        const float g_den = -gq * sd / (denom * denom);
+        const float g_max = sa > 1e-10f ? g_den : (sa == 1e-10f ? 0.5f * g_den : 0.0f);   // max(1e-10, acc)
+        gbg = gbg - (g_acc + g_max);      // dL/dw_i = g.c_i - gbg + g_dep z_i
+    }
     // backward pass from the far end; carry = sum over samples beyond this round of w_i (g.c_i - gbg)
     float carry = 0.0f;
+    float carry_z = 0.0f;    // (GEN) ... and of w_i z_i
     for (int rd = (S + 63) / 64 - 1; rd >= 0; --rd) {
         const int i = rd * 64 + lane;
         const bool on = i < S;
@@ -299,6 +331,32 @@ __device__ __forceinline__ void composite_bwd_ray(int64_t ray, int lane, float* 
         }
         const float suffix_excl = incl - q + carry;   // sum_{i' > i} w_i' (g.c_i' - gbg)
         carry += __shfl(incl, 0);
+        if constexpr (GEN) {
+            const float zi = on ? z[i] : 0.0f;
+            const float qz = on ? wi * zi : 0.0f;
+            float incl_z = qz;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const float nb = __shfl_down(incl_z, o);
+                if (lane + o < 64) incl_z += nb;
+            }
+            const float suffix_z = incl_z - qz + carry_z;   // sum_{i' > i} w_i' z_i'
+            carry_z += __shfl(incl_z, 0);
+            if (on) {
+                const float om = __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f);
+                const float dalpha_dsig = sig > 0.0f ? dist * (1.0f - alpha) : 0.0f;
+                const float* ar = add_raw ? add_raw + (ray * (int64_t)S + i) * add_C : nullptr;
+                float v[4];
+                v[0] = g0 * wi * c0 * (1.0f - c0);
+                v[1] = g1 * wi * c1 * (1.0f - c1);
+                v[2] = g2 * wi * c2 * (1.0f - c2);
+                v[3] = dalpha_dsig * (T * (gc - gbg + g_dep * zi) - (suffix_excl + g_dep * suffix_z) / om);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) dr[(int64_t)i * dC + c] = ar ? v[c] + ar[c] : v[c];
+                for (int c = 4; c < dC; ++c) dr[(int64_t)i * dC + c] = (ar && c < add_C) ? ar[c] : 0.0f;
+            }
+            continue;
+        }
         if (on) {
             const float om = __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f);
             const float dalpha_dsig = sig > 0.0f ? dist * (1.0f - alpha) : 0.0f;   // d/dsigma of 1 - exp(-relu(sigma) dist)

@@ -965,6 +965,188 @@ void set_units(Pass& ps) {
                  dw_reads_blocked && (uint64_t)ps.P * 1024u < ((uint64_t)1 << 32);
 }
 
+// ---- the phases of a training iteration, shared by nerf_train_step and the taped route ---------------------------------
+
+// What nerf_train_args and nerf_train_forward_args have in common: render(rays, retraw=True, **render_kwargs_train)'s inputs
+struct StepInputs {
+    const float* rays;
+    int64_t n_rays;
+    int ray_stride, N_samples, N_importance, slot_coarse, slot_fine, lindisp, white_bkgd, perturb;
+    const float *t_rand, *u_rand, *noise0, *noise, *z_vals_fine_in;
+};
+
+// The checks of nerf_train_step on those inputs; *nc / *nf: the networks of the two passes (the same one when shared)
+int check_step_inputs(nerf_ctx* c, const StepInputs& r, const char* what, PackedNet** nc, PackedNet** nf) {
+    if (!r.rays || r.n_rays <= 0) {
+        set_error("%s: invalid argument", what);
+        return NERF_E_INVALID;
+    }
+    const int Sc = r.N_samples, Si = r.N_importance, Sf = Sc + Si;
+    if (r.ray_stride != 8 && r.ray_stride != 11) {
+        set_error("ray_stride must be 8 or 11 floats (got %d)", r.ray_stride);
+        return NERF_E_INVALID;
+    }
+    if (Sc < 1 || Si < 0 || Sf > 4096 || (Si > 0 && Sc < 3)) {
+        set_error("unsupported sample counts N_samples=%d N_importance=%d", Sc, Si);
+        return NERF_E_INVALID;
+    }
+    if (r.perturb && (!r.t_rand || (Si > 0 && !r.u_rand))) {
+        set_error("perturb > 0 requires t_rand (and u_rand with N_importance > 0): the caller owns the RNG");
+        return NERF_E_INVALID;
+    }
+    if (r.slot_coarse < 0 || r.slot_coarse >= NERF_NUM_SLOTS || !c->nets[r.slot_coarse].loaded) {
+        set_error("no weights loaded in slot %d", r.slot_coarse);
+        return NERF_E_STATE;
+    }
+    *nc = *nf = &c->nets[r.slot_coarse];
+    if (Si > 0 && r.slot_fine >= 0) {
+        if (r.slot_fine >= NERF_NUM_SLOTS || !c->nets[r.slot_fine].loaded) {
+            set_error("no weights loaded in slot %d", r.slot_fine);
+            return NERF_E_STATE;
+        }
+        *nf = &c->nets[r.slot_fine];
+    }
+    for (PackedNet* n : {*nc, *nf}) {
+        if (n->arch.use_viewdirs && r.ray_stride < 11) {
+            set_error("the model uses viewdirs but rays carry only %d columns", r.ray_stride);
+            return NERF_E_INVALID;
+        }
+        if (n->out_ch < 4) {
+            set_error("training needs a model with >= 4 output channels");
+            return NERF_E_INVALID;
+        }
+    }
+    return NERF_OK;
+}
+
+// Precision guard (nerf_mi355x.h): events counted by work that has completed since the last look - earlier steps of this
+// loop, typically - move the training path to the fp32 kernels, from this step on and until nerf_set_precision. Returns the
+// arithmetic of this step; *fell_back: this call made the move (it reports NERF_W_PRECISION_FALLBACK).
+int enter_precision_guard(nerf_ctx* c, bool* fell_back) {
+    *fell_back = false;
+    if (c->train_precision == NERF_PRECISION_F16X2 && !c->train_force_f32 && take_new_loose_train(c) > 0) {
+        c->train_force_f32 = true;
+        *fell_back = true;
+    }
+    return c->train_force_f32 ? NERF_PRECISION_F32 : c->train_precision;
+}
+
+int prepare_nets(nerf_ctx* c, PackedNet& nc, PackedNet& nf, hipStream_t s) {
+    int rc;
+    for (PackedNet* n : {&nc, &nf}) {
+        const bool fresh = !n->train.ready;
+        if ((rc = ensure_train_state(c, *n))) return rc;
+        if (fresh && (rc = mark_params_changed(*n, s, false))) return rc;
+    }
+    return NERF_OK;
+}
+
+void init_pass(Pass& ps, PackedNet& net, int64_t N, int S, int precision, nerf_ctx* c, unsigned* maxes) {
+    ps.net = &net;
+    ps.N = N;
+    ps.P = N * S;
+    ps.S = S;
+    ps.fused_backward = !gemm_backward_requested() && net.train.d_stream_bwd != nullptr && (net.out_ch == 4 || !net.arch.use_viewdirs);
+    ps.precision = precision;
+    ps.ctx = c;
+    ps.loose = c->d_loose + kLooseTrain;
+    ps.maxes = maxes;
+    set_units(ps);
+}
+
+// render(..., retraw=True, **render_kwargs_train) (nerf.ipynb:1258) up to the last pass's network output, the small stages
+// fused: both passes with everything autograd keeps, the coarse colours (and, for the taped route, disp0 / acc0) and the
+// resampling between them. z_c / z_f / w_c / rgb_c: [N,Sc] / [N,Sf] / [N,Sc] / [N,3]; zero_block: the words the prologue zeroes.
+int forward_phase(Pass& pc, Pass& pf, const StepInputs& r, const float* rays, const float* noise0, float* z_c, float* w_c,
+                  float* rgb_c, float* z_f, unsigned* zero_block, hipStream_t s, float* disp_c = nullptr, float* acc_c = nullptr) {
+    const int64_t N = r.n_rays;
+    const int Sc = r.N_samples, Si = r.N_importance, Sf = Sc + Si;
+    int rc;
+    const Prologue pro{r.lindisp, r.perturb ? r.t_rand : nullptr, zero_block, 2 * kBwdMaxSlots + 32};
+    if ((rc = forward_pass(pc, rays, r.ray_stride, z_c, s, &pro))) return rc;
+    if (Si) {
+        HIP_TRY(launch_train_mid(pc.raw, pc.C, z_c, rays + 3, r.ray_stride, noise0, r.white_bkgd, N, Sc, rgb_c, w_c,
+                                 r.perturb ? r.u_rand : nullptr, Si, z_f, s, disp_c, acc_c));      // z_samples are detached (nerf.ipynb:464)
+        if (r.z_vals_fine_in)      // (parity tests: the fine pass at the reference's depths)
+            HIP_TRY(hipMemcpyAsync(z_f, r.z_vals_fine_in, (size_t)N * Sf * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if ((rc = forward_pass(pf, rays, r.ray_stride, z_f, s))) return rc;
+    }
+    return NERF_OK;
+}
+
+// loss.backward() from d raw of both passes (written by the epilogue) to the weight gradients: the coarse pass first, then
+// the fine one. accumulate: add into the gradients there (the taped route's .grad semantics); otherwise the coarse pass
+// overwrites them and the fine one adds only when it runs through the same network.
+int backward_phase(Pass& pc, Pass& pf, int Si, bool shared, TnScratch& sc, bool accumulate, hipStream_t s) {
+    int rc;
+    sc.P = pc.P;
+    sc.accumulate = accumulate ? 1 : 0;
+    if ((rc = backward_pass(pc, sc, s))) return rc;
+    const_cast<PackedNet*>(pc.net)->train.grads_valid = true;
+    if (Si) {
+        sc.P = pf.P;
+        sc.accumulate = (accumulate || shared) ? 1 : 0;
+        if ((rc = backward_pass(pf, sc, s))) return rc;
+        const_cast<PackedNet*>(pf.net)->train.grads_valid = true;
+    }
+    return NERF_OK;
+}
+
+// optimizer.step() (torch.optim.Adam, nerf.ipynb:905, :1275) over n distinct networks, and the refresh of what is derived
+// from their weights: at once when the passes ran in the equalised network's units (the next step - or a render - needs
+// the equalised copies anyway), lazily otherwise. *mirrored: the refresh also mirrored the precision guard's counters.
+int adam_phase(nerf_ctx* c, PackedNet* const* nets, int n, float lr, float beta1, float beta2, float eps, int step, bool eq,
+               hipStream_t s, bool* mirrored) {
+    int rc;
+    for (int i = 0; i < n; ++i) {
+        PackedNet* p = nets[i];
+        HIP_TRY(launch_adam(p->d_params, p->train.d_grad, p->train.d_m, p->train.d_v, (int64_t)p->n_params, lr, beta1, beta2,
+                            eps, step, s));
+        if ((rc = mark_params_changed(*p, s, true))) return rc;
+    }
+    if (eq) {
+        PackedNet* both[2] = {nets[0], n > 1 ? nets[1] : nets[0]};
+        if (!glue_legacy()) {
+            if ((rc = refresh_after_step(c, both, n, s, mirrored))) return rc;
+        } else if ((rc = refresh_h2_many(both, n, s))) return rc;
+    }
+    return NERF_OK;
+}
+
+// the workspace of the split-K weight gradients (sc.part / sc.dbp): what nerf_train_step budgets for them
+constexpr int kTnSlices = 256;
+size_t tn_part_floats(const PackedNet& nc) { return (size_t)kTnSlices * 256 * (size_t)(nc.arch.W + nc.arch.input_ch + 64); }
+
+// What nerf_train_backward needs of the tape nerf_train_forward left (pointers into nerf_ctx::tape_mem)
+struct Tape {
+    StepInputs in;            // (rays / noise0 / noise point at the tape's copies)
+    Pass pc, pf;
+    PackedNet *nc = nullptr, *nf = nullptr;
+    bool shared = false;
+    float *z_c = nullptr, *z_f = nullptr;
+};
+
+int ensure_tape(nerf_ctx* c, size_t bytes) {
+    if (bytes <= c->tape_bytes) return NERF_OK;
+    if (c->tape_mem) {      // (grow-only; rare: the first taped call at a given batch size)
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipFree(c->tape_mem));
+        c->tape_mem = nullptr;
+        c->tape_bytes = 0;
+    }
+    const size_t want = bytes + bytes / 8;
+    hipError_t e = hipMalloc((void**)&c->tape_mem, want);
+    if (e != hipSuccess) {
+        c->tape_mem = nullptr;
+        (void)hipGetLastError();
+        set_error("nerf_train_forward: the tape of this batch needs %zu bytes of device memory, which could not be allocated "
+                  "(%s): render fewer rays per taped call, or render without a tape", want, hipGetErrorString(e));
+        return NERF_E_NOMEM;
+    }
+    c->tape_bytes = want;
+    return NERF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -974,70 +1156,31 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
         set_error("nerf_train_step: invalid argument");
         return NERF_E_INVALID;
     }
+    const StepInputs in{r->rays, r->n_rays, r->ray_stride, r->N_samples, r->N_importance, r->slot_coarse, r->slot_fine,
+                        r->lindisp, r->white_bkgd, r->perturb, r->t_rand, r->u_rand, r->noise0, r->noise, r->z_vals_fine_in};
+    PackedNet *ncp = nullptr, *nfp = nullptr;
+    int rc = check_step_inputs(c, in, "nerf_train_step", &ncp, &nfp);
+    if (rc != NERF_OK) return rc;
     const int64_t N = r->n_rays;
     const int Sc = r->N_samples, Si = r->N_importance, Sf = Sc + Si;
-    if (r->ray_stride != 8 && r->ray_stride != 11) {
-        set_error("ray_stride must be 8 or 11 floats (got %d)", r->ray_stride);
-        return NERF_E_INVALID;
-    }
-    if (Sc < 1 || Si < 0 || Sf > 4096 || (Si > 0 && Sc < 3)) {
-        set_error("unsupported sample counts N_samples=%d N_importance=%d", Sc, Si);
-        return NERF_E_INVALID;
-    }
-    if (r->perturb && (!r->t_rand || (Si > 0 && !r->u_rand))) {
-        set_error("perturb > 0 requires t_rand (and u_rand with N_importance > 0): the caller owns the RNG");
-        return NERF_E_INVALID;
-    }
-    if (r->slot_coarse < 0 || r->slot_coarse >= NERF_NUM_SLOTS || !c->nets[r->slot_coarse].loaded) {
-        set_error("no weights loaded in slot %d", r->slot_coarse);
-        return NERF_E_STATE;
-    }
-    PackedNet& nc = c->nets[r->slot_coarse];
-    PackedNet* nfp = &nc;
-    if (Si > 0 && r->slot_fine >= 0) {
-        if (r->slot_fine >= NERF_NUM_SLOTS || !c->nets[r->slot_fine].loaded) {
-            set_error("no weights loaded in slot %d", r->slot_fine);
-            return NERF_E_STATE;
-        }
-        nfp = &c->nets[r->slot_fine];
-    }
+    PackedNet& nc = *ncp;
     PackedNet& nf = *nfp;
     // network_fine=None with N_importance > 0 (nerf.ipynb:471: run_fn = network_fn): both passes go through one
     // network and its gradient is the sum over the passes
     const bool shared = (&nf == &nc) && Si > 0;
-    for (PackedNet* n : {&nc, &nf}) {
-        if (n->arch.use_viewdirs && r->ray_stride < 11) {
-            set_error("the model uses viewdirs but rays carry only %d columns", r->ray_stride);
-            return NERF_E_INVALID;
-        }
-        if (n->out_ch < 4) {
-            set_error("training needs a model with >= 4 output channels");
-            return NERF_E_INVALID;
-        }
-    }
     DeviceGuard guard(c->device);
     hipStream_t s = (hipStream_t)r->stream;
     ScratchScope scope(c, s);
     HIP_TRY(scope.status);
-    int rc;
-    // Precision guard (nerf_mi355x.h): events counted by work that has completed since the last look - earlier steps of
-    // this loop, typically - move the training path to the fp32 kernels, from this step on and until nerf_set_precision
+    c->tape_live = false;      // (the weights the tape's activations were made with change)
     bool fell_back = false;
-    if (c->train_precision == NERF_PRECISION_F16X2 && !c->train_force_f32 && take_new_loose_train(c) > 0) {
-        c->train_force_f32 = true;
-        fell_back = true;
-    }
-    const int precision = c->train_force_f32 ? NERF_PRECISION_F32 : c->train_precision;
-    for (PackedNet* n : {&nc, &nf}) {
-        const bool fresh = !n->train.ready;
-        if ((rc = ensure_train_state(c, *n))) return rc;
-        if (fresh && (rc = mark_params_changed(*n, s, false))) return rc;
-    }
+    const int precision = enter_precision_guard(c, &fell_back);
+    if ((rc = prepare_nets(c, nc, nf, s))) return rc;
 
     // workspace: sampling buffers + both passes + split-K partials
     const int64_t Pc = N * Sc, Pf = Si ? N * Sf : 0;
-    const int n_slices = 256;
-    const size_t part_floats = (size_t)n_slices * 256 * (size_t)(nc.arch.W + nc.arch.input_ch + 64);
+    const int n_slices = kTnSlices;
+    const size_t part_floats = tn_part_floats(nc);
     const size_t small = (size_t)N * (Sc * 2 + (Si ? Si + Sf * 2 : 0) + 24) + 8192;
     rc = ensure_workspace(c, arena_bytes({small, pass_floats(nc, Pc), Si ? pass_floats(nf, Pf) : 1, part_floats,
                                           (size_t)n_slices * 512}) +
@@ -1062,29 +1205,11 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
     unsigned* zero_block = (unsigned*)ar.take(2 * kBwdMaxSlots + 32);
     double* loss_part = (double*)ar.take((size_t)4 * N + 16);      // [2][N] per-ray sums of squares
     Pass pc;
-    pc.net = &nc;
-    pc.N = N;
-    pc.P = Pc;
-    pc.S = Sc;
-    pc.fused_backward = !gemm_backward_requested() && nc.train.d_stream_bwd != nullptr && (nc.out_ch == 4 || !nc.arch.use_viewdirs);
-    pc.precision = precision;
-    pc.ctx = c;
-    pc.loose = c->d_loose + kLooseTrain;
-    pc.maxes = zero_block;
-    set_units(pc);
+    init_pass(pc, nc, N, Sc, precision, c, zero_block);
     carve_pass(ar, pc);
     Pass pf;
     if (Si) {
-        pf.net = &nf;
-        pf.N = N;
-        pf.P = Pf;
-        pf.S = Sf;
-        pf.fused_backward = !gemm_backward_requested() && nf.train.d_stream_bwd != nullptr && (nf.out_ch == 4 || !nf.arch.use_viewdirs);
-        pf.precision = precision;
-        pf.ctx = c;
-        pf.loose = c->d_loose + kLooseTrain;
-        pf.maxes = zero_block + kBwdMaxSlots;
-        set_units(pf);
+        init_pass(pf, nf, N, Sf, precision, c, zero_block + kBwdMaxSlots);
         carve_pass(ar, pf);
     }
     unsigned* ticket = zero_block + 2 * kBwdMaxSlots;
@@ -1092,15 +1217,7 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
 
     if (fused_glue) {
         // ---- forward (render(..., retraw=True, **render_kwargs_train), nerf.ipynb:1258), the small stages fused ----
-        const Prologue pro{r->lindisp, r->perturb ? r->t_rand : nullptr, zero_block, 2 * kBwdMaxSlots + 32};
-        if ((rc = forward_pass(pc, r->rays, r->ray_stride, z_c, s, &pro))) return rc;
-        if (Si) {
-            HIP_TRY(launch_train_mid(pc.raw, pc.C, z_c, r->rays + 3, r->ray_stride, r->noise0, r->white_bkgd, N, Sc, rgb_c, w_c,
-                                     r->perturb ? r->u_rand : nullptr, Si, z_f, s));      // z_samples are detached (nerf.ipynb:464)
-            if (r->z_vals_fine_in)      // (parity tests: the fine pass at the reference's depths)
-                HIP_TRY(hipMemcpyAsync(z_f, r->z_vals_fine_in, (size_t)N * Sf * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if ((rc = forward_pass(pf, r->rays, r->ray_stride, z_f, s))) return rc;
-        }
+        if ((rc = forward_phase(pc, pf, in, r->rays, r->noise0, z_c, w_c, rgb_c, z_f, zero_block, s))) return rc;
         // ---- raw2outputs of the last pass, loss = img2mse(rgb, target) [+ img2mse(rgb0, target)] (nerf.ipynb:1262-1272),
         //      and the backward of both raw2outputs: one launch ----
         Pass& pl = Si ? pf : pc;
@@ -1125,15 +1242,7 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
         e.out_stats = r->stats;
         HIP_TRY(launch_train_epilogue(e, s));
         // ---- backward ----
-        sc.P = Pc;
-        if ((rc = backward_pass(pc, sc, s))) return rc;
-        nc.train.grads_valid = true;
-        if (Si) {
-            sc.P = Pf;
-            sc.accumulate = shared ? 1 : 0;
-            if ((rc = backward_pass(pf, sc, s))) return rc;
-            nf.train.grads_valid = true;
-        }
+        if ((rc = backward_phase(pc, pf, Si, shared, sc, false, s))) return rc;
     } else {
     // ---- forward (render(..., retraw=True, **render_kwargs_train), nerf.ipynb:1258) ----
     for (Pass* p : {&pc, &pf})
@@ -1183,21 +1292,9 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
             set_error("nerf_train_step: step must be the 1-based Adam step count");
             return NERF_E_INVALID;
         }
-        for (PackedNet* n : {&nc, &nf}) {
-            HIP_TRY(launch_adam(n->d_params, n->train.d_grad, n->train.d_m, n->train.d_v, (int64_t)n->n_params, r->lr,
-                                r->beta1, r->beta2, r->eps, r->step, s));
-            if ((rc = mark_params_changed(*n, s, true))) return rc;
-            if (!Si || shared) break;
-        }
-        // the equalised copies of both networks follow at once (one pair of launches for the two): the next step - or a
-        // render - needs them anyway
-        if (pc.eq) {
-            PackedNet* both[2] = {&nc, &nf};
-            const int n_nets = (Si && !shared) ? 2 : 1;
-            if (fused_glue) {
-                if ((rc = refresh_after_step(c, both, n_nets, s, &mirrored))) return rc;
-            } else if ((rc = refresh_h2_many(both, n_nets, s))) return rc;
-        }
+        PackedNet* both[2] = {&nc, &nf};
+        const int n_nets = (Si && !shared) ? 2 : 1;
+        if ((rc = adam_phase(c, both, n_nets, r->lr, r->beta1, r->beta2, r->eps, r->step, pc.eq, s, &mirrored))) return rc;
     }
     if (!mirrored) HIP_TRY(mirror_loose(c, s));
     if (fell_back) {
@@ -1205,6 +1302,219 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
                   "kept fewer than 24 bits with these weights); training continues on the fp32 kernels");
         return NERF_W_PRECISION_FALLBACK;
     }
+    return NERF_OK;
+}
+
+int nerf_train_forward(nerf_ctx* c, const nerf_train_forward_args* r) {
+    if (!c || !r || !r->tape) {
+        set_error("nerf_train_forward: invalid argument");
+        return NERF_E_INVALID;
+    }
+    if (r->struct_size != sizeof(nerf_train_forward_args)) {
+        set_error("nerf_train_forward: struct_size is %zu, this library's nerf_train_forward_args has %zu bytes (a caller "
+                  "built against another version of nerf_mi355x.h)", r->struct_size, sizeof(nerf_train_forward_args));
+        return NERF_E_INVALID;
+    }
+    StepInputs in{r->rays, r->n_rays, r->ray_stride, r->N_samples, r->N_importance, r->slot_coarse, r->slot_fine,
+                  r->lindisp, r->white_bkgd, r->perturb, r->t_rand, r->u_rand, r->noise0, r->noise, r->z_vals_fine_in};
+    PackedNet *ncp = nullptr, *nfp = nullptr;
+    int rc = check_step_inputs(c, in, "nerf_train_forward", &ncp, &nfp);
+    if (rc != NERF_OK) return rc;
+    const int64_t N = r->n_rays;
+    const int Sc = r->N_samples, Si = r->N_importance, Sf = Sc + Si;
+    PackedNet& nc = *ncp;
+    PackedNet& nf = *nfp;
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)r->stream;
+    ScratchScope scope(c, s);
+    HIP_TRY(scope.status);
+    c->tape_live = false;      // (one tape per context: this call overwrites the arena)
+    bool fell_back = false;
+    const int precision = enter_precision_guard(c, &fell_back);
+    if ((rc = prepare_nets(c, nc, nf, s))) return rc;
+
+    // the tape: the inputs the backward pass re-reads (copied: the caller may free them), the depths, both passes
+    const int64_t Pc = N * Sc, Pf = Si ? N * Sf : 0;
+    const size_t small = (size_t)N * ((size_t)r->ray_stride + Sc * 3 + 3 + (Si ? Sf * 2 : 0)) + 8192;
+    rc = ensure_tape(c, arena_bytes({small, pass_floats(nc, Pc), Si ? pass_floats(nf, Pf) : 1}) + (1 << 20));
+    if (rc != NERF_OK) return rc;
+    auto tp = std::make_shared<Tape>();
+    Tape& t = *tp;
+    Arena ar(c->tape_mem);
+    float* rays = ar.take((size_t)N * r->ray_stride);
+    float* noise0 = r->noise0 ? ar.take((size_t)N * Sc) : nullptr;
+    float* noise = (Si && r->noise) ? ar.take((size_t)N * Sf) : nullptr;
+    HIP_TRY(hipMemcpyAsync(rays, r->rays, (size_t)N * r->ray_stride * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (noise0) HIP_TRY(hipMemcpyAsync(noise0, r->noise0, (size_t)N * Sc * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (noise) HIP_TRY(hipMemcpyAsync(noise, r->noise, (size_t)N * Sf * sizeof(float), hipMemcpyDeviceToDevice, s));
+    in.rays = rays;
+    in.noise0 = noise0;
+    in.noise = Si ? noise : nullptr;
+    float* z_c = ar.take((size_t)N * Sc);
+    float* w_c = ar.take((size_t)N * Sc);
+    float* rgb_c = ar.take((size_t)N * 3);
+    float* z_f = Si ? ar.take((size_t)N * Sf) : nullptr;
+    unsigned* zero_block = (unsigned*)ar.take(2 * kBwdMaxSlots + 32);
+    init_pass(t.pc, nc, N, Sc, precision, c, zero_block);
+    carve_pass(ar, t.pc);
+    if (Si) {
+        init_pass(t.pf, nf, N, Sf, precision, c, zero_block + kBwdMaxSlots);
+        carve_pass(ar, t.pf);
+    }
+    if ((rc = forward_phase(t.pc, t.pf, in, rays, noise0, z_c, w_c, rgb_c, z_f, zero_block, s, Si ? r->disp0 : nullptr,
+                            Si ? r->acc0 : nullptr)))
+        return rc;
+    Pass& pl = Si ? t.pf : t.pc;
+    TrainFwdEpilogue e{};
+    e.rays_d = rays + 3;
+    e.d_ld = r->ray_stride;
+    e.N = N;
+    e.white_bkgd = r->white_bkgd;
+    e.raw_l = pl.raw; e.C_l = pl.C; e.z_l = Si ? z_f : z_c; e.noise_l = Si ? noise : noise0; e.S_l = Si ? Sf : Sc;
+    e.rgb_c = Si ? rgb_c : nullptr;
+    e.out_rgb = r->rgb_map;
+    e.out_disp = r->disp_map;
+    e.out_acc = r->acc_map;
+    e.out_rgb0 = Si ? r->rgb0 : nullptr;
+    HIP_TRY(launch_train_fwd_epilogue(e, s));
+    if (r->raw)
+        HIP_TRY(hipMemcpyAsync(r->raw, pl.raw, (size_t)pl.P * pl.C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(mirror_loose(c, s));
+    t.in = in;
+    t.nc = &nc;
+    t.nf = &nf;
+    t.shared = (&nf == &nc) && Si > 0;
+    t.z_c = z_c;
+    t.z_f = z_f;
+    nc.train.eq_units = t.pc.eq;
+    if (Si) nf.train.eq_units = t.pf.eq;
+    c->tape_state = tp;
+    c->tape_id += 1;
+    c->tape_live = true;
+    *r->tape = c->tape_id;
+    if (fell_back) {
+        set_error("nerf_train_forward: the fp16-pair kernels' output-scale bound was loose in an earlier step (some activations "
+                  "kept fewer than 24 bits with these weights); training continues on the fp32 kernels");
+        return NERF_W_PRECISION_FALLBACK;
+    }
+    return NERF_OK;
+}
+
+int nerf_train_backward(nerf_ctx* c, const nerf_train_backward_args* r) {
+    if (!c || !r) {
+        set_error("nerf_train_backward: invalid argument");
+        return NERF_E_INVALID;
+    }
+    if (r->struct_size != sizeof(nerf_train_backward_args)) {
+        set_error("nerf_train_backward: struct_size is %zu, this library's nerf_train_backward_args has %zu bytes (a caller "
+                  "built against another version of nerf_mi355x.h)", r->struct_size, sizeof(nerf_train_backward_args));
+        return NERF_E_INVALID;
+    }
+    if (!c->tape_live || r->tape != c->tape_id || !c->tape_state) {
+        set_error("nerf_train_backward: tape %llu is not current (the current one is %llu%s): a tape is consumed by its backward "
+                  "and stops being current after another nerf_train_forward, nerf_train_step, nerf_adam_step or "
+                  "nerf_load_weights", (unsigned long long)r->tape, (unsigned long long)c->tape_id,
+                  c->tape_live ? "" : ", already consumed or invalidated");
+        return NERF_E_STATE;
+    }
+    Tape& t = *std::static_pointer_cast<Tape>(c->tape_state);
+    const StepInputs& in = t.in;
+    const int64_t N = in.n_rays;
+    const int Sc = in.N_samples, Si = in.N_importance, Sf = Sc + Si;
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)r->stream;
+    ScratchScope scope(c, s);
+    HIP_TRY(scope.status);
+    const size_t part_floats = tn_part_floats(*t.nc);
+    int rc = ensure_workspace(c, arena_bytes({part_floats, (size_t)kTnSlices * 512}) + (1 << 20));
+    if (rc != NERF_OK) return rc;
+    Arena ar(c->ws);
+    TnScratch sc{ar.take(part_floats), ar.take((size_t)kTnSlices * 512), kTnSlices, 0, 0, part_floats, (size_t)kTnSlices * 512};
+    // ---- raw2outputs' backward of both passes from the caller's gradients: one launch ----
+    Pass& pl = Si ? t.pf : t.pc;
+    TrainBwdEpilogue e{};
+    e.rays_d = in.rays + 3;
+    e.d_ld = in.ray_stride;
+    e.N = N;
+    e.white_bkgd = in.white_bkgd;
+    e.raw_l = pl.raw; e.C_l = pl.C; e.z_l = Si ? t.z_f : t.z_c; e.noise_l = Si ? in.noise : in.noise0; e.S_l = Si ? Sf : Sc;
+    e.d_raw_l = pl.d_raw;
+    e.dC_l = pl.dC;
+    e.g_rgb_l = r->d_rgb;
+    e.g_disp_l = r->d_disp;
+    e.g_acc_l = r->d_acc;
+    e.g_raw_l = r->d_raw;
+    if (Si) {
+        e.raw_c = t.pc.raw; e.C_c = t.pc.C; e.z_c = t.z_c; e.noise_c = in.noise0; e.S_c = Sc; e.d_raw_c = t.pc.d_raw; e.dC_c = t.pc.dC;
+        e.g_rgb_c = r->d_rgb0;
+        e.g_disp_c = r->d_disp0;
+        e.g_acc_c = r->d_acc0;
+    }
+    c->tape_live = false;      // (consumed, whatever happens below)
+    HIP_TRY(launch_train_bwd_epilogue(e, s));
+    // ---- the backward pass of nerf_train_step, adding into the gradients ----
+    if ((rc = backward_phase(t.pc, t.pf, Si, t.shared, sc, true, s))) return rc;
+    HIP_TRY(mirror_loose(c, s));
+    return NERF_OK;
+}
+
+int nerf_zero_grad(nerf_ctx* c, int slot, void* stream) {
+    if (!c || slot < 0 || slot >= NERF_NUM_SLOTS || !c->nets[slot].loaded) {
+        set_error("nerf_zero_grad: invalid slot or no weights loaded in slot %d", slot);
+        return NERF_E_INVALID;
+    }
+    PackedNet& net = c->nets[slot];
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    ScratchScope scope(c, s);
+    HIP_TRY(scope.status);
+    const bool fresh = !net.train.ready;
+    int rc = ensure_train_state(c, net);
+    if (rc != NERF_OK) return rc;
+    if (fresh && (rc = mark_params_changed(net, s, false))) return rc;
+    HIP_TRY(hipMemsetAsync(net.train.d_grad, 0, net.n_params * sizeof(float), s));
+    net.train.grads_valid = true;
+    return NERF_OK;
+}
+
+int nerf_adam_step(nerf_ctx* c, const int32_t* slots, int n, float lr, float beta1, float beta2, float eps, int step,
+                   void* stream) {
+    if (!c || !slots || n < 1 || n > 2) {
+        set_error("nerf_adam_step: invalid argument (1 or 2 slots)");
+        return NERF_E_INVALID;
+    }
+    if (step < 1) {
+        set_error("nerf_adam_step: step must be the 1-based Adam step count");
+        return NERF_E_INVALID;
+    }
+    PackedNet* nets[2] = {nullptr, nullptr};
+    for (int i = 0; i < n; ++i) {
+        if (slots[i] < 0 || slots[i] >= NERF_NUM_SLOTS || !c->nets[slots[i]].loaded) {
+            set_error("nerf_adam_step: no weights loaded in slot %d", slots[i]);
+            return NERF_E_STATE;
+        }
+        nets[i] = &c->nets[slots[i]];
+    }
+    if (n == 2 && nets[0] == nets[1]) {
+        set_error("nerf_adam_step: the slots must be distinct");
+        return NERF_E_INVALID;
+    }
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    ScratchScope scope(c, s);
+    HIP_TRY(scope.status);
+    c->tape_live = false;      // (the weights the tape's activations were made with change)
+    int rc;
+    bool eq = false;
+    for (int i = 0; i < n; ++i) {
+        const bool fresh = !nets[i]->train.ready;
+        if ((rc = ensure_train_state(c, *nets[i]))) return rc;
+        if (fresh && (rc = mark_params_changed(*nets[i], s, false))) return rc;
+        eq = eq || nets[i]->train.eq_units;
+    }
+    bool mirrored = false;
+    if ((rc = adam_phase(c, nets, n, lr, beta1, beta2, eps, step, eq, s, &mirrored))) return rc;
+    if (!mirrored) HIP_TRY(mirror_loose(c, s));
     return NERF_OK;
 }
 

@@ -771,10 +771,12 @@ __global__ __launch_bounds__(64) void train_mid_kernel(const float* __restrict__
                                                        const float* __restrict__ noise, int white_bkgd, int S,
                                                        float* __restrict__ rgb_c, float* __restrict__ w_c,
                                                        const float* __restrict__ u, int n_samples, int n_sort,
-                                                       float* __restrict__ z_f) {
+                                                       float* __restrict__ z_f, float* __restrict__ disp_c,
+                                                       float* __restrict__ acc_c) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t ray = blockIdx.x;
-    composite_ray(ray, threadIdx.x, raw, C, z_c, rays_d, d_ld, noise, white_bkgd, S, rgb_c, nullptr, nullptr, w_c, nullptr);
+    // (disp_c / acc_c: the taped forward's rgb0 companions; nullptr in nerf_train_step)
+    composite_ray(ray, threadIdx.x, raw, C, z_c, rays_d, d_ld, noise, white_bkgd, S, rgb_c, disp_c, acc_c, w_c, nullptr);
     __threadfence_block();
     __syncthreads();      // (one wavefront: the weights it wrote are what it reads next)
     sample_pdf_ray(ray, threadIdx.x, smem, nullptr, w_c, S, 1, z_c, u, S - 1, n_samples, n_sort, nullptr, z_f, nullptr);
@@ -782,7 +784,7 @@ __global__ __launch_bounds__(64) void train_mid_kernel(const float* __restrict__
 
 hipError_t launch_train_mid(const float* raw, int C, const float* z_c, const float* rays_d, int d_ld, const float* noise,
                             int white_bkgd, int64_t N, int S, float* rgb_c, float* w_c, const float* u, int n_samples,
-                            float* z_f, hipStream_t s) {
+                            float* z_f, hipStream_t s, float* disp_c, float* acc_c) {
     if (N <= 0) return hipSuccess;
     if (N > 0x7fffffffLL || S < 3) return hipErrorInvalidValue;
     const int M = S - 1;
@@ -800,7 +802,7 @@ hipError_t launch_train_mid(const float* raw, int C, const float* z_c, const flo
         raised[dev] = lds;
     }
     hipLaunchKernelGGL(train_mid_kernel, dim3((unsigned)N), dim3(64), lds, s, raw, C, z_c, rays_d, d_ld, noise, white_bkgd, S,
-                       rgb_c, w_c, u, n_samples, n_sort, z_f);
+                       rgb_c, w_c, u, n_samples, n_sort, z_f, disp_c, acc_c);
     return hipGetLastError();
 }
 
@@ -952,6 +954,62 @@ __global__ __launch_bounds__(64) void train_epilogue_kernel(const TrainEpilogue 
         }
         *e.ticket = 0u;      // for the next step (the prologue zeroes it as well)
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The taped route (nerf_train_forward / nerf_train_backward): train_epilogue_kernel cut at the loss, which is the caller's.
+// FORWARD: raw2outputs of the last pass for the caller (rgb, disp, acc) and the coarse colours copied out: one wave per ray.
+// BACKWARD: raw2outputs' backward of the last pass and - when there are two - the coarse one from the caller's gradients on
+// their outputs (composite_bwd_ray; the rgb-only function where only rgb carries one, so that a loss on the colours alone
+// gives what nerf_train_step gives), plus the caller's gradient on the returned raw: one wave per ray.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void train_fwd_epilogue_kernel(const TrainFwdEpilogue e) {
+    const int64_t ray = blockIdx.x;
+    const int lane = threadIdx.x;
+    composite_ray(ray, lane, e.raw_l, e.C_l, e.z_l, e.rays_d, e.d_ld, e.noise_l, e.white_bkgd, e.S_l, e.out_rgb, e.out_disp,
+                  e.out_acc, nullptr, nullptr);
+    if (e.rgb_c && e.out_rgb0 && lane < 3) e.out_rgb0[ray * 3 + lane] = e.rgb_c[ray * 3 + lane];
+}
+
+__device__ __forceinline__ void composite_bwd_caller(int64_t ray, int lane, float* Tsh, const float* raw, int C, const float* z,
+                                                     const float* rays_d, int d_ld, const float* noise, int white_bkgd, int S,
+                                                     float* d_raw, int dC, const float* g_rgb, const float* g_disp,
+                                                     const float* g_acc, const float* g_raw) {
+    const float g0 = g_rgb ? g_rgb[ray * 3 + 0] : 0.0f, g1 = g_rgb ? g_rgb[ray * 3 + 1] : 0.0f,
+                g2 = g_rgb ? g_rgb[ray * 3 + 2] : 0.0f;
+    if (!g_disp && !g_acc && !g_raw)
+        composite_bwd_ray(ray, lane, Tsh, raw, C, z, rays_d, d_ld, noise, white_bkgd, S, g0, g1, g2, d_raw, dC);
+    else
+        composite_bwd_ray<true>(ray, lane, Tsh, raw, C, z, rays_d, d_ld, noise, white_bkgd, S, g0, g1, g2, d_raw, dC,
+                                g_disp ? g_disp[ray] : 0.0f, g_acc ? g_acc[ray] : 0.0f, g_raw, C);
+}
+
+__global__ __launch_bounds__(64) void train_bwd_epilogue_kernel(const TrainBwdEpilogue e) {
+    extern __shared__ float Tsh[];
+    const int64_t ray = blockIdx.x;
+    const int lane = threadIdx.x;
+    composite_bwd_caller(ray, lane, Tsh, e.raw_l, e.C_l, e.z_l, e.rays_d, e.d_ld, e.noise_l, e.white_bkgd, e.S_l, e.d_raw_l,
+                         e.dC_l > 0 ? e.dC_l : e.C_l, e.g_rgb_l, e.g_disp_l, e.g_acc_l, e.g_raw_l);
+    if (e.raw_c) {
+        __syncthreads();      // (Tsh is reused)
+        composite_bwd_caller(ray, lane, Tsh, e.raw_c, e.C_c, e.z_c, e.rays_d, e.d_ld, e.noise_c, e.white_bkgd, e.S_c, e.d_raw_c,
+                             e.dC_c > 0 ? e.dC_c : e.C_c, e.g_rgb_c, e.g_disp_c, e.g_acc_c, nullptr);
+    }
+}
+
+hipError_t launch_train_fwd_epilogue(const TrainFwdEpilogue& e, hipStream_t s) {
+    if (e.N <= 0) return hipSuccess;
+    if (e.N > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(train_fwd_epilogue_kernel, dim3((unsigned)e.N), dim3(64), 0, s, e);
+    return hipGetLastError();
+}
+
+hipError_t launch_train_bwd_epilogue(const TrainBwdEpilogue& e, hipStream_t s) {
+    if (e.N <= 0) return hipSuccess;
+    if (e.N > 0x7fffffffLL) return hipErrorInvalidValue;
+    const int S = e.S_l > e.S_c ? e.S_l : e.S_c;
+    hipLaunchKernelGGL(train_bwd_epilogue_kernel, dim3((unsigned)e.N), dim3(64), (size_t)S * sizeof(float), s, e);
+    return hipGetLastError();
 }
 
 // (legacy glue: the same five numbers from the two losses the MSE kernels left)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Camera, FrameArgs, NerfArch, RenderArgs, TrainArgs, check
+from ._lib import Camera, FrameArgs, NerfArch, RenderArgs, TrainArgs, TrainBackwardArgs, TrainForwardArgs, check
 
 __all__ = [
     "NeRF", "get_embedder", "batchify", "run_network", "raw2outputs", "sample_pdf", "render_rays",
@@ -194,11 +194,13 @@ def _ptr(t):
 # ----------------------------------------------------------------------------------------------
 
 class NeRF:
-    """Forward-only stand-in for the reference ``NeRF`` ``nn.Module`` (nerf/nerf.py:8-111).
+    """Stand-in for the reference ``NeRF`` ``nn.Module`` (nerf/nerf.py:8-111) whose parameters live on the device.
 
     Same constructor; ``load_state_dict`` accepts the reference's state dict (torch tensors
     or numpy arrays, keys ``pts_linears.i.weight`` ...) and repacks it for the MFMA kernel.
     ``__call__(x)`` is ``forward`` on already-encoded rows ``[B, input_ch + input_ch_views]``.
+    After ``requires_grad_()`` the outputs of ``render`` / ``render_rays`` through this model carry a
+    ``grad_fn`` (with grad enabled): ``loss.backward()`` adds into :meth:`grad_dict`.
     """
 
     def __init__(self, D=8, W=256, input_ch=3, input_ch_views=3, output_ch=4, skips=[4], use_viewdirs=False,
@@ -211,6 +213,21 @@ class NeRF:
         self.ctx = get_context(device)
         self.slot = self.ctx.alloc_slot(self)
         self._sd = None
+        self._requires_grad = False
+        self._anchor = None       # a leaf that requires grad: what ties a taped render's outputs to this model
+
+    # -- autograd --------------------------------------------------------------------------
+    def requires_grad_(self, requires_grad=True):
+        """As ``nn.Module.requires_grad_``: with it on (and grad enabled), renders through this model are taped and
+        differentiable. Off by default."""
+        self._requires_grad = bool(requires_grad)
+        if self._requires_grad and self._anchor is None:
+            self._anchor = torch.zeros(0, device=self.ctx.device, requires_grad=True)
+        return self
+
+    @property
+    def requires_grad(self):
+        return self._requires_grad
 
     # -- state dict ------------------------------------------------------------------------
     def state_dict_keys(self):
@@ -287,7 +304,8 @@ class NeRF:
         return {k: torch.from_numpy(v.copy()) for k, v in self._sd.items()}
 
     def grad_dict(self):
-        """Gradients of the last training step, keyed like the state dict (``param.grad``)."""
+        """The gradients, keyed like the state dict (``param.grad``): those of the last ``train_on_batch``, or what
+        ``loss.backward()`` calls through taped renders have added up since ``Adam.zero_grad()``."""
         return {k: torch.from_numpy(v) for k, v in self._read_flat(self.ctx.lib.nerf_get_gradients).items()}
 
     def adam_state(self):
@@ -535,6 +553,28 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
 # render_rays (nerf.ipynb:359-492)
 # ----------------------------------------------------------------------------------------------
 
+def _render_randoms(ctx, N, Sc, Si, perturb, raw_noise_std, pytest):
+    """render_rays' random draws in the reference's order (t_rand, noise0, u, noise): each None where not drawn."""
+    o = dict(device=ctx.device, dtype=torch.float32)
+    t_rand = u = n1 = None
+    if perturb > 0.:
+        if pytest:                               # nerf.ipynb:439-442: np.random.seed(0) before each draw
+            np.random.seed(0)
+            t_rand = _dev(np.random.rand(N, Sc), ctx)
+        else:
+            t_rand = torch.rand((N, Sc), **o)
+    n0 = _noise((N, Sc), raw_noise_std, pytest, ctx)
+    if Si > 0:
+        if perturb > 0.:
+            if pytest:
+                np.random.seed(0)
+                u = _dev(np.random.rand(N, Si), ctx)
+            else:
+                u = torch.rand((N, Si), **o)
+        n1 = _noise((N, Sc + Si), raw_noise_std, pytest, ctx)
+    return t_rand, n0, u, n1
+
+
 def _render_rays_fused(ctx, ray_batch, net_c, net_f, N_samples, N_importance, retraw, lindisp, perturb,
                        white_bkgd, raw_noise_std, pytest, extras=None, z_vals_fine_in=None):
     N, stride = ray_batch.shape
@@ -546,33 +586,13 @@ def _render_rays_fused(ctx, ray_batch, net_c, net_f, N_samples, N_importance, re
     a.slot_coarse = net_c.slot
     a.slot_fine = net_f.slot if net_f is not None else -1
     a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
-    keep = []
     if perturb > 0.:
         a.perturb = 1
-        if pytest:                               # nerf.ipynb:439-442: np.random.seed(0) before each draw
-            np.random.seed(0)
-            t_rand = _dev(np.random.rand(N, Sc), ctx)
-        else:
-            t_rand = torch.rand((N, Sc), **o)
-        keep.append(t_rand)
-        a.t_rand = t_rand.data_ptr()
-    n0 = _noise((N, Sc), raw_noise_std, pytest, ctx)
-    if n0 is not None:
-        keep.append(n0)
-        a.noise0 = n0.data_ptr()
-    if Si > 0:
-        if perturb > 0.:
-            if pytest:
-                np.random.seed(0)
-                u = _dev(np.random.rand(N, Si), ctx)
-            else:
-                u = torch.rand((N, Si), **o)
-            keep.append(u)
-            a.u_rand = u.data_ptr()
-        n1 = _noise((N, Sc + Si), raw_noise_std, pytest, ctx)
-        if n1 is not None:
-            keep.append(n1)
-            a.noise = n1.data_ptr()
+    keep = []
+    for name, t in zip(("t_rand", "noise0", "u_rand", "noise"), _render_randoms(ctx, N, Sc, Si, perturb, raw_noise_std, pytest)):
+        if t is not None:
+            keep.append(t)
+            setattr(a, name, t.data_ptr())
     ret = {"rgb_map": torch.empty((N, 3), **o), "disp_map": torch.empty((N,), **o),
            "acc_map": torch.empty((N,), **o)}
     a.rgb_map, a.disp_map, a.acc_map = (ret[k].data_ptr() for k in ("rgb_map", "disp_map", "acc_map"))
@@ -605,6 +625,153 @@ def _render_rays_fused(ctx, ray_batch, net_c, net_f, N_samples, N_importance, re
     return ret
 
 
+# ----------------------------------------------------------------------------------------------
+# the taped route: render_rays with a grad_fn (nerf_train_forward / nerf_train_backward)
+# ----------------------------------------------------------------------------------------------
+
+def _wants_grad(net):
+    if isinstance(net, NeRF):
+        return net.requires_grad
+    params = getattr(net, "parameters", None)
+    if callable(params):
+        try:
+            return any(getattr(p, "requires_grad", False) for p in params())
+        except TypeError:
+            return False
+    return False
+
+
+def _grad_requested(network_fn, network_fine):
+    return torch.is_grad_enabled() and any(_wants_grad(n) for n in (network_fn, network_fine) if n is not None)
+
+
+def _taped(ray_batch, rays_need_grad, network_fn, network_fine, network_query_fn, N_importance):
+    """Whether a render_rays call takes the taped route: grad enabled, a network of the call requires grad, and the
+    query is this package's NetworkQuery over this package's models. Raises where a gradient is asked for that the
+    route cannot give."""
+    if not _grad_requested(network_fn, network_fine):
+        return False
+    nets = [n for n in (network_fn, network_fine) if n is not None]
+    if not all(isinstance(n, NeRF) for n in nets):
+        raise RuntimeError("render_rays: a network of this call requires grad but is not this package's NeRF; gradients "
+                           "flow only through the package's models (render under torch.no_grad() to render without them)")
+    has_dirs = ray_batch.shape[-1] > 8
+    if not (isinstance(network_query_fn, NetworkQuery) and all(network_query_fn.matches(n, has_dirs) for n in nets)):
+        raise RuntimeError("render_rays: the model requires grad, but network_query_fn is an opaque callable; the taped "
+                           "(differentiable) route needs the package's NetworkQuery (make_network_query_fn) over "
+                           "embedders and models that match it. Render under torch.no_grad() to use the callable.")
+    if (int(N_importance) > 0 and network_fine is not None and network_fine is not network_fn
+            and network_fn.requires_grad != network_fine.requires_grad):
+        # (the backward pass adds into both networks' gradients: a model that does not require grad must not get any)
+        raise RuntimeError("render_rays: only one of network_fn / network_fine requires grad; the taped route "
+                           "differentiates both passes, so call requires_grad_() on both models or on neither")
+    if rays_need_grad:
+        raise RuntimeError("render_rays: the rays require grad; gradients with respect to rays or camera poses are not "
+                           "supported (detach them)")
+    return True
+
+
+class _TapedCall:
+    """One taped render_rays call: its forward (nerf_train_forward) and, once, its backward (nerf_train_backward). It
+    holds no tensor once the forward has returned: the graph node keeps the call, and a reference from the call to the
+    outputs would close a cycle through the node that Python's collector cannot see, keeping every output alive."""
+
+    def __init__(self, ctx, a, outs):
+        self.ctx, self.a, self.outs, self.tape, self.done = ctx, a, outs, None, False
+
+    def forward(self):
+        tape = C.c_uint64(0)
+        self.a.tape = C.pointer(tape)
+        rc = self.ctx.lib.nerf_train_forward(self.ctx.handle, C.byref(self.a))
+        if rc == -4:      # NERF_E_NOMEM
+            msg = self.ctx.lib.nerf_last_error().decode("utf-8", "replace")
+            raise RuntimeError(f"nerf_mi355x error {rc}: {msg}. A taped render keeps every activation of all its rays at "
+                               "once; render under torch.no_grad() when no gradient is wanted.")
+        check(rc)
+        self.tape = tape.value
+        outs, self.outs = self.outs, None
+        return outs
+
+    def backward(self, grads):
+        if self.done:
+            raise RuntimeError("render_rays: backward through the same taped render a second time; its tape was "
+                               "consumed by the first (double backward and retain_graph are not supported)")
+        self.done = True
+        b = TrainBackwardArgs()
+        b.tape = self.tape
+        keep = []
+        for name, g in zip(("d_rgb", "d_disp", "d_acc", "d_rgb0", "d_disp0", "d_acc0", "d_raw"), grads):
+            if g is not None:
+                g = g.detach().to(device=self.ctx.device, dtype=torch.float32).contiguous()
+                keep.append(g)
+                setattr(b, name, g.data_ptr())
+        b.stream = self.ctx.stream().value
+        check(self.ctx.lib.nerf_train_backward(self.ctx.handle, C.byref(b)))
+
+
+class _TapedRender(torch.autograd.Function):
+    """rgb, disp, acc (, rgb0, disp0, acc0) (, raw) of one taped render_rays call; the inputs are the call and the
+    anchors of its models (leaves that require grad and receive none: the gradients go to the models' device buffers)."""
+
+    @staticmethod
+    def forward(fctx, call, *anchors):
+        fctx.set_materialize_grads(False)
+        fctx.call = call
+        fctx.n_anchors = len(anchors)
+        return call.forward()
+
+    @staticmethod
+    def backward(fctx, *grads):
+        grads = list(grads)
+        Si = fctx.call.a.N_importance
+        full = grads[:3] + (grads[3:6] if Si > 0 else [None, None, None]) + \
+            [grads[6 if Si > 0 else 3] if fctx.call.a.raw else None]
+        fctx.call.backward(full)
+        return (None,) * (1 + fctx.n_anchors)
+
+
+def _render_rays_taped(ctx, ray_batch, net_c, net_f, N_samples, N_importance, retraw, lindisp, perturb, white_bkgd,
+                       raw_noise_std, pytest, z_vals_fine_in=None):
+    """render_rays as one taped pass over all of ``ray_batch``: nerf_train_forward with the random draws of the fused
+    route, outputs tied to the models by a _TapedRender node."""
+    N, stride = ray_batch.shape
+    Sc, Si = int(N_samples), int(N_importance)
+    o = dict(device=ctx.device, dtype=torch.float32)
+    a = TrainForwardArgs()
+    a.rays, a.n_rays, a.ray_stride = ray_batch.data_ptr(), N, stride
+    a.N_samples, a.N_importance = Sc, Si
+    a.slot_coarse = net_c.slot
+    a.slot_fine = net_f.slot if (Si > 0 and net_f is not None) else -1
+    a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
+    if perturb > 0.:
+        a.perturb = 1
+    keep = [ray_batch]
+    for name, t in zip(("t_rand", "noise0", "u_rand", "noise"), _render_randoms(ctx, N, Sc, Si, perturb, raw_noise_std, pytest)):
+        if t is not None:
+            keep.append(t)
+            setattr(a, name, t.data_ptr())
+    outs = [torch.empty((N, 3), **o), torch.empty((N,), **o), torch.empty((N,), **o)]
+    a.rgb_map, a.disp_map, a.acc_map = (t.data_ptr() for t in outs)
+    if Si > 0:
+        outs += [torch.empty((N, 3), **o), torch.empty((N,), **o), torch.empty((N,), **o)]
+        a.rgb0, a.disp0, a.acc0 = (t.data_ptr() for t in outs[3:6])
+    if retraw:
+        last = net_f if (Si > 0 and net_f is not None) else net_c
+        outs.append(torch.empty((N, Sc + Si, last.out_channels), **o))
+        a.raw = outs[-1].data_ptr()
+    if z_vals_fine_in is not None and Si > 0:
+        zin = _dev(z_vals_fine_in, ctx).reshape(N, Sc + Si)
+        keep.append(zin)
+        a.z_vals_fine_in = zin.data_ptr()
+    a.stream = ctx.stream().value
+    anchors = [n._anchor for n in (net_c, net_f) if n is not None and n.requires_grad]
+    res = _TapedRender.apply(_TapedCall(ctx, a, tuple(outs)), *anchors)
+    names = ["rgb_map", "disp_map", "acc_map"] + (["rgb0", "disp0", "acc0"] if Si > 0 else []) + (["raw"] if retraw else [])
+    ret = dict(zip(names, res))
+    return {k: ret[k] for k in ["rgb_map", "disp_map", "acc_map"] + (["raw"] if retraw else []) +
+            (["rgb0", "disp0", "acc0"] if Si > 0 else [])}
+
+
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
                 pytest=False, _extras=None, _z_vals_fine=None):
@@ -615,16 +782,24 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     compositing, resampling) runs inside one C call with no host synchronisation. Any other
     ``network_query_fn`` is honoured as an opaque callable and the stages are composed
     around it as in the reference, each stage still a HIP kernel.
+
+    With grad enabled and a model that requires grad (``NeRF.requires_grad_()``) the call is taped: the outputs
+    (rgb_map, disp_map, acc_map, rgb0, disp0, acc0, raw) carry a ``grad_fn`` and ``loss.backward()`` adds the models'
+    gradients into :meth:`NeRF.grad_dict`. That route returns no ``z_std``.
     """
     if not isinstance(network_fn, NeRF):
         raise TypeError("render_rays needs this package's NeRF for network_fn (no PyTorch fallback exists)")
     ctx = network_fn.ctx
     _peek_precision(ctx, "render_rays")
+    rays_need_grad = torch.is_tensor(ray_batch) and ray_batch.requires_grad
     ray_batch = _dev(ray_batch, ctx)
     if ray_batch.dim() != 2 or ray_batch.shape[-1] not in (8, 11):
         raise RuntimeError(f"ray_batch must be [N, 8|11], got {tuple(ray_batch.shape)}")
     has_dirs = ray_batch.shape[-1] > 8
     perturb = float(perturb)
+    if _taped(ray_batch, rays_need_grad, network_fn, network_fine, network_query_fn, N_importance):
+        return _render_rays_taped(ctx, ray_batch, network_fn, network_fine, N_samples, N_importance, retraw, lindisp,
+                                  perturb, white_bkgd, raw_noise_std, pytest, _z_vals_fine)
     fused = (isinstance(network_query_fn, NetworkQuery) and network_query_fn.matches(network_fn, has_dirs)
              and (network_fine is None or network_query_fn.matches(network_fine, has_dirs)))
     if fused:
@@ -703,6 +878,10 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
         return {k: torch.cat(all_ret[k], dim=0) for k in all_ret}
 
     net = kwargs.get('network_fn')
+    if _grad_requested(net, kwargs.get('network_fine')):
+        # the taped route (render_rays): all rays in one pass - in the reference `chunk` only bounds memory, so the
+        # results do not depend on it - and the training path's own precision guard
+        return render_rays(rays_flat, **kwargs)
     ctx = getattr(net, 'ctx', None)
     if ctx is None or ctx.get_precision() != "f16x2":
         return run()
@@ -908,7 +1087,7 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     With ``c2w`` the rays are generated on the GPU (:func:`generate_rays`); a ``rays`` tuple is
     packed with torch ops exactly as the reference does."""
     model_device = next(kwargs['network_fn'].parameters()).device
-    if c2w is not None and _frame_call_applies(kwargs) and \
+    if c2w is not None and _frame_call_applies(kwargs) and not _grad_requested(kwargs['network_fn'], kwargs.get('network_fine')) and \
             kwargs['network_query_fn'].matches(kwargs['network_fn'], bool(use_viewdirs)):
         net = kwargs['network_fn']
         cam = _camera(H, W, K, c2w, ndc, near, far, use_viewdirs, c2w_staticcam)
@@ -950,7 +1129,8 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     for i, c2w in enumerate(render_poses):
         print(i, time.time() - t)
         t = time.time()
-        rgb, disp, acc, _ = render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)
+        with torch.no_grad():      # (always untaped: a frame is far more rays than a tape holds)
+            rgb, disp, acc, _ = render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)
         rgbs.append(rgb.cpu().numpy())
         disps.append(disp.cpu().numpy())
         if i == 0:
@@ -1065,8 +1245,9 @@ def create_nerf(args, device=None):
 class Adam:
     """Stand-in for ``torch.optim.Adam(params=grad_vars, lr=args.lrate, betas=(0.9, 0.999))``
     (nerf.ipynb:905) over this package's models: the moments live next to the master weights on the
-    device and the update runs inside :func:`train_on_batch`. ``param_groups[0]['lr']`` is writable so
-    the reference's decay loop (nerf.ipynb:1278-1282) works unchanged."""
+    device and the update runs inside :func:`train_on_batch`, or - after ``loss.backward()`` through taped
+    renders - in :meth:`step`. ``param_groups[0]['lr']`` is writable so the reference's decay loop
+    (nerf.ipynb:1278-1282) works unchanged."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         self.models = [m for m in params if isinstance(m, NeRF)]
@@ -1076,7 +1257,21 @@ class Adam:
         self.steps = 0
 
     def zero_grad(self):
-        pass                      # gradients are overwritten by every backward pass
+        """Zeroes the models' gradients (``loss.backward()`` adds into them; ``train_on_batch`` overwrites them)."""
+        for m in self.models:
+            check(m.ctx.lib.nerf_zero_grad(m.ctx.handle, m.slot, m.ctx.stream()))
+
+    def step(self):
+        """``optimizer.step()``: Adam with ``param_groups[0]`` on the models' gradients - the update ``train_on_batch``
+        applies after its backward pass - and one more step in ``steps`` (state_dict, checkpoints)."""
+        g = self.param_groups[0]
+        ctx = self.models[0].ctx
+        if any(m.ctx is not ctx for m in self.models):
+            raise RuntimeError("Adam.step: the models live on different devices")
+        slots = (C.c_int32 * len(self.models))(*[m.slot for m in self.models])
+        check(ctx.lib.nerf_adam_step(ctx.handle, slots, len(self.models), g['lr'], g['betas'][0], g['betas'][1], g['eps'],
+                                     self.steps + 1, ctx.stream()))
+        self.steps += 1      # (only once the step has been taken)
 
     def state_dict(self):
         """``torch.optim.Adam.state_dict()`` layout over ``list(model.parameters()) + list(model_fine.parameters())``
