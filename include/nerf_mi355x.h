@@ -527,6 +527,63 @@ typedef struct nerf_mc_args {
 
 int nerf_marching_cubes(nerf_ctx* ctx, const nerf_mc_args* args);
 
+/* Occupancy grid --------------------------------------------------------------------------------
+ * Rendering that skips the network at samples in empty space. A grid is the axis-aligned box [c1, c2] cut into
+ * (X-1) x (Y-1) x (Z-1) CELLS by the nodes of the lattice nerf_density_grid evaluates (reso = nodes per axis), one bit per
+ * cell. It is a snapshot of the networks it was built from: nothing invalidates it when the weights change.
+ *
+ * Rendering with a grid is the reference's render_rays with a masked network, in the coarse pass (S = N_samples) and in
+ * the fine pass (S = N_samples + N_importance) alike:
+ *     keep[n, i] = (i == S - 1) or occupied(cell(pts[n, i])) or (pts[n, i] outside the box and outside == NERF_OCC_EVALUATE)
+ *     raw[n, i]  = network(pts[n, i], viewdir[n]) if keep[n, i], else 0 in every channel
+ * and everything else unchanged (raw2outputs, sample_pdf on the masked coarse weights, the returned raw shows the zeros).
+ * Two rules are not optional:
+ *   - the LAST sample of every ray is always evaluated: its dists is 1e10 (nerf.ipynb:300), so skipping it where sigma is a
+ *     hair above zero would turn a whole pixel from the scene's colour to the background;
+ *   - skipped samples are ZEROS in raw, not absent: relu(0) = 0, alpha = 0, weight = 0, as for any empty sample. Where no
+ *     skipped sample has sigma > 0 the masked render equals the dense one.
+ * The cell rule: pts = rays_o + rays_d * z, product and sum each rounded to fp32. With c1, c2 rounded to fp32 and
+ * cell = (c2 - c1) / (reso - 1) (fp32, each operation rounded), a point is inside the box iff c1 <= p <= c2 on every axis,
+ * and its cell index on an axis is min(floor((p - c1) / cell), reso - 2), subtraction and division each rounded to fp32:
+ * points on an upper face belong to the last cell. A NaN or infinite position counts as occupied (the reference's NaN comes
+ * out). A cell is occupied when, in any of the n_lattices sigma lattices ([dev] [X, Y, Z] as nerf_density_grid writes them),
+ * sigma at any of its 8 corner nodes is > threshold or NaN, or when its byte of cell_mask ([dev] [X-1, Y-1, Z-1], optional)
+ * is non-zero; the set is then grown `dilate` times by one cell in all 26 directions. The lattice only samples the field: a
+ * grid is not guaranteed conservative.
+ *
+ * The kept points of a pass are listed in increasing order by three stream-ordered launches (no atomics, no workgroup waits
+ * for another), and the fused kernel runs over that list: no host synchronisation inside a frame, and two renders of the
+ * same input are bit-identical. In NERF_PRECISION_F32 a kept point's raw row is bit-identical to the dense render's.
+ * nerf_render_rays_occ / nerf_render_frame_occ are nerf_render_rays / nerf_render_frame with a grid (NULL: the plain call);
+ * the frame's precision guard re-renders with the grid too. Counters of evaluated / total points accumulate on the device
+ * and follow every call to a pinned host mirror; nerf_occupancy_stats waits for the device and reads them.
+ * nerf_occupancy_create synchronises `stream` (it returns with the count of occupied cells known). reso[a] in [2, 1024].
+ * A grid belongs to the context it was created on: use it with that context only, and destroy it before the context.
+ * Training calls and nerf_render_shard take no grid. */
+#define NERF_OCC_EVALUATE 0       /* points outside the box are evaluated                                          */
+#define NERF_OCC_EMPTY 1          /* points outside the box are skipped                                            */
+typedef struct nerf_occupancy nerf_occupancy;
+typedef struct nerf_occupancy_args {
+    double c1[3], c2[3];        /* box corners                                                                   */
+    int32_t reso[3];            /* nodes per axis (cells = reso - 1)                                             */
+    int32_t n_lattices;         /* 0..8 (0 only with cell_mask)                                                  */
+    const float* const* sigma;  /* [host] n_lattices pointers to [dev] [X, Y, Z]                                 */
+    const uint8_t* cell_mask;   /* [dev] [X-1, Y-1, Z-1] or NULL                                                 */
+    float threshold;
+    int32_t dilate;             /* >= 0                                                                          */
+    int32_t outside;            /* NERF_OCC_*                                                                    */
+    void* stream;
+} nerf_occupancy_args;
+
+int nerf_occupancy_create(nerf_ctx* ctx, const nerf_occupancy_args* args, nerf_occupancy** out);
+void nerf_occupancy_destroy(nerf_occupancy* occ);
+/* the cells as bytes (0 / 1) into mask [dev] [X-1, Y-1, Z-1] (NULL: not wanted) and their count */
+int nerf_occupancy_cells(const nerf_occupancy* occ, uint8_t* mask, int64_t* n_occupied /*[host]*/, void* stream);
+/* points the network evaluated / points of the passes rendered with this grid since the last reset */
+int nerf_occupancy_stats(nerf_occupancy* occ, int64_t* evaluated /*[host]*/, int64_t* total /*[host]*/, int reset);
+int nerf_render_rays_occ(nerf_ctx* ctx, const nerf_render_args* args, const nerf_occupancy* occ);
+int nerf_render_frame_occ(nerf_ctx* ctx, const nerf_frame_args* args, const nerf_occupancy* occ);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,5 +15,6 @@ from .datasets import load_blender_data, load_llff_data, read_png  # noqa: F401
 from .sharded import ensure_ipc_env, gather_frame, render_sharded, shard_bounds  # noqa: F401
 from .batching import RayBatcher  # noqa: F401
 from .mesh import density_grid, marching_cubes, marching_cubes_volume, save_obj  # noqa: F401
+from .occupancy import OccupancyGrid  # noqa: F401
 
 __version__ = "0.1.0"

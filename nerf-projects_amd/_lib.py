@@ -22,10 +22,12 @@ EXPORTS = (
     "nerf_shard_bounds", "nerf_render_shard", "nerf_precision_peek", "nerf_precision_check",
     "nerf_precision_detail", "nerf_profile_read_train", "nerf_set_render_precision",
     "nerf_pack_rays", "nerf_density_grid", "nerf_marching_cubes", "nerf_train_forward", "nerf_train_backward",
-    "nerf_zero_grad", "nerf_adam_step",
+    "nerf_zero_grad", "nerf_adam_step", "nerf_occupancy_create", "nerf_occupancy_destroy", "nerf_occupancy_cells",
+    "nerf_occupancy_stats", "nerf_render_rays_occ", "nerf_render_frame_occ",
 )
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
 NERF_GUARD_OFF, NERF_GUARD_REPORT, NERF_GUARD_FALLBACK = 0, 1, 2
+NERF_OCC_EVALUATE, NERF_OCC_EMPTY = 0, 1
 
 
 class NerfArch(C.Structure):
@@ -104,6 +106,12 @@ class McArgs(C.Structure):
     _fields_ = [("volume", _FP), ("reso", C.c_int32 * 3), ("iso", C.c_float), ("vertices", _FP),
                 ("vertex_capacity", C.c_int64), ("triangles", _FP), ("triangle_capacity", C.c_int64),
                 ("n_vertices", C.POINTER(C.c_int64)), ("n_triangles", C.POINTER(C.c_int64)), ("stream", C.c_void_p)]
+
+
+class OccupancyArgs(C.Structure):
+    _fields_ = [("c1", C.c_double * 3), ("c2", C.c_double * 3), ("reso", C.c_int32 * 3), ("n_lattices", C.c_int32),
+                ("sigma", C.POINTER(C.c_void_p)), ("cell_mask", _FP), ("threshold", C.c_float), ("dilate", C.c_int32),
+                ("outside", C.c_int32), ("stream", C.c_void_p)]
 
 
 _lib = None
@@ -210,6 +218,18 @@ def load():
     lib.nerf_density_grid.argtypes = [vp, C.POINTER(GridArgs)]
     lib.nerf_marching_cubes.restype = i32
     lib.nerf_marching_cubes.argtypes = [vp, C.POINTER(McArgs)]
+    lib.nerf_occupancy_create.restype = i32
+    lib.nerf_occupancy_create.argtypes = [vp, C.POINTER(OccupancyArgs), C.POINTER(vp)]
+    lib.nerf_occupancy_destroy.restype = None
+    lib.nerf_occupancy_destroy.argtypes = [vp]
+    lib.nerf_occupancy_cells.restype = i32
+    lib.nerf_occupancy_cells.argtypes = [vp, vp, C.POINTER(i64), vp]
+    lib.nerf_occupancy_stats.restype = i32
+    lib.nerf_occupancy_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), i32]
+    lib.nerf_render_rays_occ.restype = i32
+    lib.nerf_render_rays_occ.argtypes = [vp, C.POINTER(RenderArgs), vp]
+    lib.nerf_render_frame_occ.restype = i32
+    lib.nerf_render_frame_occ.argtypes = [vp, C.POINTER(FrameArgs), vp]
     _lib = lib
     return lib
 

@@ -609,7 +609,20 @@ int nerf_resample(nerf_ctx* c, const float* z_vals, const float* weights, const 
     return NERF_OK;
 }
 
-static int render_rays_locked(nerf_ctx* c, const nerf_render_args* r) {
+static hipError_t mirror_occ_stats(const nerf_occupancy* occ, hipStream_t s) {
+    if (!occ || !occ->h_stats) return hipSuccess;
+    return hipMemcpyAsync(occ->h_stats, occ->d_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+}
+
+static int check_occ(const nerf_ctx* c, const nerf_occupancy* occ, const char* who) {
+    if (occ && occ->ctx != c) {
+        set_error("%s: the occupancy grid belongs to another context", who);
+        return NERF_E_INVALID;
+    }
+    return NERF_OK;
+}
+
+static int render_rays_locked(nerf_ctx* c, const nerf_render_args* r, const nerf_occupancy* occ = nullptr) {
     if (!c || !r || (!r->rays && r->n_rays != 0) || r->n_rays < 0) {
         set_error("nerf_render_rays: NULL argument");
         return NERF_E_INVALID;
@@ -664,10 +677,37 @@ static int render_rays_locked(nerf_ctx* c, const nerf_render_args* r) {
 
     const size_t nN = (size_t)N;
     const bool raw_is_coarse = Si == 0;
+    // with a grid: the scratch of classify + compact, sized for the larger pass and reused by the second one (stream order)
+    const size_t occ_pts = occ ? nN * (Si ? Sf : Sc) : 0, occ_nb = occ ? (size_t)occ_blocks((int64_t)occ_pts) : 0;
     int rc = ensure_workspace(c, arena_bytes({nN * Sc, nN * Sc * Cc, nN * Sc, nN * (Si ? Si : 1),
-                                              nN * (Si ? Sf : 1), nN * (Si ? (size_t)Sf * Cf : 1)}));
+                                              nN * (Si ? Sf : 1), nN * (Si ? (size_t)Sf * Cf : 1),
+                                              occ_nb * 32, occ_nb + 1, occ_pts + 1, 64}));
     if (rc != NERF_OK) return rc;
     Arena ar(c->ws);
+    OccCompact oc{};
+    if (occ) {
+        oc.g = occ->g;
+        oc.rays = r->rays;
+        oc.ray_ld = r->ray_stride;
+        oc.N = N;
+        oc.keep_words = (unsigned long long*)ar.take(occ_nb * 32);
+        oc.block_counts = (int*)ar.take(occ_nb + 1);
+        oc.index = (int*)ar.take(occ_pts + 1);
+        oc.count = (int*)ar.take(64);
+        oc.stats = occ->d_stats;
+    }
+    // one pass's network evaluation: every point, or (with a grid) classify, compact and the indexed launch
+    auto evaluate = [&](MlpLaunch& m, const PackedNet& net, int S, int C) -> int {
+        if (!occ) return run_mlp(c, m, net, kInputRays, s);
+        oc.z = m.z_vals;
+        oc.S = S;
+        oc.raw = m.out;
+        oc.C = C;
+        HIP_TRY(launch_occ_compact(oc, s));
+        m.index = oc.index;
+        m.index_count = oc.count;
+        return run_mlp(c, m, net, kInputRaysIndexed, s);
+    };
     float* z_c = r->z_vals_coarse ? r->z_vals_coarse : ar.take(nN * Sc);
     float* raw_c = (raw_is_coarse && r->raw) ? r->raw : ar.take(nN * Sc * Cc);
     float* w_c = r->weights_coarse ? r->weights_coarse : ar.take(nN * Sc);
@@ -680,7 +720,7 @@ static int render_rays_locked(nerf_ctx* c, const nerf_render_args* r) {
     a.ray_ld = r->ray_stride;
     a.z_vals = z_c;
     a.out = raw_c;
-    rc = run_mlp(c, a, *nc, kInputRays, s);
+    rc = evaluate(a, *nc, Sc, Cc);
     if (rc != NERF_OK) return rc;
     HIP_TRY(launch_composite(raw_c, Cc, z_c, r->rays + 3, r->ray_stride, r->noise0, r->white_bkgd, N, Sc,
                              Si ? r->rgb0 : r->rgb_map, Si ? r->disp0 : r->disp_map, Si ? r->acc0 : r->acc_map, w_c,
@@ -707,25 +747,29 @@ static int render_rays_locked(nerf_ctx* c, const nerf_render_args* r) {
     b.ray_ld = r->ray_stride;
     b.z_vals = z_f;
     b.out = raw_f;
-    rc = run_mlp(c, b, *nf, kInputRays, s);
+    rc = evaluate(b, *nf, Sf, Cf);
     if (rc != NERF_OK) return rc;
     HIP_TRY(launch_composite(raw_f, Cf, z_f, r->rays + 3, r->ray_stride, r->noise, r->white_bkgd, N, Sf, r->rgb_map,
                              r->disp_map, r->acc_map, r->weights_fine, r->depth_map, s));
     return NERF_OK;
 }
 
-int nerf_render_rays(nerf_ctx* c, const nerf_render_args* r) {
+int nerf_render_rays_occ(nerf_ctx* c, const nerf_render_args* r, const nerf_occupancy* occ) {
     if (!c || !r) {
         set_error("nerf_render_rays: NULL argument");
         return NERF_E_INVALID;
     }
+    if (check_occ(c, occ, "nerf_render_rays_occ") != NERF_OK) return NERF_E_INVALID;
     DeviceGuard g(c->device);
     ScratchScope scope(c, (hipStream_t)r->stream);
     HIP_TRY(scope.status);
-    const int rc = render_rays_locked(c, r);
+    const int rc = render_rays_locked(c, r, occ);
     if (rc == NERF_OK) HIP_TRY(mirror_loose(c, (hipStream_t)r->stream));
+    if (rc == NERF_OK) HIP_TRY(mirror_occ_stats(occ, (hipStream_t)r->stream));
     return rc;
 }
+
+int nerf_render_rays(nerf_ctx* c, const nerf_render_args* r) { return nerf_render_rays_occ(c, r, nullptr); }
 
 int nerf_generate_rays(nerf_ctx* c, const nerf_camera* cam, int64_t first_pixel, int64_t n_pixels, float* rays,
                        void* stream) {
@@ -768,11 +812,14 @@ int nerf_pack_rays(nerf_ctx* c, const nerf_camera* cam, const float* rays_o, int
     return NERF_OK;
 }
 
-int nerf_render_frame(nerf_ctx* c, const nerf_frame_args* f) {
+int nerf_render_frame(nerf_ctx* c, const nerf_frame_args* f) { return nerf_render_frame_occ(c, f, nullptr); }
+
+int nerf_render_frame_occ(nerf_ctx* c, const nerf_frame_args* f, const nerf_occupancy* occ) {
     if (!c || !f || f->first_pixel < 0 || f->n_pixels < 0) {
         set_error("nerf_render_frame: invalid argument");
         return NERF_E_INVALID;
     }
+    if (check_occ(c, occ, "nerf_render_frame_occ") != NERF_OK) return NERF_E_INVALID;
     if (f->cam.H <= 0 || f->cam.W <= 0 || f->first_pixel + f->n_pixels > (int64_t)f->cam.H * f->cam.W) {
         set_error("nerf_render_frame: pixels [%lld, %lld) outside the %dx%d image", (long long)f->first_pixel,
                   (long long)(f->first_pixel + f->n_pixels), f->cam.H, f->cam.W);
@@ -825,10 +872,10 @@ int nerf_render_frame(nerf_ctx* c, const nerf_frame_args* f) {
         r.acc0 = f->acc0 ? f->acc0 + off : nullptr;
         r.z_std = f->z_std ? f->z_std + off : nullptr;
         r.stream = f->stream;
-        const int rc = render_rays_locked(c, &r);
+        const int rc = render_rays_locked(c, &r, occ);
         if (rc != NERF_OK) return rc;
     }
-    return NERF_OK;
+    return mirror_occ_stats(occ, s) == hipSuccess ? NERF_OK : NERF_E_HIP;
     };
     int rc = body();
     if (rc != NERF_OK) return rc;
@@ -1116,6 +1163,124 @@ int nerf_marching_cubes(nerf_ctx* c, const nerf_mc_args* m) {
         return NERF_E_INVALID;
     }
     HIP_TRY(launch_mc_emit(a, c->ws, s));
+    return NERF_OK;
+}
+
+// ---- occupancy grid -------------------------------------------------------------------------------------------------
+
+void nerf_occupancy_destroy(nerf_occupancy* occ) {
+    if (!occ) return;
+    if (occ->ctx) {
+        DeviceGuard g(occ->ctx->device);
+        (void)hipDeviceSynchronize();
+        if (occ->d_bits) (void)hipFree(occ->d_bits);
+        if (occ->d_stats) (void)hipFree(occ->d_stats);
+        if (occ->h_stats) (void)hipHostFree(occ->h_stats);
+    }
+    delete occ;
+}
+
+int nerf_occupancy_create(nerf_ctx* c, const nerf_occupancy_args* a, nerf_occupancy** out) {
+    if (!c || !a || !out) {
+        set_error("nerf_occupancy_create: NULL argument");
+        return NERF_E_INVALID;
+    }
+    *out = nullptr;
+    for (int k = 0; k < 3; ++k) {
+        if (a->reso[k] < 2 || a->reso[k] > 1024) {
+            set_error("nerf_occupancy_create: reso[%d] = %d outside [2, 1024]", k, a->reso[k]);
+            return NERF_E_INVALID;
+        }
+        if (!(std::isfinite(a->c1[k]) && std::isfinite(a->c2[k]) && (float)a->c2[k] > (float)a->c1[k])) {
+            set_error("nerf_occupancy_create: axis %d: c2 = %g must be finite and greater than c1 = %g", k, a->c2[k], a->c1[k]);
+            return NERF_E_INVALID;
+        }
+    }
+    if (a->n_lattices < 0 || a->n_lattices > 8 || (a->n_lattices > 0 && !a->sigma) || (a->n_lattices == 0 && !a->cell_mask)) {
+        set_error("nerf_occupancy_create: 1..8 sigma lattices or a cell mask are required (n_lattices = %d)", a->n_lattices);
+        return NERF_E_INVALID;
+    }
+    for (int l = 0; l < a->n_lattices; ++l)
+        if (!a->sigma[l]) {
+            set_error("nerf_occupancy_create: sigma[%d] is NULL", l);
+            return NERF_E_INVALID;
+        }
+    if (a->dilate < 0 || a->dilate > 1024 || (a->outside != NERF_OCC_EVALUATE && a->outside != NERF_OCC_EMPTY) ||
+        std::isnan(a->threshold)) {
+        set_error("nerf_occupancy_create: dilate = %d must be in [0, 1024], outside = %d a NERF_OCC_* value, threshold not NaN",
+                  a->dilate, a->outside);
+        return NERF_E_INVALID;
+    }
+    DeviceGuard dg(c->device);
+    hipStream_t s = (hipStream_t)a->stream;
+    nerf_occupancy* o = new (std::nothrow) nerf_occupancy();
+    if (!o) return NERF_E_NOMEM;
+    o->ctx = c;
+    OccGrid& g = o->g;
+    size_t cells = 1;
+    for (int k = 0; k < 3; ++k) {
+        g.nc[k] = a->reso[k] - 1;
+        g.c1[k] = (float)a->c1[k];
+        g.c2[k] = (float)a->c2[k];
+        g.cell[k] = (g.c2[k] - g.c1[k]) / (float)g.nc[k];
+        cells *= (size_t)g.nc[k];
+    }
+    g.wz = (g.nc[2] + 31) / 32;
+    g.outside_keep = a->outside == NERF_OCC_EVALUATE;
+    const size_t words = (size_t)g.nc[0] * g.nc[1] * g.wz;
+    uint8_t* tmp = nullptr;
+    unsigned long long* d_n = nullptr;
+    hipError_t e = hipMalloc((void**)&o->d_bits, words * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&o->d_stats, 3 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(o->d_stats, 0, 3 * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&o->h_stats, 2 * sizeof(unsigned long long), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&tmp, 2 * cells);
+    unsigned long long n_occ = 0;
+    if (e == hipSuccess) {
+        o->h_stats[0] = o->h_stats[1] = 0;
+        d_n = o->d_stats + 2;
+        g.bits = o->d_bits;
+        e = launch_occ_build(a->sigma, a->n_lattices, a->cell_mask, g.nc, a->threshold, a->dilate, tmp, tmp + cells, o->d_bits,
+                             d_n, s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&n_occ, d_n, sizeof(n_occ), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (tmp) (void)hipFree(tmp);
+    if (e != hipSuccess) {
+        set_error("nerf_occupancy_create: %s", hipGetErrorString(e));
+        nerf_occupancy_destroy(o);
+        return NERF_E_HIP;
+    }
+    o->n_occupied = (int64_t)n_occ;
+    *out = o;
+    return NERF_OK;
+}
+
+int nerf_occupancy_cells(const nerf_occupancy* occ, uint8_t* mask, int64_t* n_occupied, void* stream) {
+    if (!occ) {
+        set_error("nerf_occupancy_cells: NULL grid");
+        return NERF_E_INVALID;
+    }
+    if (n_occupied) *n_occupied = occ->n_occupied;
+    if (!mask) return NERF_OK;
+    DeviceGuard dg(occ->ctx->device);
+    HIP_TRY(launch_occ_unpack(occ->d_bits, occ->g.nc, mask, (hipStream_t)stream));
+    return NERF_OK;
+}
+
+int nerf_occupancy_stats(nerf_occupancy* occ, int64_t* evaluated, int64_t* total, int reset) {
+    if (!occ) {
+        set_error("nerf_occupancy_stats: NULL grid");
+        return NERF_E_INVALID;
+    }
+    DeviceGuard dg(occ->ctx->device);
+    HIP_TRY(hipDeviceSynchronize());      // (the mirror was copied behind every call: it is current now)
+    if (evaluated) *evaluated = (int64_t)((volatile unsigned long long*)occ->h_stats)[0];
+    if (total) *total = (int64_t)((volatile unsigned long long*)occ->h_stats)[1];
+    if (reset) {
+        HIP_TRY(hipMemset(occ->d_stats, 0, 2 * sizeof(unsigned long long)));
+        occ->h_stats[0] = occ->h_stats[1] = 0;
+    }
     return NERF_OK;
 }
 

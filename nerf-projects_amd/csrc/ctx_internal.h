@@ -74,6 +74,16 @@ struct nerf_ctx {
     bool tape_live = false;
 };
 
+// An occupancy grid (nerf_mi355x.h, "Occupancy grid"): the packed cells and the counters of the passes rendered with it.
+struct nerf_occupancy {
+    nerf_ctx* ctx = nullptr;
+    nerf::OccGrid g{};                       // g.bits = d_bits
+    uint32_t* d_bits = nullptr;
+    unsigned long long* d_stats = nullptr;   // [2] evaluated, total points (device; the scan launch of every pass adds to them)
+    unsigned long long* h_stats = nullptr;   // pinned mirror, copied behind every render call
+    int64_t n_occupied = 0;
+};
+
 namespace nerf {
 
 hipError_t mirror_loose(nerf_ctx* c, hipStream_t s);     // api.cpp: the precision guard's counter mirror

@@ -131,6 +131,7 @@ __device__ __forceinline__ void load_inputs(const MlpLaunch& a, int64_t pt, int 
         encode_point<WANT_XYZ, WANT_DIR>(p, d, h, a.use_viewdirs != 0, x0, x1, dd);
         return;
     }
+    // (kInputRays and kInputRaysIndexed: the caller has already replaced an indexed slot by the point it lists)
     const int64_t ray = pt / a.samples_per_ray;
     if (MODE == kInputPoints) {
         p[0] = a.pts[pt * 3 + 0];

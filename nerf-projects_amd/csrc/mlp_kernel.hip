@@ -352,13 +352,18 @@ void nerf_mlp_kernel(const MlpLaunch a) {
     // Persistent workgroup: one per CU, walking 128-point tiles with stride gridDim.x. The weight
     // ring never drains between tiles: the tail of one tile's stream prefetches the head of the
     // next (prefetch wraps modulo n_chunks), and the bias block stays in LDS.
-    const int64_t n_tiles = (a.n_points + kPointsPerGroup - 1) / kPointsPerGroup;
+    // kInputRaysIndexed: the tile loop runs over the compacted list, whose length lives on the device; a workgroup without
+    // a tile falls through
+    int64_t n_live = a.n_points;
+    if constexpr (MODE == kInputRaysIndexed) n_live = __builtin_amdgcn_readfirstlane(*a.index_count);
+    const int64_t n_tiles = (n_live + kPointsPerGroup - 1) / kPointsPerGroup;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     pipe.c = 0;
     const int64_t tile0 = tile * kPointsPerGroup + wave * kPointsPerWave;
     const int64_t pt_raw = tile0 + (lane & 31);
-    const int64_t pt = pt_raw < a.n_points ? pt_raw : a.n_points - 1;   // clamp: padded lanes recompute the last point
-    const bool live = pt_raw < a.n_points;
+    int64_t pt = pt_raw < n_live ? pt_raw : n_live - 1;   // clamp: padded lanes recompute the last point
+    if constexpr (MODE == kInputRaysIndexed) pt = a.index[pt];      // the listed point replaces the slot: inputs, output row
+    const bool live = pt_raw < n_live;
 
     f32x16 x0, x1, dd;
     load_inputs<MODE>(a, pt, h, x0, x1, dd);
@@ -759,8 +764,9 @@ hipError_t launch_mlp(const MlpLaunch& a, int mode, hipStream_t s) {
     }
     const dim3 grid((unsigned)(tiles < n_cu[dev] ? tiles : n_cu[dev])), block(256);
     const size_t lds = kBiasLdsBytes + kRing * kChunkBytes;
-    static bool raised[64][5] = {};
-    if (mode < 0 || mode > 3) return hipErrorInvalidValue;
+    static bool raised[64][6] = {};
+    if (mode < 0 || mode > 4) return hipErrorInvalidValue;
+    if (mode == kInputRaysIndexed && (a.store || !a.index || !a.index_count)) return hipErrorInvalidValue;
     if (a.store && (mode != kInputRays || a.n_points > (int64_t)1 << 22)) return hipErrorInvalidValue;   // training forward: ray records; 32-bit element offsets in store_tiles
     if (a.store) {   // the hooks inside the chunk loop are unconditional 16-byte stores (RowRef)
         bool rows_ok = !a.use_viewdirs || (training_rows_ok(a.st.feat, a.st.feat_ld) && training_rows_ok(a.st.hv, a.st.hv_ld));
@@ -768,11 +774,11 @@ hipError_t launch_mlp(const MlpLaunch& a, int mode, hipStream_t s) {
         if (!rows_ok) return hipErrorInvalidValue;
     }
     typedef void (*kernel_t)(const MlpLaunch);
-    static const kernel_t table[5] = {nerf_mlp_kernel<kInputEmbedded>, nerf_mlp_kernel<kInputPoints>,
+    static const kernel_t table[6] = {nerf_mlp_kernel<kInputEmbedded>, nerf_mlp_kernel<kInputPoints>,
                                       nerf_mlp_kernel<kInputRays>, nerf_mlp_kernel<kInputRays, true>,
-                                      nerf_mlp_kernel<kInputLattice>};
+                                      nerf_mlp_kernel<kInputLattice>, nerf_mlp_kernel<kInputRaysIndexed>};
     static_assert(kInputEmbedded == 0 && kInputPoints == 1 && kInputRays == 2 && kInputLattice == 3, "kernel table order");
-    const int which = a.store ? 3 : mode == kInputLattice ? 4 : mode;
+    const int which = a.store ? 3 : mode == kInputLattice ? 4 : mode == kInputRaysIndexed ? 5 : mode;
     // 112 KiB of dynamic LDS is above the 64 KiB default cap: raise it once per device and kernel
     if (!raised[dev][which]) {
         e = hipFuncSetAttribute((const void*)table[which], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -393,7 +393,11 @@ void nerf_mlp_h2_kernel(const MlpLaunch a) {
 
     const unsigned bias0 = lds_addr(bias_lds) + 64 * h;   // this half-wave's entries of bias-block tile 0
     const int n_layers = a.use_viewdirs ? a.D + 1 : a.D;
-    const int64_t n_tiles = (a.n_points + kPointsPerGroup - 1) / kPointsPerGroup;
+    // kInputRaysIndexed: the tile loop runs over the compacted list, whose length lives on the device (one scalar load); a
+    // workgroup without a tile falls through
+    int64_t n_live = a.n_points;
+    if constexpr (MODE == kInputRaysIndexed) n_live = __builtin_amdgcn_readfirstlane(*a.index_count);
+    const int64_t n_tiles = (n_live + kPointsPerGroup - 1) / kPointsPerGroup;
 #ifdef NERF_EXP_STAGGER      // timing experiment (profiles/r04_ab_notes.txt): workgroups out of phase with each other, so that the chip's
     // thousand waves do not issue their stores (and their weight-stream loads) in the same instants
     for (int k = 0; k < (int)((blockIdx.x >> 3) & 7); ++k) __builtin_amdgcn_s_sleep(NERF_EXP_STAGGER);
@@ -405,7 +409,8 @@ void nerf_mlp_h2_kernel(const MlpLaunch a) {
         pipe_tile_start(pipe);
         const int64_t tile0 = tile * kPointsPerGroup + wave * kPointsPerWave;
         const int64_t pt_raw = tile0 + (lane & 31);
-        const int64_t pt = pt_raw < a.n_points ? pt_raw : a.n_points - 1;
+        int64_t pt = pt_raw < n_live ? pt_raw : n_live - 1;
+        if constexpr (MODE == kInputRaysIndexed) pt = a.index[pt];      // the listed point replaces the slot: inputs, output row
 
         XT xp0, xp1;
         float m_pe;
@@ -551,7 +556,7 @@ void nerf_mlp_h2_kernel(const MlpLaunch a) {
             for (int t = 0; t < 8; ++t) accA[t] = accB[t];
         }
 
-        const bool live = pt_raw < a.n_points;
+        const bool live = pt_raw < n_live;
         if (a.use_viewdirs) {
             // views_linears[0] on cat[feature, gamma(dir)] (nerf.py:93-98): 4 output tiles; the pending layer is
             // feature_linear
@@ -671,8 +676,9 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
     }
     const dim3 grid((unsigned)(tiles < n_cu[dev] ? tiles : n_cu[dev])), block(256);
     const size_t lds = kRingH * kChunkBytes;   // + 20.5 KiB static (bias block, layer scales)
-    static bool raised[64][4] = {};
-    if (mode < 0 || mode > 3) return hipErrorInvalidValue;
+    static bool raised[64][5] = {};
+    if (mode < 0 || mode > 4) return hipErrorInvalidValue;
+    if (mode == kInputRaysIndexed && (a.store || !a.index || !a.index_count)) return hipErrorInvalidValue;
     if (a.store) {
         // training forward: ray records, a view-dependent network, buffers the one-instruction stores can address
         // (16-byte aligned rows, byte offsets below 2^32)
@@ -704,6 +710,7 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
         const void* fn = mode == kInputEmbedded ? (const void*)nerf_mlp_h2_kernel<kInputEmbedded>
                          : mode == kInputPoints ? (const void*)nerf_mlp_h2_kernel<kInputPoints>
                          : mode == kInputLattice ? (const void*)nerf_mlp_h2_kernel<kInputLattice>
+                         : mode == kInputRaysIndexed ? (const void*)nerf_mlp_h2_kernel<kInputRaysIndexed>
                                                  : (const void*)nerf_mlp_h2_kernel<kInputRays>;
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -718,6 +725,9 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
             break;
         case kInputLattice:
             hipLaunchKernelGGL(nerf_mlp_h2_kernel<kInputLattice>, grid, block, lds, s, a);
+            break;
+        case kInputRaysIndexed:
+            hipLaunchKernelGGL(nerf_mlp_h2_kernel<kInputRaysIndexed>, grid, block, lds, s, a);
             break;
         default:
             hipLaunchKernelGGL(nerf_mlp_h2_kernel<kInputRays>, grid, block, lds, s, a);

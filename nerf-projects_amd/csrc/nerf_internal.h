@@ -130,7 +130,10 @@ constexpr int kLooseBwdGuard = 1000;    // overshoot (in binades) from which a b
 
 // kInputLattice: point n is node (i, j, k) = C order over [X, Y, Z] of a regular lattice (nerf_density_grid); the kernels write
 // one float per point, relu(sigma), instead of the [n, out_ch] rows
-enum MlpInputMode { kInputEmbedded = 0, kInputPoints = 1, kInputRays = 2, kInputLattice = 3 };
+// kInputRaysIndexed: kInputRays over a compacted list - tile slot n evaluates point index[n] of the [rays, samples] grid, for
+// n < *index_count (a device-side count, read once at kernel start); inputs are read and the output row is written at the
+// listed point, every other row of `out` is left alone (occupancy_kernels.hip has zeroed it). Inference only.
+enum MlpInputMode { kInputEmbedded = 0, kInputPoints = 1, kInputRays = 2, kInputLattice = 3, kInputRaysIndexed = 4 };
 
 // Training forward pass through the fused fp32 kernel: where the activations autograd would keep are written
 // (row-major [points, channels], any row stride; nullptr = not kept). See train_api.cpp forward_pass.
@@ -193,6 +196,10 @@ struct MlpLaunch {
     // roundings, the last node exactly hi, then rounded to fp32 (lattice_coord in mlp_inputs.h); `out` is [X, Y, Z]
     double lat_lo[3], lat_hi[3], lat_step[3];
     int64_t lat_n[3];
+    // kInputRaysIndexed (last, so that the other modes' argument offsets stay where they were): the kept points' ids
+    // n * samples_per_ray + i in increasing order, and how many there are
+    const int* index;
+    const int* index_count;
 };
 
 // Fused backward-data pass (nerf_mlp_bwd_kernel): from d raw to the gradient at every pre-activation, one launch.
@@ -508,6 +515,40 @@ McScratch mc_scratch(const int32_t reso[3], char* base);
 hipError_t launch_mc_count(const McArgs& m, char* scratch, int64_t* totals_host, hipStream_t s);
 // the emitting passes (after launch_mc_count on the same scratch)
 hipError_t launch_mc_emit(const McArgs& m, char* scratch, hipStream_t s);
+
+// ---- occupancy grid (occupancy_kernels.hip) -----------------------------------------------------------
+// One bit per cell of the lattice's (X-1) x (Y-1) x (Z-1) cells, 32 cells along z per word: cell (i, j, k) is bit k & 31 of
+// bits[(i * nc[1] + j) * wz + (k >> 5)]. The cell rule (occ_keep_point) is stated in nerf_mi355x.h, "Occupancy grid".
+struct OccGrid {
+    const uint32_t* bits;
+    float c1[3], c2[3], cell[3];      // box corners and cell size, fp32: cell = (c2 - c1) / nc, each operation rounded
+    int32_t nc[3];                    // cells per axis
+    int32_t wz;                       // words per z row
+    int32_t outside_keep;             // a point outside the box is evaluated (NERF_OCC_EVALUATE) or skipped
+};
+// classify + compact of one pass: which of the N x S points of a chunk need the network. Scratch (all carved by the caller):
+// keep_words [occ_blocks(P) * 16] of 64 bits, block_counts [occ_blocks(P)], index [P], count [1].
+struct OccCompact {
+    OccGrid g;
+    const float* rays; int ray_ld;
+    const float* z;
+    int64_t N; int S;
+    float* raw; int C;                // rows of skipped points are zeroed
+    unsigned long long* keep_words;
+    int* block_counts;
+    int* index;
+    int* count;
+    unsigned long long* stats;        // [2]: evaluated += kept, total += N * S
+};
+constexpr int kOccBlockPoints = 1024;
+inline int64_t occ_blocks(int64_t n_points) { return (n_points + kOccBlockPoints - 1) / kOccBlockPoints; }
+hipError_t launch_occ_compact(const OccCompact& o, hipStream_t s);
+// cells from sigma lattices (8-corner test: sigma > threshold or NaN, OR over the lattices) and / or a byte mask, `dilate`
+// rounds of 3x3x3 growth, packed; *n_occupied (device) receives the count. tmp0 / tmp1: one byte per cell each.
+hipError_t launch_occ_build(const float* const* sigma, int n_lattices, const uint8_t* cell_mask, const int32_t nc[3],
+                            float threshold, int dilate, uint8_t* tmp0, uint8_t* tmp1, uint32_t* bits,
+                            unsigned long long* n_occupied, hipStream_t s);
+hipError_t launch_occ_unpack(const uint32_t* bits, const int32_t nc[3], uint8_t* mask, hipStream_t s);
 
 void set_error(const char* fmt, ...);
 

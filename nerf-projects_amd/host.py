@@ -576,7 +576,7 @@ def _render_randoms(ctx, N, Sc, Si, perturb, raw_noise_std, pytest):
 
 
 def _render_rays_fused(ctx, ray_batch, net_c, net_f, N_samples, N_importance, retraw, lindisp, perturb,
-                       white_bkgd, raw_noise_std, pytest, extras=None, z_vals_fine_in=None):
+                       white_bkgd, raw_noise_std, pytest, extras=None, z_vals_fine_in=None, occupancy=None):
     N, stride = ray_batch.shape
     Sc, Si = int(N_samples), int(N_importance)
     o = dict(device=ctx.device, dtype=torch.float32)
@@ -619,7 +619,10 @@ def _render_rays_fused(ctx, ray_batch, net_c, net_f, N_samples, N_importance, re
         keep.append(zin)
         a.z_vals_fine_in = zin.data_ptr()
     a.stream = ctx.stream().value
-    check(ctx.lib.nerf_render_rays(ctx.handle, C.byref(a)))
+    if occupancy is not None:
+        check(ctx.lib.nerf_render_rays_occ(ctx.handle, C.byref(a), occupancy._handle_for(ctx)))
+    else:
+        check(ctx.lib.nerf_render_rays(ctx.handle, C.byref(a)))
     # `keep` tensors are consumed by work already enqueued on the current stream; PyTorch's
     # caching allocator only reuses their memory for later work on that same stream.
     return ret
@@ -774,7 +777,7 @@ def _render_rays_taped(ctx, ray_batch, net_c, net_f, N_samples, N_importance, re
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
-                pytest=False, _extras=None, _z_vals_fine=None):
+                pytest=False, _extras=None, _z_vals_fine=None, occupancy=None):
     """Volume-render one chunk of rays; same arguments and return dict as nerf.ipynb:359-492.
 
     When ``network_query_fn`` is this package's :class:`NetworkQuery` over this package's
@@ -786,6 +789,10 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     With grad enabled and a model that requires grad (``NeRF.requires_grad_()``) the call is taped: the outputs
     (rgb_map, disp_map, acc_map, rgb0, disp0, acc0, raw) carry a ``grad_fn`` and ``loss.backward()`` adds the models'
     gradients into :meth:`NeRF.grad_dict`. That route returns no ``z_std``.
+
+    ``occupancy`` (an :class:`OccupancyGrid`) skips the network at samples in cells the grid marks empty: their ``raw``
+    rows are zeros, the last sample of every ray is always evaluated (include/nerf_mi355x.h, "Occupancy grid"). Fused
+    route only; ``None`` is the dense render.
     """
     if not isinstance(network_fn, NeRF):
         raise TypeError("render_rays needs this package's NeRF for network_fn (no PyTorch fallback exists)")
@@ -798,13 +805,19 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     has_dirs = ray_batch.shape[-1] > 8
     perturb = float(perturb)
     if _taped(ray_batch, rays_need_grad, network_fn, network_fine, network_query_fn, N_importance):
+        if occupancy is not None:
+            raise NotImplementedError("render_rays: an occupancy grid cannot be used on the taped (differentiable) route; "
+                                      "training with a grid is not supported (render under torch.no_grad())")
         return _render_rays_taped(ctx, ray_batch, network_fn, network_fine, N_samples, N_importance, retraw, lindisp,
                                   perturb, white_bkgd, raw_noise_std, pytest, _z_vals_fine)
     fused = (isinstance(network_query_fn, NetworkQuery) and network_query_fn.matches(network_fn, has_dirs)
              and (network_fine is None or network_query_fn.matches(network_fine, has_dirs)))
     if fused:
         return _render_rays_fused(ctx, ray_batch, network_fn, network_fine, N_samples, N_importance, retraw,
-                                  lindisp, perturb, white_bkgd, raw_noise_std, pytest, _extras, _z_vals_fine)
+                                  lindisp, perturb, white_bkgd, raw_noise_std, pytest, _extras, _z_vals_fine, occupancy)
+    if occupancy is not None:
+        raise NotImplementedError("render_rays: an occupancy grid needs the fused route (this package's NetworkQuery over "
+                                  "matching embedders and models); a foreign network_query_fn evaluates every point")
 
     # ---- staged route: an opaque network_query_fn is honoured; every other stage is a kernel ----------
     return _render_rays_staged(ctx, ray_batch, network_fn, network_query_fn, int(N_samples), int(N_importance),
@@ -1020,7 +1033,7 @@ def generate_rays(H, W, K, c2w, ndc=True, near=0., far=1., use_viewdirs=False, c
 
 
 def _render_frame_fused(ctx, cam, first_pixel, n_pixels, chunk, net_c, net_f, N_samples, N_importance, lindisp,
-                        white_bkgd, shard=None):
+                        white_bkgd, shard=None, occupancy=None):
     """One ``nerf_render_frame`` call: ray generation + chunk loop + render_rays, nothing but kernels enqueued.
     With ``shard = (world, rank)`` the pixel range is the rank's shard and the call is ``nerf_render_shard``."""
     if shard is not None:
@@ -1044,6 +1057,8 @@ def _render_frame_fused(ctx, cam, first_pixel, n_pixels, chunk, net_c, net_f, N_
     f.precision_guard = _lib.NERF_GUARD_FALLBACK      # a frame whose scale bound was loose comes back from the fp32 kernel
     if shard is not None:
         check(ctx.lib.nerf_render_shard(ctx.handle, C.byref(f), int(shard[0]), int(shard[1]), None, None))
+    elif occupancy is not None:
+        check(ctx.lib.nerf_render_frame_occ(ctx.handle, C.byref(f), occupancy._handle_for(ctx)))
     else:
         check(ctx.lib.nerf_render_frame(ctx.handle, C.byref(f)))
     return ret
@@ -1056,6 +1071,9 @@ def render_shard(H, W, K, world, rank, chunk=1024 * 32, c2w=None, ndc=True, near
     Returns the flat ``{rgb_map, disp_map, acc_map, (rgb0, disp0, acc0, z_std)}`` dict of ``[n_shard, ...]`` tensors;
     row i is flat pixel ``shard_bounds(H*W, world, rank)[0] + i``. An explicit ``first_pixel`` / ``n_pixels`` range
     (any partition) goes through ``nerf_render_frame`` instead."""
+    if kwargs.get('occupancy') is not None:
+        raise NotImplementedError("render_shard: sharded rendering with an occupancy grid is not supported (the shards "
+                                  "would no longer be balanced)")
     if c2w is None or not _frame_call_applies(kwargs) or \
             not kwargs['network_query_fn'].matches(kwargs['network_fn'], bool(use_viewdirs)):
         raise RuntimeError("render_shard needs c2w, this package's networks / NetworkQuery and deterministic kwargs "
@@ -1093,7 +1111,8 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
         cam = _camera(H, W, K, c2w, ndc, near, far, use_viewdirs, c2w_staticcam)
         all_ret = _render_frame_fused(net.ctx, cam, 0, int(H) * int(W), chunk, net, kwargs.get('network_fine'),
                                       kwargs['N_samples'], kwargs.get('N_importance', 0),
-                                      kwargs.get('lindisp', False), kwargs.get('white_bkgd', False))
+                                      kwargs.get('lindisp', False), kwargs.get('white_bkgd', False),
+                                      occupancy=kwargs.get('occupancy'))
         for k in all_ret:
             all_ret[k] = torch.reshape(all_ret[k], [H, W] + list(all_ret[k].shape[1:]))
         k_extract = ['rgb_map', 'disp_map', 'acc_map']
