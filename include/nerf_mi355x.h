@@ -584,6 +584,129 @@ int nerf_occupancy_stats(nerf_occupancy* occ, int64_t* evaluated /*[host]*/, int
 int nerf_render_rays_occ(nerf_ctx* ctx, const nerf_render_args* args, const nerf_occupancy* occ);
 int nerf_render_frame_occ(nerf_ctx* ctx, const nerf_frame_args* args, const nerf_occupancy* occ);
 
+/* Sparse voxel grid ------------------------------------------------------------------------------
+ * A Plenoxels grid (svox2.SparseGrid, forward side): X x Y x Z nodes, a density and 3 * basis_dim spherical-harmonic colour
+ * coefficients at every KEPT node, rendered by trilinear ray marching without any network.
+ *   links        [dev] int32 [X, Y, Z], C order: >= 0 = row of the data arrays, ANY negative value = empty node. Values < -1
+ *                carry no meaning here (the reference stores skip distances in them; they are not trusted).
+ *   density_data [dev] float [capacity, 1]
+ *   sh_data      [dev] float [capacity, 3 * basis_dim], channel-major: [r_0 .. r_(B-1), g_0 .., b_0 ..]
+ * The three arrays are BORROWED: the grid keeps the pointers, the caller keeps the memory alive and unchanged in size until
+ * nerf_grid_destroy. Values may change between calls (stream order); after a change of `links` call nerf_grid_accelerate
+ * again or nerf_grid_drop_skip - skip data made from other links is wrong. nerf_grid_create checks every link against
+ * `capacity` on the device and synchronises `stream`; as a second line the kernels read a link >= capacity as empty.
+ * Geometry: the grid covers center -+ radius; node i of axis a sits at the voxel centre
+ * center - radius + (i + 0.5) * 2 radius / reso (grid coordinate i; the box is [-0.5, reso - 0.5]).
+ *
+ * Rendering (nerf_grid_render_rays / nerf_grid_render_image) is trace_ray_cuvol of the reference with the ray set-up and
+ * the operation order of its PyTorch statement (svox2.py _volume_render_gradcheck_lerp), fp32, no fused multiply-adds:
+ *   o = offset + origin * scaling (grid coordinates);  v = dir / |dir| (unit world direction, also the SH argument);
+ *   d = v * scaling;  delta_scale = 1 / |d|;  d *= delta_scale;  tmin / tmax from the box with d == 0 axes left out,
+ *   tmin = max(tmin, near_clip);  a ray with not (tmin <= tmax) returns the background and log_transmit 0.
+ *   t = tmin; while t <= tmax: p = clamp(o + t d, 0, reso - 1); l = min(int(p), reso - 2); w = p - l;
+ *     sigma = trilinear over the 8 corners (z, then y, then x; empty corner = 0);
+ *     if sigma > sigma_thresh: c_k likewise; rgb = max(0, sum_k c_k Y_k(v) + 0.5); a = ((-step_size) sigma) delta_scale;
+ *       out += exp(log_T) (1 - exp(a)) rgb; log_T += a; if exp(log_T) < stop_thresh: log_T = -1e3, stop
+ *     t += step_size                       (accumulated in fp32, one addition per sample, also across skipped stretches)
+ *   out += exp(log_T) background_brightness
+ * Two renders of the same input are bit-identical, and so are a render with and without skip data.
+ * Termination is unconditional. A ray whose set-up is not finite - a zero direction, a NaN or an infinity in origin or
+ * direction - is a miss: background, log_transmit 0, nothing marched. The march leaves a ray as soon as t + step_size does not
+ * exceed t in fp32 (t so large that step_size is below half an ulp: nothing further can be sampled), so every pass of the loop
+ * advances t, and step_size >= 1e-3 is required. At most 2^26 rays, pixels, points or nodes per call (NERF_E_INVALID beyond).
+ * nerf_grid_accelerate builds the skip data on the device (its own array, `links` is never written): per base cell the
+ * Chebyshev distance, capped at 31 cells, to the nearest cell with a kept corner (stored value v = distance + 1, 0 = a corner
+ * of the cell is kept). A ray at a sample t0 in a cell of value v > 0 skips that sample and every following sample whose
+ * accumulated t satisfies t - t0 <= v - 1 - 1/16, without loading anything: a step moves every coordinate by at most the step
+ * in t, so none of them can have a kept node among its 8 corners, and since t is accumulated by the same additions the sample
+ * lattice of the ray is unchanged. The 1/16 covers the rounding of o + t d, which holds while |o| and |t| stay below 2^17 grid
+ * units; a ray beyond that range is marched without the skip data.
+ * A grid belongs to the context it was created on; destroy it before the context. */
+typedef struct nerf_sparse_grid nerf_sparse_grid;
+typedef struct nerf_sparse_grid_desc {
+    size_t struct_size;         /* sizeof(nerf_sparse_grid_desc), checked                                           */
+    int32_t reso[3];            /* nodes per axis, each in [2, 1024]                                                */
+    int32_t basis_dim;          /* 1, 4 or 9 (spherical harmonics of degree 0, 1, 2)                                */
+    float radius[3];            /* > 0                                                                              */
+    float center[3];
+    int64_t capacity;           /* rows of density_data / sh_data, >= 0                                             */
+    const int32_t* links;       /* [dev] [X, Y, Z]                                                                  */
+    const float* density_data;  /* [dev] [capacity, 1]          (may be NULL when capacity == 0)                    */
+    const float* sh_data;       /* [dev] [capacity, 3 * basis_dim]                                                  */
+    void* stream;
+} nerf_sparse_grid_desc;
+
+typedef struct nerf_grid_render_options {      /* svox2.RenderOptions as far as the forward cuvol kernel reads it     */
+    size_t struct_size;
+    float step_size;            /* 0.5; in voxels, >= 1e-3                                                            */
+    float sigma_thresh;         /* 1e-10                                                                            */
+    float stop_thresh;          /* 1e-7                                                                             */
+    float background_brightness; /* 1.0                                                                             */
+    float near_clip;            /* 0.0                                                                              */
+    int32_t last_sample_opaque; /* must be 0 (not built)                                                            */
+    int32_t randomize;          /* must be 0 (not built)                                                            */
+} nerf_grid_render_options;
+
+typedef struct nerf_grid_camera {              /* svox2.Camera without NDC. c2w is OpenCV: x right, y down, z forward  */
+    size_t struct_size;
+    float c2w[12];              /* [3, 4] row-major                                                                 */
+    double fx, fy, cx, cy;      /* pixel (x, y) looks along ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1)           */
+    int32_t width, height;
+} nerf_grid_camera;
+
+typedef struct nerf_grid_render_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]       (nerf_grid_render_rays only)                             */
+    const float* dirs;          /* [dev] [n_rays, 3], need not be unit                                              */
+    int64_t n_rays;             /* nerf_grid_render_image: ignored, width * height rays in row-major pixel order     */
+    float* rgb;                 /* [dev] [n_rays, 3]                                                                */
+    float* log_transmit;        /* [dev] [n_rays] or NULL                                                           */
+    unsigned long long* counters; /* [dev] [2] or NULL: += samples whose links were loaded, samples shaded (an instrumented launch
+                                     with atomics; leave NULL in timed and in reproducible work)                    */
+    int32_t use_skip;           /* 1: use the skip data if nerf_grid_accelerate made it; 0: plain march              */
+    void* stream;
+} nerf_grid_render_args;
+
+typedef struct nerf_grid_sample_args {
+    size_t struct_size;
+    const float* points;        /* [dev] [n, 3] world coordinates, or grid coordinates with grid_coords              */
+    int64_t n;
+    int32_t grid_coords;
+    int32_t want_colors;
+    float* density;             /* [dev] [n, 1]                                                                     */
+    float* sh;                  /* [dev] [n, 3 * basis_dim]; may be NULL without want_colors                         */
+    void* stream;
+} nerf_grid_sample_args;
+
+int nerf_grid_create(nerf_ctx* ctx, const nerf_sparse_grid_desc* desc, nerf_sparse_grid** out);
+void nerf_grid_destroy(nerf_sparse_grid* grid);
+int nerf_grid_render_rays(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_render_args* args);
+/* the rays of `cam` made on the device in fp64 and rounded to fp32 (svox2 Camera.gen_rays): one call per frame */
+int nerf_grid_render_image(nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_render_options* opt,
+                           const nerf_grid_render_args* args);
+/* those rays themselves: origins, dirs [dev] [height * width, 3] */
+int nerf_grid_gen_rays(nerf_ctx* ctx, const nerf_grid_camera* cam, float* origins, float* dirs, void* stream);
+/* svox2 SparseGrid.sample: trilinear, border padding, align_corners = False */
+int nerf_grid_sample(nerf_sparse_grid* grid, const nerf_grid_sample_args* args);
+int nerf_grid_accelerate(nerf_sparse_grid* grid, void* stream);
+int nerf_grid_drop_skip(nerf_sparse_grid* grid);      /* waits for the device, frees the skip data                    */
+int nerf_grid_has_skip(const nerf_sparse_grid* grid); /* 1 / 0                                                        */
+/* Baking: rows [row0, row0 + m) of sh_out [., 3 * basis_dim] from network outputs raw [dev] [m, n_dirs, 4]:
+ * sh_out[row0 + i, c * basis_dim + k] = sum_j P[k, j] * (sigmoid(raw[i, j, c]) - 0.5), fp32, the sum in order of j with
+ * product and sum each rounded. P [dev] [basis_dim, n_dirs] (staged in LDS); basis_dim * n_dirs <= 4096. */
+typedef struct nerf_grid_project_args {
+    size_t struct_size;
+    const float* raw;
+    int64_t m;
+    int32_t n_dirs;
+    int32_t basis_dim;
+    const float* P;
+    float* sh_out;
+    int64_t row0;
+    void* stream;
+} nerf_grid_project_args;
+int nerf_grid_project_sh(nerf_ctx* ctx, const nerf_grid_project_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,5 +16,7 @@ from .sharded import ensure_ipc_env, gather_frame, render_sharded, shard_bounds 
 from .batching import RayBatcher  # noqa: F401
 from .mesh import density_grid, marching_cubes, marching_cubes_volume, save_obj  # noqa: F401
 from .occupancy import OccupancyGrid  # noqa: F401
+from . import grid  # noqa: F401
+from .grid import Camera, Rays, RenderOptions, SparseGrid  # noqa: F401
 
 __version__ = "0.1.0"

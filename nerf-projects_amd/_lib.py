@@ -24,6 +24,8 @@ EXPORTS = (
     "nerf_pack_rays", "nerf_density_grid", "nerf_marching_cubes", "nerf_train_forward", "nerf_train_backward",
     "nerf_zero_grad", "nerf_adam_step", "nerf_occupancy_create", "nerf_occupancy_destroy", "nerf_occupancy_cells",
     "nerf_occupancy_stats", "nerf_render_rays_occ", "nerf_render_frame_occ",
+    "nerf_grid_create", "nerf_grid_destroy", "nerf_grid_render_rays", "nerf_grid_render_image", "nerf_grid_gen_rays",
+    "nerf_grid_sample", "nerf_grid_accelerate", "nerf_grid_drop_skip", "nerf_grid_has_skip", "nerf_grid_project_sh",
 )
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
 NERF_GUARD_OFF, NERF_GUARD_REPORT, NERF_GUARD_FALLBACK = 0, 1, 2
@@ -112,6 +114,46 @@ class OccupancyArgs(C.Structure):
     _fields_ = [("c1", C.c_double * 3), ("c2", C.c_double * 3), ("reso", C.c_int32 * 3), ("n_lattices", C.c_int32),
                 ("sigma", C.POINTER(C.c_void_p)), ("cell_mask", _FP), ("threshold", C.c_float), ("dilate", C.c_int32),
                 ("outside", C.c_int32), ("stream", C.c_void_p)]
+
+
+class _Sized(C.Structure):
+    """A struct that begins with a checked ``size_t struct_size``."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(self)
+
+
+class SparseGridDesc(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("reso", C.c_int32 * 3), ("basis_dim", C.c_int32), ("radius", C.c_float * 3),
+                ("center", C.c_float * 3), ("capacity", C.c_int64), ("links", _FP), ("density_data", _FP), ("sh_data", _FP),
+                ("stream", C.c_void_p)]
+
+
+class GridRenderOptions(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("step_size", C.c_float), ("sigma_thresh", C.c_float),
+                ("stop_thresh", C.c_float), ("background_brightness", C.c_float), ("near_clip", C.c_float),
+                ("last_sample_opaque", C.c_int32), ("randomize", C.c_int32)]
+
+
+class GridCamera(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("c2w", C.c_float * 12), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class GridRenderArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("rgb", _FP),
+                ("log_transmit", _FP), ("counters", _FP), ("use_skip", C.c_int32), ("stream", C.c_void_p)]
+
+
+class GridSampleArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("points", _FP), ("n", C.c_int64), ("grid_coords", C.c_int32),
+                ("want_colors", C.c_int32), ("density", _FP), ("sh", _FP), ("stream", C.c_void_p)]
+
+
+class GridProjectArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("raw", _FP), ("m", C.c_int64), ("n_dirs", C.c_int32), ("basis_dim", C.c_int32),
+                ("P", _FP), ("sh_out", _FP), ("row0", C.c_int64), ("stream", C.c_void_p)]
 
 
 _lib = None
@@ -230,6 +272,26 @@ def load():
     lib.nerf_render_rays_occ.argtypes = [vp, C.POINTER(RenderArgs), vp]
     lib.nerf_render_frame_occ.restype = i32
     lib.nerf_render_frame_occ.argtypes = [vp, C.POINTER(FrameArgs), vp]
+    lib.nerf_grid_create.restype = i32
+    lib.nerf_grid_create.argtypes = [vp, C.POINTER(SparseGridDesc), C.POINTER(vp)]
+    lib.nerf_grid_destroy.restype = None
+    lib.nerf_grid_destroy.argtypes = [vp]
+    lib.nerf_grid_render_rays.restype = i32
+    lib.nerf_grid_render_rays.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridRenderArgs)]
+    lib.nerf_grid_render_image.restype = i32
+    lib.nerf_grid_render_image.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridRenderOptions), C.POINTER(GridRenderArgs)]
+    lib.nerf_grid_gen_rays.restype = i32
+    lib.nerf_grid_gen_rays.argtypes = [vp, C.POINTER(GridCamera), vp, vp, vp]
+    lib.nerf_grid_sample.restype = i32
+    lib.nerf_grid_sample.argtypes = [vp, C.POINTER(GridSampleArgs)]
+    lib.nerf_grid_accelerate.restype = i32
+    lib.nerf_grid_accelerate.argtypes = [vp, vp]
+    lib.nerf_grid_drop_skip.restype = i32
+    lib.nerf_grid_drop_skip.argtypes = [vp]
+    lib.nerf_grid_has_skip.restype = i32
+    lib.nerf_grid_has_skip.argtypes = [vp]
+    lib.nerf_grid_project_sh.restype = i32
+    lib.nerf_grid_project_sh.argtypes = [vp, C.POINTER(GridProjectArgs)]
     _lib = lib
     return lib
 

@@ -1,0 +1,296 @@
+// C ABI of the sparse voxel grid (include/nerf_mi355x.h, "Sparse voxel grid"): argument checks and launches.
+#include <cmath>
+#include <new>
+
+#include "ctx_internal.h"
+#include "grid_internal.h"
+
+using namespace nerf;
+
+namespace {
+
+#define GRID_CHECK_STRUCT(fn, ptr, type)                                                              \
+    do {                                                                                              \
+        if (!(ptr)) {                                                                                 \
+            set_error(fn ": " #type " is NULL");                                                      \
+            return NERF_E_INVALID;                                                                    \
+        }                                                                                             \
+        if ((ptr)->struct_size != sizeof(type)) {                                                     \
+            set_error(fn ": " #type ".struct_size = %zu, this library expects %zu", (ptr)->struct_size, sizeof(type)); \
+            return NERF_E_INVALID;                                                                    \
+        }                                                                                             \
+    } while (0)
+
+int check_options(const char* fn, const nerf_grid_render_options* o, GridRenderOpt* out) {
+    if (!o) {
+        set_error("%s: nerf_grid_render_options is NULL", fn);
+        return NERF_E_INVALID;
+    }
+    if (o->struct_size != sizeof(nerf_grid_render_options)) {
+        set_error("%s: nerf_grid_render_options.struct_size = %zu, this library expects %zu", fn, o->struct_size,
+                  sizeof(nerf_grid_render_options));
+        return NERF_E_INVALID;
+    }
+    if (o->last_sample_opaque || o->randomize) {
+        set_error("%s: last_sample_opaque and randomize are not built", fn);
+        return NERF_E_INVALID;
+    }
+    if (!(o->step_size >= 1e-3f) || !std::isfinite(o->step_size) || std::isnan(o->sigma_thresh) || std::isnan(o->stop_thresh) ||
+        !std::isfinite(o->background_brightness) || !std::isfinite(o->near_clip)) {
+        set_error("%s: step_size = %g must be finite and >= 1e-3, the thresholds not NaN, background_brightness and near_clip finite",
+                  fn, o->step_size);
+        return NERF_E_INVALID;
+    }
+    *out = GridRenderOpt{o->step_size, o->sigma_thresh, o->stop_thresh, o->background_brightness, o->near_clip};
+    return NERF_OK;
+}
+
+int check_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out) {
+    if (!cam) {
+        set_error("%s: nerf_grid_camera is NULL", fn);
+        return NERF_E_INVALID;
+    }
+    if (cam->struct_size != sizeof(nerf_grid_camera)) {
+        set_error("%s: nerf_grid_camera.struct_size = %zu, this library expects %zu", fn, cam->struct_size, sizeof(nerf_grid_camera));
+        return NERF_E_INVALID;
+    }
+    if (cam->width < 1 || cam->height < 1 || (int64_t)cam->width * cam->height > kGridMaxItems || !(std::fabs(cam->fx) > 0.0) ||
+        !(std::fabs(cam->fy) > 0.0) || !std::isfinite(cam->fx) || !std::isfinite(cam->fy) || !std::isfinite(cam->cx) ||
+        !std::isfinite(cam->cy)) {
+        set_error("%s: camera %d x %d (at most 2^26 pixels), fx = %g, fy = %g, cx = %g, cy = %g is not usable", fn, cam->width, cam->height, cam->fx,
+                  cam->fy, cam->cx, cam->cy);
+        return NERF_E_INVALID;
+    }
+    for (int i = 0; i < 12; ++i) out->c2w[i] = (double)cam->c2w[i];
+    out->fx = cam->fx;
+    out->fy = cam->fy;
+    out->cx = cam->cx;
+    out->cy = cam->cy;
+    out->width = cam->width;
+    out->height = cam->height;
+    return NERF_OK;
+}
+
+int render(const char* fn, nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_render_options* opt,
+           const nerf_grid_render_args* a) {
+    if (!grid) {
+        set_error("%s: NULL grid", fn);
+        return NERF_E_INVALID;
+    }
+    if (!a) {
+        set_error("%s: nerf_grid_render_args is NULL", fn);
+        return NERF_E_INVALID;
+    }
+    if (a->struct_size != sizeof(nerf_grid_render_args)) {
+        set_error("%s: nerf_grid_render_args.struct_size = %zu, this library expects %zu", fn, a->struct_size,
+                  sizeof(nerf_grid_render_args));
+        return NERF_E_INVALID;
+    }
+    GridRenderOpt o{};
+    int rc = check_options(fn, opt, &o);
+    if (rc != NERF_OK) return rc;
+    GridRender r{};
+    if (cam) {
+        rc = check_camera(fn, cam, &r.cam);
+        if (rc != NERF_OK) return rc;
+        r.n_rays = (int64_t)cam->width * cam->height;
+    } else {
+        if (a->n_rays < 0 || a->n_rays > kGridMaxItems || (a->n_rays > 0 && (!a->origins || !a->dirs))) {
+            set_error("%s: n_rays = %lld must be in [0, 2^26] and needs origins and dirs", fn, (long long)a->n_rays);
+            return NERF_E_INVALID;
+        }
+        r.origins = a->origins;
+        r.dirs = a->dirs;
+        r.n_rays = a->n_rays;
+    }
+    if (r.n_rays > 0 && !a->rgb) {
+        set_error("%s: rgb is NULL", fn);
+        return NERF_E_INVALID;
+    }
+    r.rgb = a->rgb;
+    r.log_transmit = a->log_transmit;
+    r.counters = a->counters;
+    GridDev g = grid->g;
+    g.skip = a->use_skip ? grid->d_skip : nullptr;
+    DeviceGuard dg(grid->ctx->device);
+    HIP_TRY(launch_grid_render(g, o, r, (hipStream_t)a->stream));
+    return NERF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void nerf_grid_destroy(nerf_sparse_grid* grid) {
+    if (!grid) return;
+    if (grid->ctx && grid->d_skip) {
+        DeviceGuard g(grid->ctx->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(grid->d_skip);
+    }
+    delete grid;
+}
+
+int nerf_grid_create(nerf_ctx* c, const nerf_sparse_grid_desc* d, nerf_sparse_grid** out) {
+    if (!c || !out) {
+        set_error("nerf_grid_create: NULL argument");
+        return NERF_E_INVALID;
+    }
+    *out = nullptr;
+    GRID_CHECK_STRUCT("nerf_grid_create", d, nerf_sparse_grid_desc);
+    if (d->basis_dim != 1 && d->basis_dim != 4 && d->basis_dim != 9) {
+        set_error("nerf_grid_create: basis_dim = %d: spherical harmonics of 1, 4 or 9 coefficients are built", d->basis_dim);
+        return NERF_E_INVALID;
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (d->reso[k] < 2 || d->reso[k] > 1024) {
+            set_error("nerf_grid_create: reso[%d] = %d outside [2, 1024]", k, d->reso[k]);
+            return NERF_E_INVALID;
+        }
+        if (!(d->radius[k] > 0.0f) || !std::isfinite(d->radius[k]) || !std::isfinite(d->center[k])) {
+            set_error("nerf_grid_create: axis %d: radius = %g must be positive and finite, center = %g finite", k, d->radius[k],
+                      d->center[k]);
+            return NERF_E_INVALID;
+        }
+    }
+    if (d->capacity < 0 || d->capacity > 0x7fffffffLL || !d->links || (d->capacity > 0 && (!d->density_data || !d->sh_data))) {
+        set_error("nerf_grid_create: links, and with capacity = %lld > 0 density_data and sh_data, are required",
+                  (long long)d->capacity);
+        return NERF_E_INVALID;
+    }
+    DeviceGuard dg(c->device);
+    hipStream_t s = (hipStream_t)d->stream;
+    const int64_t n = (int64_t)d->reso[0] * d->reso[1] * d->reso[2];
+    int* d_bad = nullptr;
+    int bad = 0;
+    HIP_TRY(hipMalloc((void**)&d_bad, sizeof(int)));
+    hipError_t e = launch_grid_check_links(d->links, n, d->capacity, d_bad, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_bad);
+    if (e != hipSuccess) {
+        set_error("nerf_grid_create: %s", hipGetErrorString(e));
+        return NERF_E_HIP;
+    }
+    if (bad) {
+        set_error("nerf_grid_create: links holds a value >= capacity = %lld", (long long)d->capacity);
+        return NERF_E_INVALID;
+    }
+    nerf_sparse_grid* grid = new (std::nothrow) nerf_sparse_grid();
+    if (!grid) return NERF_E_NOMEM;
+    grid->ctx = c;
+    GridDev& g = grid->g;
+    g.links = d->links;
+    g.density = d->density_data;
+    g.sh = d->sh_data;
+    g.skip = nullptr;
+    g.basis_dim = d->basis_dim;
+    g.capacity = d->capacity;
+    for (int k = 0; k < 3; ++k) {
+        g.size[k] = d->reso[k];
+        // svox2.py:411-412, 1504-1506: fp32 tensors, each operation rounded
+        const float ratio = d->center[k] / d->radius[k];
+        const float one_minus = 1.0f - ratio;
+        const float off = 0.5f * one_minus;
+        const float scl = 0.5f / d->radius[k];
+        const float off_g = off * (float)d->reso[k];
+        g.offset[k] = off_g - 0.5f;
+        g.scaling[k] = scl * (float)d->reso[k];
+    }
+    *out = grid;
+    return NERF_OK;
+}
+
+int nerf_grid_render_rays(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_render_args* args) {
+    return render("nerf_grid_render_rays", grid, nullptr, opt, args);
+}
+
+int nerf_grid_render_image(nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_render_options* opt,
+                           const nerf_grid_render_args* args) {
+    if (!cam) {
+        set_error("nerf_grid_render_image: nerf_grid_camera is NULL");
+        return NERF_E_INVALID;
+    }
+    return render("nerf_grid_render_image", grid, cam, opt, args);
+}
+
+int nerf_grid_gen_rays(nerf_ctx* c, const nerf_grid_camera* cam, float* origins, float* dirs, void* stream) {
+    if (!c || !origins || !dirs) {
+        set_error("nerf_grid_gen_rays: NULL argument");
+        return NERF_E_INVALID;
+    }
+    GridCam gc{};
+    const int rc = check_camera("nerf_grid_gen_rays", cam, &gc);
+    if (rc != NERF_OK) return rc;
+    DeviceGuard dg(c->device);
+    HIP_TRY(launch_grid_gen_rays(gc, origins, dirs, (hipStream_t)stream));
+    return NERF_OK;
+}
+
+int nerf_grid_sample(nerf_sparse_grid* grid, const nerf_grid_sample_args* a) {
+    if (!grid) {
+        set_error("nerf_grid_sample: NULL grid");
+        return NERF_E_INVALID;
+    }
+    GRID_CHECK_STRUCT("nerf_grid_sample", a, nerf_grid_sample_args);
+    if (a->n < 0 || a->n > kGridMaxItems || (a->n > 0 && (!a->points || !a->density || (a->want_colors && !a->sh)))) {
+        set_error("nerf_grid_sample: n = %lld must be in [0, 2^26] and needs points, density and (with want_colors) sh", (long long)a->n);
+        return NERF_E_INVALID;
+    }
+    DeviceGuard dg(grid->ctx->device);
+    HIP_TRY(launch_grid_sample(grid->g, a->points, a->n, a->grid_coords, a->want_colors, a->density, a->sh, (hipStream_t)a->stream));
+    return NERF_OK;
+}
+
+int nerf_grid_accelerate(nerf_sparse_grid* grid, void* stream) {
+    if (!grid) {
+        set_error("nerf_grid_accelerate: NULL grid");
+        return NERF_E_INVALID;
+    }
+    DeviceGuard dg(grid->ctx->device);
+    const size_t n = (size_t)grid->g.size[0] * grid->g.size[1] * grid->g.size[2];
+    if (!grid->d_skip) {
+        hipError_t e = hipMalloc((void**)&grid->d_skip, n);
+        if (e != hipSuccess) {
+            grid->d_skip = nullptr;
+            set_error("nerf_grid_accelerate: hipMalloc(%zu) failed: %s", n, hipGetErrorString(e));
+            return NERF_E_NOMEM;
+        }
+    }
+    HIP_TRY(launch_grid_accelerate(grid->g, grid->d_skip, (hipStream_t)stream));
+    return NERF_OK;
+}
+
+int nerf_grid_drop_skip(nerf_sparse_grid* grid) {
+    if (!grid) {
+        set_error("nerf_grid_drop_skip: NULL grid");
+        return NERF_E_INVALID;
+    }
+    if (!grid->d_skip) return NERF_OK;
+    DeviceGuard dg(grid->ctx->device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipFree(grid->d_skip));
+    grid->d_skip = nullptr;
+    return NERF_OK;
+}
+
+int nerf_grid_has_skip(const nerf_sparse_grid* grid) { return grid && grid->d_skip ? 1 : 0; }
+
+int nerf_grid_project_sh(nerf_ctx* c, const nerf_grid_project_args* a) {
+    if (!c) {
+        set_error("nerf_grid_project_sh: NULL context");
+        return NERF_E_INVALID;
+    }
+    GRID_CHECK_STRUCT("nerf_grid_project_sh", a, nerf_grid_project_args);
+    if ((a->basis_dim != 1 && a->basis_dim != 4 && a->basis_dim != 9) || a->n_dirs < 1 || a->basis_dim * a->n_dirs > 4096 ||
+        a->m < 0 || a->m > kGridMaxItems || a->row0 < 0 || (a->m > 0 && (!a->raw || !a->P || !a->sh_out))) {
+        set_error("nerf_grid_project_sh: basis_dim = %d in {1, 4, 9}, 1 <= n_dirs = %d, basis_dim * n_dirs <= 4096, m = %lld "
+                  "and non-NULL raw, P, sh_out are required", a->basis_dim, a->n_dirs, (long long)a->m);
+        return NERF_E_INVALID;
+    }
+    DeviceGuard dg(c->device);
+    HIP_TRY(launch_grid_project_sh(a->raw, a->m, a->n_dirs, a->basis_dim, a->P, a->sh_out, a->row0, (hipStream_t)a->stream));
+    return NERF_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,67 @@
+// Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what grid_api.cpp and grid_kernels.hip share.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "nerf_mi355x.h"
+
+struct nerf_ctx;
+
+namespace nerf {
+
+constexpr int kGridSkipCap = 32;       // largest stored skip value: a distance of 31 cells
+constexpr float kGridSkipMaxT = 131072.0f;      // 2^17: the range of |origin| and |t| (grid units) in which skip data is used
+constexpr int64_t kGridMaxItems = (int64_t)1 << 26;   // rays / points / nodes per call: 32 lanes each stay inside one launch
+
+// the grid as the kernels see it (passed by value)
+struct GridDev {
+    const int32_t* links;
+    const float* density;
+    const float* sh;
+    const uint8_t* skip;               // [X, Y, Z] bytes indexed like links (base cell = its lowest node), or nullptr
+    int32_t size[3];
+    int32_t basis_dim;
+    int64_t capacity;
+    // world2grid of the reference, fp32, each operation rounded: _offset = 0.5 (1 - center / radius), _scaling = 0.5 / radius,
+    // offset = _offset * size - 0.5, scaling = _scaling * size
+    float offset[3], scaling[3];
+};
+
+struct GridRenderOpt {
+    float step_size, sigma_thresh, stop_thresh, background_brightness, near_clip;
+};
+
+struct GridCam {
+    double c2w[12];
+    double fx, fy, cx, cy;
+    int32_t width, height;
+};
+
+struct GridRender {
+    const float* origins;              // nullptr: the rays of `cam`
+    const float* dirs;
+    GridCam cam;
+    int64_t n_rays;
+    float* rgb;
+    float* log_transmit;
+    unsigned long long* counters;
+};
+
+hipError_t launch_grid_render(const GridDev& g, const GridRenderOpt& o, const GridRender& r, hipStream_t s);
+hipError_t launch_grid_gen_rays(const GridCam& cam, float* origins, float* dirs, hipStream_t s);
+hipError_t launch_grid_sample(const GridDev& g, const float* points, int64_t n, int grid_coords, int want_colors,
+                              float* density, float* sh, hipStream_t s);
+// skip [X * Y * Z] bytes: kGridSkipCap stream-ordered launches, no atomics
+hipError_t launch_grid_accelerate(const GridDev& g, uint8_t* skip, hipStream_t s);
+// *out (device) = 1 if any link is >= capacity, else 0
+hipError_t launch_grid_check_links(const int32_t* links, int64_t n, int64_t capacity, int* out, hipStream_t s);
+hipError_t launch_grid_project_sh(const float* raw, int64_t m, int n_dirs, int basis_dim, const float* P, float* sh_out,
+                                  int64_t row0, hipStream_t s);
+
+}  // namespace nerf
+
+struct nerf_sparse_grid {
+    nerf_ctx* ctx = nullptr;
+    nerf::GridDev g{};
+    uint8_t* d_skip = nullptr;
+};

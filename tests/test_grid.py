@@ -1,0 +1,545 @@
+"""Sparse voxel grid (Plenoxels) renderer and NeRF baking on the GPU (include/nerf_mi355x.h, "Sparse voxel grid").
+
+Against the reference: tests/golden/grid_render.npz holds what svox2's PyTorch renderer computes (fp32, and fp64 for its own
+distance ``d_ref`` from exact arithmetic); every ray has to be within ``max(3 * d_ref, 1e-5)``. Against tests/grid_oracle.py
+(the numpy restatement checked against the same fixture in tests/test_grid_cpu.py) beyond what the CPU reference can render.
+Needs a real MI355X: run with ``pytest -m gpu``."""
+import numpy as np
+import pytest
+import torch
+
+import grid_oracle as GO
+from nerf_projects_amd import synthetic
+from test_grid_cpu import GRIDS, bar, fixture_cases, fixture_grid, load_fixture
+from test_occupancy_cpu import np_cells
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def N():
+    import nerf_projects_amd as pkg
+    return pkg
+
+
+# the largest |Y_k| over the sphere, rounded up (c_max, the largest colour a grid's coefficients can produce, is bounded by
+# sum_k |c_k| max |Y_k| + 0.5)
+Y_MAX = np.array([0.2820948, 0.4886026, 0.4886026, 0.4886026, 0.5462743, 0.5462743, 0.6307832, 0.5462743, 0.5462743])
+
+
+def gpu(x):
+    return torch.as_tensor(np.ascontiguousarray(x)).cuda()
+
+
+def cpu(t):
+    return t.detach().cpu().numpy()
+
+
+def make_grid(N, g):
+    return N.SparseGrid.from_tensors(gpu(g["links"]), gpu(g["density_data"]), gpu(g["sh_data"]), g["radius"].tolist(),
+                                    g["center"].tolist())
+
+
+def set_opt(grid, bg, step, near, sigma_thresh=None, stop_thresh=None):
+    grid.opt = type(grid.opt)(background_brightness=bg, step_size=step, near_clip=near)
+    if sigma_thresh is not None:
+        grid.opt.sigma_thresh = sigma_thresh
+    if stop_thresh is not None:
+        grid.opt.stop_thresh = stop_thresh
+
+
+def random_grid(rng, reso, basis_dim, keep=0.2):
+    """a larger grid of the fixture's kind: blobs, empty border, rows in random order, arbitrary links < -1"""
+    X, Y, Z = reso
+    i, j, k = np.meshgrid(np.arange(X), np.arange(Y), np.arange(Z), indexing="ij")
+    f = np.zeros(reso)
+    for _ in range(6):
+        w, p = rng.uniform(0.1, 0.5, 3), rng.uniform(0, 2 * np.pi, 3)
+        f += np.sin(w[0] * i + p[0]) * np.sin(w[1] * j + p[1]) * np.sin(w[2] * k + p[2])
+    interior = np.zeros(reso, dtype=bool)
+    interior[1:-1, 1:-1, 1:-1] = True
+    kept = (f > np.quantile(f[interior], 1 - keep)) & interior
+    n = int(kept.sum())
+    links = np.full(reso, -1, dtype=np.int32)
+    links[kept] = rng.permutation(n).astype(np.int32)
+    links[(~kept) & (rng.random(reso) < 0.1)] = -5
+    dens = rng.uniform(-2.0, 30.0, (n, 1)).astype(np.float32)
+    sh = rng.normal(0.0, 0.7, (n, 3 * basis_dim)).astype(np.float32)
+    return {"links": links, "density_data": dens, "sh_data": sh, "radius": np.array([1.0, 1.2, 0.9], np.float32),
+            "center": np.array([0.1, 0.0, -0.1], np.float32)}
+
+
+# ---- 1. the reference's renders and samples ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", GRIDS)
+def test_every_recorded_render_plain_and_accelerated(N, name):
+    z = load_fixture()
+    g = fixture_grid(z, name)
+    tol = bar(z, name)
+    rays = N.Rays(gpu(z[f"{name}_origins"]), gpu(z[f"{name}_dirs"]))
+    grid = make_grid(N, g)
+    assert not grid.accelerated
+    plain = {}
+    for tag, bg, step, near, want in fixture_cases(z, name):
+        set_opt(grid, bg, step, near, 0.0, 0.0)
+        got = cpu(grid.volume_render(rays))
+        err = np.abs(got.astype(np.float64) - want).max(-1)
+        print(f"grid {name} {tag}: GPU vs reference max {err.max():.3e} over {len(err)} rays (bar {tol:.3e})")
+        assert np.isfinite(got).all() and err.max() <= tol, (name, tag, int(err.argmax()), err.max())      # no ray left out
+        plain[tag] = got
+    grid.accelerate()      # the fixture's links < -1 are arbitrary: trusted as skip distances they would break this
+    assert grid.accelerated
+    for tag, bg, step, near, want in fixture_cases(z, name):
+        set_opt(grid, bg, step, near, 0.0, 0.0)
+        got = cpu(grid.volume_render(rays))
+        err = np.abs(got.astype(np.float64) - want).max(-1)
+        assert err.max() <= tol, (name, tag, "accelerated", int(err.argmax()), err.max())
+        assert np.array_equal(got, plain[tag]), (name, tag)      # the skip keeps the sample lattice: bit-identical
+    v_acc, s_acc = grid.count_samples(rays=rays)
+    grid.links = grid.links      # (d) a write to links through the object drops the skip data
+    assert not grid.accelerated
+    v_plain, s_plain = grid.count_samples(rays=rays)
+    grid.accelerate()
+    grid.density_data[0, 0] += 0.0      # writes into the data do not
+    assert grid.accelerated
+    grid.links[0, 0, 0] = -1      # ... an in-place write to links does, whatever it writes
+    assert not grid.accelerated
+    assert s_acc == s_plain and v_acc < v_plain, (v_acc, v_plain, s_acc, s_plain)
+    # the oracle counts the same samples
+    _, _, (v_o, s_o) = GO.render(g, z[f"{name}_origins"], z[f"{name}_dirs"], step_size=step, sigma_thresh=0.0, stop_thresh=0.0,
+                                 background_brightness=bg, near_clip=near, return_counts=True)
+    assert abs(v_plain - v_o) <= 1e-3 * v_o and abs(s_plain - s_o) <= 1e-3 * max(s_o, 1)
+
+
+@pytest.mark.parametrize("name", GRIDS)
+def test_every_recorded_sample(N, name):
+    z = load_fixture()
+    grid = make_grid(N, fixture_grid(z, name))
+    for accelerated in (False, True):
+        if accelerated:
+            grid.accelerate()
+        for kind, coords in (("world", False), ("grid", True)):
+            pts = gpu(z[f"{name}_pts_{kind}"])
+            keep = pts.clone()
+            dens, sh = grid.sample(pts, grid_coords=coords)
+            assert torch.equal(pts, keep)
+            want_d, want_s = z[f"{name}_sample_{kind}_density"], z[f"{name}_sample_{kind}_sh"]
+            assert dens.shape == want_d.shape and sh.shape == want_s.shape
+            # the renders' 1e-5 is a bar for colours of order 1; a sample is an interpolated stored value (densities up to
+            # 40 here), so the same bar is taken relative to the largest recorded value: a few ulps of it
+            assert np.abs(cpu(dens) - want_d).max() <= 1e-5 * max(1.0, float(np.abs(want_d).max())), (name, kind)
+            assert np.abs(cpu(sh) - want_s).max() <= 1e-5 * max(1.0, float(np.abs(want_s).max())), (name, kind)
+            d_only, none = grid.sample(pts, grid_coords=coords, want_colors=False)
+            assert torch.equal(d_only, dens) and none.shape == (0, sh.shape[1])
+
+
+# ---- 2. default options -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", GRIDS)
+def test_default_thresholds_against_the_reference(N, name):
+    """sigma_thresh 1e-10, stop_thresh 1e-7: what a stopped ray drops is its remaining weights and its background term, which
+    sum to the transmittance at the stop (< stop_thresh) times at most max(background_brightness, c_max); samples with
+    0 < sigma <= 1e-10 add less than 1e-10 * world_step each (below the bar by orders of magnitude)."""
+    z = load_fixture()
+    g = fixture_grid(z, name)
+    grid = make_grid(N, g)
+    B = g["sh_data"].shape[1] // 3
+    # the largest colour the coefficients can produce: |Y_k| <= its constant's maximum over the sphere, bounded by sum |c_k| max|Y_k|
+    y_max = Y_MAX[:B]
+    c_max = float((np.abs(g["sh_data"].reshape(-1, 3, B)) * y_max).sum(-1).max() + 0.5) if len(g["sh_data"]) else 0.5
+    rays = N.Rays(gpu(z[f"{name}_origins"]), gpu(z[f"{name}_dirs"]))
+    stopped_any = 0
+    for accelerated in (False, True):
+        if accelerated:
+            grid.accelerate()
+        for tag, bg, step, near, want in fixture_cases(z, name):
+            set_opt(grid, bg, step, near)
+            assert grid.opt.sigma_thresh == 1e-10 and grid.opt.stop_thresh == 1e-7
+            got, logt = grid.volume_render(rays, return_log_transmit=True)
+            got, logt = cpu(got), cpu(logt)
+            tol = bar(z, name) + 1e-7 * max(bg, c_max)
+            err = np.abs(got.astype(np.float64) - want).max(-1)
+            assert err.max() <= tol, (name, tag, accelerated, int(err.argmax()), err.max(), tol)
+            stopped = logt < -100.0
+            assert np.all(logt[stopped] == np.float32(-1e3))
+            assert np.all(logt[~stopped] > np.log(1e-7) - 1e-3) and np.all(logt <= 0)
+            stopped_any += int(stopped.sum())
+    if name == "a":
+        assert stopped_any > 0
+
+
+# ---- 3. a larger grid against the oracle ----------------------------------------------------------------------------------
+def test_large_grid_against_the_oracle_and_bit_identity(N):
+    rng = np.random.default_rng(5)
+    g = random_grid(rng, (72, 64, 80), 9)
+    grid = make_grid(N, g)
+    n = 100_000
+    u = rng.normal(size=(n, 3))
+    o = (g["center"] + 3.0 * g["radius"] * u / np.linalg.norm(u, axis=-1, keepdims=True)).astype(np.float32)
+    target = g["center"] + g["radius"] * rng.uniform(-1.1, 1.1, (n, 3))
+    d = ((target - o) * rng.uniform(0.3, 3.0, (n, 1))).astype(np.float32)
+    o[-5000:] = (g["center"] + g["radius"] * rng.uniform(-0.9, 0.9, (5000, 3))).astype(np.float32)      # origins inside
+    d[-2500:, 1] = 0.0                                                                                   # a zero component
+    rays = N.Rays(gpu(o), gpu(d))
+    set_opt(grid, 1.0, 0.5, 0.0)
+    want, want_logt = GO.render(g, o, d)
+    got, logt = grid.volume_render(rays, return_log_transmit=True)
+    # the bar of the fixture's grid of this kind: max(3 * d_ref, 1e-5) with d_ref as recorded for grid "a", plus what the
+    # default stop rule may drop on either side
+    z = load_fixture()
+    c_max = float((np.abs(g["sh_data"].reshape(-1, 3, 9)) * Y_MAX).sum(-1).max() + 0.5)
+    tol = bar(z, "a") + 1e-7 * max(1.0, c_max)
+    err = np.abs(cpu(got).astype(np.float64) - want).max(-1)
+    print(f"large grid: GPU vs oracle max {err.max():.3e} over {n} rays (bar {tol:.3e}); stopped {int((want_logt < -100).sum())}")
+    assert err.max() <= tol, (int(err.argmax()), err.max())
+    again = grid.volume_render(rays)
+    assert torch.equal(got, again)
+    h = n // 2 + 3
+    halves = torch.cat([grid.volume_render(rays[:h]), grid.volume_render(rays[h:])])
+    assert torch.equal(got, halves)
+    grid.accelerate()
+    acc, acc_logt = grid.volume_render(rays, return_log_transmit=True)
+    assert torch.equal(got, acc) and torch.equal(logt, acc_logt)
+    assert torch.equal(acc, grid.volume_render(rays))
+    v_acc, s_acc = grid.count_samples(rays=rays)
+    _, _, (v_o, s_o) = GO.render(g, o[:5000], d[:5000], skip=GO.skip_distances(g["links"]), return_counts=True)
+    v_g, s_g = grid.count_samples(rays=rays[:5000])
+    assert abs(v_g - v_o) <= 1e-3 * v_o and abs(s_g - s_o) <= 1e-3 * s_o, (v_g, v_o, s_g, s_o)
+    # a camera: volume_render(gen_rays()) and volume_render_image run the same device function
+    pose = synthetic.pose_spherical(40.0, -25.0, 3.5)
+    cam = N.Camera.from_nerf_pose(pose, 120, 160, 150.0)
+    # ... whose rays are get_rays' (NeRF's OpenGL pose, pixel corners) up to the length of the direction
+    K = np.array([[150.0, 0, 80.0], [0, 150.0, 60.0], [0, 0, 1]])
+    ro, rd = N.get_rays(120, 160, K, gpu(np.asarray(pose, dtype=np.float32)[:3, :4]))
+    rd = rd.reshape(-1, 3)
+    gr = cam.gen_rays()
+    assert np.abs(cpu(gr.dirs) - cpu(rd / rd.norm(dim=-1, keepdim=True))).max() <= 2e-6
+    assert np.abs(cpu(gr.origins) - cpu(ro.reshape(-1, 3))).max() == 0
+    cam.cx, cam.fy = 77.5, 140.0
+    cr = cam.gen_rays()
+    img = grid.volume_render_image(cam)
+    assert img.shape == (120, 160, 3)
+    assert torch.equal(img.reshape(-1, 3), grid.volume_render(cr))
+    assert (img.reshape(-1, 3) != 1.0).any(dim=-1).float().mean() > 0.2      # the camera sees the grid
+    oo, dd = GO.gen_rays(cpu(cam.c2w), cam.fx_val, cam.fy_val, cam.cx_val, cam.cy_val, cam.width, cam.height)
+    assert np.array_equal(cpu(cr.origins), oo) and np.abs(cpu(cr.dirs) - dd).max() <= 2e-6
+
+
+def test_gen_rays_against_the_recorded_camera(N):
+    z = load_fixture()
+    fx, fy, cx, cy = z["cam_intrinsics"].tolist()
+    w, h = (int(v) for v in z["cam_size"])
+    for c2w in (torch.from_numpy(z["cam_c2w"]), gpu(z["cam_c2w"])):
+        r = N.Camera(c2w, fx=fx, fy=fy, cx=cx, cy=cy, width=w, height=h).gen_rays()
+        assert r.is_cuda and r.origins.shape == (w * h, 3)
+        assert np.array_equal(cpu(r.origins), z["cam_origins"])
+        assert np.abs(cpu(r.dirs) - z["cam_dirs"]).max() <= 2e-6
+    with pytest.raises(NotImplementedError, match="NDC"):
+        N.Camera(c2w, fx=fx, width=w, height=h, ndc_coeffs=(1.0, 1.0)).gen_rays()
+
+
+def test_in_place_write_to_links_drops_the_skip_data(N):
+    """(d): after accelerate(), a node written INTO links in place (the svox2 idiom grid.links[...] = row, also through an
+    alias) becomes kept in the middle of what the skip data calls empty space. The next render has to see it."""
+    z = load_fixture()
+    g = fixture_grid(z, "d")
+    g["density_data"] = np.concatenate([g["density_data"], np.full((1, 1), 30.0, np.float32)])
+    g["sh_data"] = np.concatenate([g["sh_data"], np.full((1, 27), 0.3, np.float32)])
+    grid = make_grid(N, g)
+    set_opt(grid, 1.0, 0.5, 0.0)
+    rays = N.Rays(gpu(z["d_origins"]), gpu(z["d_dirs"]))
+    grid.accelerate()
+    before = grid.volume_render(rays)
+    alias = grid.links
+    alias[12:52, 10, 12:52] = 1      # a slab of kept nodes far from the one kept node
+    assert not grid.accelerated
+    got = grid.volume_render(rays)
+    g2 = dict(g, links=cpu(alias))
+    fresh = make_grid(N, g2)
+    set_opt(fresh, 1.0, 0.5, 0.0)
+    want = fresh.volume_render(rays)
+    assert torch.equal(got, want)
+    assert (got != before).any(dim=-1).sum() > 50      # the slab is seen by many rays
+    grid.accelerate()
+    assert grid.accelerated and torch.equal(grid.volume_render(rays), want)
+    grid.links.view(-1)[5] = 7      # through a view, and out of range: the links are checked again
+    with pytest.raises(RuntimeError, match=">= capacity"):
+        grid.volume_render(rays)
+
+
+def test_degenerate_and_far_rays_end(N):
+    """A zero direction, NaN or infinity in a ray is a miss (background, log_transmit 0); a ray whose t is too large for
+    step_size to change it is left; both plain and accelerated, and the oracle states the same."""
+    z = load_fixture()
+    g = fixture_grid(z, "a")
+    grid = make_grid(N, g)
+    o, d = z["a_origins"][:64].copy(), z["a_dirs"][:64].copy()
+    d[0] = 0.0
+    d[1, 1] = np.nan
+    o[2, 0] = np.nan
+    d[3, 2] = np.inf
+    o[4, 1] = -np.inf
+    d[5] = [1e-30, 0.0, 0.0]      # the squared length underflows to zero
+    o[6] = g["center"] + np.array([3e7, 0.0, 0.0], np.float32)      # t ~ 3.6e8 grid units: t + 0.5 == t
+    d[6] = [-1.0, 0.0, 0.0]
+    o[7] = g["center"] + np.array([0.0, 2.0e4, 0.0], np.float32)    # far but marchable: beyond the range of the skip data
+    d[7] = [0.0, -1.0, 1e-6]
+    bad = np.arange(6)
+    for step in (0.5, 1e-3):
+        if step < 0.5:      # a thousand times the samples: a few rays are enough
+            keep = np.r_[0:8, 8:12]
+            o, d = o[keep], d[keep]
+        rays = N.Rays(gpu(o), gpu(d))
+        set_opt(grid, 0.25, step, 0.0)
+        want, want_logt = GO.render(g, o, d, step_size=step, background_brightness=0.25)
+        assert np.all(want[bad] == np.float32(0.25)) and np.all(want_logt[bad] == 0) and np.all(want[6] == np.float32(0.25))
+        first = None
+        for accelerated in (False, True):
+            if accelerated:
+                grid.accelerate()
+            got, logt = grid.volume_render(rays, return_log_transmit=True)
+            got, logt = cpu(got), cpu(logt)
+            assert np.all(got[bad] == np.float32(0.25)) and np.all(logt[bad] == 0.0)
+            assert np.all(got[6] == np.float32(0.25)) and logt[6] == 0.0
+            assert np.isfinite(got).all()
+            if step == 0.5:      # the bar of the fixture's renders plus what the default stop rule may drop
+                c_max = float((np.abs(g["sh_data"].reshape(-1, 3, 9)) * Y_MAX).sum(-1).max() + 0.5)
+                assert np.abs(got.astype(np.float64) - want).max() <= bar(z, "a") + 1e-7 * max(1.0, c_max), accelerated
+            first = got if first is None else first
+            assert np.array_equal(got, first)      # plain and accelerated: bit-identical
+        grid.links = grid.links
+    set_opt(grid, 1.0, 5e-4, 0.0)
+    with pytest.raises(RuntimeError, match="step_size"):
+        grid.volume_render(rays)
+
+
+# ---- 4. the single-node grid ----------------------------------------------------------------------------------------------
+def test_single_node_grid(N):
+    z = load_fixture()
+    g = fixture_grid(z, "d")
+    grid = make_grid(N, g)
+    o, d = z["d_origins"], z["d_dirs"]
+    rays = N.Rays(gpu(o), gpu(d))
+    set_opt(grid, 1.0, 0.5, 0.0)
+    plain = cpu(grid.volume_render(rays))
+    through = np.abs(z["d_bg1_rgb"] - 1.0).max(-1) > 1e-3
+    assert through.sum() >= 200
+    assert (np.abs(plain[through] - 1.0).max(-1) > 1e-3).all()
+    grid.accelerate()
+    acc = cpu(grid.volume_render(rays))
+    assert np.abs(acc.astype(np.float64) - plain).max() <= bar(z, "d")
+    v_acc, _ = grid.count_samples(rays=rays)
+    grid.links = grid.links
+    v_plain, _ = grid.count_samples(rays=rays)
+    assert v_acc * 5 < v_plain, (v_acc, v_plain)      # one node in 64^3: nearly everything is skipped
+    _, _, _, _, tmin, tmax, _ = GO.ray_setup(g, o, d)
+    miss = ~(tmin <= tmax)
+    assert miss.sum() >= 50
+    for bg in (1.0, 0.0, 0.25):
+        set_opt(grid, bg, 0.5, 0.0)
+        got, logt = grid.volume_render(rays, return_log_transmit=True)
+        assert np.all(cpu(got)[miss] == np.float32(bg)) and np.all(cpu(logt)[miss] == 0.0)
+
+
+# ---- 5. the bake ------------------------------------------------------------------------------------------------------------
+def _noviews_sd(sd, out_ch=5):
+    rng = np.random.default_rng(7)
+    out = {k: np.asarray(v) for k, v in sd.items() if k.startswith("pts_linears")}
+    out["views_linears.0.weight"] = np.ascontiguousarray(np.asarray(sd["views_linears.0.weight"])[:, :256])
+    out["views_linears.0.bias"] = np.asarray(sd["views_linears.0.bias"])
+    out["output_linear.weight"] = (rng.standard_normal((out_ch, 256)) * 0.05).astype(np.float32)
+    out["output_linear.bias"] = (rng.standard_normal(out_ch) * 0.1).astype(np.float32)
+    return out
+
+
+@pytest.mark.parametrize("precision", ["f16x2", "f32"])
+@pytest.mark.parametrize("views", [True, False])
+def test_bake(N, weights_pair, precision, views):
+    """links = the rule of the issue evaluated in numpy from the occupancy cells; density_data bit-identical to density_grid;
+    sh_data against P @ (sigmoid(raw) - 0.5) in fp64 from run_network's raw on the same (node, direction) pairs.
+
+    The bound per entry (k, channel), with u = 2^-24 and v_j = sigmoid(raw_j) - 0.5 in fp64:
+      (n_dirs + 1) u sum_j |P_kj| |v_j|   - the fp32 dot product of n_dirs terms (one rounding per product, one per sum:
+                                            the standard n u bound) plus the rounding of P itself to fp32 (u |P_kj|);
+      (2^-22 + 2^-25) sum_j |P_kj|        - the fp32 sigmoid 1 / (1 + expf(-x)): expf within 1 ulp (2^-23 relative), the
+                                            addition and the division one rounding each (2 u), so 2^-22 relative to a value
+                                            <= 1, and the subtraction of 0.5 at most half an ulp of 0.5 (2^-25)."""
+    ctx = N.get_context()
+    ctx.set_precision(precision)
+    try:
+        sd = weights_pair[1]
+        if views:
+            net = N.NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=4, skips=[4], use_viewdirs=True).load_state_dict(sd)
+        else:
+            net = N.NeRF(D=8, W=256, input_ch=63, input_ch_views=0, output_ch=5, skips=[4],
+                         use_viewdirs=False).load_state_dict(_noviews_sd(sd))
+        R, c1, c2 = [20, 24, 22], [-1.5, -1.4, -1.3], [1.5, 1.6, 1.2]
+        grid = N.SparseGrid.from_nerf(net, c1, c2, R, threshold=0.5, dilate=1, n_dirs=48, white_bkgd=False)
+        B, n_dirs = (9, 48) if views else (1, 1)
+        assert grid.basis_dim == B and grid.opt.background_brightness == 0.0
+        assert np.allclose(grid.radius.numpy(), [1.5, 1.5, 1.25]) and np.allclose(grid.center.numpy(), [0.0, 0.1, -0.05])
+        lo = [a + (b - a) / (2 * r) for a, b, r in zip(c1, c2, R)]
+        hi = [b - (b - a) / (2 * r) for a, b, r in zip(c1, c2, R)]
+        sigma = N.density_grid(net, lo, hi, R)
+        occ = N.OccupancyGrid.build(net, lo, hi, R, threshold=0.5, dilate=1, outside="empty")
+        cells = cpu(occ.cells())
+        assert np.array_equal(cells, np_cells([cpu(sigma)], threshold=0.5, dilate=1))
+        pad = np.zeros([r + 1 for r in R], bool)
+        pad[1:-1, 1:-1, 1:-1] = cells
+        kept = np.zeros(R, bool)
+        for a in (0, 1):
+            for b in (0, 1):
+                for c in (0, 1):
+                    kept |= pad[a:a + R[0], b:b + R[1], c:c + R[2]]
+        assert 0 < kept.sum() < kept.size
+        want_links = np.where(kept, np.cumsum(kept.reshape(-1)).reshape(R) - 1, -1).astype(np.int32)
+        assert np.array_equal(cpu(grid.links), want_links)
+        assert grid.capacity == int(kept.sum())
+        assert np.array_equal(cpu(grid.density_data)[:, 0], cpu(sigma)[kept])
+        # an occupancy grid passed in, on the lattice and off it
+        again = N.SparseGrid.from_nerf(net, c1, c2, R, occupancy=occ, n_dirs=48, white_bkgd=False)
+        assert torch.equal(again.links, grid.links) and torch.equal(again.sh_data, grid.sh_data)
+        with pytest.raises(ValueError, match="lattice"):
+            N.SparseGrid.from_nerf(net, c1, c2, R, occupancy=N.OccupancyGrid.build(net, c1, c2, R, outside="empty"))
+        # colours
+        axes = [np.linspace(l, h, n, dtype=np.float32) for l, h, n in zip(lo, hi, R)]
+        ii = np.argwhere(kept)
+        pts = np.stack([axes[0][ii[:, 0]], axes[1][ii[:, 1]], axes[2][ii[:, 2]]], -1)
+        # the directions and the projection, stated here on their own: the spherical Fibonacci lattice and pinv of the
+        # oracle's SH basis on it; the network through run_network on explicit (direction, node) pairs
+        i = np.arange(n_dirs, dtype=np.float64)
+        zc = 1.0 - (2.0 * i + 1.0) / n_dirs
+        rad, phi = np.sqrt(1.0 - zc * zc), i * np.pi * (3.0 - np.sqrt(5.0))
+        dirs = np.stack([rad * np.cos(phi), rad * np.sin(phi), zc], -1)
+        P = np.linalg.pinv(GO.sh_bases(B, dirs))
+        embed = N.get_embedder(10, 0)[0]
+        if views:
+            out = N.run_network(gpu(np.broadcast_to(pts[None], (n_dirs,) + pts.shape)), gpu(dirs.astype(np.float32)), net,
+                                embed, N.get_embedder(4, 0)[0])                          # [n_dirs, M, 4]
+            raw = cpu(out).astype(np.float64).transpose(1, 0, 2)
+        else:
+            raw = cpu(N.run_network(gpu(pts[:, None, :]), None, net, embed, None)).astype(np.float64)[..., :4]
+        assert raw.shape == (len(pts), n_dirs, 4)                                        # [M, n_dirs, 4]
+        v = 1.0 / (1.0 + np.exp(-raw[..., :3])) - 0.5                                   # [M, n_dirs, 3]
+        want = np.einsum("kj,mjc->mck", P, v).reshape(len(pts), 3 * B)
+        u = 2.0 ** -24
+        absP = np.abs(P)
+        bound = ((n_dirs + 1) * u * np.einsum("kj,mjc->mck", absP, np.abs(v)) +
+                 (2.0 ** -22 + 2.0 ** -25) * absP.sum(1)[None, None, :]).reshape(len(pts), 3 * B)
+        err = np.abs(cpu(grid.sh_data).astype(np.float64) - want)
+        print(f"bake views={views} {precision}: {len(pts)} nodes, sh_data max err {err.max():.3e}, worst err / bound "
+              f"{(err / bound).max():.3f}, |sh| max {np.abs(want).max():.3f}")
+        assert (err <= bound).all(), (err / bound).max()
+        # the baked grid renders, and an all-empty occupancy gives capacity 0 and the background
+        cam = N.Camera.from_nerf_pose(synthetic.pose_spherical(30.0, -30.0, 4.0), 40, 40, 55.0)
+        img = grid.volume_render_image(cam)
+        assert torch.isfinite(img).all() and (img != 0.0).any()
+        none = N.OccupancyGrid.from_mask(np.zeros([r - 1 for r in R], bool), lo, hi, outside="empty")
+        empty = N.SparseGrid.from_nerf(net, c1, c2, R, occupancy=none, n_dirs=48, white_bkgd=True)
+        assert empty.capacity == 0 and (cpu(empty.links) == -1).all() and empty.sh_data.shape == (0, 3 * B)
+        assert torch.equal(empty.volume_render_image(cam), torch.ones_like(img))
+        empty.accelerate()
+        assert torch.equal(empty.volume_render_image(cam), torch.ones_like(img))
+    finally:
+        ctx.set_precision("f16x2")
+
+
+# ---- 6. refusals --------------------------------------------------------------------------------------------------------
+def test_refusals(N):
+    z = load_fixture()
+    g = fixture_grid(z, "b")
+    links, dens, sh = gpu(g["links"]), gpu(g["density_data"]), gpu(g["sh_data"])
+    r, c = [1.0] * 3, [0.0] * 3
+    with pytest.raises(ValueError, match="basis_dim"):
+        N.SparseGrid.from_tensors(links, dens, gpu(np.zeros((len(g["density_data"]), 6), np.float32)), r, c)
+    bad = links.clone()
+    bad[3, 3, 3] = dens.shape[0]
+    with pytest.raises(RuntimeError, match=">= capacity"):
+        N.SparseGrid.from_tensors(bad, dens, sh, r, c)
+    with pytest.raises(ValueError, match="mismatched shapes"):
+        N.SparseGrid.from_tensors(links, dens[:-1].contiguous(), sh, r, c)
+    with pytest.raises(ValueError, match="mismatched shapes"):
+        N.SparseGrid.from_tensors(links, dens.reshape(-1), sh, r, c)
+    with pytest.raises(ValueError):
+        N.SparseGrid.from_tensors(links.reshape(-1), dens, sh, r, c)
+    with pytest.raises(RuntimeError, match="CPU"):
+        N.SparseGrid.from_tensors(links.cpu(), dens, sh, r, c)
+    with pytest.raises(RuntimeError, match="CPU"):
+        N.SparseGrid.from_tensors(links, dens.cpu(), sh, r, c)
+    with pytest.raises(TypeError, match="int32"):
+        N.SparseGrid.from_tensors(links.long(), dens, sh, r, c)
+    grid = N.SparseGrid.from_tensors(links, dens, sh, r, c)
+    rays = N.Rays(gpu(z["b_origins"]), gpu(z["b_dirs"]))
+    with pytest.raises(RuntimeError, match="CPU"):
+        grid.volume_render(N.Rays(rays.origins.cpu(), rays.dirs))
+    with pytest.raises(ValueError):
+        grid.volume_render(N.Rays(rays.origins, rays.dirs[:-1]))
+    with pytest.raises(RuntimeError, match="CPU"):
+        grid.sample(rays.origins.cpu())
+    for field, value, what in (("backend", "nvol", "cuvol"), ("backend", "svox1", "cuvol"), ("last_sample_opaque", True, "opaque"),
+                               ("use_spheric_clip", True, "spheric")):
+        grid.opt = N.RenderOptions(**{field: value})
+        with pytest.raises(NotImplementedError, match=what):
+            grid.volume_render(rays)
+    grid.opt = N.RenderOptions()
+    with pytest.raises(NotImplementedError, match="randomize"):
+        grid.volume_render(rays, randomize=True)
+    with pytest.raises(NotImplementedError, match="PyTorch"):
+        grid.volume_render(rays, use_kernel=False)
+    with pytest.raises(NotImplementedError, match="gradients"):
+        grid.volume_render(N.Rays(rays.origins.clone().requires_grad_(), rays.dirs))
+    grid.density_data = dens.clone().requires_grad_()
+    with pytest.raises(NotImplementedError, match="gradients"):
+        grid.volume_render(rays)
+    grid.density_data = dens
+    grid.opt.step_size = 0.0
+    with pytest.raises(RuntimeError, match="step_size"):
+        grid.volume_render(rays)
+    grid.opt = N.RenderOptions()
+    for name in ("volume_render_fused", "resample", "tv", "optim_density_step", "to_svox1"):
+        with pytest.raises(NotImplementedError, match=name):
+            getattr(grid, name)()
+    assert torch.isfinite(grid.volume_render(rays)).all()      # and the object is still usable
+
+
+def test_constructor_save_load_round_trip(N, tmp_path):
+    """svox2's constructor (dense, sphere bound, z order) and the .npz layout, through the device."""
+    g = N.SparseGrid(reso=[8, 10, 12], radius=[1.0, 1.2, 0.8], center=[0.0, 0.1, 0.0], basis_dim=4)
+    assert g.capacity == 960 and g.links.shape == (8, 10, 12) and g.sh_data.shape == (960, 12) and g.shape == [8, 10, 12, 13]
+    assert torch.equal(g.links.flatten(), torch.arange(960, device="cuda", dtype=torch.int32))
+    s = N.SparseGrid(reso=16, use_sphere_bound=True, use_z_order=True)
+    kept = s.links >= 0
+    assert 0.4 < kept.float().mean() < 0.7 and s.capacity == int(kept.sum()) and s.accelerated
+    assert sorted(cpu(s.links[kept]).tolist()) == list(range(s.capacity))
+    zo = N.SparseGrid(reso=4, use_z_order=True, basis_dim=1)
+    assert int(zo.links[1, 0, 0]) == 4 and int(zo.links[0, 1, 0]) == 2 and int(zo.links[0, 0, 1]) == 1 and int(zo.links[3, 3, 3]) == 63
+    pts = torch.tensor([[0.0, 0.1, 0.0], [-1.0, -1.1, -0.8], [1.0, 1.3, 0.8]], device="cuda")
+    gp = g.world2grid(pts)
+    assert np.allclose(cpu(gp), [[3.5, 4.5, 5.5], [-0.5, -0.5, -0.5], [7.5, 9.5, 11.5]], atol=1e-5)
+    assert np.allclose(cpu(g.grid2world(gp)), cpu(pts), atol=1e-6)
+    # fill, save, load: sh_data goes through fp16
+    rng = np.random.default_rng(3)
+    z = load_fixture()
+    f = fixture_grid(z, "b")
+    grid = make_grid(N, f)
+    grid.opt.background_brightness = 0.0
+    rays = N.Rays(gpu(z["b_origins"]), gpu(z["b_dirs"]))
+    path = str(tmp_path / "grid.npz")
+    grid.save(path, compress=True)
+    back = N.SparseGrid.load(path)
+    assert back.basis_dim == 4 and back.capacity == grid.capacity and not back.accelerated
+    assert torch.equal(back.density_data, grid.density_data)
+    assert torch.equal(back.links >= 0, grid.links >= 0) and int(back.links.min()) == -1
+    assert torch.equal(back.sh_data, grid.sh_data.half().float())
+    back.opt.background_brightness = 0.0
+    grid.sh_data = grid.sh_data.half().float()
+    assert torch.equal(back.volume_render(rays), grid.volume_render(rays))
+    # a file in the reference's layouts, written with numpy: the current one and the legacy `data` key
+    dens, sh = f["density_data"], f["sh_data"].astype(np.float16)
+    np.savez(str(tmp_path / "ref.npz"), radius=f["radius"], center=f["center"], links=f["links"], density_data=dens, sh_data=sh,
+             basis_type=1)
+    np.savez(str(tmp_path / "legacy.npz"), radius=f["radius"], center=f["center"], links=f["links"],
+             data=np.concatenate([dens, sh.astype(np.float32)], 1))
+    for name in ("ref.npz", "legacy.npz"):
+        got = N.SparseGrid.load(str(tmp_path / name), device="cuda")
+        got.opt.background_brightness = 0.0
+        assert torch.equal(got.sh_data, grid.sh_data) and torch.equal(got.volume_render(rays), grid.volume_render(rays))
+    del rng
