@@ -592,8 +592,11 @@ int nerf_render_frame_occ(nerf_ctx* ctx, const nerf_frame_args* args, const nerf
  *   density_data [dev] float [capacity, 1]
  *   sh_data      [dev] float [capacity, 3 * basis_dim], channel-major: [r_0 .. r_(B-1), g_0 .., b_0 ..]
  * The three arrays are BORROWED: the grid keeps the pointers, the caller keeps the memory alive and unchanged in size until
- * nerf_grid_destroy. Values may change between calls (stream order); after a change of `links` call nerf_grid_accelerate
- * again or nerf_grid_drop_skip - skip data made from other links is wrong. nerf_grid_create checks every link against
+ * nerf_grid_destroy. Values may change between calls (stream order) - nerf_grid_optim_step is how training changes them: the
+ * grid holds const pointers, the optimiser writes through the caller's own non-const pointers to the same memory, and the next
+ * call on the grid reads the new values. After a change of `links` call nerf_grid_accelerate
+ * again or nerf_grid_drop_skip - skip data made from other links is wrong (skip data depends on `links` alone: it stays
+ * valid across optimiser steps). nerf_grid_create checks every link against
  * `capacity` on the device and synchronises `stream`; as a second line the kernels read a link >= capacity as empty.
  * Geometry: the grid covers center -+ radius; node i of axis a sits at the voxel centre
  * center - radius + (i + 0.5) * 2 radius / reso (grid coordinate i; the box is [-0.5, reso - 0.5]).
@@ -706,6 +709,103 @@ typedef struct nerf_grid_project_args {
     void* stream;
 } nerf_grid_project_args;
 int nerf_grid_project_sh(nerf_ctx* ctx, const nerf_grid_project_args* args);
+
+/* Sparse voxel grid: training ---------------------------------------------------------------------
+ * The optimising half of svox2.SparseGrid: the fused render + MSE backward (volume_render_cuvol_fused without background
+ * layers), the total-variation gradient over a range of cells (tv_grad_sparse_kernel) and the masked RMSProp / SGD step.
+ * All three are stream-ordered and synchronise nothing. Gradients ACCUMULATE: the caller zeroes grad_density [capacity, 1],
+ * grad_sh [capacity, 3 * basis_dim] and mask [capacity] (bytes) when a new step begins.
+ *
+ * nerf_grid_fused_backward renders n_rays rays exactly as nerf_grid_render_rays does - rgb_out (and log_transmit) are
+ * bit-identical to that call's, with and without skip data - and adds the gradients of
+ *   loss = mean over rays and channels of (rgb_out - rgb_gt)^2
+ * with respect to density_data and sh_data. Every ray is marched a second time over the same sample lattice (the same fp32
+ * additions of t, the same sigma_thresh and stop rules, the same skip data); fp32, each operation rounded, in this order -
+ * except `remaining`, what the samples still to come add to the colour: it is the difference of two nearly equal sums, whose
+ * fp32 rounding (6e-8 of the colour) would be a relative 1e-3 of the small density gradients behind a bright sample, so it is
+ * carried in fp64:
+ *   g_c = (rgb_c - gt_c) * (2 / (3 n_rays))
+ *   remaining_c = the fp64 sum of the exact products weight * max(0, raw_c) of all shaded samples, plus exp(log_T) *
+ *                 background_brightness: rgb_c once more, without the rounding of its fp32 sum
+ *   at every shaded sample (sigma > sigma_thresh), with a, weight, log_T as in the render and raw_c = sum_k c_k Y_k + 0.5:
+ *     dot = (max(0, raw_0) g_0 + max(0, raw_1) g_1) + max(0, raw_2) g_2
+ *     remaining_c -= weight * max(0, raw_c)  (fp64, exact products);  accum = fp32(sum_c remaining_c g_c)  (svox2's accum)
+ *     d_sigma = (step_size * delta_scale) * (exp(log_T after the sample) * dot - accum)
+ *     d_coef(c, k) = (weight * Y_k) * g_c   where raw_c >= 0, else 0
+ *     at each of the 8 corners that is kept, with w8 = (w_x * w_y) * w_z its trilinear weight:
+ *       grad_density[row] += w8 * d_sigma;  grad_sh[row, c * B + k] += w8 * d_coef(c, k) (zero terms are not added);
+ *       mask[row] = 1 - for EVERY kept corner of EVERY shaded sample, whatever its weight (svox2's sparse_grad_indexer)
+ * A ray that misses the box or whose set-up is not finite writes its rgb_out (the background) and no gradient.
+ * The adds are float atomics (one hardware add each, no compare-and-swap): two calls on the same input agree to rounding of
+ * the sums, not bit for bit. beta_loss, sparsity_loss, background layers, randomize and last_sample_opaque are not built:
+ * NERF_E_INVALID naming the feature.
+ *
+ * nerf_grid_tv_grad: for the `count` nodes (start + i) mod X Y Z, i < count (svox2's contiguous random cells) and the columns
+ * [start_dim, end_dim) of the density or the SH table, with v000 the node's value and v100, v010, v001 its +x, +y, +z
+ * neighbours' (an empty or out-of-range node is 0 and receives nothing):
+ *   dx = v100 - v000, dy, dz likewise;  idelta = scale / sqrt(((1e-9 + dx dx) + dy dy) + dz dz)
+ *   dx *= X / 256, dy *= Y / 256, dz *= Z / 256
+ *   grad[v100] += dx * idelta, grad[v010] += dy * idelta, grad[v001] += dz * idelta, grad[v000] += -((dx + dy) + dz) * idelta
+ * each only if the value added is not zero, and then mask[row] = 1. ignore_edge, ignore_last_z and NDC are not built.
+ *
+ * nerf_grid_optim_step: elementwise over data [rows, cols] in the rows whose mask byte is set; other rows, and their rms,
+ * are not touched. fp32, each operation correctly rounded, in this order:
+ *   RMSProp: g2 = g * g;  rms = (rms == 0) ? g2 : g2 + beta * (rms - g2);
+ *            data = max(data - (lr * g) / (sqrt(rms) + eps), minval)
+ *   SGD:     data = max(data - lr * g, minval)
+ * (svox2 passes minval = -1e9 for densities and colours). `data` is normally the grid's own density_data or sh_data. */
+typedef struct nerf_grid_fused_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]                                                                */
+    const float* dirs;          /* [dev] [n_rays, 3], need not be unit                                              */
+    const float* rgb_gt;        /* [dev] [n_rays, 3]                                                                */
+    int64_t n_rays;             /* 0: nothing is done                                                               */
+    float* rgb_out;             /* [dev] [n_rays, 3]                                                                */
+    float* log_transmit;        /* [dev] [n_rays] or NULL                                                           */
+    float* grad_density;        /* [dev] [capacity, 1], added to                                                    */
+    float* grad_sh;             /* [dev] [capacity, 3 * basis_dim], added to                                        */
+    uint8_t* mask;              /* [dev] [capacity]                                                                 */
+    float beta_loss;            /* must be 0 (not built)                                                            */
+    float sparsity_loss;        /* must be 0 (not built)                                                            */
+    int32_t background_nlayers; /* must be 0 (not built)                                                            */
+    int32_t use_skip;           /* 1: use the skip data if nerf_grid_accelerate made it                             */
+    void* stream;
+} nerf_grid_fused_args;
+
+#define NERF_GRID_TV_DENSITY 0
+#define NERF_GRID_TV_SH 1
+typedef struct nerf_grid_tv_args {
+    size_t struct_size;
+    int32_t target;             /* NERF_GRID_TV_DENSITY / NERF_GRID_TV_SH: the grid's table that is differentiated   */
+    int32_t start_dim, end_dim; /* columns of that table                                                            */
+    int64_t start, count;       /* nodes (start + i) mod X Y Z; 0 <= start < X Y Z, 0 <= count <= X Y Z              */
+    float scale;
+    int32_t ignore_edge;        /* must be 0 (not built)                                                            */
+    int32_t ignore_last_z;      /* must be 0 (not built)                                                            */
+    int32_t use_ndc;            /* must be 0 (not built)                                                            */
+    float* grad;                /* [dev] shaped like the table, added to                                            */
+    uint8_t* mask;              /* [dev] [capacity]                                                                 */
+    void* stream;
+} nerf_grid_tv_args;
+
+#define NERF_GRID_OPTIM_RMSPROP 0
+#define NERF_GRID_OPTIM_SGD 1
+typedef struct nerf_grid_optim_args {
+    size_t struct_size;
+    float* data;                /* [dev] [rows, cols], updated in place                                             */
+    float* rms;                 /* [dev] [rows, cols] running mean of g^2 (RMSProp; may be NULL for SGD)             */
+    const float* grad;          /* [dev] [rows, cols]                                                               */
+    const uint8_t* mask;        /* [dev] [rows]                                                                     */
+    int64_t rows;
+    int32_t cols;
+    int32_t kind;               /* NERF_GRID_OPTIM_RMSPROP / NERF_GRID_OPTIM_SGD                                    */
+    float beta, lr, eps, minval;
+    void* stream;
+} nerf_grid_optim_args;
+
+int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_fused_args* args);
+int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* args);
+int nerf_grid_optim_step(nerf_ctx* ctx, const nerf_grid_optim_args* args);
 
 #ifdef __cplusplus
 }

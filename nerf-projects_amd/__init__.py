@@ -18,5 +18,7 @@ from .mesh import density_grid, marching_cubes, marching_cubes_volume, save_obj 
 from .occupancy import OccupancyGrid  # noqa: F401
 from . import grid  # noqa: F401
 from .grid import Camera, Rays, RenderOptions, SparseGrid  # noqa: F401
+from . import grid_train  # noqa: F401
+from .grid_train import GridTrainer  # noqa: F401
 
 __version__ = "0.1.0"

@@ -26,10 +26,13 @@ EXPORTS = (
     "nerf_occupancy_stats", "nerf_render_rays_occ", "nerf_render_frame_occ",
     "nerf_grid_create", "nerf_grid_destroy", "nerf_grid_render_rays", "nerf_grid_render_image", "nerf_grid_gen_rays",
     "nerf_grid_sample", "nerf_grid_accelerate", "nerf_grid_drop_skip", "nerf_grid_has_skip", "nerf_grid_project_sh",
+    "nerf_grid_fused_backward", "nerf_grid_tv_grad", "nerf_grid_optim_step",
 )
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
 NERF_GUARD_OFF, NERF_GUARD_REPORT, NERF_GUARD_FALLBACK = 0, 1, 2
 NERF_OCC_EVALUATE, NERF_OCC_EMPTY = 0, 1
+NERF_GRID_TV_DENSITY, NERF_GRID_TV_SH = 0, 1
+NERF_GRID_OPTIM_RMSPROP, NERF_GRID_OPTIM_SGD = 0, 1
 
 
 class NerfArch(C.Structure):
@@ -154,6 +157,25 @@ class GridSampleArgs(_Sized):
 class GridProjectArgs(_Sized):
     _fields_ = [("struct_size", C.c_size_t), ("raw", _FP), ("m", C.c_int64), ("n_dirs", C.c_int32), ("basis_dim", C.c_int32),
                 ("P", _FP), ("sh_out", _FP), ("row0", C.c_int64), ("stream", C.c_void_p)]
+
+
+class GridFusedArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("rgb_gt", _FP), ("n_rays", C.c_int64),
+                ("rgb_out", _FP), ("log_transmit", _FP), ("grad_density", _FP), ("grad_sh", _FP), ("mask", _FP),
+                ("beta_loss", C.c_float), ("sparsity_loss", C.c_float), ("background_nlayers", C.c_int32),
+                ("use_skip", C.c_int32), ("stream", C.c_void_p)]
+
+
+class GridTvArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("target", C.c_int32), ("start_dim", C.c_int32), ("end_dim", C.c_int32),
+                ("start", C.c_int64), ("count", C.c_int64), ("scale", C.c_float), ("ignore_edge", C.c_int32),
+                ("ignore_last_z", C.c_int32), ("use_ndc", C.c_int32), ("grad", _FP), ("mask", _FP), ("stream", C.c_void_p)]
+
+
+class GridOptimArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("data", _FP), ("rms", _FP), ("grad", _FP), ("mask", _FP), ("rows", C.c_int64),
+                ("cols", C.c_int32), ("kind", C.c_int32), ("beta", C.c_float), ("lr", C.c_float), ("eps", C.c_float),
+                ("minval", C.c_float), ("stream", C.c_void_p)]
 
 
 _lib = None
@@ -292,6 +314,12 @@ def load():
     lib.nerf_grid_has_skip.argtypes = [vp]
     lib.nerf_grid_project_sh.restype = i32
     lib.nerf_grid_project_sh.argtypes = [vp, C.POINTER(GridProjectArgs)]
+    lib.nerf_grid_fused_backward.restype = i32
+    lib.nerf_grid_fused_backward.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridFusedArgs)]
+    lib.nerf_grid_tv_grad.restype = i32
+    lib.nerf_grid_tv_grad.argtypes = [vp, C.POINTER(GridTvArgs)]
+    lib.nerf_grid_optim_step.restype = i32
+    lib.nerf_grid_optim_step.argtypes = [vp, C.POINTER(GridOptimArgs)]
     _lib = lib
     return lib
 

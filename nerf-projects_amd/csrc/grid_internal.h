@@ -1,4 +1,5 @@
-// Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what grid_api.cpp and grid_kernels.hip share.
+// Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what grid_api.cpp, grid_train_api.cpp, grid_kernels.hip and
+// grid_train_kernels.hip share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,6 +47,44 @@ struct GridRender {
     float* log_transmit;
     unsigned long long* counters;
 };
+
+// ---- training (grid_train_kernels.hip) ----
+struct GridFused {
+    const float* origins;
+    const float* dirs;
+    const float* rgb_gt;
+    int64_t n_rays;
+    float grad_scale;                  // 2 / (3 n_rays)
+    float* rgb;
+    float* log_transmit;               // or nullptr
+    float* grad_density;               // [capacity, 1], added to
+    float* grad_sh;                    // [capacity, 3 B], added to
+    uint8_t* mask;                     // [capacity], 1 stored at every kept corner of every shaded sample
+};
+
+struct GridTv {
+    const float* data;                 // the table differentiated: [capacity, cols]
+    float* grad;
+    uint8_t* mask;
+    int64_t start, count;              // cells (start + i) mod X Y Z, i < count
+    int32_t cols, start_dim, end_dim;
+    float scale;
+    float axis_scale[3];               // reso / 256
+};
+
+struct GridOptim {
+    float* data;
+    float* rms;                        // RMSProp only
+    const float* grad;
+    const uint8_t* mask;
+    int64_t rows;
+    int32_t cols;
+    float beta, lr, eps, minval;
+};
+
+hipError_t launch_grid_fused(const GridDev& g, const GridRenderOpt& o, const GridFused& r, hipStream_t s);
+hipError_t launch_grid_tv_grad(const GridDev& g, const GridTv& a, hipStream_t s);
+hipError_t launch_grid_optim_step(const GridOptim& a, int rmsprop, hipStream_t s);
 
 hipError_t launch_grid_render(const GridDev& g, const GridRenderOpt& o, const GridRender& r, hipStream_t s);
 hipError_t launch_grid_gen_rays(const GridCam& cam, float* origins, float* dirs, hipStream_t s);

@@ -14,33 +14,10 @@
 // the kernel is bound by the dependent link -> row loads, and waves in flight are what hides them.
 #include <algorithm>
 
-#include "grid_internal.h"
+#include "grid_device.h"
 
 namespace nerf {
 namespace {
-
-constexpr int kGridThreads = 256;
-
-__device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
-
-template <int B> struct GroupLanes { static constexpr int value = B == 9 ? 32 : (B == 4 ? 16 : 4); };
-
-// svox2 utils.eval_sh_bases, fp32, the reference's operation order
-__device__ __forceinline__ float sh_basis(int k, float x, float y, float z) {
-    switch (k) {
-        case 0: return 0.28209479177387814f;
-        case 1: return mul(-0.4886025119029199f, y);
-        case 2: return mul(0.4886025119029199f, z);
-        case 3: return mul(-0.4886025119029199f, x);
-        case 4: return mul(1.0925484305920792f, mul(x, y));
-        case 5: return mul(-1.0925484305920792f, mul(y, z));
-        case 6: return mul(0.31539156525252005f, sub(sub(mul(2.0f, mul(z, z)), mul(x, x)), mul(y, y)));
-        case 7: return mul(-1.0925484305920792f, mul(x, z));
-        default: return mul(0.5462742152960396f, sub(mul(x, x), mul(y, y)));
-    }
-}
 
 // svox2 Camera.gen_rays without NDC: fp64, rounded to fp32 at the end
 __device__ __forceinline__ void camera_ray(const GridCam& c, int64_t pix, float o[3], float d[3]) {
@@ -72,34 +49,6 @@ __global__ __launch_bounds__(kGridThreads) void grid_gen_rays_kernel(GridCam cam
     }
 }
 
-// base cell and weights of a position in grid coordinates (clamped to the node range): the reference's trilerp set-up
-__device__ __forceinline__ void cell_of(float p, int size, int& l, float& wb) {
-    p = fminf(fmaxf(p, 0.0f), (float)(size - 1));
-    l = min((int)p, size - 2);
-    wb = sub(p, (float)l);
-}
-
-// z, then y, then x; wa = 1 - wb (svox2.py:748-755)
-__device__ __forceinline__ float trilerp(const float v[8], const float wa[3], const float wb[3]) {
-    const float c00 = add(mul(v[0], wa[2]), mul(v[1], wb[2]));
-    const float c01 = add(mul(v[2], wa[2]), mul(v[3], wb[2]));
-    const float c10 = add(mul(v[4], wa[2]), mul(v[5], wb[2]));
-    const float c11 = add(mul(v[6], wa[2]), mul(v[7], wb[2]));
-    const float c0 = add(mul(c00, wa[1]), mul(c01, wb[1]));
-    const float c1 = add(mul(c10, wa[1]), mul(c11, wb[1]));
-    return add(mul(c0, wa[0]), mul(c1, wb[0]));
-}
-
-// the 8 links of base cell `base` (corner order 000, 001, 010, ..., 111 = x, y, z bits); anything outside [0, capacity) is -1
-__device__ __forceinline__ void load_links(const GridDev& g, int base, int lk[8]) {
-    const int sy = g.size[2], sx = g.size[1] * g.size[2];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int v = g.links[base + ((c >> 2) & 1) * sx + ((c >> 1) & 1) * sy + (c & 1)];
-        lk[c] = (v >= 0 && (int64_t)v < g.capacity) ? v : -1;
-    }
-}
-
 template <int B, bool IMAGE, bool SKIP, bool COUNT>
 __global__ __launch_bounds__(kGridThreads) void grid_render_kernel(GridDev g, GridRenderOpt opt, GridRender r) {
     constexpr int GL = GroupLanes<B>::value;
@@ -111,103 +60,47 @@ __global__ __launch_bounds__(kGridThreads) void grid_render_kernel(GridDev g, Gr
     const int col = busy ? lane : 0;  // idle lanes of a group read column 0 and contribute nothing
     const int k = col % B;
 
-    float o[3], d[3];
+    GridRay rs;
     if (IMAGE) {
-        camera_ray(r.cam, ray, o, d);
+        camera_ray(r.cam, ray, rs.o, rs.d);
     } else {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            o[i] = r.origins[ray * 3 + i];
-            d[i] = r.dirs[ray * 3 + i];
+            rs.o[i] = r.origins[ray * 3 + i];
+            rs.d[i] = r.dirs[ray * 3 + i];
         }
     }
-    // ---- ray set-up (svox2.py:662-693) ----
-    const float dn = sqrtf(add(add(mul(d[0], d[0]), mul(d[1], d[1])), mul(d[2], d[2])));
-    float v[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        o[i] = add(g.offset[i], mul(o[i], g.scaling[i]));
-        v[i] = d[i] / dn;
-        d[i] = mul(v[i], g.scaling[i]);
-    }
-    const float delta_scale = 1.0f / sqrtf(add(add(mul(d[0], d[0]), mul(d[1], d[1])), mul(d[2], d[2])));
-    float tmin = -1e9f, tmax = 1e9f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        d[i] = mul(d[i], delta_scale);
-        const float inv = 1.0f / d[i];
-        const float t1 = mul(sub(-0.5f, o[i]), inv);
-        const float t2 = mul(sub((float)g.size[i] - 0.5f, o[i]), inv);
-        const bool flat = d[i] == 0.0f;
-        tmin = fmaxf(tmin, flat ? -1e9f : fminf(t1, t2));
-        tmax = fminf(tmax, flat ? 1e9f : fmaxf(t1, t2));
-    }
-    tmin = fmaxf(tmin, opt.near_clip);
-    const float yk = busy ? sh_basis(k, v[0], v[1], v[2]) : 0.0f;
-    // A ray is marched only if its set-up is finite: a zero, NaN or infinite direction or origin is a miss (background,
-    // log_transmit 0), whatever fminf / fmaxf made of the NaNs above.
-    bool ok = dn > 0.0f && isfinite(dn) && isfinite(delta_scale) && isfinite(tmin) && isfinite(tmax);
-    float reach_o = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        ok = ok && isfinite(o[i]) && isfinite(d[i]);
-        reach_o = fmaxf(reach_o, fabsf(o[i]));
-    }
-    // the skip proof (header) needs positions exact to 1/16: |o|, |t| < 2^17 grid units; farther rays march plainly
-    const bool skip_ok = SKIP && reach_o < kGridSkipMaxT && fabsf(tmin) < kGridSkipMaxT && fabsf(tmax) < kGridSkipMaxT;
+    setup_ray<SKIP>(g, opt, rs);
+    const float yk = busy ? sh_basis(k, rs.v[0], rs.v[1], rs.v[2]) : 0.0f;
 
     float outv = 0.0f, log_t = 0.0f;
     unsigned long long visited = 0, shaded = 0;
-    if (ok && tmin <= tmax) {
+    if (rs.ok && rs.tmin <= rs.tmax) {
         const float neg_step = -opt.step_size;
-        float t = tmin;
-        while (t <= tmax) {
+        float t = rs.tmin;
+        while (t <= rs.tmax) {
             // the march ends unconditionally: every pass through this loop advances t by at least one addition of
             // step_size, and a ray whose t no longer changes under that addition (t so large that step_size is below half
             // an ulp) is left at once
             const float t_next = add(t, opt.step_size);
             if (!(t_next > t)) break;
-            int l[3];
             float wa[3], wb[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                cell_of(add(o[i], mul(t, d[i])), g.size[i], l[i], wb[i]);
-                wa[i] = sub(1.0f, wb[i]);
-            }
-            const int base = (l[0] * g.size[1] + l[1]) * g.size[2] + l[2];
+            const int base = march_cell(g, rs, t, wa, wb);
             if (SKIP) {
-                const int sv = skip_ok ? g.skip[base] : 0;
+                const int sv = rs.skip_ok ? g.skip[base] : 0;
                 if (sv > 0) {
-                    // every node within sv - 1 cells of this cell's corners is empty: so are this sample and every later
-                    // one whose t (the accumulated value itself, no estimate of it) is within sv - 1 - 1/16 of this one's
-                    const float t0 = t, reach = (float)(sv - 1) - 0.0625f;
-                    t = t_next;
-                    while (sub(t, t0) <= reach) {
-                        const float tn = add(t, opt.step_size);
-                        if (!(tn > t)) break;
-                        t = tn;
-                    }
+                    t = skip_jump(t, t_next, sv, opt.step_size);
                     continue;
                 }
             }
             if (COUNT) ++visited;      // samples whose links are loaded
             int lk[8];
             load_links(g, base, lk);
-            float cv[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) cv[c] = lk[c] >= 0 ? g.density[lk[c]] : 0.0f;
-            const float sigma = trilerp(cv, wa, wb);
+            const float sigma = sample_sigma(g, lk, wa, wb);
             if (sigma > opt.sigma_thresh) {
                 if (COUNT) ++shaded;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) cv[c] = lk[c] >= 0 ? g.sh[(int64_t)lk[c] * (3 * B) + col] : 0.0f;
-                float part = mul(yk, trilerp(cv, wa, wb));
-#pragma unroll
-                for (int off = 1; off < B; off <<= 1) {
-                    const float up = __shfl_down(part, off);
-                    if (k + off < B) part = add(part, up);
-                }
-                const float a = mul(mul(neg_step, sigma), delta_scale);
+                const float part = shade_channel<B>(g, lk, wa, wb, col, k, yk);
+                const float a = mul(mul(neg_step, sigma), rs.delta_scale);
                 const float weight = mul(expf(log_t), sub(1.0f, expf(a)));
                 outv = add(outv, mul(weight, fmaxf(add(part, 0.5f), 0.0f)));
                 log_t = add(log_t, a);

@@ -1,0 +1,173 @@
+// C ABI of sparse voxel grid training (include/nerf_mi355x.h, "Sparse voxel grid: training"): argument checks and launches.
+// Every check that needs no device comes before the first dereference of a handle.
+#include <cmath>
+
+#include "ctx_internal.h"
+#include "grid_internal.h"
+
+using namespace nerf;
+
+namespace {
+
+#define TRAIN_CHECK_STRUCT(fn, ptr, type)                                                             \
+    do {                                                                                              \
+        if (!(ptr)) {                                                                                 \
+            set_error(fn ": " #type " is NULL");                                                      \
+            return NERF_E_INVALID;                                                                    \
+        }                                                                                             \
+        if ((ptr)->struct_size != sizeof(type)) {                                                     \
+            set_error(fn ": " #type ".struct_size = %zu, this library expects %zu", (ptr)->struct_size, sizeof(type)); \
+            return NERF_E_INVALID;                                                                    \
+        }                                                                                             \
+    } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* o, const nerf_grid_fused_args* a) {
+    const char* fn = "nerf_grid_fused_backward";
+    if (!grid) {
+        set_error("%s: NULL grid", fn);
+        return NERF_E_INVALID;
+    }
+    TRAIN_CHECK_STRUCT("nerf_grid_fused_backward", o, nerf_grid_render_options);
+    TRAIN_CHECK_STRUCT("nerf_grid_fused_backward", a, nerf_grid_fused_args);
+    if (o->last_sample_opaque) {
+        set_error("%s: last_sample_opaque is not built", fn);
+        return NERF_E_INVALID;
+    }
+    if (o->randomize) {
+        set_error("%s: randomize is not built", fn);
+        return NERF_E_INVALID;
+    }
+    if (a->beta_loss != 0.0f) {
+        set_error("%s: beta_loss is not built", fn);
+        return NERF_E_INVALID;
+    }
+    if (a->sparsity_loss != 0.0f) {
+        set_error("%s: sparsity_loss is not built", fn);
+        return NERF_E_INVALID;
+    }
+    if (a->background_nlayers != 0) {
+        set_error("%s: background layers are not built", fn);
+        return NERF_E_INVALID;
+    }
+    if (!(o->step_size >= 1e-3f) || !std::isfinite(o->step_size) || std::isnan(o->sigma_thresh) || std::isnan(o->stop_thresh) ||
+        !std::isfinite(o->background_brightness) || !std::isfinite(o->near_clip)) {
+        set_error("%s: step_size = %g must be finite and >= 1e-3, the thresholds not NaN, background_brightness and near_clip finite",
+                  fn, o->step_size);
+        return NERF_E_INVALID;
+    }
+    if (a->n_rays < 0 || a->n_rays > kGridMaxItems) {
+        set_error("%s: n_rays = %lld must be in [0, 2^26]", fn, (long long)a->n_rays);
+        return NERF_E_INVALID;
+    }
+    if (a->n_rays > 0 && (!a->origins || !a->dirs || !a->rgb_gt || !a->rgb_out || !a->grad_density || !a->grad_sh || !a->mask)) {
+        set_error("%s: origins, dirs, rgb_gt, rgb_out, grad_density, grad_sh and mask are required", fn);
+        return NERF_E_INVALID;
+    }
+    if (a->n_rays == 0) return NERF_OK;
+    GridFused r{};
+    r.origins = a->origins;
+    r.dirs = a->dirs;
+    r.rgb_gt = a->rgb_gt;
+    r.n_rays = a->n_rays;
+    r.grad_scale = 2.0f / (3.0f * (float)a->n_rays);
+    r.rgb = a->rgb_out;
+    r.log_transmit = a->log_transmit;
+    r.grad_density = a->grad_density;
+    r.grad_sh = a->grad_sh;
+    r.mask = a->mask;
+    const GridRenderOpt opt{o->step_size, o->sigma_thresh, o->stop_thresh, o->background_brightness, o->near_clip};
+    GridDev g = grid->g;
+    g.skip = a->use_skip ? grid->d_skip : nullptr;
+    DeviceGuard dg(grid->ctx->device);
+    HIP_TRY(launch_grid_fused(g, opt, r, (hipStream_t)a->stream));
+    return NERF_OK;
+}
+
+int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* a) {
+    const char* fn = "nerf_grid_tv_grad";
+    if (!grid) {
+        set_error("%s: NULL grid", fn);
+        return NERF_E_INVALID;
+    }
+    TRAIN_CHECK_STRUCT("nerf_grid_tv_grad", a, nerf_grid_tv_args);
+    if (a->ignore_edge || a->ignore_last_z || a->use_ndc) {
+        set_error("%s: ignore_edge, ignore_last_z and NDC scaling are not built", fn);
+        return NERF_E_INVALID;
+    }
+    if (a->target != NERF_GRID_TV_DENSITY && a->target != NERF_GRID_TV_SH) {
+        set_error("%s: target = %d must be NERF_GRID_TV_DENSITY or NERF_GRID_TV_SH", fn, a->target);
+        return NERF_E_INVALID;
+    }
+    if (!std::isfinite(a->scale)) {
+        set_error("%s: scale = %g must be finite", fn, a->scale);
+        return NERF_E_INVALID;
+    }
+    if (a->count > 0 && (!a->grad || !a->mask)) {
+        set_error("%s: grad and mask are required", fn);
+        return NERF_E_INVALID;
+    }
+    // ---- from here on the handle is read ----
+    const GridDev& g = grid->g;
+    const int64_t n = (int64_t)g.size[0] * g.size[1] * g.size[2];
+    const int cols = a->target == NERF_GRID_TV_DENSITY ? 1 : 3 * g.basis_dim;
+    if (a->start < 0 || a->start >= n || a->count < 0 || a->count > n) {
+        set_error("%s: start = %lld must be in [0, %lld) and count = %lld in [0, %lld]", fn, (long long)a->start, (long long)n,
+                  (long long)a->count, (long long)n);
+        return NERF_E_INVALID;
+    }
+    if (a->start_dim < 0 || a->end_dim > cols || a->start_dim > a->end_dim) {
+        set_error("%s: columns [%d, %d) outside [0, %d)", fn, a->start_dim, a->end_dim, cols);
+        return NERF_E_INVALID;
+    }
+    if (a->count == 0 || a->start_dim == a->end_dim || g.capacity == 0) return NERF_OK;
+    GridTv t{};
+    t.data = a->target == NERF_GRID_TV_DENSITY ? g.density : g.sh;
+    t.grad = a->grad;
+    t.mask = a->mask;
+    t.start = a->start;
+    t.count = a->count;
+    t.cols = cols;
+    t.start_dim = a->start_dim;
+    t.end_dim = a->end_dim;
+    t.scale = a->scale;
+    for (int k = 0; k < 3; ++k) t.axis_scale[k] = (float)g.size[k] * (1.0f / 256.0f);
+    DeviceGuard dg(grid->ctx->device);
+    HIP_TRY(launch_grid_tv_grad(g, t, (hipStream_t)a->stream));
+    return NERF_OK;
+}
+
+int nerf_grid_optim_step(nerf_ctx* c, const nerf_grid_optim_args* a) {
+    const char* fn = "nerf_grid_optim_step";
+    if (!c) {
+        set_error("%s: NULL context", fn);
+        return NERF_E_INVALID;
+    }
+    TRAIN_CHECK_STRUCT("nerf_grid_optim_step", a, nerf_grid_optim_args);
+    if (a->kind != NERF_GRID_OPTIM_RMSPROP && a->kind != NERF_GRID_OPTIM_SGD) {
+        set_error("%s: kind = %d must be NERF_GRID_OPTIM_RMSPROP or NERF_GRID_OPTIM_SGD", fn, a->kind);
+        return NERF_E_INVALID;
+    }
+    if (a->rows < 0 || a->rows > 0x7fffffffLL || a->cols < 1 || a->cols > 4096) {
+        set_error("%s: rows = %lld must be in [0, 2^31) and cols = %d in [1, 4096]", fn, (long long)a->rows, a->cols);
+        return NERF_E_INVALID;
+    }
+    if (a->rows > 0 && (!a->data || !a->grad || !a->mask || (a->kind == NERF_GRID_OPTIM_RMSPROP && !a->rms))) {
+        set_error("%s: data, grad, mask and (for RMSProp) rms are required", fn);
+        return NERF_E_INVALID;
+    }
+    if (std::isnan(a->lr) || std::isnan(a->minval) || (a->kind == NERF_GRID_OPTIM_RMSPROP && (std::isnan(a->beta) || std::isnan(a->eps)))) {
+        set_error("%s: lr, minval, beta and eps must not be NaN", fn);
+        return NERF_E_INVALID;
+    }
+    if (a->rows == 0) return NERF_OK;
+    GridOptim p{a->data, a->rms, a->grad, a->mask, a->rows, a->cols, a->beta, a->lr, a->eps, a->minval};
+    DeviceGuard dg(c->device);
+    HIP_TRY(launch_grid_optim_step(p, a->kind == NERF_GRID_OPTIM_RMSPROP, (hipStream_t)a->stream));
+    return NERF_OK;
+}
+
+}  // extern "C"

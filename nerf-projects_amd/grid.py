@@ -5,7 +5,8 @@ forward (inference) side: ``volume_render``, ``volume_render_image``, ``sample``
 ``.npz`` layout of Plenoxels checkpoints. ``SparseGrid.from_nerf`` bakes one of this package's ``NeRF`` models into a grid.
 The semantics of every call are stated in include/nerf_mi355x.h, "Sparse voxel grid"; everything runs in HIP kernels
 (csrc/grid_kernels.hip) and, as everywhere in this package, there is no CPU or PyTorch fallback. What svox2 has and this
-module does not (training, background layers, learned bases, the other backends) raises ``NotImplementedError``.
+module does not (background layers, learned bases, the other backends) raises ``NotImplementedError``; so do the svox2-named
+training methods on ``SparseGrid`` - training a grid is ``grid_train.GridTrainer``, under names of its own.
 """
 import ctypes as C
 from dataclasses import dataclass

@@ -1,0 +1,299 @@
+"""Sparse voxel grid training, the parts that need no GPU: the numpy restatement (tests/grid_train_oracle.py) against the
+reference's recorded gradients and its recorded RMSProp loop, the C ABI of the training entry points, and the generated code
+of csrc/grid_train_kernels.hip."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import grid_oracle as GO  # noqa: E402
+import grid_train_oracle as GT  # noqa: E402
+
+RENDER = os.path.join(ROOT, "tests", "golden", "grid_render.npz")
+TRAIN = os.path.join(ROOT, "tests", "golden", "grid_train.npz")
+GRIDS = ("a", "b", "c", "d")
+
+
+def fixture_grid(z, name):
+    return {"links": z[f"{name}_links"], "density_data": z[f"{name}_density"], "sh_data": z[f"{name}_sh"],
+            "radius": z[f"{name}_radius"], "center": z[f"{name}_center"]}
+
+
+def grad_bar(t, name, tag, key):
+    """3x the reference's own fp32 - fp64 distance, and no tighter than 1e-5 of the tensor's largest entry"""
+    want = t[f"{name}_{tag}_grad_{key}64"].astype(np.float64)
+    return want, max(3.0 * float(t[f"{name}_{tag}_grad_{key}_d_ref"]), 1e-5 * float(np.abs(want).max()))
+
+
+def test_fixture_holds_arrays_only_and_is_small():
+    assert os.path.getsize(TRAIN) < 1 << 20
+    t = np.load(TRAIN)      # (allow_pickle is off: arrays only)
+    for name in GRIDS:
+        assert t[f"{name}_rgb_gt"].shape == (1024, 3)
+        for tag in ("bg1", "bg0"):
+            assert t[f"{name}_{tag}_grad_density64"].shape[1] == 1
+    for name in ("b", "c"):
+        assert t[f"{name}_loop_idx"].shape == (20, 256) and t[f"{name}_loop_idx"].max() < 704
+        assert t[f"{name}_loop_params"].tolist() == [0.95, 1e-8, 1e-2, 1.0]
+        l32, l64 = t[f"{name}_loop_loss32"], t[f"{name}_loop_loss64"]
+        assert np.abs(l32 - l64).max() < 1e-3 * (l64[0] - l64[-1])      # a test of the optimisation, not of noise
+
+
+@pytest.mark.parametrize("name", GRIDS)
+def test_oracle_gradients_match_the_reference_autograd(name):
+    z, t = np.load(RENDER), np.load(TRAIN)
+    g = fixture_grid(z, name)
+    o, d, gt = z[f"{name}_origins"], z[f"{name}_dirs"], t[f"{name}_rgb_gt"]
+    skip = GO.skip_distances(g["links"])
+    for tag, bg in (("bg1", 1.0), ("bg0", 0.0)):
+        rgb, gd, gs, mask = GT.fused(g, o, d, gt, sigma_thresh=0.0, stop_thresh=0.0, background_brightness=bg)
+        fwd, _ = GO.render(g, o, d, sigma_thresh=0.0, stop_thresh=0.0, background_brightness=bg)
+        assert np.array_equal(rgb, fwd)      # the restatement walks the renderer's lattice
+        touched = np.zeros(mask.shape, dtype=bool)
+        for key, got in (("density", gd), ("sh", gs)):
+            want, tol = grad_bar(t, name, tag, key)
+            err = np.abs(got.astype(np.float64) - want)
+            print(f"grid {name} {tag} d/d{key}: oracle vs fp64 autograd max {err.max():.3e} (bar {tol:.3e}, max |g| {np.abs(want).max():.3e})")
+            assert err.max() <= tol, (name, tag, key, int(err.argmax()), err.max(), tol)      # every entry
+            touched |= (want != 0).any(-1)
+        assert np.array_equal(mask != 0, touched), (name, tag, int((mask != 0).sum()), int(touched.sum()))
+        # skip data changes no sample: the same colours and rows; the terms of a row's sum arrive in another order (rays
+        # that jump fall into other passes of the vectorised loop), so the sums agree to their fp32 rounding
+        rgb_s, gd_s, gs_s, mask_s = GT.fused(g, o, d, gt, sigma_thresh=0.0, stop_thresh=0.0, background_brightness=bg, skip=skip)
+        assert np.array_equal(rgb_s, rgb) and np.array_equal(mask_s, mask)
+        assert np.abs(gd_s - gd).max() <= 1e-5 * np.abs(gd).max() and np.abs(gs_s - gs).max() <= 1e-5 * np.abs(gs).max()
+    # gradients accumulate
+    _, gd2, gs2, _ = GT.fused(g, o, d, gt, sigma_thresh=0.0, stop_thresh=0.0, background_brightness=0.0, grad_density=gd.copy(),
+                              grad_sh=gs.copy(), mask=mask.copy())
+    assert np.abs(gd2 - 2 * gd).max() <= 1e-5 * np.abs(gd).max() and np.abs(gs2 - 2 * gs).max() <= 1e-5 * np.abs(gs).max()
+
+
+def numpy_loop(z, t, name):
+    """the 20 iterations of the fixture through the restatement: losses, final tables, per-iteration masks"""
+    g = fixture_grid(z, name)
+    g["density_data"] = (np.float32(0.5) * g["density_data"]).astype(np.float32)
+    g["sh_data"] = np.zeros_like(g["sh_data"])
+    beta, eps, lr_sh, lr_sigma = t[f"{name}_loop_params"].tolist()
+    o, d = z[f"{name}_origins"][:704], z[f"{name}_dirs"][:704]
+    target = z[f"{name}_bg1_rgb64"][:704].astype(np.float32)
+    rms_d, rms_s = np.zeros_like(g["density_data"]), np.zeros_like(g["sh_data"])
+    losses, masks = [], []
+    for k in t[f"{name}_loop_idx"]:
+        rgb, gd, gs, mask = GT.fused(g, o[k], d[k], target[k], sigma_thresh=0.0, stop_thresh=0.0)
+        losses.append(float(((rgb.astype(np.float64) - target[k]) ** 2).mean()))
+        GT.optim_step(g["density_data"], rms_d, gd, mask, "rmsprop", lr_sigma, beta, eps)
+        GT.optim_step(g["sh_data"], rms_s, gs, mask, "rmsprop", lr_sh, beta, eps)
+        masks.append(mask != 0)
+    return np.array(losses), g["density_data"], g["sh_data"], np.stack(masks)
+
+
+def loop_bars(t, name):
+    l32, l64 = t[f"{name}_loop_loss32"], t[f"{name}_loop_loss64"]
+    bars = {"loss": max(3.0 * float(np.abs(l32 - l64).max()), 1e-5 * float(l64[0]))}
+    for key in ("density", "sh"):
+        a32, a64 = t[f"{name}_loop_{key}32"].astype(np.float64), t[f"{name}_loop_{key}64"]
+        bars[key] = max(3.0 * float(np.abs(a32 - a64).max()), 1e-5 * float(np.abs(a64).max()))
+    return bars
+
+
+@pytest.mark.parametrize("name", ("b", "c"))
+def test_oracle_loop_matches_the_reference_loop(name):
+    z, t = np.load(RENDER), np.load(TRAIN)
+    losses, dens, sh, masks = numpy_loop(z, t, name)
+    bars = loop_bars(t, name)
+    l64 = t[f"{name}_loop_loss64"]
+    print(f"grid {name}: loss {losses[0]:.5f} -> {losses[-1]:.5f}; vs fp64 max {np.abs(losses - l64).max():.2e} (bar {bars['loss']:.2e}); "
+          f"density {np.abs(dens - t[name + '_loop_density64']).max():.2e} (bar {bars['density']:.2e}); "
+          f"sh {np.abs(sh - t[name + '_loop_sh64']).max():.2e} (bar {bars['sh']:.2e})")
+    assert losses[-1] < 0.7 * losses[0]
+    assert np.abs(losses - l64).max() <= bars["loss"]
+    assert np.abs(dens - t[f"{name}_loop_density64"]).max() <= bars["density"]
+    assert np.abs(sh - t[f"{name}_loop_sh64"]).max() <= bars["sh"]
+    want = np.unpackbits(t[f"{name}_loop_mask64"], axis=-1)[:, :masks.shape[1]].astype(bool)
+    assert np.array_equal(masks, want)      # the touched rows of every iteration
+
+
+def test_oracle_optimiser_and_tv_basics():
+    rng = np.random.default_rng(3)
+    data = rng.normal(size=(6, 4)).astype(np.float32)
+    rms = np.zeros_like(data)
+    rms[1] = 0.25
+    grad = rng.normal(size=(6, 4)).astype(np.float32)
+    mask = np.array([1, 1, 0, 0, 1, 0], dtype=np.uint8)
+    d0, r0 = data.copy(), rms.copy()
+    GT.optim_step(data, rms, grad, mask, "rmsprop", 0.1)
+    assert np.array_equal(data[mask == 0], d0[mask == 0]) and np.array_equal(rms[mask == 0], r0[mask == 0])
+    assert np.array_equal(rms[0], grad[0] * grad[0])      # first touch: rms = g^2, the step is lr * sign(g) up to eps
+    assert np.allclose(data[0], d0[0] - 0.1 * np.sign(grad[0]), atol=1e-6)
+    assert np.allclose(rms[1], grad[1] ** 2 + 0.95 * (0.25 - grad[1] ** 2), rtol=1e-6)
+    # TV: a constant field over fully kept nodes adds nothing; the four adds of a cell sum to rounding
+    links = np.arange(4 * 5 * 6, dtype=np.int32).reshape(4, 5, 6)
+    g = {"links": links, "density_data": np.full((120, 1), 3.0, np.float32), "sh_data": rng.normal(size=(120, 3)).astype(np.float32),
+         "radius": np.ones(3, np.float32), "center": np.zeros(3, np.float32)}
+    grad_d, m = np.zeros((120, 1), np.float32), np.zeros(120, np.uint8)
+    interior = links[1, 1, 1]
+    GT.tv_grad(g, "density", int(interior), 3, 0.5, grad_d, m)
+    assert not grad_d.any() and not m.any()
+    grad_s = np.zeros((120, 3), np.float32)
+    GT.tv_grad(g, "sh", int(interior), 1, 0.5, grad_s, m)
+    assert m.sum() == 4 and np.abs(grad_s.sum(0)).max() <= 1e-6 * np.abs(grad_s).max()
+    grad_w = np.zeros((120, 3), np.float32)
+    GT.tv_grad(g, "sh", 118, 5, 0.5, grad_w, m)      # wraps past the last node
+    assert grad_w[118].any() and grad_w[119].any() and grad_w[0].any() and grad_w[2].any() and not grad_w[40].any()
+
+
+# ---- C ABI ------------------------------------------------------------------------------------------------------------
+NEW_STRUCTS = {"nerf_grid_fused_args": "GridFusedArgs", "nerf_grid_tv_args": "GridTvArgs", "nerf_grid_optim_args": "GridOptimArgs"}
+NEW_SYMBOLS = ("nerf_grid_fused_backward", "nerf_grid_tv_grad", "nerf_grid_optim_step")
+
+
+def _header_struct_fields(name):
+    text = open(os.path.join(ROOT, "include", "nerf_mi355x.h")).read()
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if not decl:
+            continue
+        names = decl.split(",")
+        fields.append(re.search(r"(\w+)\s*(\[\d+\])?$", names[0].strip()).group(1))
+        for extra in names[1:]:
+            fields.append(re.search(r"(\w+)", extra.strip()).group(1))
+    return fields
+
+
+def test_training_structs_match_a_c_compile_of_the_header(tmp_path):
+    import nerf_projects_amd  # noqa: F401
+    from nerf_projects_amd import _lib
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nerf_mi355x.h"', "int main(void) {"]
+    for cname in NEW_STRUCTS:
+        lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
+        for f in _header_struct_fields(cname):
+            lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
+    lines += ['printf("consts tv %d\\n", NERF_GRID_TV_DENSITY * 10 + NERF_GRID_TV_SH);',
+              'printf("consts optim %d\\n", NERF_GRID_OPTIM_RMSPROP * 10 + NERF_GRID_OPTIM_SGD);', "return 0;", "}"]
+    src = tmp_path / "abi.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "abi"
+    cc = next(c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if subprocess.run(
+        ["sh", "-c", f"command -v {c}"], capture_output=True).returncode == 0)
+    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    seen = {}
+    for line in out.splitlines():
+        cname, f, v = line.split()
+        seen.setdefault(cname, {})[f] = int(v)
+    assert seen.pop("consts") == {"tv": _lib.NERF_GRID_TV_DENSITY * 10 + _lib.NERF_GRID_TV_SH,
+                                  "optim": _lib.NERF_GRID_OPTIM_RMSPROP * 10 + _lib.NERF_GRID_OPTIM_SGD}
+    for cname, pyname in NEW_STRUCTS.items():
+        cls = getattr(_lib, pyname)
+        assert C.sizeof(cls) == seen[cname].pop("size"), cname
+        assert [f[0] for f in cls._fields_] == _header_struct_fields(cname), cname
+        for f, off in seen[cname].items():
+            assert getattr(cls, f).offset == off, (cname, f)
+        assert cls().struct_size == C.sizeof(cls)
+
+
+def test_training_calls_refuse_bad_arguments_before_any_device_call():
+    """Every refusal here comes before a handle is dereferenced: the grid and context pointers are fakes."""
+    import nerf_projects_amd  # noqa: F401
+    from nerf_projects_amd import _lib
+    lib = _lib.load()
+    for s in NEW_SYMBOLS:
+        assert hasattr(lib, s) and s in _lib.EXPORTS
+    fake = C.c_void_p(0x1000)
+    err = lambda: lib.nerf_last_error().decode()      # noqa: E731
+    opt, a = _lib.GridRenderOptions(), _lib.GridFusedArgs()
+    opt.step_size, opt.background_brightness = 0.5, 1.0
+    assert lib.nerf_grid_fused_backward(None, C.byref(opt), C.byref(a)) == -1 and "NULL grid" in err()
+    assert lib.nerf_grid_fused_backward(fake, None, C.byref(a)) == -1 and "NULL" in err()
+    assert lib.nerf_grid_fused_backward(fake, C.byref(opt), None) == -1 and "NULL" in err()
+    a.struct_size -= 8
+    assert lib.nerf_grid_fused_backward(fake, C.byref(opt), C.byref(a)) == -1 and "struct_size" in err()
+    a = _lib.GridFusedArgs()
+    opt.struct_size += 4
+    assert lib.nerf_grid_fused_backward(fake, C.byref(opt), C.byref(a)) == -1 and "struct_size" in err()
+    for field, obj_name, value, word in (("last_sample_opaque", "opt", 1, "last_sample_opaque"), ("randomize", "opt", 1, "randomize"),
+                                         ("beta_loss", "a", 0.1, "beta_loss"), ("sparsity_loss", "a", 0.1, "sparsity_loss"),
+                                         ("background_nlayers", "a", 4, "background")):
+        opt, a = _lib.GridRenderOptions(), _lib.GridFusedArgs()
+        opt.step_size, opt.background_brightness = 0.5, 1.0
+        setattr(opt if obj_name == "opt" else a, field, value)
+        assert lib.nerf_grid_fused_backward(fake, C.byref(opt), C.byref(a)) == -1, field
+        assert word in err() and "not built" in err(), (field, err())
+    opt, a = _lib.GridRenderOptions(), _lib.GridFusedArgs()
+    opt.step_size, opt.background_brightness = 0.5, 1.0
+    a.n_rays = 4      # and no pointers
+    assert lib.nerf_grid_fused_backward(fake, C.byref(opt), C.byref(a)) == -1 and "required" in err()
+    a.n_rays = -1
+    assert lib.nerf_grid_fused_backward(fake, C.byref(opt), C.byref(a)) == -1 and "n_rays" in err()
+    a.n_rays = 0
+    assert lib.nerf_grid_fused_backward(fake, C.byref(opt), C.byref(a)) == 0      # zero rays: nothing is done
+
+    tv = _lib.GridTvArgs()
+    assert lib.nerf_grid_tv_grad(None, C.byref(tv)) == -1 and "NULL grid" in err()
+    assert lib.nerf_grid_tv_grad(fake, None) == -1 and "NULL" in err()
+    tv.struct_size = 0
+    assert lib.nerf_grid_tv_grad(fake, C.byref(tv)) == -1 and "struct_size" in err()
+    for field in ("ignore_edge", "ignore_last_z", "use_ndc"):
+        tv = _lib.GridTvArgs()
+        setattr(tv, field, 1)
+        assert lib.nerf_grid_tv_grad(fake, C.byref(tv)) == -1 and "not built" in err(), field
+    tv = _lib.GridTvArgs()
+    tv.target = 2
+    assert lib.nerf_grid_tv_grad(fake, C.byref(tv)) == -1 and "target" in err()
+    tv = _lib.GridTvArgs()
+    tv.count = 5      # and no grad / mask
+    assert lib.nerf_grid_tv_grad(fake, C.byref(tv)) == -1 and "required" in err()
+
+    op = _lib.GridOptimArgs()
+    assert lib.nerf_grid_optim_step(None, C.byref(op)) == -1 and "NULL context" in err()
+    assert lib.nerf_grid_optim_step(fake, None) == -1 and "NULL" in err()
+    op.struct_size += 8
+    assert lib.nerf_grid_optim_step(fake, C.byref(op)) == -1 and "struct_size" in err()
+    op = _lib.GridOptimArgs()
+    op.kind, op.cols = 7, 1
+    assert lib.nerf_grid_optim_step(fake, C.byref(op)) == -1 and "kind" in err()
+    op.kind, op.cols = 0, 0
+    assert lib.nerf_grid_optim_step(fake, C.byref(op)) == -1 and "cols" in err()
+    op.cols, op.rows = 3, 10      # and no pointers
+    assert lib.nerf_grid_optim_step(fake, C.byref(op)) == -1 and "required" in err()
+    op.rows = 0
+    assert lib.nerf_grid_optim_step(fake, C.byref(op)) == 0
+
+
+def test_grid_train_kernels_use_no_scratch_no_inline_assembly_and_no_compare_and_swap(tmp_path):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("nerf_build_for_grid_train", os.path.join(ROOT, "nerf-projects_amd", "build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    assert "grid_train_kernels.hip" in build.SOURCES and "grid_train_api.cpp" in build.SOURCES
+    assert any(h.endswith("grid_device.h") for h in build.HEADERS)
+    path = os.path.join(build.CSRC, "grid_train_kernels.hip")
+    for src in (path, os.path.join(build.CSRC, "grid_device.h")):
+        assert not re.search(r"\basm\b|__asm", open(src).read()), src
+    out = tmp_path / "grid_train_kernels.s"
+    cmd = [build.hipcc()] + build.FLAGS + build.VGPR_FORM + ["-I", os.path.join(ROOT, "include"), "-I", build.CSRC,
+                                                              "--cuda-device-only", "-S", path, "-o", str(out)]
+    subprocess.run(cmd, check=True, cwd=tmp_path)
+    asm = open(out).read()
+    kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", asm, re.M)
+    assert sum("grid_fused_kernel" in k for k in kernels) == 6 and len(kernels) == 9, kernels      # B in {9, 4, 1} x skip
+    sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", asm)
+    assert len(sizes) == len(kernels) and all(int(s) == 0 for s in sizes), sizes
+    assert not re.search(r"\bscratch_(load|store)", asm)
+    assert "cmpswap" not in asm                                   # float adds are one hardware atomic each, no CAS loop
+    assert len(re.findall(r"\bglobal_atomic_add_f32\b", asm)) > 0
+    assert not re.search(r"global_atomic_add_f32[^\n]*\bsc0\b", asm)      # none returns the old value
+    lds = re.findall(r"\.group_segment_fixed_size:\s*(\d+)", asm)
+    assert all(int(s) == 0 for s in lds), lds
+    vgprs = [int(v) for v in re.findall(r"\.vgpr_count:\s*(\d+)", asm)]
+    print("vgprs per kernel:", dict(zip(kernels, vgprs)))
+    assert max(vgprs) <= 128      # at least 4 waves per SIMD
