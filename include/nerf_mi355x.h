@@ -807,6 +807,101 @@ int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_opti
 int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* args);
 int nerf_grid_optim_step(nerf_ctx* ctx, const nerf_grid_optim_args* args);
 
+/* Sparse voxel grid: resampling -------------------------------------------------------------------
+ * The stages of svox2's SparseGrid.resample (coarse-to-fine training: sample the grid on another lattice, drop the nodes that
+ * matter to no camera or hold no density, rebuild links). Every stage is stream-ordered and synchronises nothing; the caller
+ * reads the kept-node count of nerf_grid_compact to allocate the new tables, and that is the only wait of a resample.
+ * A lattice [X', Y', Z'] has at most 2^30 nodes with every side in [2, 1024]; volumes and masks are dense, C order, z fastest.
+ *
+ * nerf_grid_lattice_density: density[x, y, z] = the old grid's density at the point (xs[x], ys[y], zs[z]), given in the OLD
+ * grid's coordinates (svox2 computes them as linspace(f - 0.5, R - f - 0.5, R') with f = 0.5 R / R' in fp32; they arrive as
+ * data, nothing about them is re-derived on the device). The value is nerf_grid_sample's with grid_coords at that point, bit
+ * for bit: the same clamp, cell, weights and trilinear order.
+ *
+ * nerf_grid_weight_render (svox2 grid_weight_render): for every pixel of `cam`, with the ray of nerf_grid_gen_rays and
+ * offset / scaling of a grid of `reso`, `radius`, `center` as nerf_grid_create computes them; fp32, each operation rounded,
+ * no fused multiply-adds, in this order:
+ *   dn = sqrt((dx dx + dy dy) + dz dz);  o_i = offset_i + origin_i * scaling_i;  d_i = (dir_i / dn) * scaling_i
+ *   delta_scale = 1 / sqrt((d_x d_x + d_y d_y) + d_z d_z);  world_step = delta_scale * step_size;  d_i = d_i * delta_scale
+ *   t = 0, tmax = 2e3;  per axis with d_i != 0: t1 = (-0.5 - o_i) * (1 / d_i), t2 = ((reso_i - 0.5) - o_i) * (1 / d_i),
+ *     t = max(t, min(t1, t2)), tmax = min(tmax, max(t1, t2));  a ray with not (t <= tmax), or whose set-up is not finite,
+ *     returns at once
+ *   log_T = 0;  while t <= tmax:
+ *     p_i = clamp(o_i + t * d_i, 0, reso_i - 1);  l_i = min(int(p_i), reso_i - 2);  wb_i = p_i - l_i;  wa_i = 1 - wb_i
+ *     sigma = trilinear over density at the 8 corners of cell l (z, then y, then x, as in the renderer)
+ *     if sigma > 1e-8:  log_att = (-world_step) * sigma;  weight = exp(log_T) * (1 - exp(log_att));  log_T = log_T + log_att
+ *       max_weight[each of the 8 corners] = max(itself, weight);  if exp(log_T) < stop_thresh: stop
+ *     t = t + step_size
+ * max_weight is raised, never lowered: zero it before the first camera; it must hold no negative value and no NaN (not checked:
+ * the integer maximum below orders only non-negative floats). weight >= 0, so the maximum is taken as an unsigned
+ * integer maximum of the float's bits (one hardware atomic, no compare-and-swap): the volume does not depend on the order in
+ * which rays arrive, two calls give identical bits. last_sample_opaque is not built (NERF_E_INVALID).
+ *
+ * nerf_grid_threshold: mask[i] = volume[i] >= threshold (bytes 0 / 1; NaN is not kept).
+ * nerf_grid_dilate: one step of the OR over the 27-neighbourhood, neighbour indices clamped at the faces (svox2 dilate);
+ * `in` and `out` must not overlap.
+ * nerf_grid_compact: links[node] = the number of kept nodes before it in C order if mask[node] != 0, else -1; *count = the
+ * number of kept nodes. Deterministic (counts per 1024 nodes, one scan, no atomics). block_offsets is a workspace of
+ * nerf_grid_compact_workspace(nodes) int32.
+ * nerf_grid_gather: the tables of the new grid from `links` of nerf_grid_compact and `rows` = its count: for the kept node
+ * n of row r, density_data[r] = lattice_density[n] (the value the threshold saw) and sh_data[r, :] = the old grid's SH
+ * coefficients interpolated at (xs, ys, zs)[n] as nerf_grid_sample does. node_of_row is a workspace of `rows` int32. */
+typedef struct nerf_grid_lattice_args {
+    size_t struct_size;
+    int32_t reso[3];            /* the new lattice                                                                  */
+    const float* xs;            /* [dev] [reso[0]] node coordinates in the old grid's coordinates                    */
+    const float* ys;            /* [dev] [reso[1]]                                                                  */
+    const float* zs;            /* [dev] [reso[2]]                                                                  */
+    float* density;             /* [dev] [X', Y', Z']                                                               */
+    void* stream;
+} nerf_grid_lattice_args;
+
+typedef struct nerf_grid_weight_args {
+    size_t struct_size;
+    int32_t reso[3];
+    float radius[3];            /* > 0: the geometry of the grid the volume belongs to                              */
+    float center[3];
+    const float* density;       /* [dev] [X', Y', Z']                                                               */
+    float* max_weight;          /* [dev] [X', Y', Z'], raised                                                       */
+    float step_size;            /* svox2 uses 0.5; >= 1e-3                                                          */
+    float stop_thresh;          /* svox2's weight_render_stop_thresh, 0.2                                           */
+    int32_t last_sample_opaque; /* must be 0 (not built)                                                            */
+    void* stream;
+} nerf_grid_weight_args;
+
+typedef struct nerf_grid_compact_args {
+    size_t struct_size;
+    int32_t reso[3];
+    const uint8_t* mask;        /* [dev] [X', Y', Z']                                                               */
+    int32_t* links;             /* [dev] [X', Y', Z']                                                               */
+    int32_t* block_offsets;     /* [dev] [nerf_grid_compact_workspace(X' Y' Z')] workspace                          */
+    int32_t* count;             /* [dev] [1]                                                                        */
+    void* stream;
+} nerf_grid_compact_args;
+
+typedef struct nerf_grid_gather_args {
+    size_t struct_size;
+    int32_t reso[3];
+    const float* xs;            /* as in nerf_grid_lattice_args                                                     */
+    const float* ys;
+    const float* zs;
+    const int32_t* links;       /* [dev] [X', Y', Z'] from nerf_grid_compact                                        */
+    const float* lattice_density; /* [dev] [X', Y', Z'] from nerf_grid_lattice_density                              */
+    int64_t rows;               /* the count of nerf_grid_compact; 0: nothing is done                               */
+    int32_t* node_of_row;       /* [dev] [rows] workspace                                                           */
+    float* density_data;        /* [dev] [rows, 1]                                                                  */
+    float* sh_data;             /* [dev] [rows, 3 * basis_dim of `grid`]                                            */
+    void* stream;
+} nerf_grid_gather_args;
+
+int nerf_grid_lattice_density(nerf_sparse_grid* grid, const nerf_grid_lattice_args* args);
+int nerf_grid_weight_render(nerf_ctx* ctx, const nerf_grid_camera* cam, const nerf_grid_weight_args* args);
+int nerf_grid_threshold(nerf_ctx* ctx, const float* volume, int64_t n, float threshold, uint8_t* mask, void* stream);
+int nerf_grid_dilate(nerf_ctx* ctx, const int32_t* reso, const uint8_t* in, uint8_t* out, void* stream);
+int64_t nerf_grid_compact_workspace(int64_t nodes);
+int nerf_grid_compact(nerf_ctx* ctx, const nerf_grid_compact_args* args);
+int nerf_grid_gather(nerf_sparse_grid* grid, const nerf_grid_gather_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,5 +20,7 @@ from . import grid  # noqa: F401
 from .grid import Camera, Rays, RenderOptions, SparseGrid  # noqa: F401
 from . import grid_train  # noqa: F401
 from .grid_train import GridTrainer  # noqa: F401
+from . import grid_resample  # noqa: F401
+from .grid_resample import dilate_mask, resample_grid, weight_render  # noqa: F401
 
 __version__ = "0.1.0"

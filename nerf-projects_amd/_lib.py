@@ -27,6 +27,8 @@ EXPORTS = (
     "nerf_grid_create", "nerf_grid_destroy", "nerf_grid_render_rays", "nerf_grid_render_image", "nerf_grid_gen_rays",
     "nerf_grid_sample", "nerf_grid_accelerate", "nerf_grid_drop_skip", "nerf_grid_has_skip", "nerf_grid_project_sh",
     "nerf_grid_fused_backward", "nerf_grid_tv_grad", "nerf_grid_optim_step",
+    "nerf_grid_lattice_density", "nerf_grid_weight_render", "nerf_grid_threshold", "nerf_grid_dilate",
+    "nerf_grid_compact_workspace", "nerf_grid_compact", "nerf_grid_gather",
 )
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
 NERF_GUARD_OFF, NERF_GUARD_REPORT, NERF_GUARD_FALLBACK = 0, 1, 2
@@ -178,6 +180,28 @@ class GridOptimArgs(_Sized):
                 ("minval", C.c_float), ("stream", C.c_void_p)]
 
 
+class GridLatticeArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("reso", C.c_int32 * 3), ("xs", _FP), ("ys", _FP), ("zs", _FP), ("density", _FP),
+                ("stream", C.c_void_p)]
+
+
+class GridWeightArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("reso", C.c_int32 * 3), ("radius", C.c_float * 3), ("center", C.c_float * 3),
+                ("density", _FP), ("max_weight", _FP), ("step_size", C.c_float), ("stop_thresh", C.c_float),
+                ("last_sample_opaque", C.c_int32), ("stream", C.c_void_p)]
+
+
+class GridCompactArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("reso", C.c_int32 * 3), ("mask", _FP), ("links", _FP), ("block_offsets", _FP),
+                ("count", _FP), ("stream", C.c_void_p)]
+
+
+class GridGatherArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("reso", C.c_int32 * 3), ("xs", _FP), ("ys", _FP), ("zs", _FP), ("links", _FP),
+                ("lattice_density", _FP), ("rows", C.c_int64), ("node_of_row", _FP), ("density_data", _FP), ("sh_data", _FP),
+                ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -320,6 +344,20 @@ def load():
     lib.nerf_grid_tv_grad.argtypes = [vp, C.POINTER(GridTvArgs)]
     lib.nerf_grid_optim_step.restype = i32
     lib.nerf_grid_optim_step.argtypes = [vp, C.POINTER(GridOptimArgs)]
+    lib.nerf_grid_lattice_density.restype = i32
+    lib.nerf_grid_lattice_density.argtypes = [vp, C.POINTER(GridLatticeArgs)]
+    lib.nerf_grid_weight_render.restype = i32
+    lib.nerf_grid_weight_render.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridWeightArgs)]
+    lib.nerf_grid_threshold.restype = i32
+    lib.nerf_grid_threshold.argtypes = [vp, vp, i64, C.c_float, vp, vp]
+    lib.nerf_grid_dilate.restype = i32
+    lib.nerf_grid_dilate.argtypes = [vp, C.POINTER(C.c_int32), vp, vp, vp]
+    lib.nerf_grid_compact_workspace.restype = i64
+    lib.nerf_grid_compact_workspace.argtypes = [i64]
+    lib.nerf_grid_compact.restype = i32
+    lib.nerf_grid_compact.argtypes = [vp, C.POINTER(GridCompactArgs)]
+    lib.nerf_grid_gather.restype = i32
+    lib.nerf_grid_gather.argtypes = [vp, C.POINTER(GridGatherArgs)]
     _lib = lib
     return lib
 

@@ -119,6 +119,9 @@ int render(const char* fn, nerf_sparse_grid* grid, const nerf_grid_camera* cam, 
 
 }  // namespace
 
+// the camera check for the other grid files (grid_internal.h)
+int nerf::check_grid_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out) { return check_camera(fn, cam, out); }
+
 extern "C" {
 
 void nerf_grid_destroy(nerf_sparse_grid* grid) {

@@ -59,6 +59,23 @@ __device__ __forceinline__ void load_links(const GridDev& g, int base, int lk[8]
     }
 }
 
+// svox2 Camera.gen_rays without NDC: fp64, rounded to fp32 at the end
+__device__ __forceinline__ void camera_ray(const GridCam& c, int64_t pix, float o[3], float d[3]) {
+    const int py = (int)(pix / c.width), px = (int)(pix % c.width);
+    double xx = ((double)px + 0.5 - c.cx) / c.fx;
+    double yy = ((double)py + 0.5 - c.cy) / c.fy;
+    double zz = 1.0;
+    const double n = sqrt(xx * xx + yy * yy + zz * zz);
+    xx /= n;
+    yy /= n;
+    zz /= n;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        d[i] = (float)(c.c2w[i * 4 + 0] * xx + c.c2w[i * 4 + 1] * yy + c.c2w[i * 4 + 2] * zz);
+        o[i] = (float)c.c2w[i * 4 + 3];
+    }
+}
+
 // ---- ray set-up (svox2.py:662-693) ----
 struct GridRay {
     float o[3], d[3];      // origin and unit direction in grid coordinates

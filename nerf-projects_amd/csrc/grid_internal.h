@@ -1,5 +1,5 @@
-// Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what grid_api.cpp, grid_train_api.cpp, grid_kernels.hip and
-// grid_train_kernels.hip share.
+// Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what grid_api.cpp, grid_train_api.cpp, grid_resample_api.cpp,
+// grid_kernels.hip, grid_train_kernels.hip and grid_resample_kernels.hip share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -85,6 +85,47 @@ struct GridOptim {
 hipError_t launch_grid_fused(const GridDev& g, const GridRenderOpt& o, const GridFused& r, hipStream_t s);
 hipError_t launch_grid_tv_grad(const GridDev& g, const GridTv& a, hipStream_t s);
 hipError_t launch_grid_optim_step(const GridOptim& a, int rmsprop, hipStream_t s);
+
+// ---- resampling (grid_resample_kernels.hip) ----
+constexpr int64_t kGridMaxLattice = (int64_t)1 << 30;   // nodes of a resampling lattice: 1024^3
+
+struct GridLattice {
+    const float* axis[3];              // node coordinates per axis, in the old grid's coordinates
+    int32_t size[3];
+    float* density;                    // [X', Y', Z']
+};
+
+struct GridWeight {
+    GridCam cam;
+    const float* density;              // [X', Y', Z'] dense
+    float* max_weight;                 // [X', Y', Z'], raised
+    int32_t size[3];
+    float offset[3], scaling[3];       // world2grid of the lattice, as nerf_grid_create computes it
+    float step_size, stop_thresh;
+};
+
+struct GridGather {
+    const float* axis[3];
+    int32_t size[3];
+    const int32_t* links;              // [X', Y', Z'] of the new grid
+    const float* lattice_density;
+    int32_t* node_of_row;              // [rows] workspace
+    int64_t rows;
+    float* density_data;               // [rows, 1]
+    float* sh_data;                    // [rows, 3 B]
+};
+
+hipError_t launch_grid_lattice_density(const GridDev& g, const GridLattice& a, hipStream_t s);
+hipError_t launch_grid_weight_render(const GridWeight& a, hipStream_t s);
+hipError_t launch_grid_threshold(const float* volume, int64_t n, float threshold, uint8_t* mask, hipStream_t s);
+hipError_t launch_grid_dilate(const uint8_t* in, const int32_t size[3], uint8_t* out, hipStream_t s);
+int64_t grid_compact_blocks(int64_t n);      // entries of block_offsets
+hipError_t launch_grid_compact(const uint8_t* mask, int64_t n, int32_t* block_offsets, int32_t* links, int32_t* count,
+                               hipStream_t s);
+hipError_t launch_grid_gather(const GridDev& g, const GridGather& a, hipStream_t s);
+
+// checks a public camera (struct_size, size, intrinsics) and converts it; NERF_OK or NERF_E_INVALID with last_error set
+int check_grid_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out);
 
 hipError_t launch_grid_render(const GridDev& g, const GridRenderOpt& o, const GridRender& r, hipStream_t s);
 hipError_t launch_grid_gen_rays(const GridCam& cam, float* origins, float* dirs, hipStream_t s);

@@ -19,23 +19,6 @@
 namespace nerf {
 namespace {
 
-// svox2 Camera.gen_rays without NDC: fp64, rounded to fp32 at the end
-__device__ __forceinline__ void camera_ray(const GridCam& c, int64_t pix, float o[3], float d[3]) {
-    const int py = (int)(pix / c.width), px = (int)(pix % c.width);
-    double xx = ((double)px + 0.5 - c.cx) / c.fx;
-    double yy = ((double)py + 0.5 - c.cy) / c.fy;
-    double zz = 1.0;
-    const double n = sqrt(xx * xx + yy * yy + zz * zz);
-    xx /= n;
-    yy /= n;
-    zz /= n;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        d[i] = (float)(c.c2w[i * 4 + 0] * xx + c.c2w[i * 4 + 1] * yy + c.c2w[i * 4 + 2] * zz);
-        o[i] = (float)c.c2w[i * 4 + 3];
-    }
-}
-
 __global__ __launch_bounds__(kGridThreads) void grid_gen_rays_kernel(GridCam cam, float* __restrict__ origins,
                                                                       float* __restrict__ dirs) {
     const int64_t pix = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;

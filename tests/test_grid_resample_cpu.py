@@ -1,0 +1,292 @@
+"""Sparse voxel grid resampling, the parts that need no GPU: the numpy restatement (tests/grid_resample_oracle.py) against the
+reference's recorded ``SparseGrid.resample`` (tests/golden/grid_resample.npz), its dilation against max pooling, its weight
+render against closed forms, the C ABI of the resampling entry points, and the generated code of
+csrc/grid_resample_kernels.hip."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import grid_resample_oracle as RO  # noqa: E402
+from test_grid_train_cpu import RENDER, _header_struct_fields, fixture_grid  # noqa: E402
+
+RESAMPLE = os.path.join(ROOT, "tests", "golden", "grid_resample.npz")
+CASES = ("b_x2", "c_x2", "b_x1p5", "c_odd", "a_odd", "a_down", "b_down", "a_same", "c_same")
+
+
+def test_fixture_holds_arrays_only_and_is_small():
+    assert os.path.getsize(RESAMPLE) < 1 << 20
+    r = np.load(RESAMPLE)      # (allow_pickle is off: arrays only)
+    cases = RO.fixture_cases(r)
+    assert tuple(c[0] for c in cases) == CASES
+    z = np.load(RENDER)
+    kinds = set()
+    for case, src, reso, thresh in cases:
+        old = z[f"{src}_links"].shape
+        ratio = [n / o for n, o in zip(reso, old)]
+        kinds.add("same" if ratio == [1, 1, 1] else "x2" if ratio == [2, 2, 2] else "down" if max(ratio) < 1 else
+                  "up" if min(ratio) > 1 and any(x != int(x) for x in ratio) else "other")
+        assert r[f"{case}_links"].shape == tuple(reso) and (r[f"{case}_links"] >= 0).sum() == r[f"{case}_density"].shape[0] > 0
+    assert {"same", "x2", "down", "up"} <= kinds
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_restatement_matches_the_reference_resample(case):
+    z, r = np.load(RENDER), np.load(RESAMPLE)
+    _, src, reso, thresh = next(c for c in RO.fixture_cases(r) if c[0] == case)
+    g = fixture_grid(z, src)
+    got = RO.resample(g, reso, sigma_thresh=thresh, dilate_steps=0)
+    fig = RO.check_against_fixture(got, r, case, g, reso, thresh, "restatement")
+    assert np.array_equal(got["mask"], got["links"] >= 0)
+    assert fig["flips"] == 0      # the reference itself has none on this fixture, and neither has its restatement
+    # the fp64 statement of the same thing keeps the nodes the reference's fp64 run kept
+    got64 = RO.resample(g, reso, sigma_thresh=thresh, dilate_steps=0, dtype=np.float64)
+    m64 = np.unpackbits(r[f"{case}_mask64"])[:got64["links"].size].astype(bool).reshape(got64["links"].shape)
+    assert np.array_equal(got64["links"] >= 0, m64) and got64["sh_data"].dtype == np.float64
+
+
+def test_same_resolution_keeps_the_source_rows_exactly():
+    z = np.load(RENDER)
+    g = fixture_grid(z, "a")
+    got = RO.resample(g, list(g["links"].shape), sigma_thresh=3.0, dilate_steps=0)
+    cap = g["density_data"].shape[0]
+    kept_src = (g["links"] >= 0) & (g["links"] < cap)
+    dens = np.where(kept_src, g["density_data"][np.clip(g["links"], 0, cap - 1), 0], np.float32(0.0))
+    want = kept_src & (dens >= 3.0)
+    assert np.array_equal(got["links"] >= 0, want) and want.sum() > 100
+    assert np.array_equal(got["density_data"], g["density_data"][g["links"][want]])
+    assert np.array_equal(got["sh_data"], g["sh_data"][g["links"][want]])
+
+
+def test_lattice_axes_are_the_voxel_centres_of_the_new_grid():
+    for old, new in ((16, 32), (16, 24), (24, 9), (20, 20)):
+        ax = RO.lattice_axes([old] * 3, [new] * 3)[0]
+        assert ax.dtype == np.float32 and ax.shape == (new,)
+        want = (np.arange(new) + 0.5) * old / new - 0.5      # centre of voxel i of the new grid, in old grid coordinates
+        assert np.abs(ax - want).max() <= 4e-6 * old
+    assert np.array_equal(RO.lattice_axes([20] * 3, [20] * 3)[0], np.arange(20, dtype=np.float32))
+    assert np.array_equal(RO.lattice_axes([16] * 3, [32] * 3)[0], (np.arange(32) * 0.5 - 0.25).astype(np.float32))
+
+
+def test_restated_dilate_is_max_pooling_and_links_are_a_running_index():
+    rng = np.random.default_rng(5)
+    for shape, p in (((9, 7, 11), 0.03), ((5, 6, 4), 0.3), ((2, 2, 2), 0.2), ((12, 3, 8), 0.0)):
+        m = rng.random(shape) < p
+        if p:
+            m[0, 0, 0] = m[-1, -1, -1] = True      # corners: the clamped indices
+        want = torch.nn.functional.max_pool3d(torch.from_numpy(m.astype(np.float32))[None, None], 3, 1, 1)[0, 0].numpy() > 0
+        assert np.array_equal(RO.dilate(m), want)
+        links = RO.links_of(m)
+        assert np.array_equal(links >= 0, m) and np.array_equal(links[m], np.arange(m.sum()))
+
+
+def test_restated_weight_render_against_closed_forms():
+    # a uniform volume seen along -z from outside: every ray's first sample carries the largest weight,
+    # 1 - exp(-world_step sigma) with world_step = step / scaling = 0.5 * (2 radius / reso)
+    reso, radius, sigma = (12, 12, 12), 1.5, 4.0
+    vol = np.full(reso, sigma, dtype=np.float32)
+    c2w = np.array([[1, 0, 0, 0.02], [0, 1, 0, -0.03], [0, 0, 1, -4.0]], dtype=np.float32)
+    cam = dict(c2w=c2w, fx=60.0, fy=60.0, cx=8.0, cy=8.0, width=16, height=16)
+    w32 = RO.weight_render(vol, cam, [radius] * 3, [0.0] * 3, stop_thresh=0.0)
+    w64 = RO.weight_render(vol, cam, [radius] * 3, [0.0] * 3, stop_thresh=0.0, dtype=np.float64)
+    assert w32.dtype == np.float32 and w64.dtype == np.float64
+    first = 1.0 - np.exp(-0.5 * (2 * radius / 12) * sigma)
+    assert abs(w64.max() - first) <= 1e-3 * first and w64[:, :, 0].max() == w64.max()
+    assert w64[:, :, -1].max() < 0.2 * first      # attenuated on the far side
+    assert np.abs(w32 - w64).max() <= 1e-5
+    assert (w32[5:7, 5:7, :] > 0).all()      # the centre column is crossed from end to end
+    # stop_thresh cuts the march: with 0.2 nothing behind T < 0.2 is touched; and a second camera only raises
+    cut = RO.weight_render(vol, cam, [radius] * 3, [0.0] * 3, stop_thresh=0.2)
+    assert (cut <= w32).all() and (cut[:, :, -1] == 0).all() and np.array_equal(cut[:, :, 0], w32[:, :, 0])
+    cam2 = dict(cam, c2w=np.array([[0, 0, 1, -4.0], [0, 1, 0, 0.0], [-1, 0, 0, 0.0]], dtype=np.float32))
+    two = RO.weight_render(vol, cam2, [radius] * 3, [0.0] * 3, stop_thresh=0.2, out=cut.copy())
+    assert (two >= cut).all() and (two > cut).any()
+    # a camera that looks away raises nothing, and an empty volume has no weights
+    away = dict(cam, c2w=np.array([[1, 0, 0, 0.0], [0, 1, 0, 0.0], [0, 0, -1, -4.0]], dtype=np.float32))
+    assert not RO.weight_render(vol, away, [radius] * 3, [0.0] * 3).any()
+    assert not RO.weight_render(np.zeros(reso, np.float32), cam, [radius] * 3, [0.0] * 3).any()
+
+
+def test_sparse_grid_resample_still_raises():
+    import nerf_projects_amd as N
+    with pytest.raises(NotImplementedError, match="resample"):
+        N.SparseGrid.resample(None, 64)
+    assert callable(N.resample_grid) and callable(N.dilate_mask) and callable(N.weight_render)
+    assert hasattr(N.GridTrainer, "resample")
+
+
+def test_resample_refuses_the_cpu():
+    import nerf_projects_amd as N
+    from nerf_projects_amd import grid_resample
+    with pytest.raises(TypeError):
+        N.resample_grid(object(), 32)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        N.dilate_mask(torch.zeros((4, 4, 4), dtype=torch.bool))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        N.weight_render(torch.zeros((4, 4, 4)), N.Camera(torch.eye(4)[:3], width=4, height=4), 1.0, 0.0)
+    with pytest.raises(NotImplementedError, match="last_sample_opaque"):
+        N.weight_render(torch.zeros((4, 4, 4)), N.Camera(torch.eye(4)[:3], width=4, height=4), 1.0, 0.0, last_sample_opaque=True)
+    with pytest.raises(ValueError):
+        grid_resample._reso3([4, 4])
+    with pytest.raises(ValueError):
+        grid_resample._reso3(1)
+    axes = grid_resample.lattice_axes([16, 12, 10], [24, 24, 7])
+    assert [a.shape[0] for a in axes] == [24, 24, 7] and all(a.dtype == torch.float32 and not a.is_cuda for a in axes)
+
+
+# ---- C ABI ------------------------------------------------------------------------------------------------------------
+NEW_STRUCTS = {"nerf_grid_lattice_args": "GridLatticeArgs", "nerf_grid_weight_args": "GridWeightArgs",
+               "nerf_grid_compact_args": "GridCompactArgs", "nerf_grid_gather_args": "GridGatherArgs"}
+NEW_SYMBOLS = ("nerf_grid_lattice_density", "nerf_grid_weight_render", "nerf_grid_threshold", "nerf_grid_dilate",
+               "nerf_grid_compact_workspace", "nerf_grid_compact", "nerf_grid_gather")
+
+
+def test_resampling_structs_match_a_c_compile_of_the_header(tmp_path):
+    import nerf_projects_amd  # noqa: F401
+    from nerf_projects_amd import _lib
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nerf_mi355x.h"', "int main(void) {"]
+    for cname in NEW_STRUCTS:
+        lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
+        for f in _header_struct_fields(cname):
+            lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
+    lines += ["return 0;", "}"]
+    src = tmp_path / "abi.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "abi"
+    cc = next(c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if subprocess.run(
+        ["sh", "-c", f"command -v {c}"], capture_output=True).returncode == 0)
+    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    seen = {}
+    for line in out.splitlines():
+        cname, f, v = line.split()
+        seen.setdefault(cname, {})[f] = int(v)
+    for cname, pyname in NEW_STRUCTS.items():
+        cls = getattr(_lib, pyname)
+        assert C.sizeof(cls) == seen[cname].pop("size"), cname
+        assert [f[0] for f in cls._fields_] == _header_struct_fields(cname), cname
+        for f, off in seen[cname].items():
+            assert getattr(cls, f).offset == off, (cname, f)
+        assert cls().struct_size == C.sizeof(cls)
+
+
+def test_resampling_calls_refuse_bad_arguments_before_any_device_call():
+    """Every refusal here comes before a handle is dereferenced or a kernel launched: the pointers are fakes."""
+    import nerf_projects_amd  # noqa: F401
+    from nerf_projects_amd import _lib
+    lib = _lib.load()
+    for s in NEW_SYMBOLS:
+        assert hasattr(lib, s) and s in _lib.EXPORTS
+    fake = C.c_void_p(0x1000)
+    err = lambda: lib.nerf_last_error().decode()      # noqa: E731
+
+    a = _lib.GridLatticeArgs()
+    assert lib.nerf_grid_lattice_density(None, C.byref(a)) == -1 and "NULL grid" in err()
+    assert lib.nerf_grid_lattice_density(fake, None) == -1 and "NULL" in err()
+    a.struct_size += 8
+    assert lib.nerf_grid_lattice_density(fake, C.byref(a)) == -1 and "struct_size" in err()
+    a = _lib.GridLatticeArgs()
+    a.reso[:] = [4, 1, 4]
+    assert lib.nerf_grid_lattice_density(fake, C.byref(a)) == -1 and "reso[1]" in err()
+    a.reso[:] = [1024, 1024, 1025]
+    assert lib.nerf_grid_lattice_density(fake, C.byref(a)) == -1 and "reso[2]" in err()
+    a.reso[:] = [4, 4, 4]      # and no pointers
+    assert lib.nerf_grid_lattice_density(fake, C.byref(a)) == -1 and "required" in err()
+
+    cam, w = _lib.GridCamera(), _lib.GridWeightArgs()
+    cam.fx = cam.fy = 10.0
+    cam.width = cam.height = 4
+    w.reso[:] = [4, 4, 4]
+    w.radius[:] = [1.0, 1.0, 1.0]
+    w.step_size, w.stop_thresh = 0.5, 0.2
+    assert lib.nerf_grid_weight_render(None, C.byref(cam), C.byref(w)) == -1 and "NULL context" in err()
+    assert lib.nerf_grid_weight_render(fake, None, C.byref(w)) == -1 and "NULL" in err()
+    assert lib.nerf_grid_weight_render(fake, C.byref(cam), None) == -1 and "NULL" in err()
+    assert lib.nerf_grid_weight_render(fake, C.byref(cam), C.byref(w)) == -1 and "required" in err()
+    w.last_sample_opaque = 1
+    assert lib.nerf_grid_weight_render(fake, C.byref(cam), C.byref(w)) == -1 and "last_sample_opaque" in err() and "not built" in err()
+    w.last_sample_opaque, w.step_size = 0, 1e-4
+    assert lib.nerf_grid_weight_render(fake, C.byref(cam), C.byref(w)) == -1 and "step_size" in err()
+    w.step_size = 0.5
+    w.radius[1] = 0.0
+    w.density = w.max_weight = 0x1000
+    assert lib.nerf_grid_weight_render(fake, C.byref(cam), C.byref(w)) == -1 and "radius" in err()
+    cam.width = 0
+    assert lib.nerf_grid_weight_render(fake, C.byref(cam), C.byref(w)) == -1 and "camera" in err()
+
+    assert lib.nerf_grid_threshold(None, fake, 8, 1.0, fake, None) == -1 and "NULL context" in err()
+    assert lib.nerf_grid_threshold(fake, None, 8, 1.0, fake, None) == -1 and "needs" in err()
+    assert lib.nerf_grid_threshold(fake, fake, -1, 1.0, fake, None) == -1 and "n = -1" in err()
+    assert lib.nerf_grid_threshold(fake, fake, 8, float("nan"), fake, None) == -1 and "NaN" in err()
+
+    reso = (C.c_int32 * 3)(4, 4, 4)
+    assert lib.nerf_grid_dilate(None, reso, fake, fake, None) == -1 and "NULL context" in err()
+    assert lib.nerf_grid_dilate(fake, None, fake, fake, None) == -1 and "reso" in err()
+    assert lib.nerf_grid_dilate(fake, reso, None, fake, None) == -1 and "required" in err()
+    assert lib.nerf_grid_dilate(fake, reso, fake, C.c_void_p(0x1000 + 63), None) == -1 and "overlap" in err()
+    assert lib.nerf_grid_dilate(fake, (C.c_int32 * 3)(4, 4, 0), fake, fake, None) == -1 and "reso[2]" in err()
+
+    assert lib.nerf_grid_compact_workspace(0) == 0 and lib.nerf_grid_compact_workspace(1024) == 1
+    assert lib.nerf_grid_compact_workspace(1025) == 2 and lib.nerf_grid_compact_workspace(512 ** 3) == 512 ** 3 // 1024
+    c = _lib.GridCompactArgs()
+    assert lib.nerf_grid_compact(None, C.byref(c)) == -1 and "NULL context" in err()
+    assert lib.nerf_grid_compact(fake, None) == -1 and "NULL" in err()
+    c.reso[:] = [4, 4, 4]
+    assert lib.nerf_grid_compact(fake, C.byref(c)) == -1 and "required" in err()
+    c.struct_size = 0
+    assert lib.nerf_grid_compact(fake, C.byref(c)) == -1 and "struct_size" in err()
+
+    g = _lib.GridGatherArgs()
+    assert lib.nerf_grid_gather(None, C.byref(g)) == -1 and "NULL grid" in err()
+    assert lib.nerf_grid_gather(fake, None) == -1 and "NULL" in err()
+    g.reso[:] = [4, 4, 4]
+    g.rows = 65
+    assert lib.nerf_grid_gather(fake, C.byref(g)) == -1 and "rows" in err()
+    g.rows = 5      # and no pointers
+    assert lib.nerf_grid_gather(fake, C.byref(g)) == -1 and "required" in err()
+    g.rows = 0
+    assert lib.nerf_grid_gather(fake, C.byref(g)) == 0      # no rows: nothing is done
+
+
+def test_grid_resample_kernels_use_no_scratch_no_inline_assembly_and_a_native_atomic_max(tmp_path):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("nerf_build_for_grid_resample", os.path.join(ROOT, "nerf-projects_amd", "build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    assert "grid_resample_kernels.hip" in build.SOURCES and "grid_resample_api.cpp" in build.SOURCES
+    path = os.path.join(build.CSRC, "grid_resample_kernels.hip")
+    text = open(path).read()
+    assert not re.search(r"\basm\b|__asm", text)
+    assert '#include "grid_device.h"' in text
+    for shared in ("cell_of(", "load_links(", "trilerp("):      # the sampler's own device functions, not copies of them
+        assert shared in text and not re.search(r"void\s+%s|float\s+%s" % (re.escape(shared), re.escape(shared)), text), shared
+    out = tmp_path / "grid_resample_kernels.s"
+    cmd = [build.hipcc()] + build.FLAGS + build.VGPR_FORM + ["-I", os.path.join(ROOT, "include"), "-I", build.CSRC,
+                                                              "--cuda-device-only", "-S", path, "-o", str(out)]
+    subprocess.run(cmd, check=True, cwd=tmp_path)
+    asm = open(out).read()
+    kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", asm, re.M)
+    for name in ("grid_lattice_density_kernel", "grid_weight_render_kernel", "grid_threshold_kernel", "grid_dilate_kernel",
+                 "grid_compact_count_kernel", "grid_compact_scan_kernel", "grid_compact_links_kernel", "grid_row_nodes_kernel",
+                 "grid_gather_kernel"):
+        assert sum(name in k for k in kernels) == 1, (name, kernels)
+    assert len(kernels) == 9, kernels
+    sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", asm)
+    assert len(sizes) == len(kernels) and all(int(s) == 0 for s in sizes), sizes
+    assert not re.search(r"\bscratch_(load|store)", asm)
+    assert "cmpswap" not in asm                                   # the maximum is one hardware atomic, no CAS loop
+    atomics = re.findall(r"^\s*((?:global|flat|buffer|ds)_atomic\S*)([^\n]*)", asm, re.M)
+    assert len(atomics) == 8 and all(op == "global_atomic_umax" for op, _ in atomics), atomics      # the 8 corners, nothing else
+    assert not any(re.search(r"\b(sc0|glc)\b", rest) for _, rest in atomics)      # none returns the old value
+    lds = dict(zip(kernels, (int(s) for s in re.findall(r"\.group_segment_fixed_size:\s*(\d+)", asm))))
+    assert all(v == 0 or "compact" in k for k, v in lds.items()), lds      # LDS only in the compaction
+    vgprs = [int(v) for v in re.findall(r"\.vgpr_count:\s*(\d+)", asm)]
+    print("vgprs per kernel:", dict(zip(kernels, vgprs)))
+    assert max(vgprs) <= 64      # 8 waves per SIMD
