@@ -902,6 +902,86 @@ int64_t nerf_grid_compact_workspace(int64_t nodes);
 int nerf_grid_compact(nerf_ctx* ctx, const nerf_grid_compact_args* args);
 int nerf_grid_gather(nerf_sparse_grid* grid, const nerf_grid_gather_args* args);
 
+/* Sparse voxel grid: connected components ---------------------------------------------------------
+ * The connected components of a grid's occupied nodes: what the Floater Detection Ratio of svox2's
+ * opt/util/advanced_metrics.py (compute_FDR) needs from scipy.ndimage.label / ndimage.sum, on the device, and the two
+ * stages with which the components it calls floaters are removed from a grid. Every call except
+ * nerf_grid_components_finish is stream-ordered, allocates nothing and synchronises nothing. Volumes are dense, C order,
+ * z fastest; a lattice has at most 2^30 nodes with every side in [2, 1024].
+ *
+ * nerf_grid_components_occupancy: occupied[x, y, z] = 1 when links[x, y, z] >= 0 and, with use_density != 0,
+ * density_data[links[x, y, z], 0] > threshold (an fp32 comparison; NaN is not occupied); else 0. Any negative link is empty,
+ * not only -1. (compute_FDR thresholds only when `use_density_threshold and threshold > 0`: that decision is the caller's.)
+ *
+ * nerf_grid_components_label: two occupied nodes are neighbours when they differ by at most 1 in every coordinate and in
+ * at most 1 (connectivity 6: faces), 2 (18: + edges) or 3 (26: + corners) coordinates; nothing wraps around at the faces
+ * of the lattice; any other connectivity is NERF_E_INVALID. Components are numbered 1..n in increasing order of their
+ * smallest flat C-order index (scipy.ndimage.label's numbering); labels[node] is the number of the node's component, 0 for a
+ * node that is not occupied. status[0] = n; status[1] = the error word, 0 unless a bounded loop of the labelling hit its cap
+ * or met a parent it cannot have written (a bug or memory overwritten from outside; the labels are then not to be used).
+ * The labelling is a union-find whose only racing writes are integer minima, so two calls give identical bits. parent is a
+ * workspace of X Y Z int32, block_offsets one of nerf_grid_components_workspace(X Y Z) int32.
+ *
+ * nerf_grid_components_finish: the one wait. Copies status to the host and waits for the stream: *count = status[0];
+ * NERF_E_INTERNAL when the error word is set.
+ *
+ * nerf_grid_components_volumes: volumes[k] = the number of nodes with labels == k + 1, for k < count (zeroed first; integer
+ * additions, so the result does not depend on their order). Labels outside [1, count] are ignored.
+ *
+ * nerf_grid_components_keep: mask[node] = 1 when links[node] >= 0 and not (labels[node] in [1, count] and
+ * floater[labels[node] - 1] != 0), else 0: a kept node that is not occupied (label 0) stays.
+ *
+ * nerf_grid_copy_rows: the tables of a grid that keeps a subset of another grid's nodes on the same lattice. For every node
+ * with new_links[node] in [0, new_rows) and old_links[node] in [0, old_rows): row new_links[node] of density / sh = row
+ * old_links[node] of old_density / old_sh, copied as 32-bit words (every bit pattern survives, NaN payloads included).
+ * src_row is a workspace of new_rows int32. new_rows = 0: nothing is done. */
+#define NERF_E_INTERNAL (-5)    /* a device-side consistency check failed   */
+
+typedef struct nerf_grid_occupancy_args {
+    size_t struct_size;
+    int32_t use_density;        /* 0: occupied = kept                                                               */
+    float threshold;            /* not NaN                                                                          */
+    uint8_t* occupied;          /* [dev] [X, Y, Z] of the grid                                                      */
+    void* stream;
+} nerf_grid_occupancy_args;
+
+typedef struct nerf_grid_label_args {
+    size_t struct_size;
+    int32_t reso[3];
+    int32_t connectivity;       /* 6, 18 or 26                                                                      */
+    const uint8_t* occupied;    /* [dev] [X, Y, Z]                                                                  */
+    int32_t* parent;            /* [dev] [X, Y, Z] workspace                                                        */
+    int32_t* block_offsets;     /* [dev] [nerf_grid_components_workspace(X Y Z)] workspace                          */
+    int32_t* labels;            /* [dev] [X, Y, Z]                                                                  */
+    int32_t* status;            /* [dev] [2]: component count, error word                                           */
+    void* stream;
+} nerf_grid_label_args;
+
+typedef struct nerf_grid_copy_rows_args {
+    size_t struct_size;
+    int32_t reso[3];
+    int32_t cols;               /* columns of sh: 3 * basis_dim, >= 1                                               */
+    const int32_t* old_links;   /* [dev] [X, Y, Z]                                                                  */
+    const int32_t* new_links;   /* [dev] [X, Y, Z]                                                                  */
+    int64_t old_rows;
+    int64_t new_rows;
+    const float* old_density;   /* [dev] [old_rows, 1]                                                              */
+    const float* old_sh;        /* [dev] [old_rows, cols]                                                           */
+    int32_t* src_row;           /* [dev] [new_rows] workspace                                                       */
+    float* density;             /* [dev] [new_rows, 1]                                                              */
+    float* sh;                  /* [dev] [new_rows, cols]                                                           */
+    void* stream;
+} nerf_grid_copy_rows_args;
+
+int nerf_grid_components_occupancy(nerf_sparse_grid* grid, const nerf_grid_occupancy_args* args);
+int64_t nerf_grid_components_workspace(int64_t nodes);
+int nerf_grid_components_label(nerf_ctx* ctx, const nerf_grid_label_args* args);
+int nerf_grid_components_finish(nerf_ctx* ctx, const int32_t* status, int64_t* count, void* stream);
+int nerf_grid_components_volumes(nerf_ctx* ctx, const int32_t* labels, int64_t n, int64_t count, int32_t* volumes, void* stream);
+int nerf_grid_components_keep(nerf_ctx* ctx, const int32_t* links, const int32_t* labels, int64_t n, const uint8_t* floater,
+                              int64_t count, uint8_t* mask, void* stream);
+int nerf_grid_copy_rows(nerf_ctx* ctx, const nerf_grid_copy_rows_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,5 +22,8 @@ from . import grid_train  # noqa: F401
 from .grid_train import GridTrainer  # noqa: F401
 from . import grid_resample  # noqa: F401
 from .grid_resample import dilate_mask, resample_grid, weight_render  # noqa: F401
+from . import grid_components  # noqa: F401
+from .grid_components import (compute_all_advanced_metrics, compute_FDR, compute_MCQ, label_components,  # noqa: F401
+                              remove_floaters)
 
 __version__ = "0.1.0"

@@ -29,7 +29,10 @@ EXPORTS = (
     "nerf_grid_fused_backward", "nerf_grid_tv_grad", "nerf_grid_optim_step",
     "nerf_grid_lattice_density", "nerf_grid_weight_render", "nerf_grid_threshold", "nerf_grid_dilate",
     "nerf_grid_compact_workspace", "nerf_grid_compact", "nerf_grid_gather",
+    "nerf_grid_components_occupancy", "nerf_grid_components_workspace", "nerf_grid_components_label",
+    "nerf_grid_components_finish", "nerf_grid_components_volumes", "nerf_grid_components_keep", "nerf_grid_copy_rows",
 )
+NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
 NERF_GUARD_OFF, NERF_GUARD_REPORT, NERF_GUARD_FALLBACK = 0, 1, 2
 NERF_OCC_EVALUATE, NERF_OCC_EMPTY = 0, 1
@@ -202,6 +205,22 @@ class GridGatherArgs(_Sized):
                 ("stream", C.c_void_p)]
 
 
+class GridOccupancyArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("use_density", C.c_int32), ("threshold", C.c_float), ("occupied", _FP),
+                ("stream", C.c_void_p)]
+
+
+class GridLabelArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("reso", C.c_int32 * 3), ("connectivity", C.c_int32), ("occupied", _FP),
+                ("parent", _FP), ("block_offsets", _FP), ("labels", _FP), ("status", _FP), ("stream", C.c_void_p)]
+
+
+class GridCopyRowsArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("reso", C.c_int32 * 3), ("cols", C.c_int32), ("old_links", _FP),
+                ("new_links", _FP), ("old_rows", C.c_int64), ("new_rows", C.c_int64), ("old_density", _FP), ("old_sh", _FP),
+                ("src_row", _FP), ("density", _FP), ("sh", _FP), ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -358,6 +377,20 @@ def load():
     lib.nerf_grid_compact.argtypes = [vp, C.POINTER(GridCompactArgs)]
     lib.nerf_grid_gather.restype = i32
     lib.nerf_grid_gather.argtypes = [vp, C.POINTER(GridGatherArgs)]
+    lib.nerf_grid_components_occupancy.restype = i32
+    lib.nerf_grid_components_occupancy.argtypes = [vp, C.POINTER(GridOccupancyArgs)]
+    lib.nerf_grid_components_workspace.restype = i64
+    lib.nerf_grid_components_workspace.argtypes = [i64]
+    lib.nerf_grid_components_label.restype = i32
+    lib.nerf_grid_components_label.argtypes = [vp, C.POINTER(GridLabelArgs)]
+    lib.nerf_grid_components_finish.restype = i32
+    lib.nerf_grid_components_finish.argtypes = [vp, vp, C.POINTER(i64), vp]
+    lib.nerf_grid_components_volumes.restype = i32
+    lib.nerf_grid_components_volumes.argtypes = [vp, vp, i64, i64, vp, vp]
+    lib.nerf_grid_components_keep.restype = i32
+    lib.nerf_grid_components_keep.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp]
+    lib.nerf_grid_copy_rows.restype = i32
+    lib.nerf_grid_copy_rows.argtypes = [vp, C.POINTER(GridCopyRowsArgs)]
     _lib = lib
     return lib
 

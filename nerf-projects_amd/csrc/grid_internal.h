@@ -1,5 +1,6 @@
 // Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what grid_api.cpp, grid_train_api.cpp, grid_resample_api.cpp,
-// grid_kernels.hip, grid_train_kernels.hip and grid_resample_kernels.hip share.
+// grid_components_api.cpp, grid_kernels.hip, grid_train_kernels.hip, grid_resample_kernels.hip and grid_components_kernels.hip
+// share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -123,6 +124,37 @@ int64_t grid_compact_blocks(int64_t n);      // entries of block_offsets
 hipError_t launch_grid_compact(const uint8_t* mask, int64_t n, int32_t* block_offsets, int32_t* links, int32_t* count,
                                hipStream_t s);
 hipError_t launch_grid_gather(const GridDev& g, const GridGather& a, hipStream_t s);
+
+// ---- connected components (grid_components_kernels.hip) ----
+struct GridLabel {
+    const uint8_t* occ;                // [X, Y, Z] bytes 0 / 1
+    int32_t size[3];
+    int32_t connectivity;              // 6, 18 or 26
+    int32_t* parent;                   // [X, Y, Z] workspace
+    int32_t* block_offsets;            // [grid_label_blocks(X Y Z)] workspace
+    int32_t* labels;                   // [X, Y, Z]
+    int32_t* status;                   // [2]: the component count, the error word
+};
+
+struct GridCopyRows {
+    const int32_t* old_links;          // [X, Y, Z]
+    const int32_t* new_links;          // [X, Y, Z]: -1 or a running index over a subset of the old kept nodes
+    int64_t nodes, old_rows, new_rows;
+    int32_t cols;                      // of sh
+    const float* old_density;
+    const float* old_sh;
+    int32_t* src_row;                  // [new_rows] workspace
+    float* density;                    // [new_rows, 1]
+    float* sh;                         // [new_rows, cols]
+};
+
+hipError_t launch_grid_occupancy(const GridDev& g, int use_density, float threshold, uint8_t* occ, hipStream_t s);
+int64_t grid_label_blocks(int64_t n);        // entries of block_offsets
+hipError_t launch_grid_label(const GridLabel& a, hipStream_t s);
+hipError_t launch_grid_label_volumes(const int32_t* labels, int64_t n, int64_t count, int32_t* volumes, hipStream_t s);
+hipError_t launch_grid_keep_mask(const int32_t* links, const int32_t* labels, int64_t n, const uint8_t* floater, int64_t count,
+                                 uint8_t* mask, hipStream_t s);
+hipError_t launch_grid_copy_rows(const GridCopyRows& a, hipStream_t s);
 
 // checks a public camera (struct_size, size, intrinsics) and converts it; NERF_OK or NERF_E_INVALID with last_error set
 int check_grid_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out);

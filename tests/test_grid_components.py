@@ -1,0 +1,347 @@
+"""Connected components and floater detection on the GPU (include/nerf_mi355x.h, "Sparse voxel grid: connected components"):
+``compute_FDR``, ``label_components``, ``remove_floaters`` and ``GridTrainer.remove_floaters`` against the reference's
+recorded ``compute_FDR`` (tests/golden/grid_components.npz) and against the numpy restatement
+(tests/grid_components_oracle.py, checked against the same fixture in tests/test_grid_components_cpu.py).
+Needs a real MI355X: run with ``pytest -m gpu``."""
+import numpy as np
+import pytest
+import torch
+
+import grid_components_oracle as CO
+from test_grid import cpu, gpu, make_grid, random_grid, set_opt
+from test_grid_components_cpu import CASES, GOLDEN, case_inputs
+from test_grid_resample import ring_cameras, to_camera
+
+pytestmark = pytest.mark.gpu
+
+RADIUS, CENTER = np.array([1.0, 1.1, 0.9], np.float32), np.array([0.0, 0.1, -0.1], np.float32)
+
+
+@pytest.fixture(scope="module")
+def N():
+    import nerf_projects_amd as pkg
+    return pkg
+
+
+def grid_dict(links, density, basis_dim=1, seed=0):
+    sh = np.random.default_rng(seed).normal(0.0, 0.7, (density.shape[0], 3 * basis_dim)).astype(np.float32)
+    return {"links": links, "density_data": density, "sh_data": sh, "radius": RADIUS, "center": CENTER}
+
+
+def mask_grid(N, occ):
+    """A grid whose kept nodes are `occ` (density 1 everywhere)."""
+    occ = np.asarray(occ, dtype=bool)
+    links = np.full(occ.shape, -1, dtype=np.int32)
+    links[occ] = np.arange(int(occ.sum()), dtype=np.int32)
+    return make_grid(N, grid_dict(links, np.ones((int(occ.sum()), 1), np.float32)))
+
+
+def to_numpy(result):
+    out = dict(result)
+    if "floater_mask_3d" in out:
+        t = out["floater_mask_3d"]
+        assert torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32      # the stated deviation: labels stay on the device
+        out["floater_mask_3d"] = cpu(t)
+    return out
+
+
+def bits(t):
+    return cpu(t).view(np.int32)
+
+
+# ---- 1. the reference's recorded results -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES)
+def test_compute_fdr_against_the_reference(N, case):
+    z = np.load(GOLDEN)
+    links, density, kw = case_inputs(z, case)
+    grid = make_grid(N, grid_dict(links, density))
+    want = CO.fixture_result(z, case)
+    got = to_numpy(N.compute_FDR(grid, **kw))
+    CO.assert_same_result(got, want, case)
+    labels, volumes = N.label_components(grid, kw["threshold"], kw["use_density_threshold"], kw["connectivity"])
+    assert labels.dtype == torch.int32 and volumes.dtype == torch.int64 and volumes.is_cuda
+    assert tuple(volumes.shape) == (want["num_components"],)
+    if want["num_components"]:
+        assert np.array_equal(cpu(labels), want["floater_mask_3d"])
+        assert np.array_equal(cpu(volumes), np.bincount(want["floater_mask_3d"].reshape(-1))[1:])
+    else:
+        assert not labels.any()
+    flat = N.compute_all_advanced_metrics(grid, 30.0, fdr_threshold=kw["threshold"], fdr_min_object_size=kw["min_object_size"],
+                                          fdr_size_gap_ratio=kw["size_gap_ratio"], fdr_use_adaptive=kw["use_adaptive"],
+                                          fdr_connectivity=kw["connectivity"], peak_gpu_memory_mb=1024.0, verbose=False)
+    if kw["use_density_threshold"]:      # (compute_all_advanced_metrics has no switch for it, as in the reference)
+        assert flat["FDR"] == want["FDR"] and flat["FDR_num_components"] == want["num_components"]
+        assert set(flat) == {"MCQ", "FDR"} | {f"MCQ_{k}" for k in N.compute_MCQ(30.0, 1024.0)} | {f"FDR_{k}" for k in want}
+
+
+# ---- 2. the restatement on random grids ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("basis_dim,reso,seed", [(9, (28, 33, 44), 1), (4, (40, 36, 31), 2), (1, (44, 44, 44), 3)])
+@pytest.mark.parametrize("connectivity", [6, 18, 26])
+def test_kernels_equal_the_restatement_on_random_grids(N, basis_dim, reso, seed, connectivity):
+    rng = np.random.default_rng(seed)
+    g = random_grid(rng, reso, basis_dim, keep=0.12)
+    specks = (g["links"] < 0) & (rng.random(reso) < 0.03)      # dust around the blobs
+    n0, extra = g["density_data"].shape[0], int(specks.sum())
+    g["links"][specks] = n0 + rng.permutation(extra).astype(np.int32)
+    g["density_data"] = np.concatenate([g["density_data"], rng.uniform(-2.0, 30.0, (extra, 1)).astype(np.float32)])
+    g["sh_data"] = np.concatenate([g["sh_data"], rng.normal(0, 0.7, (extra, 3 * basis_dim)).astype(np.float32)])
+    grid = make_grid(N, g)
+    for kw in (dict(threshold=0.01, min_object_size=200), dict(threshold=12.0, min_object_size=20, size_gap_ratio=0.5),
+               dict(use_density_threshold=False, min_object_size=50, use_adaptive=False)):
+        kw = dict(kw, connectivity=connectivity)
+        want = CO.compute_fdr(g["links"], g["density_data"], **kw)
+        got = to_numpy(N.compute_FDR(grid, **kw))
+        CO.assert_same_result(got, want, (reso, kw))
+        assert want["num_components"] > 20
+    # two calls give identical bits
+    a, va = N.label_components(grid, 0.01, True, connectivity)
+    b, vb = N.label_components(grid, 0.01, True, connectivity)
+    assert torch.equal(a, b) and torch.equal(va, vb)
+
+
+# ---- 3. the worst cases of a union-find ----------------------------------------------------------------------------------
+def serpentine(shape):
+    """One 6-connected path through the whole lattice: every second z row of every second x slab, joined at alternating ends."""
+    sx, sy, sz = shape
+    occ = np.zeros(shape, dtype=bool)
+    end_y = 0
+    for x in range(0, sx, 2):
+        ys = list(range(0, sy, 2))
+        if end_y != 0:
+            ys = ys[::-1]
+        end_z = 0
+        for k, y in enumerate(ys):
+            occ[x, y, :] = True
+            if k + 1 < len(ys):      # the link to the next row, at the end the walk along this row stops at
+                end_z = sz - 1 if end_z == 0 else 0
+                occ[x, (y + ys[k + 1]) // 2, end_z] = True
+        end_y = ys[-1]
+        if x + 2 < sx:      # the link to the next slab
+            occ[x + 1, end_y, end_z] = True
+    return occ
+
+
+def adversarial_masks():
+    i, j, k = np.indices((20, 18, 22))
+    rng = np.random.default_rng(9)
+    long_runs = rng.random((3, 5, 1000)) < 0.97      # runs of hundreds of nodes along z, cut at random
+    # contacts that cross a wavefront (64 nodes) or a workgroup tile (1024 nodes = 8 rows of 128) and nothing else
+    touch = np.zeros((4, 16, 128), dtype=bool)
+    touch[0, 3, 60:70] = True      # a: a run along z across a wavefront boundary
+    touch[0, 7, 100:110] = True    # b: the last row of tile 0 ...
+    touch[0, 8, 109] = True        #    ... and a face neighbour in tile 1
+    touch[1, 7, 110] = True        # d: an edge neighbour of (0, 7, 109), in another tile
+    touch[1, 9, 110] = True        # c: a corner neighbour of (0, 8, 109)
+    return {
+        "serpentine": serpentine((21, 23, 44)),
+        "full": np.ones((24, 20, 40), dtype=bool),
+        "checkerboard": (i + j + k) % 2 == 0,
+        "two_by_two": np.ones((2, 2, 1000), dtype=bool),
+        "two_by_two_cut": rng.random((2, 2, 1000)) < 0.6,
+        "long_runs": long_runs,
+        "tile_boundary": touch,
+        "wave_boundary": rng.random((5, 7, 96)) < 0.5,      # rows of 96: wavefronts start in the middle of rows
+        "odd_rows": rng.random((6, 9, 37)) < 0.45,
+    }
+
+
+@pytest.mark.parametrize("name", list(adversarial_masks()))
+def test_adversarial_shapes(N, name):
+    from nerf_projects_amd import grid_components as GC
+    occ = adversarial_masks()[name]
+    want_counts = {}
+    for conn in (6, 18, 26):
+        want, n = CO.label(occ, conn)
+        labels, count = GC.label_mask(gpu(occ.astype(np.uint8)), conn)      # raises if the error word is set
+        assert count == n and np.array_equal(cpu(labels), want), (name, conn)
+        vol = GC.component_volumes(labels, count)
+        assert np.array_equal(cpu(vol), CO.volumes(want, n))
+        want_counts[conn] = n
+    if name in ("serpentine", "full", "two_by_two"):
+        assert want_counts == {6: 1, 18: 1, 26: 1}
+    if name == "checkerboard":
+        assert want_counts == {6: int(occ.sum()), 18: 1, 26: 1}
+    if name == "tile_boundary":
+        assert want_counts == {6: 4, 18: 3, 26: 2}
+    # through a grid, as compute_FDR sees it
+    grid = mask_grid(N, occ)
+    res = N.compute_FDR(grid, min_object_size=1, use_adaptive=False)
+    assert res["num_components"] == want_counts[26] and res["FDR"] == 0.0 and res["total_volume"] == int(occ.sum())
+
+
+def test_bool_masks_and_refusals(N):
+    from nerf_projects_amd import grid_components as GC
+    occ = np.random.default_rng(2).random((6, 7, 8)) < 0.4
+    a, na = GC.label_mask(gpu(occ), 26)      # a bool mask
+    b, nb = GC.label_mask(gpu(occ.astype(np.uint8) * 7), 26)      # any non-zero byte is occupied
+    assert na == nb and torch.equal(a, b)
+    with pytest.raises(ValueError, match="connectivity"):
+        GC.label_mask(gpu(occ), 4)
+    with pytest.raises(TypeError):
+        GC.label_mask(torch.zeros((4, 4, 4), device="cuda"), 6)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        GC.label_mask(torch.zeros((4, 4, 4), dtype=torch.uint8), 6)
+    with pytest.raises(TypeError):
+        N.compute_FDR(occ)
+
+
+# ---- 4. removal ----------------------------------------------------------------------------------------------------------
+def test_remove_floaters(N):
+    z = np.load(GOLDEN)
+    links, density, _ = case_inputs(z, "blobs_26")
+    g = grid_dict(links, density, basis_dim=4, seed=4)
+    grid = make_grid(N, g)
+    before = {k: cpu(t).copy() for k, t in (("links", grid.links), ("density", grid.density_data), ("sh", grid.sh_data))}
+    new, res = N.remove_floaters(grid)
+    old = to_numpy(res)
+    CO.assert_same_result(old, CO.fixture_result(z, "blobs_26"), "blobs_26")
+    assert old["num_floaters"] > 1000 and new.accelerated and list(new.links.shape) == list(links.shape)
+    # the source is untouched
+    assert np.array_equal(cpu(grid.links), before["links"]) and np.array_equal(bits(grid.sh_data), before["sh"].view(np.int32))
+    # the restatement's tables, bit for bit
+    wl, wd, ws = CO.remove_floaters(g["links"], g["density_data"], g["sh_data"], old)
+    assert np.array_equal(cpu(new.links), wl) and np.array_equal(bits(new.density_data), wd.view(np.int32))
+    assert np.array_equal(bits(new.sh_data), ws.view(np.int32))
+    # kept rows are bit-equal through links; nodes below the threshold (the shell of the fixture) stay
+    keep = cpu(new.links) >= 0
+    assert np.array_equal(bits(new.density_data)[cpu(new.links)[keep]], before["density"].view(np.int32)[links[keep]])
+    assert np.array_equal(bits(new.sh_data)[cpu(new.links)[keep]], before["sh"].view(np.int32)[links[keep]])
+    below = (links >= 0) & (old["floater_mask_3d"] == 0)
+    assert below.sum() > 100 and keep[below].all()
+    removed = (links >= 0) & ~keep
+    assert np.array_equal(removed, np.isin(old["floater_mask_3d"], old["floater_component_ids"]))
+    assert new.capacity == int(keep.sum()) == before["density"].shape[0] - old["floater_volume"]
+    # removed nodes sample density 0
+    pts = gpu(np.argwhere(removed).astype(np.float32))
+    dens, _ = new.sample(pts, grid_coords=True, want_colors=False)
+    assert pts.shape[0] == old["floater_volume"] and not dens.any()
+    kept_pts = gpu(np.argwhere(keep).astype(np.float32))
+    dens_new, sh_new = new.sample(kept_pts, grid_coords=True)
+    dens_old, sh_old = grid.sample(kept_pts, grid_coords=True)
+    assert torch.equal(dens_new, dens_old) and torch.equal(sh_new, sh_old)
+    # the metric of the result: no floaters left, the main objects with their volumes
+    after = to_numpy(N.compute_FDR(new))
+    assert after["FDR"] == 0.0 and after["num_floaters"] == 0 and after["num_components"] == old["num_main_objects"] == 3
+    vol_old = np.bincount(old["floater_mask_3d"].reshape(-1))[1:][old["main_component_ids"] - 1]
+    vol_new = np.bincount(after["floater_mask_3d"].reshape(-1))[1:]
+    assert np.array_equal(vol_new, vol_old) and after["main_volume"] == old["main_volume"]
+
+
+def test_remove_floaters_with_none_and_with_values_that_are_not_finite(N):
+    z = np.load(GOLDEN)
+    links, density, _ = case_inputs(z, "edge_001")
+    g = grid_dict(links, density, basis_dim=9, seed=6)
+    g["sh_data"][::7, 3] = np.nan
+    g["sh_data"][::11, 5] = -np.inf
+    g["sh_data"].view(np.int32)[::13, 8] = 0x7FC12345      # a NaN with a payload
+    grid = make_grid(N, g)
+    # no floaters: the tables come back equal (rows in C order of their nodes)
+    new, res = N.remove_floaters(grid, accelerate=False, threshold=0.01, min_object_size=1, use_adaptive=False)
+    assert res["num_floaters"] == 0 and res["FDR"] == 0.0 and not new.accelerated
+    order = links[links >= 0]
+    assert np.array_equal(cpu(new.links) >= 0, links >= 0) and new.capacity == density.shape[0]
+    assert np.array_equal(bits(new.density_data), density.view(np.int32)[order])
+    assert np.array_equal(bits(new.sh_data), g["sh_data"].view(np.int32)[order])
+    # rows already in C order: identical tables
+    again, _ = N.remove_floaters(new, threshold=0.01, min_object_size=1, use_adaptive=False)
+    assert torch.equal(again.links, new.links) and np.array_equal(bits(again.density_data), bits(new.density_data))
+    assert np.array_equal(bits(again.sh_data), bits(new.sh_data))
+    # with floaters, against the restatement, NaN payloads included
+    new, res = N.remove_floaters(grid, threshold=0.3, min_object_size=5, connectivity=6)
+    old = to_numpy(res)
+    CO.assert_same_result(old, CO.fixture_result(z, "edge_03"), "edge_03")
+    wl, wd, ws = CO.remove_floaters(g["links"], g["density_data"], g["sh_data"], old)
+    assert np.array_equal(cpu(new.links), wl) and np.array_equal(bits(new.density_data), wd.view(np.int32))
+    assert np.array_equal(bits(new.sh_data), ws.view(np.int32)) and old["num_floaters"] > 100
+    # an empty occupancy removes nothing; an empty grid stays empty
+    # (this grid holds +inf densities, which pass every finite threshold: only threshold = inf leaves nothing occupied)
+    same, res = N.remove_floaters(grid, threshold=1e9, min_object_size=1, use_adaptive=False)
+    assert res["num_components"] == CO.compute_fdr(links, density, threshold=1e9)["num_components"] > 0
+    assert res["total_volume"] == int(np.isposinf(density).sum()) and same.capacity == grid.capacity
+    same, res = N.remove_floaters(grid, threshold=float("inf"))
+    assert res["num_components"] == 0 and same.capacity == grid.capacity
+    assert np.array_equal(cpu(same.links) >= 0, links >= 0)
+    links0, density0, _ = case_inputs(z, "empty_links")
+    none, res = N.remove_floaters(make_grid(N, grid_dict(links0, density0)))
+    assert res["num_components"] == 0 and none.capacity == 0 and (none.links == -1).all()
+
+
+def test_trainer_remove_floaters_keeps_training(N):
+    rng = np.random.default_rng(11)
+    g = random_grid(rng, (32, 32, 32), 4, keep=0.25)
+    g["density_data"] = np.abs(g["density_data"]).astype(np.float32)
+    teacher = make_grid(N, g)
+    set_opt(teacher, 1.0, 0.5, 0.0)
+    cams = [to_camera(N, c) for c in ring_cameras(g, 6, 64, 80.0)]
+    rays_o, rays_d, gts = [], [], []
+    for cam in cams:
+        r = cam.gen_rays("cuda")
+        rays_o.append(r.origins)
+        rays_d.append(r.dirs)
+        gts.append(teacher.volume_render_image(cam).view(-1, 3))
+    rays_o, rays_d, gts = torch.cat(rays_o), torch.cat(rays_d), torch.cat(gts)
+    gen = torch.Generator(device="cpu").manual_seed(5)
+
+    def steps(trainer, n, fixed=False):
+        losses = []
+        idx = torch.randint(0, rays_o.shape[0], (4096,), generator=gen).cuda()
+        for _ in range(n):
+            if not fixed:
+                idx = torch.randint(0, rays_o.shape[0], (4096,), generator=gen).cuda()
+            losses.append(trainer.train_step(N.Rays(rays_o[idx], rays_d[idx]), gts[idx], lr_sigma=0.5, lr_sh=1e-2)["mse"])
+        return losses
+
+    # the student: the teacher with halved densities and no colour, plus dust that belongs to nothing
+    s = {k: v.copy() for k, v in g.items()}
+    dust = (s["links"] < 0) & (rng.random(s["links"].shape) < 0.02)
+    n0, extra = s["density_data"].shape[0], int(dust.sum())
+    s["links"][dust] = n0 + np.arange(extra, dtype=np.int32)
+    s["density_data"] = np.concatenate([0.5 * s["density_data"], np.full((extra, 1), 3.0, np.float32)])
+    s["sh_data"] = np.zeros((n0 + extra, 12), np.float32)
+    grid = make_grid(N, s)
+    set_opt(grid, 1.0, 0.5, 0.0)
+    grid.accelerate()
+    trainer = N.GridTrainer(grid)
+    first = steps(trainer, 10)
+    old_key, old_links, old_cap = grid._handle_key, grid.links, grid.capacity
+    res = trainer.remove_floaters(min_object_size=30, use_adaptive=False)
+    assert res["num_floaters"] > 50 and res["num_main_objects"] >= 1
+    assert grid.links is not old_links and grid.capacity == old_cap - res["floater_volume"]
+    assert grid._handle_key != old_key and grid._handle_key[0][0] == grid.links.data_ptr() and grid.accelerated
+    trainer._check_capacity()
+    for t, cols in ((trainer.grad_density, 1), (trainer.grad_sh, 12), (trainer.density_rms, 1), (trainer.sh_rms, 12)):
+        assert tuple(t.shape) == (grid.capacity, cols) and not t.any()
+    assert tuple(trainer.mask.shape) == (grid.capacity,) and not trainer.mask.any()
+    assert N.compute_FDR(grid, min_object_size=30, use_adaptive=False)["FDR"] == 0.0
+    plain = N.SparseGrid.from_tensors(grid.links.clone(), grid.density_data.clone(), grid.sh_data.clone(), grid.radius, grid.center)
+    plain.opt = grid.opt
+    assert not plain.accelerated
+    assert torch.equal(grid.volume_render_image(cams[0]), plain.volume_render_image(cams[0]))
+    after = steps(trainer, 10, fixed=True)      # one batch ten times: its loss before each step
+    print(f"before removal: mse {first[0]:.5f} -> {first[-1]:.5f}; after ({old_cap} -> {grid.capacity} rows): "
+          f"{after[0]:.5f} -> {after[-1]:.5f}")
+    assert after[-1] < after[0] and np.mean(after[-3:]) < np.mean(after[:3])      # the loss still falls
+    assert grid.accelerated
+
+
+def test_a_refused_call_leaves_grid_and_trainer_untouched(N):
+    z = np.load(GOLDEN)
+    links, density, _ = case_inputs(z, "dust_26")
+    grid = make_grid(N, grid_dict(links, density, basis_dim=1))
+    grid.accelerate()
+    trainer = N.GridTrainer(grid)
+    held = (grid.links, grid.density_data, grid.sh_data, trainer.grad_sh, trainer.sh_rms)
+    key = grid._handle_key
+    for exc, kw in ((ValueError, dict(connectivity=8)), (ValueError, dict(connectivity=0)), (TypeError, dict(no_such_argument=1)),
+                    (TypeError, dict(threshold="high"))):
+        with pytest.raises(exc):
+            trainer.remove_floaters(**kw)
+        with pytest.raises(exc):
+            N.remove_floaters(grid, **kw)
+    with pytest.raises(TypeError):
+        N.remove_floaters("grid")
+    now = (grid.links, grid.density_data, grid.sh_data, trainer.grad_sh, trainer.sh_rms)
+    assert all(a is b for a, b in zip(held, now)) and grid._handle_key == key and grid.accelerated
+    res = trainer.remove_floaters(min_object_size=4)
+    assert res["num_floaters"] == 7 and grid.accelerated and grid.capacity == res["main_volume"] + int(
+        ((links >= 0) & (cpu(res["floater_mask_3d"]) == 0)).sum())
