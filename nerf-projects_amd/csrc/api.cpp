@@ -9,6 +9,7 @@
 #include <utility>
 #include <vector>
 
+#include "compact_device.h"
 #include "nerf_internal.h"
 
 namespace nerf {
@@ -678,7 +679,7 @@ static int render_rays_locked(nerf_ctx* c, const nerf_render_args* r, const nerf
     const size_t nN = (size_t)N;
     const bool raw_is_coarse = Si == 0;
     // with a grid: the scratch of classify + compact, sized for the larger pass and reused by the second one (stream order)
-    const size_t occ_pts = occ ? nN * (Si ? Sf : Sc) : 0, occ_nb = occ ? (size_t)occ_blocks((int64_t)occ_pts) : 0;
+    const size_t occ_pts = occ ? nN * (Si ? Sf : Sc) : 0, occ_nb = occ ? (size_t)compact_blocks((int64_t)occ_pts) : 0;
     int rc = ensure_workspace(c, arena_bytes({nN * Sc, nN * Sc * Cc, nN * Sc, nN * (Si ? Si : 1),
                                               nN * (Si ? Sf : 1), nN * (Si ? (size_t)Sf * Cf : 1),
                                               occ_nb * 32, occ_nb + 1, occ_pts + 1, 64}));

@@ -18,6 +18,19 @@
         }                                                                                    \
     } while (0)
 
+// refuses a NULL argument struct and one of another size than this library's (fn: the entry point's name, a const char*)
+#define NERF_CHECK_STRUCT(fn, ptr, type)                                                                      \
+    do {                                                                                                      \
+        if (!(ptr)) {                                                                                         \
+            nerf::set_error("%s: " #type " is NULL", fn);                                                     \
+            return NERF_E_INVALID;                                                                            \
+        }                                                                                                     \
+        if ((ptr)->struct_size != sizeof(type)) {                                                             \
+            nerf::set_error("%s: " #type ".struct_size = %zu, this library expects %zu", fn, (ptr)->struct_size, sizeof(type)); \
+            return NERF_E_INVALID;                                                                            \
+        }                                                                                                     \
+    } while (0)
+
 struct nerf_ctx {
     int device = 0;
     int precision = NERF_PRECISION_F16X2;   // arithmetic of the fused MLP kernel in the RENDERING calls (nerf_set_precision,

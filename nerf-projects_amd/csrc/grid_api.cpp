@@ -1,4 +1,6 @@
-// C ABI of the sparse voxel grid (include/nerf_mi355x.h, "Sparse voxel grid"): argument checks and launches.
+// C ABI of the sparse voxel grid (include/nerf_mi355x.h, "Sparse voxel grid"): argument checks and launches, and the checks
+// the other grid_*_api.cpp files share (grid_internal.h). Every check that needs no device comes before the first dereference
+// of a handle and before any launch.
 #include <cmath>
 #include <new>
 
@@ -7,32 +9,40 @@
 
 using namespace nerf;
 
-namespace {
+int nerf::require_ctx(const char* fn, const nerf_ctx* c) {
+    if (c) return NERF_OK;
+    set_error("%s: NULL context", fn);
+    return NERF_E_INVALID;
+}
 
-#define GRID_CHECK_STRUCT(fn, ptr, type)                                                              \
-    do {                                                                                              \
-        if (!(ptr)) {                                                                                 \
-            set_error(fn ": " #type " is NULL");                                                      \
-            return NERF_E_INVALID;                                                                    \
-        }                                                                                             \
-        if ((ptr)->struct_size != sizeof(type)) {                                                     \
-            set_error(fn ": " #type ".struct_size = %zu, this library expects %zu", (ptr)->struct_size, sizeof(type)); \
-            return NERF_E_INVALID;                                                                    \
-        }                                                                                             \
-    } while (0)
+int nerf::require_grid(const char* fn, const nerf_sparse_grid* grid) {
+    if (grid) return NERF_OK;
+    set_error("%s: NULL grid", fn);
+    return NERF_E_INVALID;
+}
 
-int check_options(const char* fn, const nerf_grid_render_options* o, GridRenderOpt* out) {
-    if (!o) {
-        set_error("%s: nerf_grid_render_options is NULL", fn);
+int nerf::check_grid_reso(const char* fn, const int32_t* reso, int64_t* nodes) {
+    if (!reso) {
+        set_error("%s: reso is NULL", fn);
         return NERF_E_INVALID;
     }
-    if (o->struct_size != sizeof(nerf_grid_render_options)) {
-        set_error("%s: nerf_grid_render_options.struct_size = %zu, this library expects %zu", fn, o->struct_size,
-                  sizeof(nerf_grid_render_options));
+    for (int k = 0; k < 3; ++k)
+        if (reso[k] < 2 || reso[k] > 1024) {
+            set_error("%s: reso[%d] = %d outside [2, 1024]", fn, k, reso[k]);
+            return NERF_E_INVALID;
+        }
+    *nodes = (int64_t)reso[0] * reso[1] * reso[2];
+    if (*nodes > kGridMaxLattice) {
+        set_error("%s: %lld nodes, at most 2^30", fn, (long long)*nodes);
         return NERF_E_INVALID;
     }
+    return NERF_OK;
+}
+
+int nerf::check_grid_options(const char* fn, const nerf_grid_render_options* o, GridRenderOpt* out) {
+    NERF_CHECK_STRUCT(fn, o, nerf_grid_render_options);
     if (o->last_sample_opaque || o->randomize) {
-        set_error("%s: last_sample_opaque and randomize are not built", fn);
+        set_error("%s: %s is not built", fn, o->last_sample_opaque ? "last_sample_opaque" : "randomize");
         return NERF_E_INVALID;
     }
     if (!(o->step_size >= 1e-3f) || !std::isfinite(o->step_size) || std::isnan(o->sigma_thresh) || std::isnan(o->stop_thresh) ||
@@ -45,15 +55,8 @@ int check_options(const char* fn, const nerf_grid_render_options* o, GridRenderO
     return NERF_OK;
 }
 
-int check_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out) {
-    if (!cam) {
-        set_error("%s: nerf_grid_camera is NULL", fn);
-        return NERF_E_INVALID;
-    }
-    if (cam->struct_size != sizeof(nerf_grid_camera)) {
-        set_error("%s: nerf_grid_camera.struct_size = %zu, this library expects %zu", fn, cam->struct_size, sizeof(nerf_grid_camera));
-        return NERF_E_INVALID;
-    }
+int nerf::check_grid_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out) {
+    NERF_CHECK_STRUCT(fn, cam, nerf_grid_camera);
     if (cam->width < 1 || cam->height < 1 || (int64_t)cam->width * cam->height > kGridMaxItems || !(std::fabs(cam->fx) > 0.0) ||
         !(std::fabs(cam->fy) > 0.0) || !std::isfinite(cam->fx) || !std::isfinite(cam->fy) || !std::isfinite(cam->cx) ||
         !std::isfinite(cam->cy)) {
@@ -71,27 +74,19 @@ int check_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out) {
     return NERF_OK;
 }
 
+namespace {
+
 int render(const char* fn, nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_render_options* opt,
            const nerf_grid_render_args* a) {
-    if (!grid) {
-        set_error("%s: NULL grid", fn);
-        return NERF_E_INVALID;
-    }
-    if (!a) {
-        set_error("%s: nerf_grid_render_args is NULL", fn);
-        return NERF_E_INVALID;
-    }
-    if (a->struct_size != sizeof(nerf_grid_render_args)) {
-        set_error("%s: nerf_grid_render_args.struct_size = %zu, this library expects %zu", fn, a->struct_size,
-                  sizeof(nerf_grid_render_args));
-        return NERF_E_INVALID;
-    }
+    int rc = require_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_render_args);
     GridRenderOpt o{};
-    int rc = check_options(fn, opt, &o);
+    rc = check_grid_options(fn, opt, &o);
     if (rc != NERF_OK) return rc;
     GridRender r{};
     if (cam) {
-        rc = check_camera(fn, cam, &r.cam);
+        rc = check_grid_camera(fn, cam, &r.cam);
         if (rc != NERF_OK) return rc;
         r.n_rays = (int64_t)cam->width * cam->height;
     } else {
@@ -119,9 +114,6 @@ int render(const char* fn, nerf_sparse_grid* grid, const nerf_grid_camera* cam, 
 
 }  // namespace
 
-// the camera check for the other grid files (grid_internal.h)
-int nerf::check_grid_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out) { return check_camera(fn, cam, out); }
-
 extern "C" {
 
 void nerf_grid_destroy(nerf_sparse_grid* grid) {
@@ -135,27 +127,22 @@ void nerf_grid_destroy(nerf_sparse_grid* grid) {
 }
 
 int nerf_grid_create(nerf_ctx* c, const nerf_sparse_grid_desc* d, nerf_sparse_grid** out) {
+    const char* fn = "nerf_grid_create";
     if (!c || !out) {
         set_error("nerf_grid_create: NULL argument");
         return NERF_E_INVALID;
     }
     *out = nullptr;
-    GRID_CHECK_STRUCT("nerf_grid_create", d, nerf_sparse_grid_desc);
+    NERF_CHECK_STRUCT(fn, d, nerf_sparse_grid_desc);
     if (d->basis_dim != 1 && d->basis_dim != 4 && d->basis_dim != 9) {
         set_error("nerf_grid_create: basis_dim = %d: spherical harmonics of 1, 4 or 9 coefficients are built", d->basis_dim);
         return NERF_E_INVALID;
     }
-    for (int k = 0; k < 3; ++k) {
-        if (d->reso[k] < 2 || d->reso[k] > 1024) {
-            set_error("nerf_grid_create: reso[%d] = %d outside [2, 1024]", k, d->reso[k]);
-            return NERF_E_INVALID;
-        }
-        if (!(d->radius[k] > 0.0f) || !std::isfinite(d->radius[k]) || !std::isfinite(d->center[k])) {
-            set_error("nerf_grid_create: axis %d: radius = %g must be positive and finite, center = %g finite", k, d->radius[k],
-                      d->center[k]);
-            return NERF_E_INVALID;
-        }
-    }
+    int64_t n = 0;
+    float offset[3], scaling[3];
+    int rc = check_grid_reso(fn, d->reso, &n);
+    if (rc == NERF_OK) rc = grid_world2grid(fn, d->center, d->radius, d->reso, offset, scaling);
+    if (rc != NERF_OK) return rc;
     if (d->capacity < 0 || d->capacity > 0x7fffffffLL || !d->links || (d->capacity > 0 && (!d->density_data || !d->sh_data))) {
         set_error("nerf_grid_create: links, and with capacity = %lld > 0 density_data and sh_data, are required",
                   (long long)d->capacity);
@@ -163,7 +150,6 @@ int nerf_grid_create(nerf_ctx* c, const nerf_sparse_grid_desc* d, nerf_sparse_gr
     }
     DeviceGuard dg(c->device);
     hipStream_t s = (hipStream_t)d->stream;
-    const int64_t n = (int64_t)d->reso[0] * d->reso[1] * d->reso[2];
     int* d_bad = nullptr;
     int bad = 0;
     HIP_TRY(hipMalloc((void**)&d_bad, sizeof(int)));
@@ -191,14 +177,8 @@ int nerf_grid_create(nerf_ctx* c, const nerf_sparse_grid_desc* d, nerf_sparse_gr
     g.capacity = d->capacity;
     for (int k = 0; k < 3; ++k) {
         g.size[k] = d->reso[k];
-        // svox2.py:411-412, 1504-1506: fp32 tensors, each operation rounded
-        const float ratio = d->center[k] / d->radius[k];
-        const float one_minus = 1.0f - ratio;
-        const float off = 0.5f * one_minus;
-        const float scl = 0.5f / d->radius[k];
-        const float off_g = off * (float)d->reso[k];
-        g.offset[k] = off_g - 0.5f;
-        g.scaling[k] = scl * (float)d->reso[k];
+        g.offset[k] = offset[k];
+        g.scaling[k] = scaling[k];
     }
     *out = grid;
     return NERF_OK;
@@ -223,7 +203,7 @@ int nerf_grid_gen_rays(nerf_ctx* c, const nerf_grid_camera* cam, float* origins,
         return NERF_E_INVALID;
     }
     GridCam gc{};
-    const int rc = check_camera("nerf_grid_gen_rays", cam, &gc);
+    const int rc = check_grid_camera("nerf_grid_gen_rays", cam, &gc);
     if (rc != NERF_OK) return rc;
     DeviceGuard dg(c->device);
     HIP_TRY(launch_grid_gen_rays(gc, origins, dirs, (hipStream_t)stream));
@@ -231,11 +211,9 @@ int nerf_grid_gen_rays(nerf_ctx* c, const nerf_grid_camera* cam, float* origins,
 }
 
 int nerf_grid_sample(nerf_sparse_grid* grid, const nerf_grid_sample_args* a) {
-    if (!grid) {
-        set_error("nerf_grid_sample: NULL grid");
-        return NERF_E_INVALID;
-    }
-    GRID_CHECK_STRUCT("nerf_grid_sample", a, nerf_grid_sample_args);
+    const int rc = require_grid("nerf_grid_sample", grid);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT("nerf_grid_sample", a, nerf_grid_sample_args);
     if (a->n < 0 || a->n > kGridMaxItems || (a->n > 0 && (!a->points || !a->density || (a->want_colors && !a->sh)))) {
         set_error("nerf_grid_sample: n = %lld must be in [0, 2^26] and needs points, density and (with want_colors) sh", (long long)a->n);
         return NERF_E_INVALID;
@@ -246,10 +224,8 @@ int nerf_grid_sample(nerf_sparse_grid* grid, const nerf_grid_sample_args* a) {
 }
 
 int nerf_grid_accelerate(nerf_sparse_grid* grid, void* stream) {
-    if (!grid) {
-        set_error("nerf_grid_accelerate: NULL grid");
-        return NERF_E_INVALID;
-    }
+    const int rc = require_grid("nerf_grid_accelerate", grid);
+    if (rc != NERF_OK) return rc;
     DeviceGuard dg(grid->ctx->device);
     const size_t n = (size_t)grid->g.size[0] * grid->g.size[1] * grid->g.size[2];
     if (!grid->d_skip) {
@@ -265,10 +241,8 @@ int nerf_grid_accelerate(nerf_sparse_grid* grid, void* stream) {
 }
 
 int nerf_grid_drop_skip(nerf_sparse_grid* grid) {
-    if (!grid) {
-        set_error("nerf_grid_drop_skip: NULL grid");
-        return NERF_E_INVALID;
-    }
+    const int rc = require_grid("nerf_grid_drop_skip", grid);
+    if (rc != NERF_OK) return rc;
     if (!grid->d_skip) return NERF_OK;
     DeviceGuard dg(grid->ctx->device);
     HIP_TRY(hipDeviceSynchronize());
@@ -280,11 +254,9 @@ int nerf_grid_drop_skip(nerf_sparse_grid* grid) {
 int nerf_grid_has_skip(const nerf_sparse_grid* grid) { return grid && grid->d_skip ? 1 : 0; }
 
 int nerf_grid_project_sh(nerf_ctx* c, const nerf_grid_project_args* a) {
-    if (!c) {
-        set_error("nerf_grid_project_sh: NULL context");
-        return NERF_E_INVALID;
-    }
-    GRID_CHECK_STRUCT("nerf_grid_project_sh", a, nerf_grid_project_args);
+    const int rc = require_ctx("nerf_grid_project_sh", c);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT("nerf_grid_project_sh", a, nerf_grid_project_args);
     if ((a->basis_dim != 1 && a->basis_dim != 4 && a->basis_dim != 9) || a->n_dirs < 1 || a->basis_dim * a->n_dirs > 4096 ||
         a->m < 0 || a->m > kGridMaxItems || a->row0 < 0 || (a->m > 0 && (!a->raw || !a->P || !a->sh_out))) {
         set_error("nerf_grid_project_sh: basis_dim = %d in {1, 4, 9}, 1 <= n_dirs = %d, basis_dim * n_dirs <= 4096, m = %lld "

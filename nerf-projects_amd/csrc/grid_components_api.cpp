@@ -3,38 +3,13 @@
 // any launch.
 #include <cmath>
 
+#include "compact_device.h"
 #include "ctx_internal.h"
 #include "grid_internal.h"
 
 using namespace nerf;
 
 namespace {
-
-#define COMPONENTS_CHECK_STRUCT(fn, ptr, type)                                                        \
-    do {                                                                                              \
-        if (!(ptr)) {                                                                                 \
-            set_error(fn ": " #type " is NULL");                                                      \
-            return NERF_E_INVALID;                                                                    \
-        }                                                                                             \
-        if ((ptr)->struct_size != sizeof(type)) {                                                     \
-            set_error(fn ": " #type ".struct_size = %zu, this library expects %zu", (ptr)->struct_size, sizeof(type)); \
-            return NERF_E_INVALID;                                                                    \
-        }                                                                                             \
-    } while (0)
-
-int check_lattice(const char* fn, const int32_t* reso, int64_t* nodes) {
-    for (int k = 0; k < 3; ++k)
-        if (reso[k] < 2 || reso[k] > 1024) {
-            set_error("%s: reso[%d] = %d outside [2, 1024]", fn, k, reso[k]);
-            return NERF_E_INVALID;
-        }
-    *nodes = (int64_t)reso[0] * reso[1] * reso[2];
-    if (*nodes > kGridMaxLattice) {
-        set_error("%s: %lld nodes, at most 2^30", fn, (long long)*nodes);
-        return NERF_E_INVALID;
-    }
-    return NERF_OK;
-}
 
 int check_count(const char* fn, int64_t n, int64_t count) {
     if (n < 1 || n > kGridMaxLattice || count < 0 || count > n) {
@@ -50,11 +25,9 @@ extern "C" {
 
 int nerf_grid_components_occupancy(nerf_sparse_grid* grid, const nerf_grid_occupancy_args* a) {
     const char* fn = "nerf_grid_components_occupancy";
-    if (!grid) {
-        set_error("%s: NULL grid", fn);
-        return NERF_E_INVALID;
-    }
-    COMPONENTS_CHECK_STRUCT("nerf_grid_components_occupancy", a, nerf_grid_occupancy_args);
+    int rc = require_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_occupancy_args);
     if (std::isnan(a->threshold)) {
         set_error("%s: threshold is NaN", fn);
         return NERF_E_INVALID;
@@ -65,24 +38,22 @@ int nerf_grid_components_occupancy(nerf_sparse_grid* grid, const nerf_grid_occup
     }
     // ---- from here on the handle is read ----
     int64_t n = 0;
-    const int rc = check_lattice(fn, grid->g.size, &n);
+    rc = check_grid_reso(fn, grid->g.size, &n);
     if (rc != NERF_OK) return rc;
     DeviceGuard dg(grid->ctx->device);
     HIP_TRY(launch_grid_occupancy(grid->g, a->use_density != 0, a->threshold, a->occupied, (hipStream_t)a->stream));
     return NERF_OK;
 }
 
-int64_t nerf_grid_components_workspace(int64_t nodes) { return nodes > 0 ? grid_label_blocks(nodes) : 0; }
+int64_t nerf_grid_components_workspace(int64_t nodes) { return nodes > 0 ? compact_blocks(nodes) : 0; }
 
 int nerf_grid_components_label(nerf_ctx* c, const nerf_grid_label_args* a) {
     const char* fn = "nerf_grid_components_label";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
-    COMPONENTS_CHECK_STRUCT("nerf_grid_components_label", a, nerf_grid_label_args);
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_label_args);
     int64_t n = 0;
-    const int rc = check_lattice(fn, a->reso, &n);
+    rc = check_grid_reso(fn, a->reso, &n);
     if (rc != NERF_OK) return rc;
     if (a->connectivity != 6 && a->connectivity != 18 && a->connectivity != 26) {
         set_error("%s: connectivity = %d must be 6, 18 or 26", fn, a->connectivity);
@@ -111,10 +82,8 @@ int nerf_grid_components_label(nerf_ctx* c, const nerf_grid_label_args* a) {
 
 int nerf_grid_components_finish(nerf_ctx* c, const int32_t* status, int64_t* count, void* stream) {
     const char* fn = "nerf_grid_components_finish";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
     if (!status || !count) {
         set_error("%s: status and count are required", fn);
         return NERF_E_INVALID;
@@ -138,11 +107,9 @@ int nerf_grid_components_finish(nerf_ctx* c, const int32_t* status, int64_t* cou
 
 int nerf_grid_components_volumes(nerf_ctx* c, const int32_t* labels, int64_t n, int64_t count, int32_t* volumes, void* stream) {
     const char* fn = "nerf_grid_components_volumes";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
-    const int rc = check_count(fn, n, count);
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
+    rc = check_count(fn, n, count);
     if (rc != NERF_OK) return rc;
     if (count == 0) return NERF_OK;
     if (!labels || !volumes) {
@@ -157,11 +124,9 @@ int nerf_grid_components_volumes(nerf_ctx* c, const int32_t* labels, int64_t n, 
 int nerf_grid_components_keep(nerf_ctx* c, const int32_t* links, const int32_t* labels, int64_t n, const uint8_t* floater,
                               int64_t count, uint8_t* mask, void* stream) {
     const char* fn = "nerf_grid_components_keep";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
-    const int rc = check_count(fn, n, count);
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
+    rc = check_count(fn, n, count);
     if (rc != NERF_OK) return rc;
     if (!links || !labels || !mask || (count > 0 && !floater)) {
         set_error("%s: links, labels, mask and (with count > 0) floater are required", fn);
@@ -174,13 +139,11 @@ int nerf_grid_components_keep(nerf_ctx* c, const int32_t* links, const int32_t* 
 
 int nerf_grid_copy_rows(nerf_ctx* c, const nerf_grid_copy_rows_args* a) {
     const char* fn = "nerf_grid_copy_rows";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
-    COMPONENTS_CHECK_STRUCT("nerf_grid_copy_rows", a, nerf_grid_copy_rows_args);
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_copy_rows_args);
     int64_t n = 0;
-    const int rc = check_lattice(fn, a->reso, &n);
+    rc = check_grid_reso(fn, a->reso, &n);
     if (rc != NERF_OK) return rc;
     if (a->cols < 1 || a->cols > 3 * 9) {
         set_error("%s: cols = %d outside [1, 27]", fn, a->cols);

@@ -6,17 +6,15 @@
 // component's root is its smallest flat index, and the only writes that race are atomicMin, so the result does not depend on
 // the order of arrival: two calls give identical bits. Node counts reach 2^30, so a node index fits int32; flat thread
 // indices are int64_t. No scratch, no inline assembly, no float atomic, no compare-and-swap; LDS only in the root count / rank
-// (16 ballots per workgroup and the one-workgroup scan). Every pointer-chasing loop has an iteration cap that sets the error
-// word instead of spinning.
+// (compact_device.h: 16 ballots per workgroup and the one-workgroup scan). Every pointer-chasing loop has an iteration cap that
+// sets the error word instead of spinning.
+#include "compact_device.h"
 #include "grid_device.h"
 
 namespace nerf {
 namespace {
 
-constexpr int kRankNodes = 1024;          // nodes per workgroup of the root count / rank: 4 rounds of 256 threads
 constexpr int kChaseCap = 1 << 22;        // steps of one find, and rounds of one union, before the error word is set
-
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kGridThreads - 1) / kGridThreads); }
 
 // ---- occupancy: one thread per node -----------------------------------------------------------------------------------------
 // kept and, with use_density, density > threshold in fp32 (NaN is not occupied); any negative link is empty
@@ -146,16 +144,14 @@ __global__ __launch_bounds__(kGridThreads) void grid_label_merge_kernel(const ui
 }
 
 // A later launch (so every parent of the merge is visible): every occupied node gets its root as its parent, and the roots
-// are counted per workgroup. Nodes are rewritten while other lanes still walk through them; a walker then sees the old parent
+// are counted per workgroup (the count launch of compact_device.h). Nodes are rewritten while other lanes still walk through them; a walker then sees the old parent
 // or the root, both ancestors, and a root's own entry never changes here.
 __global__ __launch_bounds__(kGridThreads) void grid_label_flatten_kernel(const uint8_t* __restrict__ occ, int64_t n, int32_t* parent,
                                                                            int32_t* __restrict__ block_offsets, int32_t* err) {
-    __shared__ int wave_count[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int roots = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int64_t node = (int64_t)blockIdx.x * kRankNodes + r * kGridThreads + threadIdx.x;
+        const int64_t node = compact_item(r);
         bool is_root = false;
         if (node < n && occ[node] != 0) {
             const int root = find_root<false>(parent, (int)node, err);
@@ -166,34 +162,13 @@ __global__ __launch_bounds__(kGridThreads) void grid_label_flatten_kernel(const 
         }
         roots += __popcll(__ballot(is_root));
     }
-    if (lane == 0) wave_count[wave] = roots;
-    __syncthreads();
-    if (threadIdx.x == 0) block_offsets[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+    compact_store_count(roots, block_offsets);
 }
 
 // one workgroup turns the per-workgroup counts into exclusive offsets (in place) and stores the total
 __global__ __launch_bounds__(1024) void grid_label_scan_kernel(int32_t* counts, int64_t n, int32_t* total) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024;
-    const int64_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-    int sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += counts[i];
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - sum;
-    for (int64_t i = lo; i < hi; ++i) {
-        const int c = counts[i];
-        counts[i] = run;
-        run += c;
-    }
-    if (t == 1023) *total = part[1023];
+    const int v = compact_scan(counts, n);
+    if (threadIdx.x == 1023) *total = v;
 }
 
 // labels[root] = 1 + the number of roots before it in C order (no atomics: the numbering is that of the lattice)
@@ -201,33 +176,16 @@ __global__ __launch_bounds__(kGridThreads) void grid_label_rank_kernel(const uin
                                                                         const int32_t* __restrict__ parent,
                                                                         const int32_t* __restrict__ block_offsets,
                                                                         int32_t* __restrict__ labels) {
-    __shared__ unsigned long long words[16];
-    __shared__ int word_off[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     bool is_root[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int64_t node = (int64_t)blockIdx.x * kRankNodes + r * kGridThreads + threadIdx.x;
+        const int64_t node = compact_item(r);
         is_root[r] = node < n && occ[node] != 0 && parent[node] == (int32_t)node;
-        const unsigned long long ballot = __ballot(is_root[r]);
-        if (lane == 0) words[r * 4 + wave] = ballot;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = block_offsets[blockIdx.x];
-        for (int q = 0; q < 16; ++q) {
-            word_off[q] = run;
-            run += __popcll(words[q]);
-        }
-    }
-    __syncthreads();
+    const CompactRanks ranks = compact_ranks(is_root, block_offsets);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int64_t node = (int64_t)blockIdx.x * kRankNodes + r * kGridThreads + threadIdx.x;
-        if (!is_root[r]) continue;
-        const unsigned long long w = words[r * 4 + wave];
-        labels[node] = 1 + word_off[r * 4 + wave] + __popcll(w & ((1ull << lane) - 1ull));
-    }
+    for (int r = 0; r < 4; ++r)
+        if (is_root[r]) labels[compact_item(r)] = 1 + ranks.rank(r);
 }
 
 // every other node: its root's label, or 0 when it is not occupied (a root's own entry is left as the rank kernel wrote it)
@@ -308,11 +266,9 @@ hipError_t launch_grid_occupancy(const GridDev& g, int use_density, float thresh
     return hipGetLastError();
 }
 
-int64_t grid_label_blocks(int64_t n) { return (n + kRankNodes - 1) / kRankNodes; }
-
 hipError_t launch_grid_label(const GridLabel& a, hipStream_t s) {
     const int64_t n = (int64_t)a.size[0] * a.size[1] * a.size[2];
-    const int64_t nb = grid_label_blocks(n);
+    const int64_t nb = compact_blocks(n);
     hipError_t e = hipMemsetAsync(a.status, 0, 2 * sizeof(int32_t), s);
     if (e != hipSuccess) return e;
     grid_label_init_kernel<<<blocks_for(n), kGridThreads, 0, s>>>(a.occ, n, a.size[2], a.parent);

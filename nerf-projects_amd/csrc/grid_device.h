@@ -1,6 +1,6 @@
-// Sparse voxel grid: the device functions grid_kernels.hip (rendering) and grid_train_kernels.hip (training) share, so that
-// both walk the same sample lattice with the same fp32 operations: rounded arithmetic, the SH basis, the trilinear set-up,
-// the ray set-up and the steps of the march including the skip rule. Semantics: include/nerf_mi355x.h, "Sparse voxel grid".
+// Sparse voxel grid: the device functions the grid kernels (rendering, training, resampling, components) share, so that all
+// walk the same sample lattice with the same fp32 operations: rounded arithmetic, the SH basis, the trilinear set-up, the ray
+// set-up and the steps of the march including the skip rule. Semantics: include/nerf_mi355x.h, "Sparse voxel grid".
 #pragma once
 #include "grid_internal.h"
 
@@ -8,6 +8,15 @@ namespace nerf {
 namespace {
 
 constexpr int kGridThreads = 256;
+
+inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kGridThreads - 1) / kGridThreads); }      // one thread per item
+
+// flat C-order index of a node (z fastest) -> its coordinates
+__device__ __forceinline__ void node_to_xyz(int64_t idx, const int32_t size[3], int& ix, int& iy, int& iz) {
+    iz = (int)(idx % size[2]);
+    iy = (int)((idx / size[2]) % size[1]);
+    ix = (int)(idx / ((int64_t)size[2] * size[1]));
+}
 
 __device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }

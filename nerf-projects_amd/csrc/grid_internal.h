@@ -1,9 +1,14 @@
-// Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what grid_api.cpp, grid_train_api.cpp, grid_resample_api.cpp,
-// grid_components_api.cpp, grid_kernels.hip, grid_train_kernels.hip, grid_resample_kernels.hip and grid_components_kernels.hip
-// share.
+// Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what the host and the device side of the grid share.
+//   grid_api.cpp            create / render / sample / accelerate, and the argument checks every grid_*_api.cpp uses (below)
+//   grid_train_api.cpp      fused backward, TV gradient, optimiser step
+//   grid_resample_api.cpp   lattice density, weight render, threshold, dilate, compact, gather
+//   grid_components_api.cpp occupancy, labelling, volumes, keep mask, row copy
+//   grid_*_kernels.hip      the kernels of each, on grid_device.h (sampling, rays) and compact_device.h (compaction)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <cmath>
 
 #include "nerf_mi355x.h"
 
@@ -101,7 +106,7 @@ struct GridWeight {
     const float* density;              // [X', Y', Z'] dense
     float* max_weight;                 // [X', Y', Z'], raised
     int32_t size[3];
-    float offset[3], scaling[3];       // world2grid of the lattice, as nerf_grid_create computes it
+    float offset[3], scaling[3];       // world2grid of the lattice (grid_world2grid)
     float step_size, stop_thresh;
 };
 
@@ -120,7 +125,7 @@ hipError_t launch_grid_lattice_density(const GridDev& g, const GridLattice& a, h
 hipError_t launch_grid_weight_render(const GridWeight& a, hipStream_t s);
 hipError_t launch_grid_threshold(const float* volume, int64_t n, float threshold, uint8_t* mask, hipStream_t s);
 hipError_t launch_grid_dilate(const uint8_t* in, const int32_t size[3], uint8_t* out, hipStream_t s);
-int64_t grid_compact_blocks(int64_t n);      // entries of block_offsets
+// block_offsets: [compact_blocks(n)] workspace (compact_device.h)
 hipError_t launch_grid_compact(const uint8_t* mask, int64_t n, int32_t* block_offsets, int32_t* links, int32_t* count,
                                hipStream_t s);
 hipError_t launch_grid_gather(const GridDev& g, const GridGather& a, hipStream_t s);
@@ -131,7 +136,7 @@ struct GridLabel {
     int32_t size[3];
     int32_t connectivity;              // 6, 18 or 26
     int32_t* parent;                   // [X, Y, Z] workspace
-    int32_t* block_offsets;            // [grid_label_blocks(X Y Z)] workspace
+    int32_t* block_offsets;            // [compact_blocks(X Y Z)] workspace (compact_device.h)
     int32_t* labels;                   // [X, Y, Z]
     int32_t* status;                   // [2]: the component count, the error word
 };
@@ -149,15 +154,41 @@ struct GridCopyRows {
 };
 
 hipError_t launch_grid_occupancy(const GridDev& g, int use_density, float threshold, uint8_t* occ, hipStream_t s);
-int64_t grid_label_blocks(int64_t n);        // entries of block_offsets
 hipError_t launch_grid_label(const GridLabel& a, hipStream_t s);
 hipError_t launch_grid_label_volumes(const int32_t* labels, int64_t n, int64_t count, int32_t* volumes, hipStream_t s);
 hipError_t launch_grid_keep_mask(const int32_t* links, const int32_t* labels, int64_t n, const uint8_t* floater, int64_t count,
                                  uint8_t* mask, hipStream_t s);
 hipError_t launch_grid_copy_rows(const GridCopyRows& a, hipStream_t s);
 
-// checks a public camera (struct_size, size, intrinsics) and converts it; NERF_OK or NERF_E_INVALID with last_error set
+// ---- argument checks (grid_api.cpp): NERF_OK, or NERF_E_INVALID with last_error set. None needs a device or reads a handle. ----
+void set_error(const char* fmt, ...);
+int require_ctx(const char* fn, const nerf_ctx* c);                      // "NULL context"
+int require_grid(const char* fn, const nerf_sparse_grid* grid);          // "NULL grid"
+// reso not NULL, every side in [2, 1024] (so that a cell exists on every axis), at most 2^30 nodes
+int check_grid_reso(const char* fn, const int32_t* reso, int64_t* nodes);
+// a public camera (struct_size, size, intrinsics) / the public render options (struct_size, what is not built, ranges), converted
 int check_grid_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out);
+int check_grid_options(const char* fn, const nerf_grid_render_options* o, GridRenderOpt* out);
+
+// world2grid of the reference (svox2.py:411-412, 1504-1506: fp32 tensors, each operation rounded; compiled with
+// -ffp-contract=off) after the check that radius is positive and finite and center finite: GridDev::offset / scaling
+inline int grid_world2grid(const char* fn, const float center[3], const float radius[3], const int32_t reso[3], float offset[3],
+                           float scaling[3]) {
+    for (int k = 0; k < 3; ++k) {
+        if (!(radius[k] > 0.0f) || !std::isfinite(radius[k]) || !std::isfinite(center[k])) {
+            set_error("%s: axis %d: radius = %g must be positive and finite, center = %g finite", fn, k, radius[k], center[k]);
+            return NERF_E_INVALID;
+        }
+        const float ratio = center[k] / radius[k];
+        const float one_minus = 1.0f - ratio;
+        const float off = 0.5f * one_minus;
+        const float scl = 0.5f / radius[k];
+        const float off_g = off * (float)reso[k];
+        offset[k] = off_g - 0.5f;
+        scaling[k] = scl * (float)reso[k];
+    }
+    return NERF_OK;
+}
 
 hipError_t launch_grid_render(const GridDev& g, const GridRenderOpt& o, const GridRender& r, hipStream_t s);
 hipError_t launch_grid_gen_rays(const GridCam& cam, float* origins, float* dirs, hipStream_t s);

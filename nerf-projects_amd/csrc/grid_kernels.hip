@@ -226,8 +226,6 @@ __global__ __launch_bounds__(kGridThreads) void grid_project_sh_kernel(const flo
     sh_out[(row0 + i) * cols + col] = acc;
 }
 
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kGridThreads - 1) / kGridThreads); }
-
 }  // namespace
 
 hipError_t launch_grid_render(const GridDev& g, const GridRenderOpt& o, const GridRender& r, hipStream_t s) {

@@ -2,57 +2,21 @@
 // launches. Every check that needs no device comes before the first dereference of a handle and before any launch.
 #include <cmath>
 
+#include "compact_device.h"
 #include "ctx_internal.h"
 #include "grid_internal.h"
 
 using namespace nerf;
 
-namespace {
-
-#define RESAMPLE_CHECK_STRUCT(fn, ptr, type)                                                          \
-    do {                                                                                              \
-        if (!(ptr)) {                                                                                 \
-            set_error(fn ": " #type " is NULL");                                                      \
-            return NERF_E_INVALID;                                                                    \
-        }                                                                                             \
-        if ((ptr)->struct_size != sizeof(type)) {                                                     \
-            set_error(fn ": " #type ".struct_size = %zu, this library expects %zu", (ptr)->struct_size, sizeof(type)); \
-            return NERF_E_INVALID;                                                                    \
-        }                                                                                             \
-    } while (0)
-
-// every side in [2, 1024] (so that a cell exists on every axis), at most 2^30 nodes
-int check_reso(const char* fn, const int32_t* reso, int64_t* nodes) {
-    if (!reso) {
-        set_error("%s: reso is NULL", fn);
-        return NERF_E_INVALID;
-    }
-    for (int k = 0; k < 3; ++k)
-        if (reso[k] < 2 || reso[k] > 1024) {
-            set_error("%s: reso[%d] = %d outside [2, 1024]", fn, k, reso[k]);
-            return NERF_E_INVALID;
-        }
-    *nodes = (int64_t)reso[0] * reso[1] * reso[2];
-    if (*nodes > kGridMaxLattice) {
-        set_error("%s: %lld nodes, at most 2^30", fn, (long long)*nodes);
-        return NERF_E_INVALID;
-    }
-    return NERF_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int nerf_grid_lattice_density(nerf_sparse_grid* grid, const nerf_grid_lattice_args* a) {
     const char* fn = "nerf_grid_lattice_density";
-    if (!grid) {
-        set_error("%s: NULL grid", fn);
-        return NERF_E_INVALID;
-    }
-    RESAMPLE_CHECK_STRUCT("nerf_grid_lattice_density", a, nerf_grid_lattice_args);
+    int rc = require_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_lattice_args);
     int64_t n = 0;
-    const int rc = check_reso(fn, a->reso, &n);
+    rc = check_grid_reso(fn, a->reso, &n);
     if (rc != NERF_OK) return rc;
     if (!a->xs || !a->ys || !a->zs || !a->density) {
         set_error("%s: xs, ys, zs and density are required", fn);
@@ -74,20 +38,18 @@ int nerf_grid_lattice_density(nerf_sparse_grid* grid, const nerf_grid_lattice_ar
 
 int nerf_grid_weight_render(nerf_ctx* c, const nerf_grid_camera* cam, const nerf_grid_weight_args* a) {
     const char* fn = "nerf_grid_weight_render";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
-    RESAMPLE_CHECK_STRUCT("nerf_grid_weight_render", a, nerf_grid_weight_args);
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_weight_args);
     GridWeight w{};
-    int rc = check_grid_camera(fn, cam, &w.cam);
+    rc = check_grid_camera(fn, cam, &w.cam);
     if (rc != NERF_OK) return rc;
     if (a->last_sample_opaque) {
         set_error("%s: last_sample_opaque is not built", fn);
         return NERF_E_INVALID;
     }
     int64_t n = 0;
-    rc = check_reso(fn, a->reso, &n);
+    rc = check_grid_reso(fn, a->reso, &n);
     if (rc != NERF_OK) return rc;
     if (!(a->step_size >= 1e-3f) || !std::isfinite(a->step_size) || std::isnan(a->stop_thresh)) {
         set_error("%s: step_size = %g must be finite and >= 1e-3, stop_thresh not NaN", fn, a->step_size);
@@ -97,21 +59,9 @@ int nerf_grid_weight_render(nerf_ctx* c, const nerf_grid_camera* cam, const nerf
         set_error("%s: density and max_weight are required", fn);
         return NERF_E_INVALID;
     }
-    for (int k = 0; k < 3; ++k) {
-        if (!(a->radius[k] > 0.0f) || !std::isfinite(a->radius[k]) || !std::isfinite(a->center[k])) {
-            set_error("%s: axis %d: radius = %g must be positive and finite, center = %g finite", fn, k, a->radius[k], a->center[k]);
-            return NERF_E_INVALID;
-        }
-        w.size[k] = a->reso[k];
-        // as nerf_grid_create: fp32, each operation rounded
-        const float ratio = a->center[k] / a->radius[k];
-        const float one_minus = 1.0f - ratio;
-        const float off = 0.5f * one_minus;
-        const float scl = 0.5f / a->radius[k];
-        const float off_g = off * (float)a->reso[k];
-        w.offset[k] = off_g - 0.5f;
-        w.scaling[k] = scl * (float)a->reso[k];
-    }
+    rc = grid_world2grid(fn, a->center, a->radius, a->reso, w.offset, w.scaling);
+    if (rc != NERF_OK) return rc;
+    for (int k = 0; k < 3; ++k) w.size[k] = a->reso[k];
     w.density = a->density;
     w.max_weight = a->max_weight;
     w.step_size = a->step_size;
@@ -123,10 +73,8 @@ int nerf_grid_weight_render(nerf_ctx* c, const nerf_grid_camera* cam, const nerf
 
 int nerf_grid_threshold(nerf_ctx* c, const float* volume, int64_t n, float threshold, uint8_t* mask, void* stream) {
     const char* fn = "nerf_grid_threshold";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
     if (n < 0 || n > kGridMaxLattice || (n > 0 && (!volume || !mask))) {
         set_error("%s: n = %lld must be in [0, 2^30] and needs volume and mask", fn, (long long)n);
         return NERF_E_INVALID;
@@ -142,12 +90,10 @@ int nerf_grid_threshold(nerf_ctx* c, const float* volume, int64_t n, float thres
 
 int nerf_grid_dilate(nerf_ctx* c, const int32_t* reso, const uint8_t* in, uint8_t* out, void* stream) {
     const char* fn = "nerf_grid_dilate";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
     int64_t n = 0;
-    const int rc = check_reso(fn, reso, &n);
+    rc = check_grid_reso(fn, reso, &n);
     if (rc != NERF_OK) return rc;
     if (!in || !out) {
         set_error("%s: in and out are required", fn);
@@ -162,17 +108,15 @@ int nerf_grid_dilate(nerf_ctx* c, const int32_t* reso, const uint8_t* in, uint8_
     return NERF_OK;
 }
 
-int64_t nerf_grid_compact_workspace(int64_t nodes) { return nodes > 0 ? grid_compact_blocks(nodes) : 0; }
+int64_t nerf_grid_compact_workspace(int64_t nodes) { return nodes > 0 ? compact_blocks(nodes) : 0; }
 
 int nerf_grid_compact(nerf_ctx* c, const nerf_grid_compact_args* a) {
     const char* fn = "nerf_grid_compact";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
-    RESAMPLE_CHECK_STRUCT("nerf_grid_compact", a, nerf_grid_compact_args);
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_compact_args);
     int64_t n = 0;
-    const int rc = check_reso(fn, a->reso, &n);
+    rc = check_grid_reso(fn, a->reso, &n);
     if (rc != NERF_OK) return rc;
     if (!a->mask || !a->links || !a->block_offsets || !a->count) {
         set_error("%s: mask, links, block_offsets and count are required", fn);
@@ -185,13 +129,11 @@ int nerf_grid_compact(nerf_ctx* c, const nerf_grid_compact_args* a) {
 
 int nerf_grid_gather(nerf_sparse_grid* grid, const nerf_grid_gather_args* a) {
     const char* fn = "nerf_grid_gather";
-    if (!grid) {
-        set_error("%s: NULL grid", fn);
-        return NERF_E_INVALID;
-    }
-    RESAMPLE_CHECK_STRUCT("nerf_grid_gather", a, nerf_grid_gather_args);
+    int rc = require_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_gather_args);
     int64_t n = 0;
-    const int rc = check_reso(fn, a->reso, &n);
+    rc = check_grid_reso(fn, a->reso, &n);
     if (rc != NERF_OK) return rc;
     if (a->rows < 0 || a->rows > n) {
         set_error("%s: rows = %lld must be in [0, %lld] (the nodes of the lattice)", fn, (long long)a->rows, (long long)n);

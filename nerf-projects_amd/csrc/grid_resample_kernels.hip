@@ -6,23 +6,21 @@
 // Everything that interpolates goes through grid_device.h (cell_of, load_links, trilerp, the rounded add / mul / sub): a
 // resampled value is the value grid_sample_kernel gives at the same point, bit for bit. Node counts reach 1024^3 = 2^30 and
 // rows * columns passes 2^31 at 512^3 * 27, so every flat index is int64_t. No scratch, no inline assembly; LDS only in the
-// compaction (16 ballots per workgroup and the one-workgroup scan); the only atomic is the weight render's integer maximum.
+// compaction (compact_device.h: 16 ballots per workgroup and the one-workgroup scan); the only atomic is the weight render's
+// integer maximum.
+#include "compact_device.h"
 #include "grid_device.h"
 
 namespace nerf {
 namespace {
-
-constexpr int kCompactNodes = 1024;      // nodes per workgroup of the compaction: 4 rounds of 256 threads
-
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kGridThreads - 1) / kGridThreads); }
 
 // ---- lattice density: one thread per node of the new lattice, z fastest ------------------------------------------------
 __global__ __launch_bounds__(kGridThreads) void grid_lattice_density_kernel(GridDev g, GridLattice a) {
     const int64_t n = (int64_t)a.size[0] * a.size[1] * a.size[2];
     const int64_t idx = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
     if (idx >= n) return;
-    const int iz = (int)(idx % a.size[2]), iy = (int)((idx / a.size[2]) % a.size[1]);
-    const int ix = (int)(idx / ((int64_t)a.size[2] * a.size[1]));
+    int ix, iy, iz;
+    node_to_xyz(idx, a.size, ix, iy, iz);
     const float p[3] = {a.axis[0][ix], a.axis[1][iy], a.axis[2][iz]};
     int l[3];
     float wa[3], wb[3];
@@ -130,7 +128,9 @@ __global__ __launch_bounds__(kGridThreads) void grid_dilate_kernel(const uint8_t
     const int64_t n = (int64_t)sx * sy * sz;
     const int64_t idx = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
     if (idx >= n) return;
-    const int z = (int)(idx % sz), y = (int)((idx / sz) % sy), x = (int)(idx / ((int64_t)sz * sy));
+    const int32_t size[3] = {sx, sy, sz};
+    int x, y, z;
+    node_to_xyz(idx, size, x, y, z);
     const int xs[3] = {max(x - 1, 0), x, min(x + 1, sx - 1)};
     const int ys[3] = {max(y - 1, 0), y, min(y + 1, sy - 1)};
     const int zs[3] = {max(z - 1, 0), z, min(z + 1, sz - 1)};
@@ -145,76 +145,38 @@ __global__ __launch_bounds__(kGridThreads) void grid_dilate_kernel(const uint8_t
     out[idx] = v ? 1 : 0;
 }
 
-// ---- compaction: mask -> links (count per workgroup, scan, write; the pattern of occupancy_kernels.hip) -------------------
+// ---- compaction: mask -> links (compact_device.h: count per workgroup, scan, rank) ------------------------------------------
 __global__ __launch_bounds__(kGridThreads) void grid_compact_count_kernel(const uint8_t* __restrict__ mask, int64_t n,
                                                                            int32_t* __restrict__ block_offsets) {
-    __shared__ int wave_count[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int kept = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int64_t node = (int64_t)blockIdx.x * kCompactNodes + r * kGridThreads + threadIdx.x;
+        const int64_t node = compact_item(r);
         kept += __popcll(__ballot(node < n && mask[node] != 0));
     }
-    if (lane == 0) wave_count[wave] = kept;
-    __syncthreads();
-    if (threadIdx.x == 0) block_offsets[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+    compact_store_count(kept, block_offsets);
 }
 
 // one workgroup turns the per-workgroup counts into exclusive offsets (in place) and stores the total
 __global__ __launch_bounds__(1024) void grid_compact_scan_kernel(int32_t* counts, int64_t n, int32_t* total) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024;
-    const int64_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-    int sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += counts[i];
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {      // inclusive scan of the 1024 partial sums
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - sum;
-    for (int64_t i = lo; i < hi; ++i) {
-        const int c = counts[i];
-        counts[i] = run;
-        run += c;
-    }
-    if (t == 1023) *total = part[1023];
+    const int v = compact_scan(counts, n);
+    if (threadIdx.x == 1023) *total = v;
 }
 
 __global__ __launch_bounds__(kGridThreads) void grid_compact_links_kernel(const uint8_t* __restrict__ mask, int64_t n,
                                                                            const int32_t* __restrict__ block_offsets,
                                                                            int32_t* __restrict__ links) {
-    __shared__ unsigned long long words[16];
-    __shared__ int word_off[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     bool keep[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int64_t node = (int64_t)blockIdx.x * kCompactNodes + r * kGridThreads + threadIdx.x;
+        const int64_t node = compact_item(r);
         keep[r] = node < n && mask[node] != 0;
-        const unsigned long long ballot = __ballot(keep[r]);
-        if (lane == 0) words[r * 4 + wave] = ballot;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = block_offsets[blockIdx.x];
-        for (int q = 0; q < 16; ++q) {
-            word_off[q] = run;
-            run += __popcll(words[q]);
-        }
-    }
-    __syncthreads();
+    const CompactRanks ranks = compact_ranks(keep, block_offsets);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int64_t node = (int64_t)blockIdx.x * kCompactNodes + r * kGridThreads + threadIdx.x;
-        if (node >= n) continue;
-        const unsigned long long w = words[r * 4 + wave];
-        links[node] = keep[r] ? word_off[r * 4 + wave] + __popcll(w & ((1ull << lane) - 1ull)) : -1;
+        const int64_t node = compact_item(r);
+        if (node < n) links[node] = keep[r] ? ranks.rank(r) : -1;
     }
 }
 
@@ -238,8 +200,8 @@ __global__ __launch_bounds__(kGridThreads) void grid_gather_kernel(GridDev g, Gr
     if (row >= a.rows) return;
     const int64_t node = a.node_of_row[row];
     if (node < 0 || node >= (int64_t)a.size[0] * a.size[1] * a.size[2]) return;      // (links that are no compaction: nothing is read)
-    const int iz = (int)(node % a.size[2]), iy = (int)((node / a.size[2]) % a.size[1]);
-    const int ix = (int)(node / ((int64_t)a.size[2] * a.size[1]));
+    int ix, iy, iz;
+    node_to_xyz(node, a.size, ix, iy, iz);
     const float p[3] = {a.axis[0][ix], a.axis[1][iy], a.axis[2][iz]};
     int l[3];
     float wa[3], wb[3];
@@ -282,11 +244,9 @@ hipError_t launch_grid_dilate(const uint8_t* in, const int32_t size[3], uint8_t*
     return hipGetLastError();
 }
 
-int64_t grid_compact_blocks(int64_t n) { return (n + kCompactNodes - 1) / kCompactNodes; }
-
 hipError_t launch_grid_compact(const uint8_t* mask, int64_t n, int32_t* block_offsets, int32_t* links, int32_t* count,
                                hipStream_t s) {
-    const int64_t nb = grid_compact_blocks(n);
+    const int64_t nb = compact_blocks(n);
     grid_compact_count_kernel<<<(unsigned)nb, kGridThreads, 0, s>>>(mask, n, block_offsets);
     grid_compact_scan_kernel<<<1, 1024, 0, s>>>(block_offsets, nb, count);
     grid_compact_links_kernel<<<(unsigned)nb, kGridThreads, 0, s>>>(mask, n, block_offsets, links);

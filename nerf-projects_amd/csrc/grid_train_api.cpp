@@ -7,40 +7,16 @@
 
 using namespace nerf;
 
-namespace {
-
-#define TRAIN_CHECK_STRUCT(fn, ptr, type)                                                             \
-    do {                                                                                              \
-        if (!(ptr)) {                                                                                 \
-            set_error(fn ": " #type " is NULL");                                                      \
-            return NERF_E_INVALID;                                                                    \
-        }                                                                                             \
-        if ((ptr)->struct_size != sizeof(type)) {                                                     \
-            set_error(fn ": " #type ".struct_size = %zu, this library expects %zu", (ptr)->struct_size, sizeof(type)); \
-            return NERF_E_INVALID;                                                                    \
-        }                                                                                             \
-    } while (0)
-
-}  // namespace
-
 extern "C" {
 
 int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* o, const nerf_grid_fused_args* a) {
     const char* fn = "nerf_grid_fused_backward";
-    if (!grid) {
-        set_error("%s: NULL grid", fn);
-        return NERF_E_INVALID;
-    }
-    TRAIN_CHECK_STRUCT("nerf_grid_fused_backward", o, nerf_grid_render_options);
-    TRAIN_CHECK_STRUCT("nerf_grid_fused_backward", a, nerf_grid_fused_args);
-    if (o->last_sample_opaque) {
-        set_error("%s: last_sample_opaque is not built", fn);
-        return NERF_E_INVALID;
-    }
-    if (o->randomize) {
-        set_error("%s: randomize is not built", fn);
-        return NERF_E_INVALID;
-    }
+    int rc = require_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
+    GridRenderOpt opt{};
+    rc = check_grid_options(fn, o, &opt);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_fused_args);
     if (a->beta_loss != 0.0f) {
         set_error("%s: beta_loss is not built", fn);
         return NERF_E_INVALID;
@@ -51,12 +27,6 @@ int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_opti
     }
     if (a->background_nlayers != 0) {
         set_error("%s: background layers are not built", fn);
-        return NERF_E_INVALID;
-    }
-    if (!(o->step_size >= 1e-3f) || !std::isfinite(o->step_size) || std::isnan(o->sigma_thresh) || std::isnan(o->stop_thresh) ||
-        !std::isfinite(o->background_brightness) || !std::isfinite(o->near_clip)) {
-        set_error("%s: step_size = %g must be finite and >= 1e-3, the thresholds not NaN, background_brightness and near_clip finite",
-                  fn, o->step_size);
         return NERF_E_INVALID;
     }
     if (a->n_rays < 0 || a->n_rays > kGridMaxItems) {
@@ -79,7 +49,6 @@ int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_opti
     r.grad_density = a->grad_density;
     r.grad_sh = a->grad_sh;
     r.mask = a->mask;
-    const GridRenderOpt opt{o->step_size, o->sigma_thresh, o->stop_thresh, o->background_brightness, o->near_clip};
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;
     DeviceGuard dg(grid->ctx->device);
@@ -89,11 +58,9 @@ int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_opti
 
 int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* a) {
     const char* fn = "nerf_grid_tv_grad";
-    if (!grid) {
-        set_error("%s: NULL grid", fn);
-        return NERF_E_INVALID;
-    }
-    TRAIN_CHECK_STRUCT("nerf_grid_tv_grad", a, nerf_grid_tv_args);
+    int rc = require_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_tv_args);
     if (a->ignore_edge || a->ignore_last_z || a->use_ndc) {
         set_error("%s: ignore_edge, ignore_last_z and NDC scaling are not built", fn);
         return NERF_E_INVALID;
@@ -142,11 +109,9 @@ int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* a) {
 
 int nerf_grid_optim_step(nerf_ctx* c, const nerf_grid_optim_args* a) {
     const char* fn = "nerf_grid_optim_step";
-    if (!c) {
-        set_error("%s: NULL context", fn);
-        return NERF_E_INVALID;
-    }
-    TRAIN_CHECK_STRUCT("nerf_grid_optim_step", a, nerf_grid_optim_args);
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_optim_args);
     if (a->kind != NERF_GRID_OPTIM_RMSPROP && a->kind != NERF_GRID_OPTIM_SGD) {
         set_error("%s: kind = %d must be NERF_GRID_OPTIM_RMSPROP or NERF_GRID_OPTIM_SGD", fn, a->kind);
         return NERF_E_INVALID;

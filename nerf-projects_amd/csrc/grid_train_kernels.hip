@@ -186,7 +186,8 @@ __global__ __launch_bounds__(kGridThreads) void grid_tv_grad_kernel(GridDev g, G
     const int col = (int)(tid % ncol) + a.start_dim;
     const int64_t n = (int64_t)g.size[0] * g.size[1] * g.size[2];
     const int64_t cell = (a.start + i) % n;
-    const int z = (int)(cell % g.size[2]), y = (int)((cell / g.size[2]) % g.size[1]), x = (int)(cell / ((int64_t)g.size[2] * g.size[1]));
+    int x, y, z;
+    node_to_xyz(cell, g.size, x, y, z);
     const int sy = g.size[2], sx = g.size[1] * g.size[2];
     int lk[4];      // 000, +x, +y, +z
     lk[0] = g.links[cell];
@@ -234,8 +235,6 @@ __global__ __launch_bounds__(kGridThreads) void grid_optim_step_kernel(GridOptim
         a.data[tid] = fmaxf(sub(a.data[tid], mul(a.lr, gr)), a.minval);
     }
 }
-
-unsigned blocks_for(int64_t n) { return (unsigned)((n + kGridThreads - 1) / kGridThreads); }
 
 }  // namespace
 

@@ -527,7 +527,7 @@ struct OccGrid {
     int32_t outside_keep;             // a point outside the box is evaluated (NERF_OCC_EVALUATE) or skipped
 };
 // classify + compact of one pass: which of the N x S points of a chunk need the network. Scratch (all carved by the caller):
-// keep_words [occ_blocks(P) * 16] of 64 bits, block_counts [occ_blocks(P)], index [P], count [1].
+// keep_words [compact_blocks(P) * 16] of 64 bits, block_counts [compact_blocks(P)] (compact_device.h), index [P], count [1].
 struct OccCompact {
     OccGrid g;
     const float* rays; int ray_ld;
@@ -540,8 +540,6 @@ struct OccCompact {
     int* count;
     unsigned long long* stats;        // [2]: evaluated += kept, total += N * S
 };
-constexpr int kOccBlockPoints = 1024;
-inline int64_t occ_blocks(int64_t n_points) { return (n_points + kOccBlockPoints - 1) / kOccBlockPoints; }
 hipError_t launch_occ_compact(const OccCompact& o, hipStream_t s);
 // cells from sigma lattices (8-corner test: sigma > threshold or NaN, OR over the lattices) and / or a byte mask, `dilate`
 // rounds of 3x3x3 growth, packed; *n_occupied (device) receives the count. tmp0 / tmp1: one byte per cell each.

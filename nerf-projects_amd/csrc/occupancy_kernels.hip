@@ -5,6 +5,7 @@
 // come out in increasing order (count per workgroup, scan, scatter - three launches), so the fp16-pair kernel, which
 // takes its scales per wavefront, sees the same wavefronts from run to run. The only atomic is the integer count of
 // occupied cells at construction (order-independent).
+#include "compact_device.h"
 #include "mlp_inputs.h"
 
 namespace nerf {
@@ -27,17 +28,16 @@ __device__ __forceinline__ bool occ_keep_point(const OccGrid& g, const float (&p
 }
 
 // ---- classify: one thread per (ray, sample) -----------------------------------------------------------
-// Workgroup b owns points [b * 1024, (b + 1) * 1024) in four rounds of 256; wavefront w of round r owns 64 consecutive
-// points and leaves their keep flags as one 64-bit ballot in keep_words[b * 16 + r * 4 + w]. The last sample of every ray is
-// kept whatever the grid says (its dists is 1e10: nerf.ipynb:300). Rows of skipped points are zeroed here.
+// The count launch of the compaction (compact_device.h) over the points; the classification is the expensive part, so the
+// 16 ballots of workgroup b are left in keep_words[b * 16 ..] for the scatter. The last sample of every ray is kept whatever
+// the grid says (its dists is 1e10: nerf.ipynb:300). Rows of skipped points are zeroed here.
 __global__ __launch_bounds__(256) void occ_classify_kernel(const OccCompact o) {
-    __shared__ int wave_count[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t P = o.N * o.S;
     const bool vec = o.C == 4 && (reinterpret_cast<uintptr_t>(o.raw) & 15) == 0;      // (uniform)
     int kept = 0;
     for (int r = 0; r < 4; ++r) {
-        const int64_t pt = (int64_t)blockIdx.x * kOccBlockPoints + r * 256 + threadIdx.x;
+        const int64_t pt = compact_item(r);
         bool keep = false;
         if (pt < P) {
             const int64_t ray = pt / o.S;
@@ -64,38 +64,17 @@ __global__ __launch_bounds__(256) void occ_classify_kernel(const OccCompact o) {
         if (lane == 0) o.keep_words[(int64_t)blockIdx.x * 16 + r * 4 + wave] = ballot;
         kept += __popcll(ballot);
     }
-    if (lane == 0) wave_count[wave] = kept;
-    __syncthreads();
-    if (threadIdx.x == 0) o.block_counts[blockIdx.x] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+    compact_store_count(kept, o.block_counts);
 }
 
 // ---- scan: one workgroup turns the per-workgroup counts into exclusive offsets (in place) ---------------
 __global__ __launch_bounds__(1024) void occ_scan_kernel(int* counts, int64_t n, int* total, unsigned long long* stats,
                                                         unsigned long long n_points) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (n + 1023) / 1024;
-    const int64_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
-    int sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += counts[i];
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {      // inclusive scan of the 1024 partial sums
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - sum;
-    for (int64_t i = lo; i < hi; ++i) {
-        const int c = counts[i];
-        counts[i] = run;
-        run += c;
-    }
-    if (t == 1023) {
-        *total = part[1023];
+    const int v = compact_scan(counts, n);
+    if (threadIdx.x == 1023) {
+        *total = v;
         if (stats) {      // (stream-ordered launches of one thread each: no atomics needed)
-            stats[0] += (unsigned long long)part[1023];
+            stats[0] += (unsigned long long)v;
             stats[1] += n_points;
         }
     }
@@ -103,33 +82,16 @@ __global__ __launch_bounds__(1024) void occ_scan_kernel(int* counts, int64_t n, 
 
 // ---- scatter: ids of the kept points, in increasing order ---------------------------------------------
 __global__ __launch_bounds__(256) void occ_scatter_kernel(const OccCompact o) {
-    __shared__ unsigned long long words[16];
-    __shared__ int word_off[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x < 16) words[threadIdx.x] = o.keep_words[(int64_t)blockIdx.x * 16 + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = o.block_counts[blockIdx.x];
-        for (int q = 0; q < 16; ++q) {
-            word_off[q] = run;
-            run += __popcll(words[q]);
-        }
-    }
-    __syncthreads();
-    for (int r = 0; r < 4; ++r) {
-        const unsigned long long w = words[r * 4 + wave];
-        if ((w >> lane) & 1ull) {
-            const int64_t pt = (int64_t)blockIdx.x * kOccBlockPoints + r * 256 + threadIdx.x;
-            o.index[word_off[r * 4 + wave] + __popcll(w & ((1ull << lane) - 1ull))] = (int)pt;
-        }
-    }
+    const CompactRanks ranks = compact_ranks(o.keep_words + (int64_t)blockIdx.x * 16, o.block_counts);
+    for (int r = 0; r < 4; ++r)
+        if (ranks.kept(r)) o.index[ranks.rank(r)] = (int)compact_item(r);
 }
 
 hipError_t launch_occ_compact(const OccCompact& o, hipStream_t s) {
     const int64_t P = o.N * o.S;
     if (P <= 0) return hipSuccess;
     if (P > 0x7fffffffLL || !o.keep_words || !o.block_counts || !o.index || !o.count || !o.g.bits) return hipErrorInvalidValue;
-    const int64_t nb = occ_blocks(P);
+    const int64_t nb = compact_blocks(P);
     hipLaunchKernelGGL(occ_classify_kernel, dim3((unsigned)nb), dim3(256), 0, s, o);
     hipLaunchKernelGGL(occ_scan_kernel, dim3(1), dim3(1024), 0, s, o.block_counts, nb, o.count, o.stats, (unsigned long long)P);
     hipLaunchKernelGGL(occ_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, s, o);

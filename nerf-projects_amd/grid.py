@@ -9,7 +9,7 @@ module does not (background layers, learned bases, the other backends) raises ``
 training methods on ``SparseGrid`` - training a grid is ``grid_train.GridTrainer``, under names of its own.
 """
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import List, Optional, Tuple, Union
 
 import numpy as np
@@ -199,6 +199,44 @@ def _three(v, name):
     return torch.tensor(vals, dtype=torch.float32, device="cpu")
 
 
+MAX_LATTICE = 1 << 30
+
+
+def _reso3(reso, name="reso"):
+    if isinstance(reso, (int, np.integer)) and not isinstance(reso, bool):
+        reso = [int(reso)] * 3
+    else:
+        try:
+            reso = [int(r) for r in reso]
+        except TypeError:
+            raise ValueError(f"{name} must be an integer or indexable object of 3 ints") from None
+    if len(reso) != 3:
+        raise ValueError(f"{name} must be an integer or indexable object of 3 ints")
+    if any(r < 2 or r > 1024 for r in reso) or reso[0] * reso[1] * reso[2] > MAX_LATTICE:
+        raise ValueError(f"{name} = {reso}: every side must be in [2, 1024] and the lattice hold at most 2^30 nodes")
+    return reso
+
+
+def _volume_arg(t, name, dtype, ctx=None):
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} is on the CPU: grid resampling has no CPU fallback")
+    if ctx is not None and t.device != ctx.device:
+        raise RuntimeError(f"{name} is on {t.device}, the grid on {ctx.device}")
+    if t.dim() != 3:
+        raise ValueError(f"{name} must be [X, Y, Z], got {tuple(t.shape)}")
+    if t.dtype != dtype and not (dtype == torch.uint8 and t.dtype == torch.bool):
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    _reso3(list(t.shape), name + ".shape")
+    return t.detach().contiguous()
+
+
+def _as_u8(mask):
+    """A bool mask as the uint8 bytes the kernels read (the same memory)."""
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
 def _morton(n):
     """Morton code of every node of an n^3 cube (x in the highest bit of each triple), int64 ``[n, n, n]``."""
     a = np.arange(n, dtype=np.int64)
@@ -301,6 +339,17 @@ class SparseGrid:
         g.capacity = int(sh_data.shape[0])
         g._links, g._density, g._sh = links, torch.as_tensor(density_data), sh_data
         g._handle()      # validates
+        return g
+
+    def _like(self, links, density_data, sh_data, accelerate):
+        """A new grid around three fresh tensors, with this grid's radius, center, basis and a copy of its ``opt``."""
+        g = SparseGrid.__new__(SparseGrid)
+        g._init_common(list(links.shape), self.radius, self.center, BASIS_TYPE_SH, self.basis_dim, 0, self.ctx.device)
+        g.capacity = int(density_data.shape[0])
+        g._links, g._density, g._sh = links, density_data, sh_data
+        g.opt = replace(self.opt)
+        if accelerate:
+            g.accelerate()
         return g
 
     # ---- the borrowed tensors -------------------------------------------------------------------------------

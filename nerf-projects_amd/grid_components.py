@@ -19,14 +19,14 @@ reference's array), and ``verbose`` prints other text. There is no CPU or PyTorc
 for the device once, to read the component count.
 """
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import torch
 
 from ._lib import GridCopyRowsArgs, GridLabelArgs, GridOccupancyArgs, check
-from .grid import BASIS_TYPE_SH, SparseGrid
-from .grid_resample import _reso3, compact_mask
+from .grid import SparseGrid, _as_u8, _reso3, _volume_arg
+from .grid_resample import compact_mask
+from .host import get_context
 
 __all__ = ["label_components", "classify_components", "compute_FDR", "compute_MCQ", "compute_all_advanced_metrics",
            "remove_floaters"]
@@ -62,12 +62,10 @@ def occupancy(grid, threshold=0.01, use_density_threshold=True):
 def label_mask(occupied, connectivity=26):
     """``(labels, count)`` of a uint8 / bool ``[X, Y, Z]`` device mask: int32 labels 1..count in increasing order of the
     components' smallest C-order index, 0 where the mask is 0. Waits for the device once, for ``count``."""
-    from .grid_resample import _volume_arg
-    from .host import get_context
     connectivity = _check_connectivity(connectivity)
     m = _volume_arg(occupied, "occupied", torch.uint8)
     ctx = get_context(m.device)
-    occ = m.view(torch.uint8) if m.dtype == torch.bool else m
+    occ = _as_u8(m)
     dev = ctx.device
     labels = torch.empty(list(occ.shape), dtype=torch.int32, device=dev)
     parent = torch.empty(list(occ.shape), dtype=torch.int32, device=dev)
@@ -86,7 +84,6 @@ def label_mask(occupied, connectivity=26):
 
 def component_volumes(labels, count):
     """int64 ``[count]`` device tensor: the number of nodes of every label 1..count."""
-    from .host import get_context
     ctx = get_context(labels.device)
     vol = torch.empty((count,), dtype=torch.int32, device=ctx.device)
     check(ctx.lib.nerf_grid_components_volumes(ctx.handle, labels.data_ptr(), labels.numel(), count, vol.data_ptr(), ctx.stream()))
@@ -264,11 +261,4 @@ def remove_floaters(grid, accelerate=True, **fdr_kwargs):
     skip data."""
     with torch.no_grad():
         links, density, sh, result = _without_floaters(grid, fdr_kwargs)
-    new = SparseGrid.__new__(SparseGrid)
-    new._init_common(list(links.shape), grid.radius, grid.center, BASIS_TYPE_SH, grid.basis_dim, 0, grid.ctx.device)
-    new.capacity = int(density.shape[0])
-    new._links, new._density, new._sh = links, density, sh
-    new.opt = dataclasses.replace(grid.opt)
-    if accelerate:
-        new.accelerate()
-    return new, result
+    return grid._like(links, density, sh, accelerate), result

@@ -19,49 +19,15 @@ the only wait of a resample (``max_elements > 0``, a cold path in torch as in sv
 the threshold and, when that exceeds ``max_elements``, the top-k threshold).
 """
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import torch
 
 from ._lib import GridCompactArgs, GridGatherArgs, GridLatticeArgs, GridWeightArgs, check
-from .grid import BASIS_TYPE_SH, Camera, SparseGrid, _three
+from .grid import Camera, SparseGrid, _as_u8, _reso3, _three, _volume_arg
 from .host import get_context
 
 __all__ = ["resample_grid", "lattice_axes", "lattice_density", "weight_render", "threshold_mask", "dilate_mask", "compact_mask"]
-
-MAX_LATTICE = 1 << 30
-
-
-def _reso3(reso, name="reso"):
-    if isinstance(reso, (int, np.integer)) and not isinstance(reso, bool):
-        reso = [int(reso)] * 3
-    else:
-        try:
-            reso = [int(r) for r in reso]
-        except TypeError:
-            raise ValueError(f"{name} must be an integer or indexable object of 3 ints") from None
-    if len(reso) != 3:
-        raise ValueError(f"{name} must be an integer or indexable object of 3 ints")
-    if any(r < 2 or r > 1024 for r in reso) or reso[0] * reso[1] * reso[2] > MAX_LATTICE:
-        raise ValueError(f"{name} = {reso}: every side must be in [2, 1024] and the lattice hold at most 2^30 nodes")
-    return reso
-
-
-def _volume_arg(t, name, dtype, ctx=None):
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} is on the CPU: grid resampling has no CPU fallback")
-    if ctx is not None and t.device != ctx.device:
-        raise RuntimeError(f"{name} is on {t.device}, the grid on {ctx.device}")
-    if t.dim() != 3:
-        raise ValueError(f"{name} must be [X, Y, Z], got {tuple(t.shape)}")
-    if t.dtype != dtype and not (dtype == torch.uint8 and t.dtype == torch.bool):
-        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
-    _reso3(list(t.shape), name + ".shape")
-    return t.detach().contiguous()
-
 
 def lattice_axes(old_reso, reso):
     """The node coordinates of a lattice of ``reso`` in the coordinates of a grid of ``old_reso``, per axis, as svox2 makes
@@ -149,7 +115,7 @@ def dilate_mask(mask, steps=1):
     m = _volume_arg(mask, "mask", torch.uint8)
     ctx = get_context(m.device)
     as_bool = m.dtype == torch.bool
-    cur = m.view(torch.uint8) if as_bool else m
+    cur = _as_u8(m)
     reso = (C.c_int32 * 3)(*cur.shape)
     for _ in range(int(steps)):
         nxt = torch.empty_like(cur)
@@ -163,7 +129,7 @@ def compact_mask(mask):
     of kept nodes as a one-element int32 device tensor (reading it waits for the device)."""
     m = _volume_arg(mask, "mask", torch.uint8)
     ctx = get_context(m.device)
-    cur = m.view(torch.uint8) if m.dtype == torch.bool else m
+    cur = _as_u8(m)
     links = torch.empty(list(cur.shape), dtype=torch.int32, device=ctx.device)
     work = torch.empty((int(ctx.lib.nerf_grid_compact_workspace(cur.numel())),), dtype=torch.int32, device=ctx.device)
     count = torch.zeros((1,), dtype=torch.int32, device=ctx.device)
@@ -259,11 +225,4 @@ def resample_grid(grid, reso, sigma_thresh=5.0, weight_thresh=0.01, dilate=2, ca
     with torch.no_grad():
         links, density, sh = _resample_tensors(grid, reso, sigma_thresh, weight_thresh, dilate, cameras,
                                                weight_render_stop_thresh, int(max_elements))
-    new = SparseGrid.__new__(SparseGrid)
-    new._init_common(reso, grid.radius, grid.center, BASIS_TYPE_SH, grid.basis_dim, 0, grid.ctx.device)
-    new.capacity = int(density.shape[0])
-    new._links, new._density, new._sh = links, density, sh
-    new.opt = dataclasses.replace(grid.opt)
-    if accelerate:
-        new.accelerate()
-    return new
+    return grid._like(links, density, sh, accelerate)

@@ -62,6 +62,17 @@ class GridTrainer:
         self.density_rms = torch.zeros((cap, 1), dtype=torch.float32, device=dev)
         self.sh_rms = torch.zeros((cap, cols), dtype=torch.float32, device=dev)
 
+    def _replace_tables(self, new: SparseGrid, accelerate: bool):
+        """The tables of ``new`` (made from this trainer's grid, so every argument has been accepted) replace the grid's in
+        place; the training state is allocated anew and zeroed; the handle, and with ``accelerate`` the skip data, are rebuilt."""
+        g = self.grid
+        g.links, g.density_data, g.sh_data = new.links, new.density_data, new.sh_data
+        self._allocate()
+        if accelerate:
+            g.accelerate()
+        else:
+            g._handle()
+
     def resample(self, reso, sigma_thresh: float = 5.0, weight_thresh: float = 0.01, dilate: int = 2, cameras=None,
                  accelerate: bool = True, weight_render_stop_thresh: float = 0.2, max_elements: int = 0):
         """svox2's ``grid.resample`` inside a training loop: :func:`~nerf_projects_amd.grid_resample.resample_grid` of the
@@ -71,15 +82,8 @@ class GridTrainer:
         the trainer as they were."""
         from .grid_resample import resample_grid
         self._check_capacity()
-        new = resample_grid(self.grid, reso, sigma_thresh, weight_thresh, dilate, cameras, False, weight_render_stop_thresh,
-                            max_elements)
-        g = self.grid
-        g.links, g.density_data, g.sh_data = new.links, new.density_data, new.sh_data
-        self._allocate()
-        if accelerate:
-            g.accelerate()
-        else:
-            g._handle()
+        self._replace_tables(resample_grid(self.grid, reso, sigma_thresh, weight_thresh, dilate, cameras, False,
+                                           weight_render_stop_thresh, max_elements), accelerate)
 
     def remove_floaters(self, accelerate: bool = True, **fdr_kwargs):
         """:func:`~nerf_projects_amd.grid_components.remove_floaters` inside a training loop, with the contract of
@@ -90,13 +94,7 @@ class GridTrainer:
         from .grid_components import remove_floaters
         self._check_capacity()
         new, result = remove_floaters(self.grid, False, **fdr_kwargs)
-        g = self.grid
-        g.links, g.density_data, g.sh_data = new.links, new.density_data, new.sh_data
-        self._allocate()
-        if accelerate:
-            g.accelerate()
-        else:
-            g._handle()
+        self._replace_tables(new, accelerate)
         return result
 
     def zero_grad(self):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import grid_components_oracle as CO
+import grid_resample_oracle as RO
 from test_grid import cpu, gpu, make_grid, random_grid, set_opt
 from test_grid_components_cpu import CASES, GOLDEN, case_inputs
 from test_grid_resample import ring_cameras, to_camera
@@ -167,6 +168,33 @@ def test_adversarial_shapes(N, name):
     grid = mask_grid(N, occ)
     res = N.compute_FDR(grid, min_object_size=1, use_adaptive=False)
     assert res["num_components"] == want_counts[26] and res["FDR"] == 0.0 and res["total_volume"] == int(occ.sum())
+
+
+# The count / scan / rank of csrc/compact_device.h at its boundaries: a partial wavefront, one node short of a workgroup's
+# 1024, exactly one workgroup, a second workgroup holding one node, and 1040 workgroups - more than the scan's 1024 threads,
+# so that every thread owns two counts and the last ones none.
+BOUNDARY_LATTICES = [(2, 2, 2), (3, 11, 31), (2, 2, 256), (5, 5, 41), (128, 128, 65)]
+
+
+@pytest.mark.parametrize("shape", BOUNDARY_LATTICES)
+def test_compaction_and_labelling_at_workgroup_and_scan_boundaries(N, shape):
+    from nerf_projects_amd import grid_components as GC
+    from nerf_projects_amd import grid_resample as GR
+    rng = np.random.default_rng(shape[2])
+    for m in (np.zeros(shape, dtype=bool), np.ones(shape, dtype=bool), rng.random(shape) < 0.3):
+        links, count = GR.compact_mask(gpu(m.astype(np.uint8)))
+        assert np.array_equal(cpu(links), RO.links_of(m)) and int(count.item()) == m.sum()
+    dust = np.zeros(shape, dtype=bool)
+    dust[::2, ::2, ::2] = True      # no occupied node has an occupied 26-neighbour: every one is its own component
+    for conn in (6, 18, 26):
+        labels, count = GC.label_mask(gpu(np.ones(shape, dtype=np.uint8)), conn)
+        assert count == 1 and bool((labels == 1).all())
+        labels, count = GC.label_mask(gpu(np.zeros(shape, dtype=np.uint8)), conn)
+        assert count == 0 and not labels.any()
+        labels, count = GC.label_mask(gpu(dust.astype(np.uint8)), conn)
+        assert count == dust.sum() and np.array_equal(cpu(labels), np.where(dust, RO.links_of(dust) + 1, 0))
+        vol = GC.component_volumes(labels, count)
+        assert tuple(vol.shape) == (count,) and bool((vol == 1).all())
 
 
 def test_bool_masks_and_refusals(N):

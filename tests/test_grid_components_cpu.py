@@ -15,7 +15,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grid_components_oracle as CO  # noqa: E402
-from test_grid_train_cpu import _header_struct_fields  # noqa: E402
+from grid_testlib import assert_structs_match_c_header, compile_kernels_to_asm  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "grid_components.npz")
 CASES = ("blobs_26", "blobs_18", "blobs_6", "blobs_gap", "blobs_single", "blobs_none_large", "blobs_simple", "blobs_small_gap",
@@ -204,32 +204,8 @@ NEW_SYMBOLS = ("nerf_grid_components_occupancy", "nerf_grid_components_workspace
 def test_component_structs_match_a_c_compile_of_the_header(tmp_path):
     import nerf_projects_amd  # noqa: F401
     from nerf_projects_amd import _lib
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nerf_mi355x.h"', "int main(void) {",
-             'printf("code internal %d\\n", NERF_E_INTERNAL);']
-    for cname in NEW_STRUCTS:
-        lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
-        for f in _header_struct_fields(cname):
-            lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
-    lines += ["return 0;", "}"]
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    cc = next(c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if subprocess.run(
-        ["sh", "-c", f"command -v {c}"], capture_output=True).returncode == 0)
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    seen = {}
-    for line in out.splitlines():
-        cname, f, v = line.split()
-        seen.setdefault(cname, {})[f] = int(v)
-    assert seen.pop("code") == {"internal": _lib.NERF_E_INTERNAL} and _lib.NERF_E_INTERNAL == -5
-    for cname, pyname in NEW_STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert C.sizeof(cls) == seen[cname].pop("size"), cname
-        assert [f[0] for f in cls._fields_] == _header_struct_fields(cname), cname
-        for f, off in seen[cname].items():
-            assert getattr(cls, f).offset == off, (cname, f)
-        assert cls().struct_size == C.sizeof(cls)
+    code = assert_structs_match_c_header(tmp_path, NEW_STRUCTS, extra_prints=['printf("code internal %d\\n", NERF_E_INTERNAL);'])
+    assert code == {"code": {"internal": _lib.NERF_E_INTERNAL}} and _lib.NERF_E_INTERNAL == -5
 
 
 def test_component_calls_refuse_bad_arguments_before_any_device_call():
@@ -308,21 +284,11 @@ def test_component_calls_refuse_bad_arguments_before_any_device_call():
 def test_grid_components_kernels_generated_code(tmp_path):
     """No scratch, no inline assembly, no compare-and-swap, no float atomic: integer minimum and integer add only, and the
     only atomic that returns a value is the minimum of the union. At most 64 VGPRs: 8 waves per SIMD."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("nerf_build_for_grid_components", os.path.join(ROOT, "nerf-projects_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
+    text, asm, build = compile_kernels_to_asm(tmp_path, "grid_components_kernels.hip")
     assert "grid_components_kernels.hip" in build.SOURCES and "grid_components_api.cpp" in build.SOURCES
-    path = os.path.join(build.CSRC, "grid_components_kernels.hip")
-    text = open(path).read()
     assert not re.search(r"\basm\b|__asm", text)
     assert "atomicCAS" not in text and "atomicExch" not in text and not re.search(r"atomic\w*\(\s*\(?\s*float", text)
     assert set(re.findall(r"\b(atomic[A-Z]\w*)\(", text)) == {"atomicMin", "atomicAdd"}
-    out = tmp_path / "grid_components_kernels.s"
-    cmd = [build.hipcc()] + build.FLAGS + build.VGPR_FORM + ["-I", os.path.join(ROOT, "include"), "-I", build.CSRC,
-                                                              "--cuda-device-only", "-S", path, "-o", str(out)]
-    subprocess.run(cmd, check=True, cwd=tmp_path)
-    asm = open(out).read()
     kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", asm, re.M)
     names = ("grid_occupancy_kernel", "grid_label_init_kernel", "grid_label_merge_kernel", "grid_label_flatten_kernel",
              "grid_label_scan_kernel", "grid_label_rank_kernel", "grid_label_spread_kernel", "grid_label_volumes_kernel",

@@ -3,7 +3,6 @@ new entry points, the generated code of the grid kernels, the .npz layout, and t
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grid_oracle as GO  # noqa: E402
+from grid_testlib import assert_structs_match_c_header, compile_kernels_to_asm  # noqa: E402
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "grid_render.npz")
 GRIDS = ("a", "b", "c", "d")
@@ -124,51 +124,8 @@ NEW_SYMBOLS = ("nerf_grid_create", "nerf_grid_destroy", "nerf_grid_render_rays",
                "nerf_grid_sample", "nerf_grid_accelerate", "nerf_grid_drop_skip", "nerf_grid_has_skip", "nerf_grid_project_sh")
 
 
-def _header_struct_fields(name):
-    text = open(os.path.join(ROOT, "include", "nerf_mi355x.h")).read()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        names = decl.split(",")
-        first = re.search(r"(\w+)\s*(\[\d+\])?$", names[0].strip()).group(1)
-        fields.append(first)
-        for extra in names[1:]:
-            fields.append(re.search(r"(\w+)", extra.strip()).group(1))
-    return fields
-
-
 def test_new_structs_match_a_c_compile_of_the_header(tmp_path):
-    import nerf_projects_amd  # noqa: F401
-    from nerf_projects_amd import _lib
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nerf_mi355x.h"', "int main(void) {"]
-    for cname in NEW_STRUCTS:
-        lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
-        for f in _header_struct_fields(cname):
-            lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
-    lines += ["return 0;", "}"]
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    cc = next(c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if subprocess.run(
-        ["sh", "-c", f"command -v {c}"], capture_output=True).returncode == 0)
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    seen = {}
-    for line in out.splitlines():
-        cname, f, v = line.split()
-        seen.setdefault(cname, {})[f] = int(v)
-    for cname, pyname in NEW_STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert C.sizeof(cls) == seen[cname].pop("size"), cname
-        assert [f[0] for f in cls._fields_] == _header_struct_fields(cname), cname
-        assert cls._fields_[0][0] == "struct_size" and getattr(cls, "struct_size").offset == 0
-        for f, off in seen[cname].items():
-            assert getattr(cls, f).offset == off, (cname, f)
-        assert cls().struct_size == C.sizeof(cls)
+    assert_structs_match_c_header(tmp_path, NEW_STRUCTS)
 
 
 def test_new_symbols_are_exported_and_a_wrong_struct_size_is_refused():
@@ -196,18 +153,8 @@ def test_new_symbols_are_exported_and_a_wrong_struct_size_is_refused():
 
 
 def test_grid_kernels_use_no_scratch_and_no_inline_assembly(tmp_path):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("nerf_build_for_grid", os.path.join(ROOT, "nerf-projects_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
-    path = os.path.join(build.CSRC, "grid_kernels.hip")
-    text = open(path).read()
+    text, asm, _ = compile_kernels_to_asm(tmp_path, "grid_kernels.hip")
     assert not re.search(r"\basm\b|__asm", text)
-    out = tmp_path / "grid_kernels.s"
-    cmd = [build.hipcc()] + build.FLAGS + build.VGPR_FORM + ["-I", os.path.join(ROOT, "include"), "-I", build.CSRC,
-                                                              "--cuda-device-only", "-S", path, "-o", str(out)]
-    subprocess.run(cmd, check=True, cwd=tmp_path)
-    asm = open(out).read()
     kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", asm, re.M)
     assert sum("grid_render_kernel" in k for k in kernels) == 24 and len(kernels) == 30, kernels
     sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", asm)

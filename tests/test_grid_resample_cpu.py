@@ -5,7 +5,6 @@ csrc/grid_resample_kernels.hip."""
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -15,7 +14,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grid_resample_oracle as RO  # noqa: E402
-from test_grid_train_cpu import RENDER, _header_struct_fields, fixture_grid  # noqa: E402
+from grid_testlib import assert_structs_match_c_header, compile_kernels_to_asm  # noqa: E402
+from test_grid_train_cpu import RENDER, fixture_grid  # noqa: E402
 
 RESAMPLE = os.path.join(ROOT, "tests", "golden", "grid_resample.npz")
 CASES = ("b_x2", "c_x2", "b_x1p5", "c_odd", "a_odd", "a_down", "b_down", "a_same", "c_same")
@@ -149,32 +149,7 @@ NEW_SYMBOLS = ("nerf_grid_lattice_density", "nerf_grid_weight_render", "nerf_gri
 
 
 def test_resampling_structs_match_a_c_compile_of_the_header(tmp_path):
-    import nerf_projects_amd  # noqa: F401
-    from nerf_projects_amd import _lib
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nerf_mi355x.h"', "int main(void) {"]
-    for cname in NEW_STRUCTS:
-        lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
-        for f in _header_struct_fields(cname):
-            lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
-    lines += ["return 0;", "}"]
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    cc = next(c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if subprocess.run(
-        ["sh", "-c", f"command -v {c}"], capture_output=True).returncode == 0)
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    seen = {}
-    for line in out.splitlines():
-        cname, f, v = line.split()
-        seen.setdefault(cname, {})[f] = int(v)
-    for cname, pyname in NEW_STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert C.sizeof(cls) == seen[cname].pop("size"), cname
-        assert [f[0] for f in cls._fields_] == _header_struct_fields(cname), cname
-        for f, off in seen[cname].items():
-            assert getattr(cls, f).offset == off, (cname, f)
-        assert cls().struct_size == C.sizeof(cls)
+    assert_structs_match_c_header(tmp_path, NEW_STRUCTS)
 
 
 def test_resampling_calls_refuse_bad_arguments_before_any_device_call():
@@ -256,22 +231,12 @@ def test_resampling_calls_refuse_bad_arguments_before_any_device_call():
 
 
 def test_grid_resample_kernels_use_no_scratch_no_inline_assembly_and_a_native_atomic_max(tmp_path):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("nerf_build_for_grid_resample", os.path.join(ROOT, "nerf-projects_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
+    text, asm, build = compile_kernels_to_asm(tmp_path, "grid_resample_kernels.hip")
     assert "grid_resample_kernels.hip" in build.SOURCES and "grid_resample_api.cpp" in build.SOURCES
-    path = os.path.join(build.CSRC, "grid_resample_kernels.hip")
-    text = open(path).read()
     assert not re.search(r"\basm\b|__asm", text)
-    assert '#include "grid_device.h"' in text
+    assert '#include "grid_device.h"' in text and '#include "compact_device.h"' in text
     for shared in ("cell_of(", "load_links(", "trilerp("):      # the sampler's own device functions, not copies of them
         assert shared in text and not re.search(r"void\s+%s|float\s+%s" % (re.escape(shared), re.escape(shared)), text), shared
-    out = tmp_path / "grid_resample_kernels.s"
-    cmd = [build.hipcc()] + build.FLAGS + build.VGPR_FORM + ["-I", os.path.join(ROOT, "include"), "-I", build.CSRC,
-                                                              "--cuda-device-only", "-S", path, "-o", str(out)]
-    subprocess.run(cmd, check=True, cwd=tmp_path)
-    asm = open(out).read()
     kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", asm, re.M)
     for name in ("grid_lattice_density_kernel", "grid_weight_render_kernel", "grid_threshold_kernel", "grid_dilate_kernel",
                  "grid_compact_count_kernel", "grid_compact_scan_kernel", "grid_compact_links_kernel", "grid_row_nodes_kernel",

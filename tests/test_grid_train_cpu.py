@@ -4,7 +4,6 @@ of csrc/grid_train_kernels.hip."""
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -14,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grid_oracle as GO  # noqa: E402
 import grid_train_oracle as GT  # noqa: E402
+from grid_testlib import assert_structs_match_c_header, compile_kernels_to_asm  # noqa: E402
 
 RENDER = os.path.join(ROOT, "tests", "golden", "grid_render.npz")
 TRAIN = os.path.join(ROOT, "tests", "golden", "grid_train.npz")
@@ -153,52 +153,14 @@ NEW_STRUCTS = {"nerf_grid_fused_args": "GridFusedArgs", "nerf_grid_tv_args": "Gr
 NEW_SYMBOLS = ("nerf_grid_fused_backward", "nerf_grid_tv_grad", "nerf_grid_optim_step")
 
 
-def _header_struct_fields(name):
-    text = open(os.path.join(ROOT, "include", "nerf_mi355x.h")).read()
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        names = decl.split(",")
-        fields.append(re.search(r"(\w+)\s*(\[\d+\])?$", names[0].strip()).group(1))
-        for extra in names[1:]:
-            fields.append(re.search(r"(\w+)", extra.strip()).group(1))
-    return fields
-
-
 def test_training_structs_match_a_c_compile_of_the_header(tmp_path):
     import nerf_projects_amd  # noqa: F401
     from nerf_projects_amd import _lib
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nerf_mi355x.h"', "int main(void) {"]
-    for cname in NEW_STRUCTS:
-        lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
-        for f in _header_struct_fields(cname):
-            lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
-    lines += ['printf("consts tv %d\\n", NERF_GRID_TV_DENSITY * 10 + NERF_GRID_TV_SH);',
-              'printf("consts optim %d\\n", NERF_GRID_OPTIM_RMSPROP * 10 + NERF_GRID_OPTIM_SGD);', "return 0;", "}"]
-    src = tmp_path / "abi.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "abi"
-    cc = next(c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if subprocess.run(
-        ["sh", "-c", f"command -v {c}"], capture_output=True).returncode == 0)
-    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    seen = {}
-    for line in out.splitlines():
-        cname, f, v = line.split()
-        seen.setdefault(cname, {})[f] = int(v)
-    assert seen.pop("consts") == {"tv": _lib.NERF_GRID_TV_DENSITY * 10 + _lib.NERF_GRID_TV_SH,
-                                  "optim": _lib.NERF_GRID_OPTIM_RMSPROP * 10 + _lib.NERF_GRID_OPTIM_SGD}
-    for cname, pyname in NEW_STRUCTS.items():
-        cls = getattr(_lib, pyname)
-        assert C.sizeof(cls) == seen[cname].pop("size"), cname
-        assert [f[0] for f in cls._fields_] == _header_struct_fields(cname), cname
-        for f, off in seen[cname].items():
-            assert getattr(cls, f).offset == off, (cname, f)
-        assert cls().struct_size == C.sizeof(cls)
+    consts = assert_structs_match_c_header(tmp_path, NEW_STRUCTS, extra_prints=[
+        'printf("consts tv %d\\n", NERF_GRID_TV_DENSITY * 10 + NERF_GRID_TV_SH);',
+        'printf("consts optim %d\\n", NERF_GRID_OPTIM_RMSPROP * 10 + NERF_GRID_OPTIM_SGD);'])
+    assert consts == {"consts": {"tv": _lib.NERF_GRID_TV_DENSITY * 10 + _lib.NERF_GRID_TV_SH,
+                                 "optim": _lib.NERF_GRID_OPTIM_RMSPROP * 10 + _lib.NERF_GRID_OPTIM_SGD}}
 
 
 def test_training_calls_refuse_bad_arguments_before_any_device_call():
@@ -270,20 +232,11 @@ def test_training_calls_refuse_bad_arguments_before_any_device_call():
 
 
 def test_grid_train_kernels_use_no_scratch_no_inline_assembly_and_no_compare_and_swap(tmp_path):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("nerf_build_for_grid_train", os.path.join(ROOT, "nerf-projects_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
+    text, asm, build = compile_kernels_to_asm(tmp_path, "grid_train_kernels.hip")
     assert "grid_train_kernels.hip" in build.SOURCES and "grid_train_api.cpp" in build.SOURCES
     assert any(h.endswith("grid_device.h") for h in build.HEADERS)
-    path = os.path.join(build.CSRC, "grid_train_kernels.hip")
-    for src in (path, os.path.join(build.CSRC, "grid_device.h")):
-        assert not re.search(r"\basm\b|__asm", open(src).read()), src
-    out = tmp_path / "grid_train_kernels.s"
-    cmd = [build.hipcc()] + build.FLAGS + build.VGPR_FORM + ["-I", os.path.join(ROOT, "include"), "-I", build.CSRC,
-                                                              "--cuda-device-only", "-S", path, "-o", str(out)]
-    subprocess.run(cmd, check=True, cwd=tmp_path)
-    asm = open(out).read()
+    for name, src in (("grid_train_kernels.hip", text), ("grid_device.h", open(os.path.join(build.CSRC, "grid_device.h")).read())):
+        assert not re.search(r"\basm\b|__asm", src), name
     kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", asm, re.M)
     assert sum("grid_fused_kernel" in k for k in kernels) == 6 and len(kernels) == 9, kernels      # B in {9, 4, 1} x skip
     sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", asm)
