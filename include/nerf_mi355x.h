@@ -753,7 +753,12 @@ int nerf_grid_project_sh(nerf_ctx* ctx, const nerf_grid_project_args* args);
  *   RMSProp: g2 = g * g;  rms = (rms == 0) ? g2 : g2 + beta * (rms - g2);
  *            data = max(data - (lr * g) / (sqrt(rms) + eps), minval)
  *   SGD:     data = max(data - lr * g, minval)
- * (svox2 passes minval = -1e9 for densities and colours). `data` is normally the grid's own density_data or sh_data. */
+ * (svox2 passes minval = -1e9 for densities and colours). `data` is normally the grid's own density_data or sh_data.
+ * Every operation is IEEE fp32: subnormal operands and results are kept (on a first touch a g whose square underflows to 0
+ * leaves rms = 0 and steps by lr * g / eps, with eps = 0 by +-inf or NaN), -0 is a zero, and any non-zero mask byte selects
+ * its row.
+ * `max` is C fmaxf, as in svox2's CUDA: a NaN operand is dropped, so an element whose new value is NaN (a NaN gradient or
+ * rms, inf - inf, 0 / 0) becomes minval; a NaN that reaches rms is stored there and stays. +-inf follow IEEE arithmetic. */
 typedef struct nerf_grid_fused_args {
     size_t struct_size;
     const float* origins;       /* [dev] [n_rays, 3]                                                                */

@@ -81,9 +81,10 @@ def _march(grid, origins, dirs, step_size, sigma_thresh, stop_thresh, near_clip,
 
 
 def fused(grid, origins, dirs, rgb_gt, step_size=0.5, sigma_thresh=1e-10, stop_thresh=1e-7, background_brightness=1.0,
-          near_clip=0.0, skip=None, grad_density=None, grad_sh=None, mask=None):
+          near_clip=0.0, skip=None, grad_density=None, grad_sh=None, mask=None, stats=None):
     """rgb_out [N, 3], grad_density [C, 1], grad_sh [C, 3 B], mask [C] uint8 of ``mean((rgb_out - rgb_gt) ** 2)``; the
-    last three are added to when passed in."""
+    last three are added to when passed in. ``stats``: a dict that receives ``shaded`` (samples with sigma > sigma_thresh),
+    ``clamped`` (those of them with a raw colour channel below 0) and ``marched`` (rays that were marched)."""
     cap, cols = grid["density_data"].shape[0], grid["sh_data"].shape[1]
     B = cols // 3
     gd = np.zeros((cap, 1), dtype=F) if grad_density is None else grad_density
@@ -101,7 +102,13 @@ def fused(grid, origins, dirs, rgb_gt, step_size=0.5, sigma_thresh=1e-10, stop_t
     gc = ((rgb - np.asarray(rgb_gt, F)).astype(F) * scale).astype(F)
     step_ds = (F(step_size) * delta_scale).astype(F)
 
+    if stats is not None:
+        stats.update(shaded=0, clamped=0, marched=int(marched.sum()))
+
     def shade(rays, lk, wa, wb, raw, weight, log_t_after):
+        if stats is not None:
+            stats["shaded"] += len(rays)
+            stats["clamped"] += int((raw < 0).any(-1).sum())
         col = np.maximum(raw, F(0.0))
         g = gc[rays]
         dot = (((col[:, 0] * g[:, 0]).astype(F) + (col[:, 1] * g[:, 1]).astype(F)).astype(F) + (col[:, 2] * g[:, 2]).astype(F)).astype(F)
@@ -161,15 +168,18 @@ def tv_grad(grid, target, start, count, scale, grad, mask, start_dim=0, end_dim=
 
 
 def optim_step(data, rms, grad, mask, kind, lr, beta=0.95, eps=1e-8, minval=-1e9):
-    """in place on the rows with mask != 0; ``kind`` "rmsprop" or "sgd"; every operation one fp32 rounding"""
+    """in place on the rows with mask != 0 (any non-zero byte); ``kind`` "rmsprop" or "sgd"; every operation one IEEE fp32
+    rounding, subnormals kept. ``max`` is C ``fmaxf`` (np.fmax): a NaN operand is dropped, so an element whose update is NaN
+    lands on ``minval`` (np.maximum would keep the NaN). A NaN in ``rms`` stays there."""
     m = np.asarray(mask) != 0
     g = grad[m].astype(F)
-    if kind == "rmsprop":
-        g2 = (g * g).astype(F)
-        r = rms[m]
-        r = np.where(r == 0, g2, (g2 + (F(beta) * (r - g2).astype(F)).astype(F)).astype(F)).astype(F)
-        rms[m] = r
-        upd = ((F(lr) * g).astype(F) / (np.sqrt(r).astype(F) + F(eps)).astype(F)).astype(F)
-    else:
-        upd = (F(lr) * g).astype(F)
-    data[m] = np.maximum((data[m] - upd).astype(F), F(minval)).astype(F)
+    with np.errstate(all="ignore"):      # non-finite and subnormal inputs are ordinary inputs here
+        if kind == "rmsprop":
+            g2 = (g * g).astype(F)
+            r = rms[m]
+            r = np.where(r == 0, g2, (g2 + (F(beta) * (r - g2).astype(F)).astype(F)).astype(F)).astype(F)
+            rms[m] = r
+            upd = ((F(lr) * g).astype(F) / (np.sqrt(r).astype(F) + F(eps)).astype(F)).astype(F)
+        else:
+            upd = (F(lr) * g).astype(F)
+        data[m] = np.fmax((data[m] - upd).astype(F), F(minval)).astype(F)

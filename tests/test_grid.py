@@ -69,6 +69,22 @@ def random_grid(rng, reso, basis_dim, keep=0.2):
             "center": np.array([0.1, 0.0, -0.1], np.float32)}
 
 
+def random_grid_with_faces(rng, reso, basis_dim, keep=0.3, sh_std=0.7):
+    """nodes kept at random over the WHOLE lattice - faces, edges and the 8 corners included (random_grid leaves the outermost
+    layer empty) -, rows in random order, links < -1 at a tenth of the empty nodes"""
+    kept = rng.random(reso) < keep
+    kept[::reso[0] - 1, ::reso[1] - 1, ::reso[2] - 1] = True      # the 8 corners
+    n = int(kept.sum())
+    links = np.full(reso, -1, dtype=np.int32)
+    links[kept] = rng.permutation(n).astype(np.int32)
+    low = (~kept) & (rng.random(reso) < 0.1)
+    links[low] = rng.integers(-9, -1, int(low.sum())).astype(np.int32)
+    dens = rng.uniform(-2.0, 30.0, (n, 1)).astype(np.float32)
+    sh = rng.normal(0.0, sh_std, (n, 3 * basis_dim)).astype(np.float32)
+    return {"links": links, "density_data": dens, "sh_data": sh, "radius": np.array([1.0, 1.2, 0.9], np.float32),
+            "center": np.array([0.1, 0.0, -0.1], np.float32)}
+
+
 # ---- 1. the reference's renders and samples ---------------------------------------------------------------------------
 @pytest.mark.parametrize("name", GRIDS)
 def test_every_recorded_render_plain_and_accelerated(N, name):

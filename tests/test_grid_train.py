@@ -1,15 +1,21 @@
 """Sparse voxel grid training on the GPU (include/nerf_mi355x.h, "Sparse voxel grid: training"): GridTrainer against the
-reference's recorded autograd gradients and RMSProp loop (tests/golden/grid_train.npz) and against the numpy restatement
-(tests/grid_train_oracle.py, checked against the same fixture in tests/test_grid_train_cpu.py).
+reference's recorded autograd gradients and RMSProp loop (tests/golden/grid_train.npz, and grid_train_variants.npz off its one
+setting) and against the numpy restatement (tests/grid_train_oracle.py, checked against the same fixtures in
+tests/test_grid_train_cpu.py); from section 12 on, the settings, batch shapes and inputs where a kernel goes wrong unseen:
+off-default thresholds on grids that keep their faces, batches around a wavefront and a workgroup, colliding rays, hostile
+rays, total variation against fp64 autograd, and the optimiser on subnormal and non-finite values.
 Needs a real MI355X: run with ``pytest -m gpu``."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import grid_oracle as GO
 import grid_train_oracle as GT
-from test_grid import cpu, gpu, make_grid, random_grid, set_opt
-from test_grid_train_cpu import GRIDS, RENDER, TRAIN, fixture_grid, grad_bar, loop_bars
+from test_grid import cpu, gpu, make_grid, random_grid, random_grid_with_faces, set_opt
+from test_grid_train_cpu import (GRIDS, RENDER, TRAIN, TV_LATTICES, TV_SCALING, TV_TARGETS, VARIANT_CASES, VARIANTS, fixture_grid,
+                                 grad_bar, loop_bars, tv_case, tv_lattice, variant_oracle)
 
 pytestmark = pytest.mark.gpu
 
@@ -344,3 +350,365 @@ def test_renders_see_the_trained_values_without_a_new_handle(N):
         grid.volume_render_fused()
     with pytest.raises(NotImplementedError):
         grid.optim_density_step()
+
+
+# =========================================================================================================================
+# Settings, batch shapes and inputs off the beaten path. The helpers first.
+def mixed_rays(rng, g, n):
+    """half through-rays, a quarter starting inside the box, a quarter axis-parallel (two direction components exactly 0)"""
+    radius, center = g["radius"].astype(np.float64), g["center"].astype(np.float64)
+    a, b = n // 2, n // 4
+    m = n - a - b
+    o1, d1 = through_rays(rng, g, a)
+    o2 = center + radius * rng.uniform(-0.95, 0.95, (b, 3))
+    d2 = rng.normal(size=(b, 3)) * rng.uniform(0.5, 2.0, (b, 1))
+    o3 = center + radius * rng.uniform(-0.99, 0.99, (m, 3))
+    d3 = np.zeros((m, 3))
+    ax, sgn = rng.integers(0, 3, m), rng.choice([-1.0, 1.0], m)
+    d3[np.arange(m), ax] = sgn * rng.uniform(0.5, 2.0, m)
+    o3[np.arange(m), ax] = center[ax] - sgn * 2.5 * radius[ax]
+    return np.concatenate([o1, o2, o3]).astype(np.float32), np.concatenate([d1, d2, d3]).astype(np.float32)
+
+
+def run_fused(N, grid, trainer, o, d, gt):
+    """zero_grad + forward_backward: (rgb, log_transmit, grad_density, grad_sh, mask) as numpy, and rgb is the renderer's"""
+    rays = N.Rays(gpu(o), gpu(d))
+    trainer.zero_grad()
+    rgb, logt = trainer.forward_backward(rays, gpu(gt), return_log_transmit=True)
+    want_rgb, want_logt = grid.volume_render(rays, return_log_transmit=True)
+    assert torch.equal(rgb, want_rgb) and torch.equal(logt, want_logt)      # bit-identical to the renderer
+    return cpu(rgb).copy(), cpu(logt).copy(), cpu(trainer.grad_density).copy(), cpu(trainer.grad_sh).copy(), cpu(trainer.mask).copy()
+
+
+def assert_matches_restatement(label, got, want):
+    """got = run_fused's, want = GT.fused's: every gradient entry within 1e-5 of the tensor's largest, the masks differing
+    only on rows whose restated gradient is below that bar in every entry (rows reached beyond a stopping point)"""
+    rgb, _, gd, gs, mask = got
+    rgb_o, gd_o, gs_o, mask_o = want
+    assert np.abs(rgb - rgb_o).max() <= 1e-5, label
+    below = np.ones(mask.shape, dtype=bool)
+    for key, g_, w_ in (("density", gd, gd_o), ("sh", gs, gs_o)):
+        big = float(np.abs(w_).max())
+        assert big > 0, (label, key, "the case differentiates nothing")
+        err = np.abs(g_.astype(np.float64) - w_)
+        print(f"{label} d/d{key}: GPU vs restatement max {err.max():.3e} (bar {1e-5 * big:.3e})")
+        assert np.isfinite(g_).all() and err.max() <= 1e-5 * big, (label, key, int(err.argmax()), err.max(), 1e-5 * big)
+        below &= (np.abs(w_) <= 1e-5 * big).all(-1)
+    differ = (mask != 0) != (mask_o != 0)
+    assert set(np.unique(mask).tolist()) <= {0, 1}
+    assert not (differ & ~below).any(), (label, int((differ & ~below).sum()))
+    return int(differ.sum())
+
+
+# ---- 12. the reference's gradients off the recorded setting ----------------------------------------------------------
+@pytest.mark.parametrize("name,tag", VARIANT_CASES)
+def test_forward_backward_against_the_reference_autograd_off_the_recorded_setting(N, name, tag):
+    """tests/golden/grid_train_variants.npz: step_size 0.3, near_clip 6 and (background 0.5, step_size 0.8, near_clip 2.5), where
+    step_size * delta_scale, the background's part of `remaining` and the clamp of tmin are not what they are at the setting
+    of grid_train.npz. Against the fp64 autograd under grad_bar's rule, and against the restatement at 1e-5 of the largest
+    entry (the reference's own bar is weak where one of its fp32 samples lands on the other side of tmax)."""
+    z, t, v = np.load(RENDER), np.load(TRAIN), np.load(VARIANTS)
+    g = fixture_grid(z, name)
+    bg, step, near = v[f"{name}_{tag}_variant"].tolist()
+    o, d, gt = z[f"{name}_origins"], z[f"{name}_dirs"], t[f"{name}_rgb_gt"]
+    want = variant_oracle(name, tag)
+    grid = make_grid(N, g)
+    trainer = N.GridTrainer(grid)
+    for accelerated in (False, True):
+        if accelerated:
+            grid.accelerate()
+        set_opt(grid, bg, step, near, 0.0, 0.0)
+        label = f"grid {name} {tag} {'accelerated' if accelerated else 'plain'}"
+        got = run_fused(N, grid, trainer, o, d, gt)
+        touched = np.zeros(grid.capacity, dtype=bool)
+        for key, got_g in (("density", got[2]), ("sh", got[3])):
+            ref, tol = grad_bar(v, name, tag, key)
+            err = np.abs(got_g.astype(np.float64) - ref)
+            print(f"{label} d/d{key}: GPU vs fp64 autograd max {err.max():.3e} (bar {tol:.3e}, max |g| {np.abs(ref).max():.3e})")
+            assert np.isfinite(got_g).all() and err.max() <= tol, (label, key, int(err.argmax()), err.max(), tol)
+            touched |= (ref != 0).any(-1)
+        assert np.array_equal(got[4] != 0, touched), label
+        assert assert_matches_restatement(label, got, want) == 0
+        assert abs(float(v[f"{name}_{tag}_loss64"]) - float(((got[0].astype(np.float64) - gt) ** 2).mean())) <= 1e-5
+
+
+# ---- 13. off-default thresholds on grids that keep their faces -------------------------------------------------------
+THRESHOLD_CASES = {
+    # most samples are unshaded and most rays stop early: the two marches have to agree on every decision
+    "sparse": dict(sigma_thresh=5.0, stop_thresh=0.2, near_clip=3.0, background_brightness=0.3, step_size=0.8),
+    # every sample is shaded, those of negative density included; no ray stops
+    "all": dict(sigma_thresh=-1.0, stop_thresh=0.0, near_clip=0.0, background_brightness=1.0, step_size=0.5),
+}
+
+
+@pytest.mark.parametrize("case", sorted(THRESHOLD_CASES))
+@pytest.mark.parametrize("basis_dim,reso", [(9, (20, 18, 22)), (4, (19, 21, 20)), (1, (22, 20, 17))])
+def test_forward_backward_off_default_thresholds_with_kept_faces(N, basis_dim, reso, case):
+    rng = np.random.default_rng(200 + basis_dim)
+    g = random_grid_with_faces(rng, reso, basis_dim, keep=0.3, sh_std=4.0)
+    assert all((f >= 0).any() for f in (g["links"][0], g["links"][-1], g["links"][:, 0], g["links"][:, -1], g["links"][:, :, 0],
+                                        g["links"][:, :, -1])) and (g["links"] < -1).any()
+    o, d = mixed_rays(rng, g, 1000)
+    gt = rng.uniform(0, 1, (1000, 3)).astype(np.float32)
+    c = THRESHOLD_CASES[case]
+    stats = {}
+    skip = GO.skip_distances(g["links"])      # (with it the samples of empty cells are not looked at; they add nothing)
+    want = GT.fused(g, o, d, gt, skip=skip, stats=stats, **c)
+    _, logt_o, (visited, shaded) = GO.render(g, o, d, skip=skip, return_counts=True, **c)
+    stopped = int((logt_o == np.float32(-1e3)).sum())
+    print(f"B = {basis_dim} {case}: {stats}, samples looked at {visited}, rays stopped {stopped}, rows {int(want[3].sum())} of {len(want[3])}")
+    # the raw_own >= 0 branch is taken both ways: at least a tenth of the shaded samples have a clamped channel
+    assert shaded == stats["shaded"] and 10 * stats["clamped"] >= stats["shaded"] and stats["clamped"] < stats["shaded"]
+    if case == "sparse":
+        assert 2 * shaded < visited and 2 * stopped > stats["marched"]
+    else:
+        assert stopped == 0 and (g["density_data"] < 0).any()
+    grid = make_grid(N, g)
+    trainer = N.GridTrainer(grid)
+    for accelerated in (False, True):
+        if accelerated:
+            grid.accelerate()
+        set_opt(grid, c["background_brightness"], c["step_size"], c["near_clip"], c["sigma_thresh"], c["stop_thresh"])
+        got = run_fused(N, grid, trainer, o, d, gt)
+        differ = assert_matches_restatement(f"B = {basis_dim} {case} {'accelerated' if accelerated else 'plain'}", got, want)
+        print(f"B = {basis_dim} {case}: mask rows differing {differ}")
+
+
+# ---- 14. batch edges and additivity ------------------------------------------------------------------------------------
+LANES = {9: 32, 4: 16, 1: 4}      # lanes that own a ray: 64 / LANES rays per wavefront, 256 / LANES per workgroup
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(basis_dim):
+    """a small grid with kept faces, 3 w + 1 rays through it (w = rays of a workgroup) and their targets"""
+    rng = np.random.default_rng(300 + basis_dim)
+    g = random_grid_with_faces(rng, (14, 12, 16), basis_dim, keep=0.4, sh_std=2.0)
+    n = 3 * (256 // LANES[basis_dim]) + 1
+    o, d = through_rays(rng, g, n)
+    return g, o, d, rng.uniform(0, 1, (n, 3)).astype(np.float32), GO.skip_distances(g["links"])
+
+
+@pytest.mark.parametrize("basis_dim", [9, 4, 1])
+def test_batch_sizes_around_a_wavefront_and_a_workgroup(N, basis_dim):
+    g, o, d, gt, skip = edge_case(basis_dim)
+    r, w = 64 // LANES[basis_dim], 256 // LANES[basis_dim]
+    sizes = sorted({n for n in (1, r - 1, r, r + 1, w - 1, w, w + 1, 3 * w + 1) if n > 0})
+    assert (r, w) in ((2, 8), (4, 16), (16, 64)) and sizes[-1] == len(o)
+    grid = make_grid(N, g)
+    trainer = N.GridTrainer(grid)
+    want = {n: GT.fused(g, o[:n], d[:n], gt[:n], skip=skip) for n in sizes}
+    for accelerated in (False, True):
+        if accelerated:
+            grid.accelerate()
+        for n in sizes:
+            got = run_fused(N, grid, trainer, o[:n], d[:n], gt[:n])
+            assert_matches_restatement(f"B = {basis_dim} n = {n} {'accelerated' if accelerated else 'plain'}", got, want[n])
+
+
+@pytest.mark.parametrize("basis_dim", [9, 4, 1])
+def test_a_batch_is_the_sum_of_its_halves(N, basis_dim):
+    """w + 1 rays against their two halves run alone, each scaled by n_half / n (the loss is a mean); 1e-5 of the largest entry"""
+    g, o, d, gt, _ = edge_case(basis_dim)
+    n = 256 // LANES[basis_dim] + 1
+    h = n // 2
+    grid = make_grid(N, g)
+    trainer = N.GridTrainer(grid)
+    whole = run_fused(N, grid, trainer, o[:n], d[:n], gt[:n])
+    first = run_fused(N, grid, trainer, o[:h], d[:h], gt[:h])
+    second = run_fused(N, grid, trainer, o[h:n], d[h:n], gt[h:n])
+    assert np.array_equal(whole[0], np.concatenate([first[0], second[0]]))
+    assert np.array_equal(whole[4], first[4] | second[4]) and whole[4].any()
+    for i, key in ((2, "density"), (3, "sh")):
+        want = first[i].astype(np.float64) * (h / n) + second[i].astype(np.float64) * ((n - h) / n)
+        err, big = float(np.abs(whole[i] - want).max()), float(np.abs(want).max())
+        print(f"B = {basis_dim}: {n} rays vs {h} + {n - h}, d/d{key}: {err:.3e} = {err / big:.2e} of the largest entry")
+        assert big > 0 and err <= 1e-5 * big
+
+
+# ---- 15. contention ------------------------------------------------------------------------------------------------------
+def contention_case(basis_dim):
+    """8 rays through the dense part of a grid, and the same 8 rays 256 times over, interleaved"""
+    rng = np.random.default_rng(400 + basis_dim)
+    g = random_grid(rng, (20, 18, 22), basis_dim, keep=0.4)
+    o, d = through_rays(rng, g, 8)
+    gt = rng.uniform(0, 1, (8, 3)).astype(np.float32)
+    idx = np.tile(np.arange(8), 256)
+    return g, (o, d, gt), (o[idx], d[idx], gt[idx])
+
+
+# what the restatement (sequential fp32 sums, np.add.at) shows for the same experiment on the same grid and rays, as a part
+# of the largest entry; the test prints it. 256 equal terms summed one after the other: about 256 * 2^-24 = 1.5e-5.
+# Measured: basis_dim 9: density 1.17e-5, sh 1.24e-5; basis_dim 1: density 1.01e-5, sh 1.53e-5. The larger of each pair:
+CONTENTION_RESTATED = {9: 1.24e-5, 1: 1.53e-5}
+
+
+@pytest.mark.parametrize("basis_dim", [9, 1])
+def test_many_rays_adding_into_the_same_rows(N, basis_dim):
+    """2048 rays that are 8 rays 256 times: every row is hit by 256 identical adds at once. grad_scale differs from the 8-ray
+    run's by exactly 2^8, so every term is the 8-ray term times 2^-8 exactly and the sums agree to the rounding of the
+    summation. The bar is 3x what the restatement shows; an add lost to a race costs 1 / 256 of an entry, far above it."""
+    g, few, many = contention_case(basis_dim)
+    bar = 3.0 * CONTENTION_RESTATED[basis_dim]
+    assert bar < 1.0 / 256.0 / 10.0
+    grid = make_grid(N, g)
+    trainer = N.GridTrainer(grid)
+    a = run_fused(N, grid, trainer, *few)
+    b = run_fused(N, grid, trainer, *many)
+    assert np.array_equal(b[0], a[0][np.tile(np.arange(8), 256)])
+    assert np.array_equal(a[4], b[4]) and a[4].sum() > 50
+    for i, key in ((2, "density"), (3, "sh")):
+        big = float(np.abs(a[i]).max())
+        err = float(np.abs(b[i].astype(np.float64) - a[i]).max())
+        print(f"B = {basis_dim} d/d{key}: 2048 rays vs 8: {err:.3e} = {err / big:.2e} of the largest entry (bar {bar:.2e}; the "
+              f"restatement shows {CONTENTION_RESTATED[basis_dim]:.2e})")
+        assert big > 0 and err <= bar * big, (key, err / big)
+
+
+# ---- 16. hostile rays inside a batch -----------------------------------------------------------------------------------
+def hostile_rays(g):
+    """eight rays that are defined to write the background and no gradient (include/nerf_mi355x.h): (origins, dirs)"""
+    c, r = g["center"].astype(np.float64), g["radius"].astype(np.float64)
+    inside = c + 0.1 * r
+    far = c + np.array([40.0, 35.0, -50.0]) * r
+    nan, inf = np.nan, np.inf
+    rays = [(inside, [0.0, 0.0, 0.0]),                       # zero direction
+            (inside, [0.3, nan, 0.5]),                       # NaN in the direction
+            ([inf, 0.0, 0.0], [1.0, 0.2, 0.1]),              # infinity in the origin
+            (inside, [inf, 1.0, 0.0]),                       # infinite direction
+            ([0.0, nan, 0.0], [0.0, 1.0, 0.0]),              # NaN origin
+            (inside, [1e-30, -1e-30, 1e-30]),                # a direction whose length underflows
+            ([1e30, -1e30, 1e30], [-1.0, 1.0, -1.0]),        # an origin at 1e30
+            (far, far - c)]                                  # pointing away from far outside
+    return np.array([o for o, _ in rays], np.float32), np.array([d for _, d in rays], np.float32)
+
+
+@pytest.mark.parametrize("basis_dim", [9, 1])
+def test_hostile_rays_in_a_training_batch_write_the_background_and_no_gradient(N, basis_dim):
+    rng = np.random.default_rng(500 + basis_dim)
+    g = random_grid(rng, (20, 18, 22), basis_dim, keep=0.4)
+    o64, d64 = through_rays(rng, g, 64)
+    gt64 = rng.uniform(0, 1, (64, 3)).astype(np.float32)
+    ho, hd = hostile_rays(g)
+    where = np.array([0, 1, 2, 35, 36, 37, 70, 71])      # the start, the middle and the end of the batch of 72
+    good = np.setdiff1d(np.arange(72), where)
+    o, d, gt = np.zeros((72, 3), np.float32), np.zeros((72, 3), np.float32), rng.uniform(0, 1, (72, 3)).astype(np.float32)
+    o[good], d[good], gt[good] = o64, d64, gt64
+    o[where], d[where] = ho, hd
+    gt_nan = gt.copy()
+    gt_nan[where] = np.nan
+    grid = make_grid(N, g)
+    set_opt(grid, 0.4, 0.5, 0.0)
+    trainer = N.GridTrainer(grid)
+    for accelerated in (False, True):
+        if accelerated:
+            grid.accelerate()
+        base = run_fused(N, grid, trainer, o64, d64, gt64)
+        assert base[4].any()
+        for label, target in (("finite targets", gt), ("NaN targets on the hostile rays", gt_nan)):
+            got = run_fused(N, grid, trainer, o, d, target)
+            assert np.array_equal(got[0][where], np.full((8, 3), 0.4, np.float32)) and not got[1][where].any(), label
+            assert np.array_equal(got[0][good], base[0]) and np.array_equal(got[1][good], base[1])
+            assert np.array_equal(got[4], base[4]), label      # the mask, bit for bit
+            for i, key in ((2, "density"), (3, "sh")):
+                want = base[i].astype(np.float64) * (64.0 / 72.0)
+                err, big = float(np.abs(got[i] - want).max()), float(np.abs(want).max())
+                print(f"B = {basis_dim} {'accelerated' if accelerated else 'plain'}, {label}, d/d{key}: {err / big:.2e} of the largest entry")
+                assert np.isfinite(got[i]).all() and big > 0 and err <= 1e-5 * big, (label, key)
+    # the restatement says the same
+    rgb_o, gd_o, gs_o, mask_o = GT.fused(g, o, d, gt_nan, background_brightness=0.4, skip=GO.skip_distances(g["links"]))
+    assert np.array_equal(rgb_o[where], got[0][where]) and np.isfinite(gd_o).all() and np.isfinite(gs_o).all()
+    assert_matches_restatement(f"B = {basis_dim} hostile", got, (rgb_o, gd_o, gs_o, mask_o))
+
+
+# ---- 17. total variation against the fp64 statement -----------------------------------------------------------------
+@pytest.mark.parametrize("reso", TV_LATTICES)
+def test_tv_gradient_against_the_fp64_autograd_statement(N, reso):
+    """Every node covered by a range that wraps (sparse_frac 1, start n - 1), kept nodes on every face, a plateau of equal
+    neighbours, both tables and a column sub-range: the kernel against fp64 autograd (tests/test_grid_train_cpu.py,
+    tv_grad_fp64) and against the restatement, 1e-5 of the largest entry each; the mask is the restatement's."""
+    g, plateau = tv_lattice(reso)
+    grid = make_grid(N, g)
+    trainer = N.GridTrainer(grid)
+    n = g["links"].size
+    for target, d0, d1 in TV_TARGETS:
+        _, _, scale, want64, want32, mask = tv_case(reso, target, d0, d1)
+        trainer.zero_grad()
+        s, count = trainer.add_tv_grad(target, scaling=TV_SCALING, sparse_frac=1.0, start=n - 1, start_dim=d0, end_dim=d1)
+        assert (s, count) == (n - 1, n)
+        got = cpu(trainer.grad_density if target == "density" else trainer.grad_sh)
+        big = float(np.abs(want64).max())
+        e64, e32 = float(np.abs(got - want64).max()), float(np.abs(got.astype(np.float64) - want32).max())
+        print(f"tv {reso} {target}[{d0}:{d1}]: GPU vs fp64 autograd {e64 / big:.2e}, vs restatement {e32 / big:.2e} of the largest entry")
+        assert big > 0 and e64 <= 1e-5 * big and e32 <= 1e-5 * big
+        assert np.array_equal(cpu(trainer.mask), mask) and not mask[plateau].any() and not got[plateau].any()
+        assert not cpu(trainer.grad_sh if target == "density" else trainer.grad_density).any()
+
+
+# ---- 18. the optimiser at its edges, bit for bit -----------------------------------------------------------------------
+def same_bits(a, b):
+    """equal bit for bit (so -0.0 is not 0.0), except that a NaN equals any NaN (the payload of a NaN is not specified)"""
+    nan = np.isnan(a)
+    return np.array_equal(nan, np.isnan(b)) and np.array_equal(a.view(np.uint32)[~nan], b.view(np.uint32)[~nan])
+
+
+@pytest.mark.parametrize("optim,beta,eps", [("rmsprop", 0.0, 1e-8), ("rmsprop", 1.0, 1e-8), ("rmsprop", 0.95, 0.0),
+                                            ("rmsprop", 0.0, 0.0), ("sgd", 0.95, 1e-8)])
+def test_step_edges_are_bit_identical_to_the_restatement(N, optim, beta, eps):
+    """Gradients from 1e-24 (g * g subnormal or 0) to 1, -0.0, NaN and +-inf; rms 0, subnormal, tiny, ordinary, NaN and inf;
+    beta 0 and 1; eps 0; mask bytes other than 1; rows * cols no multiple of the 256 threads of a workgroup. IEEE fp32, one
+    rounding per operation, subnormals kept; max is fmaxf, so an element whose new value is NaN lands on minval
+    (include/nerf_mi355x.h)."""
+    rng = np.random.default_rng(17)
+    g = random_grid_with_faces(rng, (11, 9, 13), 4)
+    grid = make_grid(N, g)
+    trainer = N.GridTrainer(grid)
+    cap = grid.capacity
+    assert cap % 256 and (cap * 12) % 256
+    mask = rng.choice(np.array([0, 0, 1, 1, 2, 128, 255], np.uint8), cap)
+    state = {}
+    for key, cols in (("density", 1), ("sh", 12)):
+        shape = (cap, cols)
+        grad = (rng.normal(size=shape) * 10.0 ** rng.uniform(-24, 0, shape)).astype(np.float32)
+        kind = rng.integers(0, 20, shape)
+        for k, v in ((0, 0.0), (1, -0.0), (2, np.nan), (3, np.inf), (4, -np.inf), (5, 1e-24), (6, -3e-23)):
+            grad[kind == k] = np.float32(v)
+        rms = (rng.uniform(0, 1, shape) ** 4).astype(np.float32)
+        kind = rng.integers(0, 20, shape)
+        rms[kind < 6] = 0.0      # never touched yet
+        rms[kind == 6] = (rng.uniform(0, 1, int((kind == 6).sum())) * 1e-39).astype(np.float32)      # subnormal
+        rms[kind == 7] = np.float32(1e-30)
+        rms[kind == 8] = np.nan
+        rms[kind == 9] = np.inf
+        assert ((rms > 0) & (rms < np.finfo(np.float32).tiny)).any() and np.signbit(grad[grad == 0]).any()
+        g2 = grad[np.isfinite(grad)] ** 2
+        assert ((g2 > 0) & (g2 < np.finfo(np.float32).tiny)).any() and ((g2 == 0) & (grad[np.isfinite(grad)] != 0)).any()
+        state[key] = (grad, rms)
+    trainer.grad_density.copy_(gpu(state["density"][0]))
+    trainer.grad_sh.copy_(gpu(state["sh"][0]))
+    trainer.density_rms.copy_(gpu(state["density"][1]))
+    trainer.sh_rms.copy_(gpu(state["sh"][1]))
+    trainer.mask.copy_(gpu(mask))
+    lr_sigma, lr_sh, minval = 30.0, 1e-2, -0.5
+    want = {}
+    for key, lr in (("density", lr_sigma), ("sh", lr_sh)):
+        data, rms = g[f"{key}_data"].copy(), state[key][1].copy()
+        GT.optim_step(data, rms, state[key][0], mask, optim, lr, beta, eps, minval)
+        want[key] = (data, rms)
+    trainer.step(lr_sigma, lr_sh, beta=beta, epsilon=eps, optim=optim, minval=minval)
+    on = mask != 0
+    for key, data, rms in (("density", grid.density_data, trainer.density_rms), ("sh", grid.sh_data, trainer.sh_rms)):
+        got_d, got_r = cpu(data), cpu(rms)
+        bad = ~((got_d.view(np.uint32) == want[key][0].view(np.uint32)) | (np.isnan(got_d) & np.isnan(want[key][0])))
+        assert same_bits(got_d, want[key][0]), (key, int(bad.sum()), state[key][0][bad][:4], state[key][1][bad][:4], got_d[bad][:4],
+                                                want[key][0][bad][:4])
+        assert same_bits(got_r, want[key][1]), key
+        assert not np.isnan(got_d).any()      # fmaxf drops the NaN ...
+        nan_in = np.isnan(state[key][0]) & on[:, None]
+        assert nan_in.any() and (got_d[nan_in] == np.float32(minval)).all()      # ... a NaN gradient lands on minval
+        assert same_bits(got_d[~on], g[f"{key}_data"][~on]) and same_bits(got_r[~on], state[key][1][~on])
+        assert (got_d[on] != g[f"{key}_data"][on]).any()
+        if optim == "sgd":
+            assert same_bits(got_r, state[key][1])
+        else:
+            assert np.isnan(got_r[nan_in]).all()      # a NaN that reaches rms stays there
+    assert same_bits(cpu(trainer.grad_sh), state["sh"][0]) and np.array_equal(cpu(trainer.mask), mask)      # left as they are
