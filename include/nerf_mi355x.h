@@ -117,6 +117,24 @@ int nerf_get_precision(nerf_ctx* ctx);
  * range in fp32 after a precision warning uses (the Python mirror's batchify_rays): a validation render inside a training
  * loop must not put the loop back on the fp16-pair kernels. nerf_get_precision returns the rendering arithmetic. */
 int nerf_set_render_precision(nerf_ctx* ctx, int precision);
+/* View fold (NERF_PRECISION_F16X2, inference launches of view-dependent networks). feature_linear (nerf/nerf.py:89) has no
+ * activation and views_linears.0 is its only consumer, so the forward kernel evaluates the view layer straight on the trunk
+ * output: pre = W_vf h + W_v[:, W:] gamma(d) + b_vf with W_vf = W_v[:, :W] W_f, b_vf = W_v[:, :W] b_f + b_v, formed on the
+ * device in fp64 and rounded once whenever the fp16-pair data are rebuilt (at load, after optimiser steps) - 66 weight
+ * chunks per 32 points instead of 74; sigma (alpha_linear on the trunk output) is computed as before, bit for bit. A
+ * network is folded only when every parameter involved and the fold are finite, feature_linear cannot overflow for trunk
+ * outputs up to 2^64, and the two column blocks of the folded layer are within 2^8 of each other in size; otherwise it runs
+ * the three layers one after the other, as do the fp32 kernel and the training passes always (they keep the feature vector
+ * for the backward pass). nerf_render_rays with random draws (perturb, noise0 / noise) does not fold either: it is the
+ * render nerf_train_forward and nerf_train_step reproduce bit for bit. A taped render without random draws differs from
+ * the untaped one in the colours by the fold's rounding (within 2e-5 in rgb_map). The one deviation: where the
+ * reference's feature vector would overflow fp32 on a trunk output beyond that range, the folded kernel counts a
+ * loose-bound event (precision guard below; one per such point) instead of returning NaN colours itself.
+ * nerf_set_view_fold: on (default) / off for the following launches of this context; results are valid either way.
+ * nerf_view_fold_status: *folded = 1 if deterministic fp16-pair inference launches of `slot` use the fold (0: not eligible, no
+ * view branch, or switched off). Synchronises the device. */
+int nerf_set_view_fold(nerf_ctx* ctx, int on);
+int nerf_view_fold_status(nerf_ctx* ctx, int slot, int* folded);
 /* NERF_PRECISION_F16X2 chooses a layer's per-point output scale from an a-priori bound (largest row sum of |W| x
  * largest |input| + largest |bias|). A bound 2^12 or more above a point's real outputs starts to cost low-order
  * bits; each such (wavefront, layer) occurrence is counted, never silent. Synchronises the device; `reset` zeroes the

@@ -21,6 +21,7 @@ EXPORTS = (
     "nerf_get_precision", "nerf_precision_status", "nerf_get_adam_state", "nerf_set_adam_state",
     "nerf_shard_bounds", "nerf_render_shard", "nerf_precision_peek", "nerf_precision_check",
     "nerf_precision_detail", "nerf_profile_read_train", "nerf_set_render_precision",
+    "nerf_set_view_fold", "nerf_view_fold_status",
     "nerf_pack_rays", "nerf_density_grid", "nerf_marching_cubes", "nerf_train_forward", "nerf_train_backward",
     "nerf_zero_grad", "nerf_adam_step", "nerf_occupancy_create", "nerf_occupancy_destroy", "nerf_occupancy_cells",
     "nerf_occupancy_stats", "nerf_render_rays_occ", "nerf_render_frame_occ",
@@ -307,6 +308,10 @@ def load():
     lib.nerf_pack_rays.argtypes = [vp, C.POINTER(Camera), vp, i32, vp, i32, i64, vp, vp]
     lib.nerf_set_render_precision.restype = i32
     lib.nerf_set_render_precision.argtypes = [vp, i32]
+    lib.nerf_set_view_fold.restype = i32
+    lib.nerf_set_view_fold.argtypes = [vp, i32]
+    lib.nerf_view_fold_status.restype = i32
+    lib.nerf_view_fold_status.argtypes = [vp, i32, C.POINTER(i32)]
     lib.nerf_get_precision.restype = i32
     lib.nerf_get_precision.argtypes = [vp]
     lib.nerf_get_adam_state.restype = i32

@@ -20,7 +20,7 @@ SOURCES = ["api.cpp", "train_api.cpp", "pack_weights.cpp", "mlp_kernel.hip", "ml
            "grid_resample_api.cpp", "grid_resample_kernels.hip",
            "grid_components_api.cpp", "grid_components_kernels.hip"]
 HEADERS = [os.path.join(CSRC, "nerf_internal.h"), os.path.join(CSRC, "ctx_internal.h"),
-           os.path.join(CSRC, "mlp_inputs.h"), os.path.join(CSRC, "mlp_pair_common.h"), os.path.join(CSRC, "ray_device.h"), os.path.join(CSRC, "grid_internal.h"), os.path.join(CSRC, "grid_device.h"), os.path.join(CSRC, "compact_device.h"),
+           os.path.join(CSRC, "mlp_inputs.h"), os.path.join(CSRC, "mlp_pair_common.h"), os.path.join(CSRC, "mlp_kernel_h2_body.inc"), os.path.join(CSRC, "ray_device.h"), os.path.join(CSRC, "grid_internal.h"), os.path.join(CSRC, "grid_device.h"), os.path.join(CSRC, "compact_device.h"),
            os.path.join(ROOT, "include", "nerf_mi355x.h")]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17",

@@ -37,6 +37,10 @@ int run_mlp(nerf_ctx* c, MlpLaunch& a, const PackedNet& net_in, int mode, hipStr
         const int rc = refresh_h2(net, s);          // the weights have been trained since the last fp16-pair launch
         if (rc != NERF_OK) return rc;
     }
+    if (c->precision == NERF_PRECISION_F16X2 && net.fold_dirty) {
+        const int rc = refresh_fold(net, s);        // ... and the view fold follows them
+        if (rc != NERF_OK) return rc;
+    }
     if (c->precision != NERF_PRECISION_F16X2 && net.f32_dirty) {
         const int rc = refresh_f32(net, s);
         if (rc != NERF_OK) return rc;
@@ -55,6 +59,13 @@ int run_mlp(nerf_ctx* c, MlpLaunch& a, const PackedNet& net_in, int mode, hipStr
     a.out_ch = net.out_ch;
     a.in_ch = net.arch.input_ch;
     a.in_ch_views = net.arch.input_ch_views;
+    // the view fold: every inference launch of a network takes the same decision, from the word refresh_fold wrote
+    // (a.no_fold: a render with random draws, which has to equal the training forward pass - see MlpLaunch)
+    const bool may_fold = c->view_fold && c->precision == NERF_PRECISION_F16X2 && net.d_fold_word && !a.store && !a.no_fold;
+    a.fold_word = may_fold ? net.d_fold_word : nullptr;
+    a.stream_fold = net.d_stream_fold;
+    a.bias_fold = net.d_bias_fold;
+    a.descale_fold = net.d_descale_fold;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->profiling) {
         for (hipEvent_t* e : {&e0, &e1}) {
@@ -184,8 +195,26 @@ int refresh_h2_many(PackedNet* const* nets, int n, hipStream_t s) {
                                          net.d_descale, s));
         HIP_TRY(launch_layer_gains(net.d_params_eq, gain_refs(net.arch, net.linears), net.d_gain, s));
         net.h2_dirty = false;
+        net.fold_dirty = true;
         if (net.train.bwd_is_eq) net.train.bwd_dirty = true;      // d_params_eq moved
     }
+    return NERF_OK;
+}
+
+int refresh_fold(PackedNet& net, hipStream_t s) {
+    net.fold_dirty = false;
+    if (!net.d_fold_word) return NERF_OK;      // (no view branch: nothing to fold)
+    const int D = net.arch.D, W = net.arch.W;
+    const LinearDesc &views = net.linears[D], &feature = net.linears[D + 1];
+    const ViewFoldRefs r{(unsigned)views.w_off, (unsigned)views.b_off, (unsigned)feature.w_off, (unsigned)feature.b_off,
+                         (unsigned)net.n_params, W, views.out, views.in - W};
+    HIP_TRY(launch_view_fold(net.d_params_eq, net.d_params_eq + net.n_params, r, net.d_fold_word, s));
+    HIP_TRY(launch_gather(net.d_params_eq, net.d_fold_stream_table, (int64_t)net.n_fold_stream_table, net.d_stream_eq_fold, s));
+    HIP_TRY(launch_gather(net.d_params_eq, net.d_fold_bias_table, (int64_t)net.bias_table.size(), net.d_bias_fold, s));
+    HIP_TRY(launch_convert_stream_h2(net.d_stream_eq_fold, net.d_chunk_layer_fold, net.n_chunks_fold, net.d_chunk_max_fold,
+                                     net.d_stream_fold, net.d_descale_fold, s));
+    // (the folded stream ends with four view chunks, the alpha_linear tile and the gamma(dir) chunk)
+    HIP_TRY(launch_view_fold_eligible(net.d_gain, D, net.d_chunk_max_fold, net.n_chunks_fold - 6, net.d_fold_word, s));
     return NERF_OK;
 }
 
@@ -216,7 +245,9 @@ void free_net(PackedNet& n) {
                     (void*)n.train.d_bias_table, (void*)n.train.d_bwd_table, (void*)n.train.d_stream_bwd, (void*)n.d_stream_h2, (void*)n.d_descale, (void*)n.d_chunk_layer,
                     (void*)n.d_chunk_max, (void*)n.d_gain, (void*)n.d_params_eq, (void*)n.d_stream_eq, (void*)n.d_bias_h2,
                     (void*)n.d_row_exp, (void*)n.d_eq_flags, (void*)n.train.d_stream_bwd_h2, (void*)n.train.d_descale_bwd, (void*)n.train.d_gain_bwd,
-                    (void*)n.train.d_chunk_layer_bwd, (void*)n.train.d_chunk_max_bwd})
+                    (void*)n.train.d_chunk_layer_bwd, (void*)n.train.d_chunk_max_bwd, (void*)n.d_fold_stream_table,
+                    (void*)n.d_fold_bias_table, (void*)n.d_stream_eq_fold, (void*)n.d_stream_fold, (void*)n.d_bias_fold,
+                    (void*)n.d_descale_fold, (void*)n.d_chunk_layer_fold, (void*)n.d_chunk_max_fold, (void*)n.d_fold_word})
         if (p) (void)hipFree(p);
     n = PackedNet{};
 }
@@ -370,6 +401,42 @@ int nerf_set_render_precision(nerf_ctx* c, int precision) {
 
 int nerf_get_precision(nerf_ctx* c) { return c ? c->precision : NERF_E_INVALID; }
 
+int nerf_set_view_fold(nerf_ctx* c, int on) {
+    if (!c) {
+        set_error("nerf_set_view_fold: ctx is NULL");
+        return NERF_E_INVALID;
+    }
+    c->view_fold = on != 0;
+    return NERF_OK;
+}
+
+int nerf_view_fold_status(nerf_ctx* c, int slot, int* folded) {
+    if (!c || !folded) {
+        set_error("nerf_view_fold_status: NULL argument");
+        return NERF_E_INVALID;
+    }
+    *folded = 0;
+    const PackedNet* net_in = get_net(c, slot);
+    if (!net_in) return NERF_E_STATE;
+    PackedNet& net = const_cast<PackedNet&>(*net_in);
+    DeviceGuard g(c->device);
+    if (!net.d_fold_word) return NERF_OK;      // no view branch
+    // what the next fp16-pair launch would read (the default stream follows the others')
+    if (net.h2_dirty) {
+        const int rc = refresh_h2(net, nullptr);
+        if (rc != NERF_OK) return rc;
+    }
+    if (net.fold_dirty) {
+        const int rc = refresh_fold(net, nullptr);
+        if (rc != NERF_OK) return rc;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned word = 0;
+    HIP_TRY(hipMemcpy(&word, net.d_fold_word, sizeof(word), hipMemcpyDeviceToHost));
+    *folded = (word != 0 && c->view_fold) ? 1 : 0;
+    return NERF_OK;
+}
+
 int nerf_load_weights(nerf_ctx* c, int slot, const nerf_arch* arch, const float* const* tensors, int n_tensors) {
     if (!c || !arch || !tensors) {
         set_error("nerf_load_weights: NULL argument");
@@ -393,14 +460,17 @@ int nerf_load_weights(nerf_ctx* c, int slot, const nerf_arch* arch, const float*
     // flat master copy + the index tables that map the packed layouts back to it (for training)
     net.linears = describe_linears(*arch, mask);
     std::vector<float> flat, fake;
+    std::vector<int> fold_stream_table, fold_bias_table;      // the folded stream's (view-dependent networks)
+    const size_t fold_rows = arch->use_viewdirs ? (size_t)(arch->W / 2) : 0, fold_tail = fold_rows * arch->W + fold_rows;
+    int fnc = 0;
     {
         std::vector<const float*> fake_ptrs;
         size_t total = 0;
         for (const LinearDesc& d : net.linears) total += (size_t)d.out * d.in + d.out;
         flat.resize(total);
-        fake.resize(total);
-        for (size_t i = 0; i < total; ++i) fake[i] = (float)(i + 1);   // exact: total < 2^24
-        if (total >= (1u << 24)) {
+        fake.resize(total + fold_tail);      // (the fold lives in a tail behind the parameters: PackedNet::d_stream_fold)
+        for (size_t i = 0; i < total + fold_tail; ++i) fake[i] = (float)(i + 1);   // exact: below 2^24
+        if (total + fold_tail >= (1u << 24)) {
             free(hs);
             free(hb);
             set_error("model too large for the index tables (%zu parameters)", total);
@@ -429,6 +499,29 @@ int nerf_load_weights(nerf_ctx* c, int slot, const nerf_arch* arch, const float*
         free(ts);
         free(tb);
         net.n_params = total;
+        if (fold_tail) {
+            float *fs = nullptr, *fb = nullptr;
+            int fnb = 0;
+            rc = pack_weights_folded(*arch, fake_ptrs.data(), n_tensors, fake.data() + total,
+                                     fake.data() + total + fold_rows * arch->W, &fs, &fnc, &fb, &fnb);
+            if (rc == NERF_OK && fnb != tnb) {
+                set_error("internal: the folded bias block has %d tiles, the plain one %d", fnb, tnb);
+                rc = NERF_E_INVALID;
+            }
+            if (rc != NERF_OK) {
+                free(fs);
+                free(fb);
+                free(hs);
+                free(hb);
+                return rc;
+            }
+            fold_stream_table.resize((size_t)fnc * kChunkFloats);
+            fold_bias_table.resize((size_t)fnb * kBiasTileFloats);
+            for (size_t i = 0; i < fold_stream_table.size(); ++i) fold_stream_table[i] = (int)fs[i] - 1;
+            for (size_t i = 0; i < fold_bias_table.size(); ++i) fold_bias_table[i] = (int)fb[i] - 1;
+            free(fs);
+            free(fb);
+        }
         // index table of the fused backward-data kernel's stream (training; view-dependent networks only)
         net.bwd_table.clear();
         // (narrower networks, one-layer trunks without a view branch and heads of more than kBwdMaxOutRows channels train on
@@ -471,7 +564,30 @@ int nerf_load_weights(nerf_ctx* c, int slot, const nerf_arch* arch, const float*
         e = hipMemcpy(net.d_chunk_layer, layer_of.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void**)&net.d_gain, 2 * (kMaxDepth + 2) * sizeof(float));
     // the row-equalised copy the fp16-pair kernel evaluates, and the index tables that cut streams out of parameters
-    if (e == hipSuccess) e = hipMalloc((void**)&net.d_params_eq, net.n_params * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&net.d_params_eq, (net.n_params + fold_tail) * sizeof(float));
+    if (e == hipSuccess && fold_tail) {
+        const std::vector<int> fold_layer_of = chunk_layers(*arch, mask, true);
+        if ((int)fold_layer_of.size() != fnc) {
+            set_error("internal: %zu chunk scale groups for %d folded chunks", fold_layer_of.size(), fnc);
+            free_net(net);      // (hs and hb are freed above; the device buffers allocated so far go with the slot)
+            return NERF_E_INVALID;
+        }
+        auto up = [&](void** dst, const void* src, size_t bytes) {
+            if (e == hipSuccess) e = hipMalloc(dst, bytes);
+            if (e == hipSuccess) e = src ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipMemset(*dst, 0, bytes);
+        };
+        up((void**)&net.d_fold_stream_table, fold_stream_table.data(), fold_stream_table.size() * sizeof(int));
+        up((void**)&net.d_fold_bias_table, fold_bias_table.data(), fold_bias_table.size() * sizeof(int));
+        up((void**)&net.d_chunk_layer_fold, fold_layer_of.data(), (size_t)fnc * sizeof(int));
+        up((void**)&net.d_stream_eq_fold, nullptr, (size_t)fnc * kChunkBytes);
+        up((void**)&net.d_stream_fold, nullptr, (size_t)(fnc + kStreamTailChunks) * kChunkBytes);
+        up((void**)&net.d_bias_fold, nullptr, (size_t)nbt * kBiasTileFloats * sizeof(float));
+        up((void**)&net.d_descale_fold, nullptr, (kMaxDepth + 3) * sizeof(float));
+        up((void**)&net.d_chunk_max_fold, nullptr, (size_t)fnc * sizeof(float));
+        up((void**)&net.d_fold_word, nullptr, 2 * sizeof(unsigned));
+        net.n_fold_stream_table = fold_stream_table.size();
+        net.n_chunks_fold = fnc;
+    }
     if (e == hipSuccess) e = hipMalloc((void**)&net.d_stream_eq, (size_t)nc * kChunkBytes);
     if (e == hipSuccess) e = hipMalloc((void**)&net.d_bias_h2, (size_t)nbt * kBiasTileFloats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&net.d_row_exp, (size_t)kMaxLinears * 256 * sizeof(int));
@@ -485,11 +601,16 @@ int nerf_load_weights(nerf_ctx* c, int slot, const nerf_arch* arch, const float*
         net.arch = *arch;           // (refresh_h2 reads these; set again below with the rest)
         net.n_chunks = nc;
         net.n_bias_tiles = nbt;
-        if (refresh_h2(net, nullptr) != NERF_OK) return NERF_E_HIP;
+        if (refresh_h2(net, nullptr) != NERF_OK || refresh_fold(net, nullptr) != NERF_OK) {
+            (void)hipDeviceSynchronize();
+            free_net(net);
+            return NERF_E_HIP;
+        }
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         set_error("uploading packed weights failed: %s", hipGetErrorString(e));
+        free_net(net);
         return NERF_E_HIP;
     }
     net.arch = *arch;
@@ -714,7 +835,11 @@ static int render_rays_locked(nerf_ctx* c, const nerf_render_args* r, const nerf
     float* w_c = r->weights_coarse ? r->weights_coarse : ar.take(nN * Sc);
 
     HIP_TRY(launch_stratified(r->rays, r->ray_stride, N, Sc, r->lindisp, r->perturb ? r->t_rand : nullptr, z_c, s));
+    // A render with random draws (stratified jitter, density noise) is a training-time render: nerf_train_forward on the same
+    // rays and draws returns the same bits, and its kernels keep feature_linear for the backward pass. So it does not fold.
+    const bool random_draws = r->perturb || r->noise0 || r->noise;
     MlpLaunch a{};
+    a.no_fold = random_draws;
     a.n_points = N * Sc;
     a.samples_per_ray = Sc;
     a.rays = r->rays;
@@ -742,6 +867,7 @@ static int render_rays_locked(nerf_ctx* c, const nerf_render_args* r, const nerf
         }
     }
     MlpLaunch b{};
+    b.no_fold = random_draws;
     b.n_points = N * Sf;
     b.samples_per_ray = Sf;
     b.rays = r->rays;

@@ -37,6 +37,7 @@ struct nerf_ctx {
                                             // nerf_set_render_precision)
     int train_precision = NERF_PRECISION_F16X2;   // ... in nerf_train_step (nerf_set_precision only)
     nerf::PackedNet nets[NERF_NUM_SLOTS];
+    bool view_fold = true;         // nerf_set_view_fold: inference launches may use a network's view fold (PackedNet::d_fold_word)
     unsigned* d_loose = nullptr;   // see nerf_precision_status
     // The precision guard (nerf_mi355x.h, "Precision guard"): a pinned host mirror of d_loose, refreshed by a 64-byte copy
     // enqueued behind every render / training call, so that a later call can see - without synchronising - whether the

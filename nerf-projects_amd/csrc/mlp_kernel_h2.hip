@@ -25,6 +25,10 @@
 //     tile, rgb_linear an fp32 dot product on the last layer's values.
 //
 // Cost per layer and wave: 384 MFMAs of 32 cycles against 1024 of 64.
+//
+// Inference launches of an eligible view-dependent network skip feature_linear altogether (the view fold: the view layer reads
+// the trunk output through W_v[:, :W] W_f, formed on the device - nerf_mlp_h2_fold_kernel below, refresh_kernels.hip): 66
+// chunks and 3 144 MFMAs per wave tile instead of 74 and 3 528.
 #include "mlp_pair_common.h"
 
 namespace nerf {
@@ -349,316 +353,33 @@ __device__ __forceinline__ float row_dot4(const f32x16 (&x)[4], unsigned w_addr)
 // STORE: the training forward pass - also writes what autograd would keep (MlpLaunch::st: every trunk layer's post-ReLU
 // output, the feature vector, the view layer's output), each value as it leaves conv_slice0 / convert_pair / finish_views.
 // The stream it is given is the PLAIN network's (no row equalisation): the kept activations are the reference's.
+//
+// The view fold is a kernel of its own, nerf_mlp_h2_fold_kernel, with the same body (mlp_kernel_h2_body.inc). Whether a network
+// is folded is one word in device memory, written when its fp16-pair data were rebuilt; the host does not know it. An
+// inference launch with MlpLaunch::fold_word set therefore enqueues BOTH kernels: each reads the word once per workgroup
+// into a scalar register and the one it does not belong to (`idle`) runs no tile: it fills its ring and leaves, a few
+// microseconds beside the milliseconds of the other (no early return: tools/audit_lds_waits.py reads a kernel up to its first
+// s_endpgm). With the flag a run-time value inside one kernel hipcc needed 64 more registers across the view section and
+// spilled to scratch in the embedded-rows kernel - tests/test_kernel_audit.py refuses that: the weight ring owns the
+// vector-memory counter - and two copies of the tile loop in one kernel spilled everywhere.
 template <int MODE, int STORE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void nerf_mlp_h2_kernel(const MlpLaunch a) {
-    // The ring is the dynamic LDS allocation; the bias block and the small per-layer tables are static.
-    extern __shared__ __attribute__((aligned(16))) char ring_lds[];
-    __shared__ __attribute__((aligned(16))) float bias_lds[kBiasLdsBytes / 4];
-    __shared__ __attribute__((aligned(16))) float layer_tab[4 * (kMaxDepth + 3)];   // per layer [descale, gain, max|b|, -]
-    __shared__ unsigned max_record[kBwdMaxSlots];      // STORE: enter_max's records
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = lane >> 5;
-
-    PipeH pipe{(const char*)a.stream_h2, ring_lds, 0, 0, a.n_chunks, wave, lane, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
-    pipe_start(pipe);
-#ifdef NERF_STAMPS
-    pipe.st = Stamper{a.stamps, 0, -1, 0, blockIdx.x == 0 && wave == 0 && a.stamps != nullptr};
-#endif
-    for (int k = 0; k < 2; ++k) {
-        prefetch_pieces<0, 4>(piece_src(pipe, k), piece_dst(pipe, k));
-        prefetch_pieces<0, 4>(piece_src(pipe, k) + 4096, piece_dst(pipe, k) + 4096);
-    }
-    prefetch_pieces<0, 4>(piece_src(pipe, 2), piece_dst(pipe, 2));   // chunk 0's first-half steps issue the other four
-    for (int i = threadIdx.x; i < a.n_bias_tiles * kBiasTileFloats; i += 256) bias_lds[i] = a.bias[i];
-    if (STORE != 0 && threadIdx.x < kBwdMaxSlots) max_record[threadIdx.x] = threadIdx.x == kBwdMaxGammaD ? 0x3f800000u : 0u;      // (|gamma(d)| <= 1)
-    if (threadIdx.x < a.D + 3) {
-        const int l = threadIdx.x;
-        const bool has_gain = l <= (a.use_viewdirs ? a.D : a.D - 1);
-        layer_tab[4 * l] = a.descale[l];
-        layer_tab[4 * l + 1] = has_gain ? a.gain[2 * l] : 0.0f;
-        layer_tab[4 * l + 2] = has_gain ? a.gain[2 * l + 1] : 0.0f;
-        layer_tab[4 * l + 3] = 0.0f;
-    }
-    __syncthreads();   // chunks 0, 1, the bias block and the layer tables are in LDS
-    Frag4 cur;
-    {
-        const unsigned fr0 = lds_byte_addr(ring_lds) + lane * 16;
-        frag_issue<0>(cur.q[0], fr0);
-        frag_issue<1024>(cur.q[1], fr0);
-        frag_issue<2048>(cur.q[2], fr0);
-        frag_issue<3072>(cur.q[3], fr0);
-    }
-
-    const unsigned bias0 = lds_addr(bias_lds) + 64 * h;   // this half-wave's entries of bias-block tile 0
-    const int n_layers = a.use_viewdirs ? a.D + 1 : a.D;
-    // kInputRaysIndexed: the tile loop runs over the compacted list, whose length lives on the device (one scalar load); a
-    // workgroup without a tile falls through
-    int64_t n_live = a.n_points;
-    if constexpr (MODE == kInputRaysIndexed) n_live = __builtin_amdgcn_readfirstlane(*a.index_count);
-    const int64_t n_tiles = (n_live + kPointsPerGroup - 1) / kPointsPerGroup;
-#ifdef NERF_EXP_STAGGER      // timing experiment (profiles/r04_ab_notes.txt): workgroups out of phase with each other, so that the chip's
-    // thousand waves do not issue their stores (and their weight-stream loads) in the same instants
-    for (int k = 0; k < (int)((blockIdx.x >> 3) & 7); ++k) __builtin_amdgcn_s_sleep(NERF_EXP_STAGGER);
-#endif
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-#ifdef NERF_STAMPS
-        pipe.c = 0;
-#endif
-        pipe_tile_start(pipe);
-        const int64_t tile0 = tile * kPointsPerGroup + wave * kPointsPerWave;
-        const int64_t pt_raw = tile0 + (lane & 31);
-        int64_t pt = pt_raw < n_live ? pt_raw : n_live - 1;
-        if constexpr (MODE == kInputRaysIndexed) pt = a.index[pt];      // the listed point replaces the slot: inputs, output row
-
-        XT xp0, xp1;
-        float m_pe;
-        int t_pe;
-        {
-            f32x16 x0, x1, dd;
-            load_inputs<MODE, true, false>(a, pt, h, x0, x1, dd);   // gamma(dir) waits for the view layer
-            // The ranges of the encoded inputs are taken over the whole wavefront: wave-uniform, so they live in SGPRs
-            // (the kernel has no vector register to spare: kept per lane, one of them was spilled to scratch, and its
-            // reload - a VMEM load - drained the LDS-DMA weight pipeline with s_waitcnt vmcnt(0) twice per layer).
-            // A wave's points share a ray or two, so the common scale costs the split nothing.
-            m_pe = wave_max(tile_absmax(x1, tile_absmax(x0, 0.0f)));
-            t_pe = pick_exponent(m_pe);
-            if constexpr (STORE != 0) enter_max(&max_record[kBwdMaxGammaX], m_pe);      // the gamma(x) columns' weight gradients scale by it
-            split_tile(xp0, x0, pow2f(t_pe));
-            split_tile(xp1, x1, pow2f(t_pe));
-        }
-
-        XT hid[8];
-        f32x16 accA[8], accB[8];
-        Pending pd;
-        float sigma = 0.0f;
-        float m_prev = 0.0f;    // largest |activation| of the layer before the pending one... of its inputs
-
-        // what the raw sums of layer l become: called when its chunks are done. m_in = largest |input| of layer l
-        // (true units), t_in = exponent its inputs were scaled by
-        Tile16 bias0_req;      // bias entries of the pending layer's tile 0, requested by make_pending
-        auto make_pending = [&](int l, float m_in, int t_in) {
-            const bool is_feature = a.use_viewdirs && l == a.D;
-            const unsigned baddr = bias0 + 128 * (is_feature ? 8 * a.D + 1 : 8 * l);
-            // the scale-table row and the bias entries of tile 0 in one go: five reads and ONE wait for all of them (one
-            // exposed LDS latency per layer instead of two). One statement: with reads still in flight across the
-            // arithmetic below, hipcc moved their destination registers whenever that arithmetic changed.
-            f32x4 tab;
-            asm volatile("ds_read_b128 %0, %5\n\tds_read_b128 %1, %6\n\tds_read_b128 %2, %6 offset:16\n\t"
-                         "ds_read_b128 %3, %6 offset:32\n\tds_read_b128 %4, %6 offset:48\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&v"(tab), "=&v"(bias0_req.q[0]), "=&v"(bias0_req.q[1]), "=&v"(bias0_req.q[2]), "=&v"(bias0_req.q[3])
-                         : "v"(lds_byte_addr(layer_tab + 4 * l)), "v"(baddr)
-                         : "memory");
-            pd.c = tab[0] * pow2f(-t_in);
-            pd.floor = is_feature ? -__builtin_inff() : 0.0f;
-            float bound = fmaf(tab[1], m_in, tab[2]) * 1.001f;
-            // the next layer may concatenate these outputs with inputs that must fit the same scale
-            if (is_feature) {
-                // range of gamma(dir), which the view layer concatenates: re-read from the ray record here (once per
-                // tile) rather than kept in a register through the trunk
-                f32x16 x0, x1, dd;
-                float m_dd;
-                load_inputs<MODE, false, false>(a, pt, h, x0, x1, dd, &m_dd);
-                bound = fmaxf(bound, wave_max(m_dd));
-            }
-            else if ((a.skip_in_mask >> (l + 1)) & 1) bound = fmaxf(bound, m_pe);
-            pd.t_out = pick_exponent(bound);
-            pd.sc = pow2f(pd.t_out);
-            pd.bias_addr = baddr;
-            // The running maximum starts at 0 - or at +inf when the layer before had overflowed ON THIS POINT (m_prev = inf; not
-            // m_in, which takes in the wave-wide range of the encodings): an activation beyond the fp32 range poisons
-            // everything downstream in the reference (F.relu keeps +inf and NaN, nerf.py:72; the next Linear mixes
-            // inf - inf), v_max_f32 would quietly drop the NaNs, and carrying the fact in the maximum costs no register:
-            // the heads below turn m = inf into the reference's NaN.
-            pd.m = fmaxf(m_prev - 3.4028234663852886e38f, 0.0f);
-            if constexpr (STORE) {
-                pd.maskw = 0u;
-                pd.mask_base = wave_uniform(is_feature ? a.st.mask_hv : a.st.mask[l]);      // (feature_linear: not written)
-                pd.mask_off = 16u * (2u * (unsigned)pt + (unsigned)h);
-                pd.keep_base = (is_feature ? a.st.feat : a.st.h[l]) + (STORE == 2 ? 1024 : 0);      // (blocked: keep_pairs)
-                pd.keep_off = 4u * ((unsigned)pt * (unsigned)(is_feature ? a.st.feat_ld : a.st.h_ld[l]) + 4u * (unsigned)h);
-                if constexpr (STORE == 2)      // blocked by 32 points: 32 KiB per group of a 256-wide buffer, 32 bytes per point of a piece
-                    pd.keep_off = ((unsigned)pt >> 5) * 32768u + ((unsigned)pt & 31u) * 32u + (unsigned)h * 16u;
-            }
-        };
-        // all 8 tiles of the pending layer are converted: its true output range
-        auto close_pending = [&](int slot) {
-            m_prev = half_max(pd.m);
-            if constexpr (STORE) {
-                // this layer's ReLU-mask record (for feature_linear, which has no ReLU, the buffer is nullptr-free scratch:
-                // see make_pending)
-                if (slot != kBwdMaxFeatValue)
-                    asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" : : "v"(pd.mask_off), "v"(pd.maskq), "s"(pd.mask_base) : "memory");
-                // the largest kept activation of this layer, for the weight-gradient kernel's scale (MlpStore::maxes)
-                enter_max(&max_record[slot], m_prev);
-            }
-            // the scale was chosen for a bound of 2^(10 - t_out); outputs 2^12 and more below it have begun to lose
-            // low-half bits (see Pending). Counted, never silent: nerf_precision_status.
-            const int slack = 10 - pd.t_out - __builtin_amdgcn_frexp_expf(m_prev);
-            if (m_prev > 0.0f && m_prev < __builtin_inff() && slack >= 12 && pd.t_out > -60 && a.loose) atomicAdd(a.loose, 1u);
-        };
-
-        // layer 0: gamma(xyz) -> W (nerf.py:70-73)
-        chunk_ktile8<-1, true>(pipe, cur, accA, xp0, hid, accB, pd);
-        chunk_ktile8<-1, false>(pipe, cur, accA, xp1, hid, accB, pd);
-        make_pending(0, m_pe, t_pe);
-
-        // trunk layers 1..D-1, then (with viewdirs) feature_linear as layer D without ReLU. Layer l accumulates
-        // into `out` while the pending layer l-1 is converted out of `pend`.
-        auto layer_pass = [&](f32x16 (&pend)[8], f32x16 (&out)[8], int l) {
-            convert_tile0_with<STORE>(hid[0], pend[0], pd, bias0_req);
-            chunk_ktile8<1, true, STORE>(pipe, cur, out, hid[0], hid, pend, pd);
-            next_tile_pair<STORE>(pd);
-            chunk_ktile8<2, false, STORE>(pipe, cur, out, hid[1], hid, pend, pd);
-            chunk_ktile8<3, false, STORE>(pipe, cur, out, hid[2], hid, pend, pd);
-            next_tile_pair<STORE>(pd);
-            chunk_ktile8<4, false, STORE>(pipe, cur, out, hid[3], hid, pend, pd);
-            chunk_ktile8<5, false, STORE>(pipe, cur, out, hid[4], hid, pend, pd);
-            next_tile_pair<STORE>(pd);
-            chunk_ktile8<6, false, STORE>(pipe, cur, out, hid[5], hid, pend, pd);
-            chunk_ktile8<7, false, STORE>(pipe, cur, out, hid[6], hid, pend, pd);
-            chunk_ktile8<-1, false>(pipe, cur, out, hid[7], hid, pend, pd);
-            close_pending(kBwdMaxKept + l - 1);
-            const int t_in = pd.t_out;
-            float m_in = m_prev;
-            if (a.use_viewdirs && l == a.D) {
-                // alpha_linear reads the post-ReLU trunk output (nerf.py:86), i.e. this layer's input: one more
-                // chunk, a single-row tile accumulated into a pending tile that is no longer needed
-                chunk_row8(pipe, cur, pend[0], hid);
-                sigma = fmaf(pend[0][0], lds_scalar(layer_tab + 4 * (a.D + 2)) * pow2f(-t_in), lds_scalar(bias_lds + (8 * a.D) * 32));
-                if (!(m_prev < __builtin_inff())) sigma = __builtin_nanf("");      // the trunk overflowed on this point (make_pending)
-            }
-            if (!(a.use_viewdirs && l == a.D) && ((a.skip_in_mask >> l) & 1)) {
-                // h = cat[input_pts, h] (nerf.py:79-80): bring the encoded inputs to this layer's scale
-                rescale_tile(xp0, t_in - t_pe);
-                rescale_tile(xp1, t_in - t_pe);
-                t_pe = t_in;
-                chunk_ktile8<-1, false>(pipe, cur, out, xp0, hid, pend, pd);
-                chunk_ktile8<-1, false>(pipe, cur, out, xp1, hid, pend, pd);
-                m_in = fmaxf(m_in, m_pe);
-            }
-            make_pending(l, m_in, t_in);
-        };
-        int l = 1;
-        bool pend_in_a = true;
-        while (l < n_layers) {
-            layer_pass(accA, accB, l);
-            ++l;
-            pend_in_a = false;
-            if (l >= n_layers) break;
-            layer_pass(accB, accA, l);
-            ++l;
-            pend_in_a = true;
-        }
-        if (!pend_in_a) {
-#pragma unroll
-            for (int t = 0; t < 8; ++t) accA[t] = accB[t];
-        }
-
-        const bool live = pt_raw < n_live;
-        if (a.use_viewdirs) {
-            // views_linears[0] on cat[feature, gamma(dir)] (nerf.py:93-98): 4 output tiles; the pending layer is
-            // feature_linear
-            convert_tile0_with<STORE>(hid[0], accA[0], pd, bias0_req);
-            convert_tile<1, STORE>(hid[1], accA[1], pd);
-            next_tile_pair<STORE>(pd);
-            chunk_pair4<2, true, STORE>(pipe, cur, accB, hid[0], hid[1], hid, accA, pd);
-            next_tile_pair<STORE>(pd);
-            chunk_pair4<4, false, STORE>(pipe, cur, accB, hid[2], hid[3], hid, accA, pd);
-            next_tile_pair<STORE>(pd);
-            chunk_pair4<6, false, STORE>(pipe, cur, accB, hid[4], hid[5], hid, accA, pd);
-            chunk_pair4<-1, false>(pipe, cur, accB, hid[6], hid[7], hid, accA, pd);
-            close_pending(kBwdMaxFeatValue);
-            const bool rgb_poisoned = !(m_prev < __builtin_inff());      // the trunk or feature_linear overflowed (make_pending)
-            XT xd;
-            {
-                f32x16 x0, x1, dd;
-                load_inputs<MODE, false, true>(a, pt, h, x0, x1, dd);
-                split_tile(xd, dd, pd.sc);
-            }
-            chunk_ktile4(pipe, cur, accB, xd);
-            unsigned bad;     // raw inputs re-read (a value kept across the view layer costs the step a register): requested
-            {                 // here, behind the last MFMA chunk, so that the round trip runs under the colour head's arithmetic
-                f32x16 x0, x1, dd;
-                load_inputs<MODE, false, false>(a, pt, h, x0, x1, dd, nullptr, &bad);
-            }
-            f32x16 y[4];
-            finish_views(y, accB, bias0 + 128 * (8 * a.D + 9), lds_scalar(layer_tab + 4 * (a.D + 1)) * pow2f(-pd.t_out));
-            if constexpr (STORE) {
-                const unsigned off = 4u * ((unsigned)pt * (unsigned)a.st.hv_ld + 4u * (unsigned)h);
-                keep_tiles4<0>(a.st.hv, off, y);
-                // the view layer's ReLU mask in the bit order of the trunk layers' (MlpStore::mask_hv, words 0 and 1)
-                const unsigned moff = 16u * (2u * (unsigned)pt + (unsigned)h);
-                const u32x4 rec = {relu_mask_word(y[0], y[1]), relu_mask_word(y[2], y[3]), 0u, 0u};
-                asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" : : "v"(moff), "v"(rec), "s"(a.st.mask_hv) : "memory");
-            }
-            // rgb_linear (nerf.py:101): three rows over the 128-wide view layer
-            const float* rb = bias_lds + (8 * a.D + 13) * 32;
-            const float r0 = row_dot4(y, bias0 + 128 * (8 * a.D + 22)) + lds_scalar(rb);
-            const float r1 = row_dot4(y, bias0 + 128 * (8 * a.D + 26)) + lds_scalar(rb + 1);
-            const float r2 = row_dot4(y, bias0 + 128 * (8 * a.D + 30)) + lds_scalar(rb + 2);
-            if (MODE == kInputLattice) {
-                // the density lattice keeps sigma alone: relu(raw[..., 3]) (nerf.ipynb:291)
-                if (live && h == 0) a.out[pt] = relu_keep_nan((bad & kBadXyz) ? __builtin_nanf("") : sigma);
-            } else if (live && h == 0) {
-                f32x4 o = {r0, r1, r2, sigma};   // outputs = cat[rgb, alpha] (nerf.py:106)
-                if (bad || rgb_poisoned) {       // NaN / Inf inputs propagate as through F.relu (see kBadXyz)
-                    const float qnan = __builtin_nanf("");
-                    o = f32x4{qnan, qnan, qnan, (bad & kBadXyz) ? qnan : sigma};
-                }
-                *(f32x4*)(a.out + pt * 4) = o;
-            }
-        } else {
-            // output_linear (nerf.py:109): rows 0..out_ch-1 of one tile; the pending layer is trunk layer D-1 (STORE: kept, with
-            // its mask record and maximum, like every other trunk layer - the training pass of networks without view directions)
-            convert_tile0_with<STORE>(hid[0], accA[0], pd, bias0_req);
-            convert_tile<1, STORE>(hid[1], accA[1], pd);
-            next_tile_pair<STORE>(pd);
-            convert_tile<2, STORE>(hid[2], accA[2], pd);
-            convert_tile<3, STORE>(hid[3], accA[3], pd);
-            next_tile_pair<STORE>(pd);
-            convert_tile<4, STORE>(hid[4], accA[4], pd);
-            convert_tile<5, STORE>(hid[5], accA[5], pd);
-            next_tile_pair<STORE>(pd);
-            convert_tile<6, STORE>(hid[6], accA[6], pd);
-            convert_tile<7, STORE>(hid[7], accA[7], pd);
-            if constexpr (STORE != 0) close_pending(kBwdMaxKept + a.D - 1);
-            const bool poisoned = !(half_max(pd.m) < __builtin_inff());      // the trunk overflowed on this point (make_pending)
-            f32x16 o;
-            chunk_row8(pipe, cur, o, hid);
-            Tile16 b = lds_tile_issue(bias0 + 128 * (8 * a.D));
-            lds_tile_wait(b);
-            const float c = lds_scalar(layer_tab + 4 * a.D) * pow2f(-pd.t_out);
-            unsigned bad;
-            {
-                f32x16 x0, x1, dd;
-                load_inputs<MODE, false, false>(a, pt, h, x0, x1, dd, nullptr, &bad);
-            }
-            if (live) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const float v = ((bad & kBadXyz) || poisoned) ? __builtin_nanf("") : fmaf(o[r], c, b.q[r >> 2][r & 3]);
-                    if (MODE == kInputLattice) {
-                        if (row == 3) a.out[pt] = relu_keep_nan(v);      // sigma alone (nerf.ipynb:291)
-                    } else if (row < a.out_ch) {
-                        a.out[pt * a.out_ch + row] = v;
-                    }
-                }
-            }
-        }
-#ifdef NERF_STAMPS
-        STAMP(pipe, 0x7fffff00);
-        pipe.st.on = false;   // first tile only
-#endif
-    }   // tile loop
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if constexpr (STORE) {
-        __syncthreads();
-        flush_maxes(a.st.maxes, max_record, kBwdMaxSlots);
-    }
+    constexpr bool fold = false;
+    bool idle = false;      // the network is folded: this launch is nerf_mlp_h2_fold_kernel's
+    if constexpr (STORE == 0) idle = a.fold_word != nullptr && __builtin_amdgcn_readfirstlane(*a.fold_word) != 0u;
+#include "mlp_kernel_h2_body.inc"
 }
+
+template <int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void nerf_mlp_h2_fold_kernel(const MlpLaunch a) {
+    constexpr bool fold = true;
+    constexpr int STORE = 0;
+    const bool idle = __builtin_amdgcn_readfirstlane(*a.fold_word) == 0u;      // not eligible: nerf_mlp_h2_kernel's launch
+#include "mlp_kernel_h2_body.inc"
+}
+
 
 hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
     if (a.n_points <= 0) return hipSuccess;
@@ -715,6 +436,40 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         raised[dev][mode] = true;
+    }
+    if (a.fold_word) {
+        // the folded twin, first: whichever of the two the network's word does not name returns at once (see the kernels)
+        if (!a.stream_fold || !a.bias_fold || !a.descale_fold || !a.use_viewdirs) return hipErrorInvalidValue;
+        static bool raised_fold[64][5] = {};
+        const void* fn = mode == kInputEmbedded ? (const void*)nerf_mlp_h2_fold_kernel<kInputEmbedded>
+                         : mode == kInputPoints ? (const void*)nerf_mlp_h2_fold_kernel<kInputPoints>
+                         : mode == kInputLattice ? (const void*)nerf_mlp_h2_fold_kernel<kInputLattice>
+                         : mode == kInputRaysIndexed ? (const void*)nerf_mlp_h2_fold_kernel<kInputRaysIndexed>
+                                                 : (const void*)nerf_mlp_h2_fold_kernel<kInputRays>;
+        if (!raised_fold[dev][mode]) {
+            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            raised_fold[dev][mode] = true;
+        }
+        switch (mode) {
+            case kInputEmbedded:
+                hipLaunchKernelGGL(nerf_mlp_h2_fold_kernel<kInputEmbedded>, grid, block, lds, s, a);
+                break;
+            case kInputPoints:
+                hipLaunchKernelGGL(nerf_mlp_h2_fold_kernel<kInputPoints>, grid, block, lds, s, a);
+                break;
+            case kInputLattice:
+                hipLaunchKernelGGL(nerf_mlp_h2_fold_kernel<kInputLattice>, grid, block, lds, s, a);
+                break;
+            case kInputRaysIndexed:
+                hipLaunchKernelGGL(nerf_mlp_h2_fold_kernel<kInputRaysIndexed>, grid, block, lds, s, a);
+                break;
+            default:
+                hipLaunchKernelGGL(nerf_mlp_h2_fold_kernel<kInputRays>, grid, block, lds, s, a);
+                break;
+        }
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
     }
     switch (mode) {
         case kInputEmbedded:

@@ -112,6 +112,24 @@ struct PackedNet {
     // row_exponents_layers_kernel (one workgroup per linear): flag k = the launch's epoch once linear k's exponents are written
     unsigned* d_eq_flags = nullptr;
     unsigned eq_epoch = 0;
+    // View fold (view-dependent networks; mlp_kernel_h2.hip, inference launches only). feature_linear has no activation and
+    // one consumer, so the view layer can read the trunk output through W_vf = W_v[:, :W] W_f, b_vf = W_v[:, :W] b_f + b_v.
+    // refresh_fold (api.cpp) forms both from d_params_eq in fp64, rounded once, into the TAIL of d_params_eq ([W/2, W] then
+    // [W/2], behind the n_params parameters), cuts the folded stream and bias block out of parameters + tail through their own
+    // index tables, and writes d_fold_word[0] = 1 when the fold may be used (view_fold_eligible_kernel has the conditions;
+    // word 1 collects "a non-finite entry was seen"). Lazily, like the data above: fold_dirty is set wherever those are rebuilt.
+    int* d_fold_stream_table = nullptr;
+    int* d_fold_bias_table = nullptr;
+    size_t n_fold_stream_table = 0;
+    float* d_stream_eq_fold = nullptr;
+    uint32_t* d_stream_fold = nullptr;
+    float* d_bias_fold = nullptr;
+    float* d_descale_fold = nullptr;
+    int* d_chunk_layer_fold = nullptr;
+    float* d_chunk_max_fold = nullptr;
+    unsigned* d_fold_word = nullptr;
+    int n_chunks_fold = 0;
+    bool fold_dirty = false;
     int n_chunks = 0;
     int n_bias_tiles = 0;
     uint32_t skip_in_mask = 0;   // bit i: trunk layer i reads [input_pts, h]
@@ -200,6 +218,16 @@ struct MlpLaunch {
     // n * samples_per_ray + i in increasing order, and how many there are
     const int* index;
     const int* index_count;
+    // The view fold (PackedNet::d_stream_fold; STORE == 0 kernels only): *fold_word != 0 -> the launch reads these instead of
+    // stream_h2 / bias / descale and skips feature_linear. nullptr: never.
+    const unsigned* fold_word;
+    const uint32_t* stream_fold;
+    const float* bias_fold;
+    const float* descale_fold;
+    // Host only (run_mlp): this launch must not fold whatever the word says. Set by renders with random draws (stratified
+    // jitter, density noise): those are training-time renders, which nerf_train_forward / nerf_train_step reproduce bit for
+    // bit with kernels that keep feature_linear for the backward pass and so never fold.
+    bool no_fold;
 };
 
 // Fused backward-data pass (nerf_mlp_bwd_kernel): from d raw to the gradient at every pre-activation, one launch.
@@ -241,7 +269,11 @@ int pack_backward_stream(const nerf_arch& arch, const float* const* tensors, uin
                          int* n_chunks);
 
 // scale group ("layer") of every chunk of the stream, in stream order
-std::vector<int> chunk_layers(const nerf_arch& arch, uint32_t skip_in_mask);
+std::vector<int> chunk_layers(const nerf_arch& arch, uint32_t skip_in_mask, bool folded = false);
+
+// the folded stream and bias block of a view-dependent network (pack_weights.cpp; PackedNet::d_stream_fold)
+int pack_weights_folded(const nerf_arch& arch, const float* const* tensors, int n_tensors, const float* fold_w,
+                        const float* fold_b, float** stream_out, int* n_chunks, float** bias_out, int* n_bias_tiles);
 
 // kernel launchers (mlp_kernel.hip, mlp_kernel_h2.hip, ray_kernels.hip)
 hipError_t launch_mlp(const MlpLaunch& a, int mode, hipStream_t s);
@@ -286,6 +318,17 @@ struct PackedNet;
 // everything the fp16-pair kernel reads, rebuilt from the master parameters (api.cpp; at load and, lazily, after training steps)
 int refresh_h2(PackedNet& net, hipStream_t s);
 int refresh_h2_many(PackedNet* const* nets, int n, hipStream_t s);
+// the view fold of a view-dependent network, from d_params_eq as it stands (after refresh_h2 / refresh_after_step)
+int refresh_fold(PackedNet& net, hipStream_t s);
+struct ViewFoldRefs {      // offsets into the (equalised) parameters; tail_off: where W_vf [n_view, W] and b_vf [n_view] go
+    unsigned wv_off, bv_off, wf_off, bf_off, tail_off;
+    int W, n_view, n_dir;      // views_linears.0 is [n_view, W + n_dir]
+};
+// gain: the fp16-pair kernel's gain table (feature_linear's pair at [2 D]); chunk_max: the folded stream's, whose chunks
+// first_view .. first_view + 3 hold W_vf and first_view + 5 the gamma(dir) columns; word: PackedNet::d_fold_word
+hipError_t launch_view_fold(const float* params_eq, float* tail, const ViewFoldRefs& r, unsigned* word, hipStream_t s);
+hipError_t launch_view_fold_eligible(const float* gain, int D, const float* chunk_max, int first_view, unsigned* word,
+                                     hipStream_t s);
 // the fp32 kernels' stream and bias block, likewise
 int refresh_f32(PackedNet& net, hipStream_t s);
 hipError_t launch_convert_stream_h2(const float* stream, const int* chunk_layer, int n_chunks, float* chunk_max,

@@ -98,13 +98,19 @@ inline int hid_col(int kt, int t, int h) { return hidden_col(kt, t, h); }
 
 // Mirrors the chunk order pack_weights emits below: trunk layer i (hidden chunks, then its encoding chunks when it
 // reads cat[input_pts, h]), then feature_linear (id D), the alpha_linear tile (id D+2) and views_linears.0 (id D+1), or output_linear (id D).
-std::vector<int> chunk_layers(const nerf_arch& a, uint32_t mask) {
+// `folded` (pack_weights_folded): the trunk, then the four view chunks on the folded matrix (id D+1), the alpha_linear tile
+// (id D+2) and the view layer's gamma(dir) chunk (id D+1).
+std::vector<int> chunk_layers(const nerf_arch& a, uint32_t mask, bool folded) {
     std::vector<int> ids;
     for (int i = 0; i < a.D; ++i) {
         const bool pe_in = (i == 0) || (mask >> i & 1);
         ids.insert(ids.end(), (pe_in ? 2 : 0) + (i > 0 ? 8 : 0), i);
     }
-    if (a.use_viewdirs) {
+    if (a.use_viewdirs && folded) {
+        ids.insert(ids.end(), 4, a.D + 1);
+        ids.insert(ids.end(), 1, a.D + 2);
+        ids.insert(ids.end(), 1, a.D + 1);
+    } else if (a.use_viewdirs) {
         ids.insert(ids.end(), 8, a.D);
         ids.insert(ids.end(), 1, a.D + 2);   // the alpha_linear tile
         ids.insert(ids.end(), 5, a.D + 1);
@@ -162,9 +168,10 @@ int pack_backward_stream(const nerf_arch& a, const float* const* tensors, uint32
     return NERF_OK;
 }
 
-int pack_weights(const nerf_arch& a, const float* const* tensors, int n_tensors, float** stream_out,
-                 int* n_chunks, float** bias_out, int* n_bias_tiles, uint32_t* skip_in_mask,
-                 int* out_ch) {
+// fold_w / fold_b: nullptr, or the folded view layer of pack_weights_folded below
+static int pack_impl(const nerf_arch& a, const float* const* tensors, int n_tensors, float** stream_out,
+                     int* n_chunks, float** bias_out, int* n_bias_tiles, uint32_t* skip_in_mask,
+                     int* out_ch, const float* fold_w, const float* fold_b) {
     // The kernels' register tiling is kWidth = 256 wide (8 accumulator tiles per layer, 4 for the view layer). A narrower
     // network (nerf/nerf.py:9: any W) is packed into it with ZERO rows and columns for the units it does not have: their
     // pre-activations are exactly 0, relu(0) = 0 feeds exact zeros on, and x + 0 * y = x in IEEE arithmetic - the same
@@ -268,29 +275,44 @@ int pack_weights(const nerf_arch& a, const float* const* tensors, int n_tensors,
         // would be 97 % / 91 % padding (128 + 64 MFMAs per 32 points), so the kernel evaluates them as
         // per-lane dot products over the activation registers it already holds. Their weights travel in the
         // bias block, arranged per accumulator register exactly like a bias (row_tiles below).
-        bias_tiles(bias, alpha, 1);
-        // feature_linear (nerf.py:89): a trunk-shaped layer without ReLU
-        bias_tiles(bias, feature, 8);
-        for (int kt = 0; kt < 8; ++kt) chunk_ktile(st, feature, 8, hid(kt, 0, a.W));
+        // the hidden part of the view layer (the feature columns of views_linears.0, or the folded matrix on the trunk output):
+        // two k-tiles per chunk: group = (ktl*4 + ot)*4 + t4
+        auto view_hidden_chunks = [&](const Linear& L) {
+            for (int kp = 0; kp < 4; ++kp) {
+                float* c = st.new_chunk();
+                for (int ktl = 0; ktl < 2; ++ktl)
+                    for (int ot = 0; ot < 4; ++ot)
+                        for (int t4 = 0; t4 < 4; ++t4) {
+                            const int kt = 2 * kp + ktl;
+                            fill_group(c, (ktl * 4 + ot) * 4 + t4, L, ot, t4, hid(kt, 0, a.W));
+                        }
+            }
+        };
         // alpha_linear once more as a one-row MFMA tile over the 8 k-tiles (group = kt*4 + t4), for the fp16-pair
         // kernel, whose vector pipe is busy converting activations; the fp32 kernel passes over this chunk
-        {
+        auto alpha_chunk = [&]() {
             float* c = st.new_chunk();
             for (int kt = 0; kt < 8; ++kt)
                 for (int t4 = 0; t4 < 4; ++t4)
                     fill_group(c, kt * 4 + t4, alpha, 0, t4, hid(kt, 0, a.W));
-        }
-        // views_linears.0 (nerf.py:93-98): input cat[feature(W), gamma(dir)], 4 output tiles.
-        // two feature k-tiles per chunk: group = (ktl*4 + ot)*4 + t4
-        bias_tiles(bias, views, 4);
-        for (int kp = 0; kp < 4; ++kp) {
-            float* c = st.new_chunk();
-            for (int ktl = 0; ktl < 2; ++ktl)
-                for (int ot = 0; ot < 4; ++ot)
-                    for (int t4 = 0; t4 < 4; ++t4) {
-                        const int kt = 2 * kp + ktl;
-                        fill_group(c, (ktl * 4 + ot) * 4 + t4, views, ot, t4, hid(kt, 0, a.W));
-                    }
+        };
+        bias_tiles(bias, alpha, 1);
+        // feature_linear (nerf.py:89): a trunk-shaped layer without ReLU (the folded block keeps its bias tiles, unread, so that
+        // every tile keeps its number)
+        bias_tiles(bias, feature, 8);
+        if (fold_w) {
+            // pre = W_vf h_{D-1} + W_v[:, W:] gamma(d) + b_vf: the view layer straight on the trunk output, then alpha_linear,
+            // which reads the same operands
+            Linear vf{fold_w, fold_b, a.W / 2, a.W};
+            bias_tiles(bias, vf, 4);
+            view_hidden_chunks(vf);
+            alpha_chunk();
+        } else {
+            for (int kt = 0; kt < 8; ++kt) chunk_ktile(st, feature, 8, hid(kt, 0, a.W));
+            alpha_chunk();
+            // views_linears.0 (nerf.py:93-98): input cat[feature(W), gamma(dir)], 4 output tiles.
+            bias_tiles(bias, views, 4);
+            view_hidden_chunks(views);
         }
         {
             const int off = a.W;
@@ -342,6 +364,28 @@ int pack_weights(const nerf_arch& a, const float* const* tensors, int n_tensors,
     *n_bias_tiles = (int)(nb / kBiasTileFloats);
     *skip_in_mask = mask;
     return NERF_OK;
+}
+
+int pack_weights(const nerf_arch& a, const float* const* tensors, int n_tensors, float** stream_out,
+                 int* n_chunks, float** bias_out, int* n_bias_tiles, uint32_t* skip_in_mask,
+                 int* out_ch) {
+    return pack_impl(a, tensors, n_tensors, stream_out, n_chunks, bias_out, n_bias_tiles, skip_in_mask, out_ch, nullptr, nullptr);
+}
+
+// The FOLDED stream and bias block of a view-dependent network (mlp_kernel_h2.hip, inference): feature_linear has no
+// activation and one consumer, so views_linears.0 can read the trunk output through fold_w = W_v[:, :W] W_f ([W/2, W]
+// row-major) and fold_b = W_v[:, :W] b_f + b_v ([W/2]) - eight chunks fewer. Chunk order: the trunk as in pack_weights, four
+// view chunks on fold_w, the alpha_linear tile, the gamma(dir) chunk. The bias block keeps pack_weights' tile numbers, with
+// fold_b in the view layer's four tiles.
+int pack_weights_folded(const nerf_arch& a, const float* const* tensors, int n_tensors, const float* fold_w, const float* fold_b,
+                        float** stream_out, int* n_chunks, float** bias_out, int* n_bias_tiles) {
+    if (!a.use_viewdirs || !fold_w || !fold_b) {
+        set_error("pack_weights_folded: view-dependent networks only");
+        return NERF_E_INVALID;
+    }
+    uint32_t mask = 0;
+    int out_ch = 0;
+    return pack_impl(a, tensors, n_tensors, stream_out, n_chunks, bias_out, n_bias_tiles, &mask, &out_ch, fold_w, fold_b);
 }
 
 }  // namespace nerf

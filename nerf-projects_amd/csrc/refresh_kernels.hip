@@ -225,4 +225,87 @@ hipError_t launch_refresh(const RefreshBatch& b, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- the view fold (PackedNet::d_stream_fold) -------------------------------------------------------------------------
+// W_vf = W_v[:, :W] W_f and b_vf = W_v[:, :W] b_f + b_v from the row-equalised parameters, every entry accumulated in fp64 in
+// index order and rounded once to fp32. Equalisation scales unit j of feature_linear by 2^e_j and column j of the view layer
+// by 2^-e_j, so the product of the equalised matrices IS the equalised fold. 8.4 MFLOP per network: a workgroup per view
+// unit, a thread per trunk unit. A workgroup also looks at every entry it reads or writes (its row of the view layer, the
+// rows r, r + n_view, ... of feature_linear): one that is not finite sets word[1].
+__global__ __launch_bounds__(256) void view_fold_kernel(const float* params, float* tail, const ViewFoldRefs refs, unsigned* word) {
+    __shared__ float wv[kWidth];
+    __shared__ double part[kWidth];
+    const int r = blockIdx.x, c = threadIdx.x, W = refs.W, ld = refs.W + refs.n_dir;
+    const float* row = params + refs.wv_off + (size_t)r * ld;
+    const float inf = __builtin_inff();
+    bool bad = false;
+    for (int j = c; j < ld; j += 256) {
+        const float v = row[j];
+        if (j < W) wv[j] = v;
+        bad = bad || !(fabsf(v) < inf);
+    }
+    __syncthreads();
+    if (c < W) {
+        double acc = 0.0;
+        for (int j = 0; j < W; ++j) acc = fma((double)wv[j], (double)params[refs.wf_off + (size_t)j * W + c], acc);
+        const float o = (float)acc;
+        tail[(size_t)r * W + c] = o;
+        bad = bad || !(fabsf(o) < inf);
+        for (int j = r; j < W; j += refs.n_view) bad = bad || !(fabsf(params[refs.wf_off + (size_t)j * W + c]) < inf);
+        const float bf = params[refs.bf_off + c];
+        bad = bad || !(fabsf(bf) < inf);
+        part[c] = (double)wv[c] * (double)bf;
+    }
+    __syncthreads();
+    if (c == 0) {
+        const float bv = params[refs.bv_off + r];
+        double acc = 0.0;
+        for (int j = 0; j < W; ++j) acc += part[j];
+        const float o = (float)(acc + (double)bv);
+        tail[(size_t)refs.n_view * W + r] = o;
+        bad = bad || !(fabsf(o) < inf) || !(fabsf(bv) < inf);
+    }
+    if (bad) atomicOr(&word[1], 1u);
+}
+
+// Whether the fp16-pair kernel may use the fold: word[0] = 1 only if
+//  * every entry of W_f, b_f, W_v, b_v, W_vf, b_vf is finite (word[1], above);
+//  * feature_linear cannot overflow on any trunk output the kernel would accept: with its gain pair (largest row sum of |W_f|,
+//    largest |b_f|) gain * m + bmax is finite for every m <= kFoldMaxTrunk = 2^64. The reference turns an overflowing feature
+//    vector into NaN colours, which the folded kernel, never forming the vector, cannot see: a network that can overflow
+//    below 2^64 keeps the unfolded path, and for the others the kernel counts a point whose trunk output is large enough
+//    to make the bound infinite as a loose-bound event. 2^64 is beyond any activation a trained network
+//    produces (|h| of the lego networks stays below 2^6) and leaves feature_linear 2^63 of headroom for its gain;
+//  * the largest |W_vf| and the largest |W_v[:, W:]| - they share the view layer's scale in the stream - are within 2^8 of
+//    each other: the larger maps to [2^12, 2^13), so the smaller block's largest entry sits at 2^4 or above and its entries
+//    down to 2^-6 of that keep whole low halves (normal fp16 from 2^-2 up: Pending in mlp_kernel_h2.hip); below that the
+//    absolute error 2^-25 is 2^-29 of the block's largest entry, under the fp32 rounding of the terms that dominate the sum.
+//    The unfolded layer pairs W_v[:, :W] with the same columns and is not checked: it is what the kernel has always run. A
+//    block of zeros (max 0) loses nothing.
+constexpr float kFoldMaxTrunk = 18446744073709551616.0f;      // 2^64
+__global__ void view_fold_eligible_kernel(const float* gain, int D, const float* chunk_max, int first_view, unsigned* word) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const float inf = __builtin_inff();
+    bool ok = word[1] == 0u;
+    ok = ok && fmaf(gain[2 * D], kFoldMaxTrunk, gain[2 * D + 1]) < inf;
+    float m_vf = 0.0f;
+    for (int k = 0; k < 4; ++k) m_vf = fmaxf(m_vf, chunk_max[first_view + k]);
+    const float m_d = chunk_max[first_view + 5];
+    if (m_vf > 0.0f && m_d > 0.0f) ok = ok && m_vf <= m_d * 256.0f && m_d <= m_vf * 256.0f;
+    word[0] = ok ? 1u : 0u;
+}
+
+hipError_t launch_view_fold(const float* params_eq, float* tail, const ViewFoldRefs& r, unsigned* word, hipStream_t s) {
+    if (!params_eq || !tail || !word || r.W < 2 || r.W > kWidth || r.n_view < 1 || r.n_dir < 0) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(word, 0, 2 * sizeof(unsigned), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(view_fold_kernel, dim3((unsigned)r.n_view), dim3(256), 0, s, params_eq, tail, r, word);
+    return hipGetLastError();
+}
+
+hipError_t launch_view_fold_eligible(const float* gain, int D, const float* chunk_max, int first_view, unsigned* word,
+                                     hipStream_t s) {
+    hipLaunchKernelGGL(view_fold_eligible_kernel, dim3(1), dim3(64), 0, s, gain, D, chunk_max, first_view, word);
+    return hipGetLastError();
+}
+
 }  // namespace nerf

@@ -175,6 +175,7 @@ int refresh_after_step(nerf_ctx* c, PackedNet* const* nets, int n, hipStream_t s
             t.bwd_dirty = true;      // (rebuilt by refresh_bwd when a backward pass next wants it)
         }
         net.h2_dirty = false;
+        net.fold_dirty = true;      // (rebuilt by the next inference launch: run_mlp)
     }
     if (c->h_loose_dev && (c->precision == NERF_PRECISION_F16X2 || c->train_precision == NERF_PRECISION_F16X2)) {
         b.mirror_src = c->d_loose;

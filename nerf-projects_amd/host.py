@@ -64,6 +64,18 @@ class Context:
             raise ValueError(f"precision {name!r}: expected one of {sorted(self.PRECISIONS)}")
         check(self.lib.nerf_set_render_precision(self.handle, self.PRECISIONS[name]))
 
+    def set_view_fold(self, on=True):
+        """Whether fp16-pair inference launches may evaluate the view layer straight on the trunk output (the fold of
+        feature_linear into views_linears.0, nerf_set_view_fold). On by default; results are valid either way."""
+        check(self.lib.nerf_set_view_fold(self.handle, int(bool(on))))
+
+    def view_fold_status(self, slot):
+        """True if the next fp16-pair inference launch of the network in ``slot`` uses the view fold
+        (nerf_view_fold_status). Synchronises."""
+        n = C.c_int32()
+        check(self.lib.nerf_view_fold_status(self.handle, int(slot), C.byref(n)))
+        return bool(n.value)
+
     def precision_status(self, reset=True):
         """Number of (wavefront, layer) events since the last reset in which the fp16-pair kernel's a-priori output
         bound was >= 2^12 too wide (0 for NeRF-like weights; otherwise prefer ``set_precision("f32")``). Synchronises."""
