@@ -129,7 +129,10 @@ int nerf_set_render_precision(nerf_ctx* ctx, int precision);
  * render nerf_train_forward and nerf_train_step reproduce bit for bit. A taped render without random draws differs from
  * the untaped one in the colours by the fold's rounding (within 2e-5 in rgb_map). The one deviation: where the
  * reference's feature vector would overflow fp32 on a trunk output beyond that range, the folded kernel counts a
- * loose-bound event (precision guard below; one per such point) instead of returning NaN colours itself.
+ * loose-bound event (precision guard below; one per such point) instead of returning NaN colours itself. That range is
+ * [2^64, 2^76): the fp16-pair kernels scale a point's activations by 2^-60 at most and carry them as fp16 numbers, so
+ * neither kernel represents a trunk output of 2^76 or more (tests/test_view_fold.py works inside [2^68, 2^76): a folded
+ * network's gain is below 2^64, and one the tests can call eligible before equalisation has a gain of at most 2^60).
  * nerf_set_view_fold: on (default) / off for the following launches of this context; results are valid either way.
  * nerf_view_fold_status: *folded = 1 if deterministic fp16-pair inference launches of `slot` use the fold (0: not eligible, no
  * view branch, or switched off). Synchronises the device. */

@@ -239,9 +239,10 @@
                 // Its a-priori bound (feature_linear's gain pair) says whether it could have: not provably finite on a finite
                 // trunk output = one loose-bound event, and the guard's fp32 pass settles it (DESIGN 8). Eligibility
                 // (view_fold_eligible_kernel) keeps this to trunk outputs beyond 2^64. One event per point: m_prev is the
-                // point's (half_max), and the lower half-wave's lane counts it.
+                // point's (half_max), and the lower half-wave's lane counts it - a live one: the slots behind the batch's end
+                // evaluate its last point again and must not count it again.
                 const float feat_bound = fmaf(lds_scalar(layer_tab + 4 * a.D + 1), m_prev, lds_scalar(layer_tab + 4 * a.D + 2));
-                if (h == 0 && !rgb_poisoned && !(feat_bound < __builtin_inff()) && a.loose) atomicAdd(a.loose, 1u);
+                if (h == 0 && live && !rgb_poisoned && !(feat_bound < __builtin_inff()) && a.loose) atomicAdd(a.loose, 1u);
             }
             XT xd;
             {

@@ -5,14 +5,19 @@ What is asserted: sigma and everything that depends on sigma alone is bit-identi
 stay as close to an fp64 evaluation as test_mlp_precisions_vs_fp64 asks of the pair kernel (relative to the fp32 kernel
 measured on the same inputs: rms <= 1.25x + 1e-8, max <= 2x + 1e-7); rgb_map moves by at most 2e-5, the bar oracle/parity.py
 sets for the fine pass at fixed depths; eligibility is what the header says; and the fold follows the weights through
-optimiser steps."""
+optimiser steps, reloads and a deferred refresh.
+
+Every decision that is asserted is tests/view_fold_rule.py's verdict of the state dict, which tests/test_view_fold_cpu.py shows
+to be determined for each network named here. Under f16x2 the input scale is taken per wavefront: every on / off pair below
+packs the same points in the same order. The distances in the docstrings are what the tests printed on an MI355X."""
 import numpy as np
 import pytest
 import torch
 
+import view_fold_rule as R
 from conftest import load_golden
 from nerf_projects_amd import synthetic
-from test_hip_parity import _forward_fp64, cpu, gpu, make_net
+from test_hip_parity import _forward_fp64, cpu, gpu, make_net, npd
 
 pytestmark = pytest.mark.gpu
 
@@ -101,43 +106,16 @@ def test_on_against_off(N, rows):
     assert d <= 2e-5, d
 
 
-def _hostile(case):
-    arch = dict(ARCH)
-    if case == "W=128":
-        arch["W"] = 128
-        return dict(synthetic.synthetic_state_dict(41, W=128)), arch
-    if case == "W=100":
-        arch["W"] = 100
-        return dict(synthetic.synthetic_state_dict(44, W=100)), arch
-    if case == "default init":
-        return dict(synthetic.default_init_state_dict(3)), arch
-    sd = dict(synthetic.synthetic_state_dict(7))
-    wf, wv = np.asarray(sd["feature_linear.weight"]).copy(), np.asarray(sd["views_linears.0.weight"]).copy()
-    if case == "1/8 of the feature rows x2^13":        # the same function: the matching view columns x2^-13
-        wf[::8] *= np.float32(2.0 ** 13)
-        sd["feature_linear.bias"] = np.asarray(sd["feature_linear.bias"]).copy()
-        sd["feature_linear.bias"][::8] *= np.float32(2.0 ** 13)
-        wv[:, :256:8] *= np.float32(2.0 ** -13)
-    elif case == "W_f x1e3, W_v[:, :W] x1e-3":
-        wf *= np.float32(1e3)
-        wv[:, :256] *= np.float32(1e-3)
-    elif case == "gamma(dir) columns x2^-10":
-        wv[:, 256:] *= np.float32(2.0 ** -10)
-    else:
-        raise AssertionError(case)
-    sd["feature_linear.weight"], sd["views_linears.0.weight"] = wf, wv
-    return sd, arch
-
-
-@pytest.mark.parametrize("case", ["1/8 of the feature rows x2^13", "W_f x1e3, W_v[:, :W] x1e-3", "gamma(dir) columns x2^-10",
-                                  "W=128", "W=100", "default init"])
+@pytest.mark.parametrize("case", R.HOSTILE)
 def test_hostile_folds_against_fp64(N, rows, case):
     """Folds whose factors are far apart in size, zero padding, and the weights a training run starts from: whatever the
     network reports - folded, or not eligible - its rows keep the pair kernel's bars against fp64."""
-    sd, arch = _hostile(case)
-    net = make_net(N, sd, **arch)
+    sd, arch = R.hostile(case)
+    net = make_net(N, sd, **R.net_kwargs(arch))
     on, off, f32, folded = _three_ways(N, net, rows)
-    print(f"{case}: folded = {int(folded)}")
+    print(f"{case}: folded = {int(folded)}; the rule: {R.verdict(sd, arch)}")
+    if R.verdict(sd, arch) != "undetermined":
+        assert folded == (R.verdict(sd, arch) == "eligible")
     want = _forward_fp64(sd, rows, 8, [4], True)
     assert np.array_equal(on[:, 3], off[:, 3])
     if not folded:
@@ -151,24 +129,13 @@ def test_eligibility(N, rows):
     ctx = N.get_context()
     x = rows[:700]
 
-    def scaled(changes, **kw):
-        sd = dict(synthetic.synthetic_state_dict(7, **kw))
-        for key, f in changes.items():
-            sd[key] = (np.asarray(sd[key]) * np.float32(f)).astype(np.float32)
-        return sd
-
     bench = [make_net(N, sd) for sd in synthetic.synthetic_pair(0)]
     assert all(ctx.view_fold_status(n.slot) for n in bench)
     # the overflow networks of test_nonfinite_values_born_inside_the_network: the reference's NaN colours come from a feature
     # vector (or a view layer) the fold never forms, so they must run unfolded
-    nan_w = np.asarray(synthetic.synthetic_state_dict(7)["feature_linear.weight"]).copy()
-    nan_w[17, 5] = np.nan
-    not_eligible = {
-        "feature": scaled({"pts_linears.7.weight": 1e10, "feature_linear.weight": 1e30}),
-        "views": scaled({"feature_linear.weight": 1e20, "views_linears.0.weight": 1e20}),
-        "one NaN": dict(synthetic.synthetic_state_dict(7), **{"feature_linear.weight": nan_w}),
-    }
+    not_eligible = R.eligibility_networks()
     for name, sd in not_eligible.items():
+        assert R.verdict(sd, R.BENCH) == "not eligible"
         net = make_net(N, sd)
         assert not ctx.view_fold_status(net.slot), name
         on = cpu(net(x))
@@ -226,3 +193,483 @@ def test_fold_follows_the_weights(N):
     stale, ref = _errors(before, want), _errors(f32, want)
     assert stale[0] > 1.25 * ref[0] + 1e-8 and stale[1] > 2.0 * ref[1] + 1e-7, (stale, ref)
     ctx.precision_status(reset=True)
+
+
+# ---- shared by the tests below -----------------------------------------------------------------------------------------------
+
+def _on_off(ctx, fn):
+    """fn() with the fold on, then with it off."""
+    out = {}
+    try:
+        for on in (True, False):
+            ctx.set_view_fold(on)
+            out[on] = fn()
+    finally:
+        ctx.set_view_fold(True)
+    return out[True], out[False]
+
+
+def _f32(ctx, fn):
+    try:
+        ctx.set_precision("f32")
+        return fn()
+    finally:
+        ctx.set_precision("f16x2")
+
+
+def _same_bits(a, b, what):
+    assert np.array_equal(cpu(a), cpu(b), equal_nan=True), (what, np.abs(cpu(a) - cpu(b)).max())
+
+
+def _query(N, multires=10, multires_views=4, i_embed=0):
+    return N.make_network_query_fn(N.get_embedder(multires, i_embed)[0], N.get_embedder(multires_views, i_embed)[0])
+
+
+def _embed64(x, L):
+    out = [x]
+    for k in range(L):
+        out += [np.sin(x * 2.0 ** k), np.cos(x * 2.0 ** k)]
+    return np.concatenate(out, -1)
+
+
+@pytest.fixture(scope="module")
+def bench(N):
+    """The bench pair: state dicts, networks (both asserted folded) and the query."""
+    sds = R.bench_pair()
+    nets = [make_net(N, sd) for sd in sds]
+    assert all(R.verdict(sd, R.BENCH) == "eligible" for sd in sds)
+    assert all(N.get_context().view_fold_status(n.slot) for n in nets)
+    return sds, nets, _query(N)
+
+
+@pytest.fixture(scope="module")
+def fine_yardstick(N, bench, rows):
+    """The fine bench network on the 2048-row batch: each channel's largest |value| and the fp32 kernel's max error in
+    those units - the yardstick of the batches too small to measure a ratio of two errors on."""
+    want = _forward_fp64(bench[0][1], rows, 8, [4], True)
+    scale = np.abs(want).max(0)
+    f32 = _f32(N.get_context(), lambda: cpu(bench[1][1](rows)))
+    return scale, (np.abs(f32.astype(np.float64) - want) / scale).max()
+
+
+LEGO = dict(white_bkgd=True, perturb=0., raw_noise_std=0.)
+SIGMA_ONLY = ("acc_map", "disp_map", "z_std", "acc0", "disp0")
+
+
+# ---- 2. every input mode, the tile loop and the tails ----------------------------------------------------------------------
+
+def test_embedded_rows_tile_loop_and_tails(N, bench, fine_yardstick):
+    """net(x) on the fine bench network from one row to two tiles per workgroup and a ragged tail: sigma bit-identical on and
+    off, the colours on the other path, and the bars against fp64 (below 512 rows the max bar in the 2048-row batch's units).
+    MI355X: 700 rows rms 3.32e-7 max 1.30e-6 (fp32 kernel 3.93e-7 / 1.52e-6); 65 669 rows 2.55e-7 / 1.61e-6 (2.98e-7 / 1.82e-6);
+    1 .. 129 rows max 6.1e-7 .. 1.08e-6 against 2 x 2.50e-6; 94 % of the colour values differ, sigma never."""
+    ctx = N.get_context()
+    sd, net = bench[0][1], bench[1][1]
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    sizes = (1, 31, 32, 33, 127, 129, 700, 2 * cus * 128 + 128 + 5)
+    torch.manual_seed(7)
+    x_all = torch.rand(sizes[-1], 90, device="cuda") * 2 - 1
+    want_all = _forward_fp64(sd, x_all, 8, [4], True)
+    scale, f32_max = fine_yardstick
+    for n in sizes:
+        x = x_all[:n].contiguous()
+        assert ctx.view_fold_status(net.slot)
+        on, off = _on_off(ctx, lambda: cpu(net(x)))
+        assert on.shape == (n, 4)
+        assert np.array_equal(on[:, 3], off[:, 3]), n
+        differ = int((on[:, :3] != off[:, :3]).sum())
+        print(f"n = {n}: {differ} of {3 * n} colour values differ between the folded and the unfolded kernel")
+        assert differ > 0, n
+        want = want_all[:n]
+        if n >= 512:
+            _assert_bars(f"embedded rows, n = {n}", on, _f32(ctx, lambda: cpu(net(x))), want)
+        else:
+            e = (np.abs(on.astype(np.float64) - want) / scale).max()
+            print(f"n = {n}: folded-path max error {e:.3e} (2048-row units); fp32 kernel on 2048 rows {f32_max:.3e}")
+            assert e <= 2.0 * f32_max + 1e-7, (n, e, f32_max)
+    assert ctx.precision_status(reset=True) == 0
+
+
+@pytest.mark.parametrize("n,s", [(32, 8), (33, 7), (1, 1)])
+def test_points_mode(N, bench, n, s):
+    """run_network on raw points with per-ray directions (kInputPoints): the encoding is the kernel's own, so fp64 encodes
+    on the host and the fp32 kernel on the same points absorbs the encoding's error. MI355X (rms / max, fp32 kernel in
+    brackets): 32 x 8 3.47e-7 / 1.46e-6 (3.64e-7 / 1.51e-6); 33 x 7 3.81e-7 / 1.63e-6 (4.54e-7 / 1.89e-6); 1 x 1 3.27e-6 /
+    6.48e-6 (3.79e-6 / 7.21e-6)."""
+    ctx = N.get_context()
+    sd, net = bench[0][1], bench[1][1]
+    rs = np.random.RandomState(100 * n + s)
+    pts = rs.uniform(-1.2, 1.2, size=(n, s, 3)).astype(np.float32)
+    dirs = rs.standard_normal((n, 3))
+    dirs = (dirs / np.linalg.norm(dirs, axis=1, keepdims=True)).astype(np.float32)
+    e, ed = N.get_embedder(10, 0)[0], N.get_embedder(4, 0)[0]
+    run = lambda: cpu(N.run_network(gpu(pts), gpu(dirs), net, e, ed)).reshape(-1, 4)
+    assert ctx.view_fold_status(net.slot)
+    on, off = _on_off(ctx, run)
+    assert np.array_equal(on[:, 3], off[:, 3])
+    assert not np.array_equal(on[:, :3], off[:, :3])
+    x64 = np.concatenate([_embed64(pts.astype(np.float64).reshape(-1, 3), 10),
+                          _embed64(np.repeat(dirs.astype(np.float64), s, axis=0), 4)], -1)
+    want = _forward_fp64(sd, torch.as_tensor(x64), 8, [4], True)
+    _assert_bars(f"points {n} x {s}", on, _f32(ctx, run), want)
+
+
+def test_lattice_mode(N, bench):
+    """density_grid (kInputLattice) at 37 000 points - more than one tile per workgroup, a tail that is no multiple of 32 -
+    and at 12: bit-identical on and off, and equal to relu(run_network(...)[..., 3]) as tests/test_mesh.py states it."""
+    from test_mesh import C1, C2, RESO, lattice_points, sigma_via_run_network
+    ctx = N.get_context()
+    net = bench[1][1]
+    assert ctx.view_fold_status(net.slot)
+    for c1, c2, reso in ((C1, C2, RESO), ((-0.5, -0.4, -0.3), (0.5, 0.6, 0.7), (3, 2, 2))):
+        on, off = _on_off(ctx, lambda: N.density_grid(net, c1, c2, reso))
+        assert tuple(on.shape) == tuple(reso)
+        assert torch.equal(on, off), reso
+        want = sigma_via_run_network(N, net, lattice_points(c1, c2, reso)).reshape(reso)
+        assert torch.equal(on, want), reso
+    assert ctx.precision_status(reset=True) == 0
+
+
+def test_indexed_rays_mode(N, bench):
+    """render_rays(occupancy=...) (kInputRaysIndexed) through a 24^3 checkerboard on +-1.5, 100 lego rays at 64 + 128:
+    sigma, the skipped rows, the grid's counters and everything that depends on sigma alone do not see the fold.
+    MI355X: 16 963 of 25 600 points evaluated; largest |rgb_map on - off| 5.96e-8 (bar 2e-5)."""
+    ctx = N.get_context()
+    _, (net_c, net_f), q = bench
+    i, j, k = np.indices((24, 24, 24))
+    occ = N.OccupancyGrid.from_mask((i + j + k) % 2 == 0, -1.5, 1.5)
+    rays = gpu(load_golden("render_rays_lego")["rays"][:100])
+
+    def run():
+        occ.stats(reset=True)
+        ret = npd(N.render_rays(rays, net_c, q, N_samples=64, N_importance=128, network_fine=net_f, retraw=True,
+                                occupancy=occ, **LEGO))
+        return ret, occ.stats()
+
+    (on, st_on), (off, st_off) = _on_off(ctx, run)
+    print(f"evaluated {st_on[0]} of {st_on[1]} points")
+    assert st_on == st_off and 0 < st_on[0] < st_on[1] == 100 * (64 + 64 + 128)
+    assert np.array_equal(on["raw"][..., 3], off["raw"][..., 3])
+    skipped = ~off["raw"].any(-1)
+    assert skipped.any() and np.array_equal(skipped, ~on["raw"].any(-1))
+    for r in (on, off):      # +0, not -0
+        assert not r["raw"][skipped].view(np.uint32).any()
+    for key in SIGMA_ONLY:
+        assert np.array_equal(on[key], off[key]), key
+    d = np.abs(on["rgb_map"] - off["rgb_map"]).max()
+    print(f"indexed rays: largest |rgb_map on - off| over 100 rays: {d:.3e}")
+    assert 0 < d <= 2e-5
+
+
+@pytest.mark.parametrize("n_rays,Sc,Si", [(1, 3, 1), (5, 7, 9), (33, 65, 63), (3, 1, 0)])
+def test_rays_mode_small_and_odd_shapes(N, bench, n_rays, Sc, Si):
+    """test_small_and_odd_shapes' shapes. MI355X: largest |rgb_map on - off| 0, 5.96e-8, 5.96e-8, 0 (bar 2e-5)."""
+    ctx = N.get_context()
+    _, (net_c, net_f), q = bench
+    rays = gpu(load_golden("render_rays_lego")["rays"][:n_rays])
+
+    def run():
+        ex = {}
+        ret = npd(N.render_rays(rays, net_c, q, N_samples=Sc, N_importance=Si, network_fine=net_f if Si else None,
+                                _extras=ex, **LEGO))
+        return ret, npd(ex)
+
+    (on, ex_on), (off, ex_off) = _on_off(ctx, run)
+    for key in SIGMA_ONLY:
+        if key in off:
+            assert np.array_equal(on[key], off[key]), key
+    if Si:
+        assert np.array_equal(ex_on["z_fine"], ex_off["z_fine"])
+    d = np.abs(on["rgb_map"] - off["rgb_map"]).max()
+    print(f"{n_rays} rays at {Sc} + {Si}: largest |rgb_map on - off| {d:.3e}")
+    assert d <= 2e-5
+
+
+# ---- 3. the decision at its edges ------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("W", [256, 100])
+def test_decision_at_its_edges(N, rows, W):
+    """view_fold_status is the rule's verdict on both sides of the overflow rule (g = 124 / 132), of the ratio rule in both
+    directions (r = +-5 / +-11), with either column block zero, and with one NaN or inf in the last element of each tensor
+    the decision reads. Whatever the decision: sigma is bit-identical; not folded means the unfolded kernel exactly; folded
+    and finite means the bars against fp64 of that state dict. MI355X, the folded ones (rms / max, fp32 kernel in brackets):
+    W = 256 g = 124 2.46e-7 / 1.15e-6 (2.98e-7 / 1.56e-6), r = +5 2.71e-7 / 1.23e-6 (3.30e-7 / 1.83e-6), r = -5 1.37e-7 / 1.15e-6
+    (1.43e-7 / 8.59e-7), zero blocks 2.67e-7 / 1.24e-6 (3.22e-7 / 1.92e-6) and 1.36e-7 / 1.15e-6 (1.41e-7 / 8.59e-7); W = 100
+    between 1.54e-7 / 1.12e-6 and 2.48e-7 / 1.30e-6, each within its bars."""
+    ctx = N.get_context()
+    x = rows[:700]
+    for tag, sd, arch, folds in list(R.boundary_networks(W)) + list(R.nonfinite_networks(W)):
+        assert R.verdict(sd, arch) == ("eligible" if folds else "not eligible"), tag
+        net = make_net(N, sd, **R.net_kwargs(arch))
+        on, off, f32, folded = _three_ways(N, net, x)
+        finite = R.fold_rule(sd, arch)[0]
+        print(f"{tag}: folded = {int(folded)}")
+        assert folded == folds, tag
+        assert np.array_equal(on[:, 3], off[:, 3], equal_nan=True), tag
+        if not folded:
+            assert np.array_equal(on, off, equal_nan=True), tag
+        elif finite:
+            _assert_bars(tag, on, f32, _forward_fp64(sd, x, 8, [4], True))
+    ctx.precision_status(reset=True)
+
+
+# ---- 4. architectures ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("tag,seed,arch,L,Lv,i_embed", R.VARIANTS, ids=[v[0] for v in R.VARIANTS])
+def test_architectures_fold(N, tag, seed, arch, L, Lv, i_embed):
+    """Depths, skips, encoding widths and a narrow trunk, every one asserted FOLDED: rows against fp64, then 40 lego rays.
+    MI355X, rows rms / max (fp32 kernel), then |rgb_map on - off|: D=2 1.11e-7 / 5.02e-7 (1.43e-7 / 6.91e-7), 8.05e-7; D=6
+    2.03e-7 / 1.16e-6 (2.57e-7 / 1.21e-6), 1.19e-7; D=3 1.44e-7 / 6.28e-7 (1.84e-7 / 8.33e-7), 1.19e-7; multires 6 / 2 2.87e-7 /
+    1.32e-6 (3.27e-7 / 1.30e-6), 2.38e-7; identity 3.04e-7 / 1.64e-6 (3.47e-7 / 1.77e-6), 1.19e-7; W=64 1.46e-7 / 8.33e-7
+    (1.60e-7 / 1.07e-6), 5.96e-8."""
+    ctx = N.get_context()
+    sd = R.variant_state_dict(seed, arch)
+    assert R.verdict(sd, arch) == "eligible"
+    net = make_net(N, sd, **R.net_kwargs(arch))
+    torch.manual_seed(5)
+    x = torch.rand(2048, arch["input_ch"] + arch["input_ch_views"], device="cuda") * 2 - 1
+    on, off, f32, folded = _three_ways(N, net, x)
+    assert folded, tag
+    assert np.array_equal(on[:, 3], off[:, 3])
+    assert not np.array_equal(on[:, :3], off[:, :3])
+    _assert_bars(tag, on, f32, _forward_fp64(sd, x, arch["D"], list(arch["skips"]), True, input_ch=arch["input_ch"]))
+    rays = gpu(load_golden("render_rays_lego")["rays"][:40])
+    q = _query(N, L, Lv, i_embed)
+    on, off = _on_off(ctx, lambda: npd(N.render_rays(rays, net, q, N_samples=32, retraw=True, **LEGO)))
+    assert np.array_equal(on["raw"][..., 3], off["raw"][..., 3])
+    d = np.abs(on["rgb_map"] - off["rgb_map"]).max()
+    print(f"{tag}: largest |rgb_map on - off| over 40 rays: {d:.3e}")
+    assert d <= 2e-5
+    ctx.precision_status(reset=True)
+
+
+# ---- 5. two networks, two decisions ----------------------------------------------------------------------------------------
+
+def test_two_networks_two_decisions(N, bench):
+    """One render whose coarse network is folded and whose fine one is not, and the reverse. A launch enqueues both kernels
+    and the one the network's word does not name runs no tile: each pass must be exactly the pass of a render in which its
+    network took the same decision. The unfoldable twins are the same functions (the overflow scaling), and sigma never
+    reads what was scaled, so the depths of the fine pass are the same bits throughout."""
+    ctx = N.get_context()
+    (sd_c, sd_f), (net_c, net_f), q = bench
+    net_cx, net_fx = make_net(N, R.unfoldable_twin(sd_c)), make_net(N, R.unfoldable_twin(sd_f))
+    assert not ctx.view_fold_status(net_cx.slot) and not ctx.view_fold_status(net_fx.slot)
+    rays = gpu(load_golden("render_rays_lego")["rays"][:96])
+
+    def render(c, f, on):
+        ex = {}
+        try:
+            ctx.set_view_fold(on)
+            ret = npd(N.render_rays(rays, c, q, N_samples=64, N_importance=128, network_fine=f, retraw=True, _extras=ex, **LEGO))
+        finally:
+            ctx.set_view_fold(True)
+        ret["z_fine"] = cpu(ex["z_fine"])
+        return ret
+
+    coarse_pass, fine_pass = ("rgb0", "acc0", "disp0", "z_fine"), ("raw", "rgb_map", "acc_map", "disp_map")
+    both_on = render(net_c, net_f, True)
+    # coarse folded, fine not
+    mixed, off = render(net_c, net_fx, True), render(net_c, net_fx, False)
+    for k in coarse_pass:
+        assert np.array_equal(mixed[k], both_on[k]), k
+    for k in fine_pass:
+        assert np.array_equal(mixed[k], off[k]), k
+    assert not np.array_equal(mixed["rgb0"], off["rgb0"])
+    assert not np.array_equal(mixed["rgb_map"], both_on["rgb_map"])
+    # coarse not, fine folded
+    mixed, off = render(net_cx, net_f, True), render(net_cx, net_f, False)
+    for k in coarse_pass:
+        assert np.array_equal(mixed[k], off[k]), k
+    for k in fine_pass:
+        assert np.array_equal(mixed[k], both_on[k]), k
+    assert not np.array_equal(mixed["rgb_map"], off["rgb_map"])
+    assert not np.array_equal(mixed["rgb0"], both_on["rgb0"])
+    assert ctx.precision_status(reset=True) == 0
+
+
+# ---- 6. what must not fold, and what must not notice -----------------------------------------------------------------------
+
+def _train_kw(N, net_c, net_f):
+    return dict(network_fn=net_c, network_fine=net_f, N_samples=8, N_importance=8, white_bkgd=True, perturb=1.0,
+                raw_noise_std=1.0, pytest=True, ndc=False, use_viewdirs=True, near=2., far=6., network_query_fn=_query(N))
+
+
+def test_random_draws_do_not_fold(N, bench):
+    """render_rays with jitter and noise is the render the training passes reproduce bit for bit: no output, raw included,
+    sees the switch."""
+    ctx = N.get_context()
+    _, (net_c, net_f), q = bench
+    rays = gpu(load_golden("render_rays_lego")["rays"][:96])
+    assert ctx.view_fold_status(net_c.slot) and ctx.view_fold_status(net_f.slot)
+    kw = dict(N_samples=64, N_importance=128, network_fine=net_f, retraw=True, white_bkgd=True, pytest=True)
+    on, off = _on_off(ctx, lambda: npd(N.render_rays(rays, net_c, q, perturb=1.0, raw_noise_std=1.0, **kw)))
+    assert set(on) == set(off) and "raw" in on
+    for k in on:
+        assert np.array_equal(on[k], off[k]), k
+    # (the control: without draws the same call does see it)
+    on, off = _on_off(ctx, lambda: npd(N.render_rays(rays, net_c, q, perturb=0., raw_noise_std=0., **kw)))
+    assert not np.array_equal(on["raw"][..., :3], off["raw"][..., :3])
+
+
+def test_training_does_not_see_the_fold(N):
+    """Two train_on_batch steps (the train_step fixture's 32 rays, 8 + 8 samples) on identical model pairs, one with the fold on and one with it off: losses, rgb, weights and
+    Adam state bit-identical; then a taped deterministic render and its gradients, bit-identical too; and the taped render
+    against the untaped one - within 2e-5 in rgb_map with the fold on (the header's sentence), and with it off every output
+    equal bit for bit, which is what tests/test_autograd.py::test_taped_outputs_equal_untaped asserted before the fold.
+    MI355X: largest |rgb_map taped - untaped| with the fold on 1.19e-7."""
+    g = load_golden("train_step")
+    ctx = N.get_context()
+    sd_c, sd_f = R.bench_pair()
+    rays = g["rays"][:64]
+    batch_rays, target = (gpu(rays[:, 0:3]), gpu(rays[:, 3:6])), gpu(g["target"][:64])
+    packed = gpu(load_golden("render_rays_lego")["rays"][:target.shape[0]])
+    state = {}
+    try:
+        for on in (True, False):
+            ctx.set_view_fold(on)
+            net_c, net_f = make_net(N, sd_c), make_net(N, sd_f)
+            assert ctx.view_fold_status(net_f.slot) == on
+            kw = _train_kw(N, net_c, net_f)
+            opt = N.Adam([net_c, net_f], lr=5e-3)
+            out = [N.train_on_batch(800, 800, None, batch_rays, target, opt, **kw) for _ in range(2)]
+            s = {f"step {i} {k}": cpu(o[k]) for i, o in enumerate(out) for k in ("loss", "rgb", "rgb0")}
+            for tag, net in (("c", net_c), ("f", net_f)):
+                s.update({f"{tag} {k}": cpu(v) for k, v in net.state_dict().items()})
+                m, v = net.adam_state()
+                s.update({f"{tag} m {k}": a for k, a in m.items()})
+                s.update({f"{tag} v {k}": a for k, a in v.items()})
+            rkw = dict(N_samples=8, N_importance=8, network_fine=net_f, retraw=True, **LEGO)
+            untaped = npd(N.render_rays(packed, net_c, kw["network_query_fn"], **rkw))
+            net_c.requires_grad_()
+            net_f.requires_grad_()
+            opt.zero_grad()
+            ret = N.render_rays(packed, net_c, kw["network_query_fn"], **rkw)
+            assert ret["rgb_map"].grad_fn is not None
+            (N.img2mse(ret["rgb_map"], target) + N.img2mse(ret["rgb0"], target)).backward()
+            taped = npd(ret)
+            s.update({f"taped {k}": v for k, v in taped.items()})
+            for tag, net in (("c", net_c), ("f", net_f)):
+                s.update({f"{tag} grad {k}": cpu(v) for k, v in net.grad_dict().items()})
+            state[on] = (s, taped, untaped)
+    finally:
+        ctx.set_view_fold(True)
+    assert set(state[True][0]) == set(state[False][0])
+    for k, v in state[True][0].items():
+        assert np.array_equal(v, state[False][0][k]), k
+    assert any(np.abs(v).max() > 0 for k, v in state[True][0].items() if " grad " in k)
+    _, taped, untaped = state[True]
+    d = np.abs(taped["rgb_map"] - untaped["rgb_map"]).max()
+    print(f"fold on: largest |rgb_map taped - untaped| over 64 rays: {d:.3e}")
+    assert d <= 2e-5
+    _, taped, untaped = state[False]
+    for k in ("rgb_map", "disp_map", "acc_map", "raw", "rgb0", "disp0", "acc0"):
+        assert np.array_equal(taped[k], untaped[k]), k
+    ctx.precision_status(reset=True)
+
+
+def test_reload_into_a_live_slot(N, rows):
+    """One NeRF object: eligible A, then the unfoldable twin of another function B, then eligible C. The fold follows every
+    load_state_dict; A's rows - what a stale fold would give - miss C's bars."""
+    ctx = N.get_context()
+    x = rows[:512]
+    sd_a, sd_b, sd_c = R.bench_pair()[1], R.unfoldable_twin(R.reload_state_dict("B")), R.reload_state_dict("C")
+    net = make_net(N, sd_a)
+    assert ctx.view_fold_status(net.slot)
+    rows_a = cpu(net(x))
+    net.load_state_dict(sd_b)
+    assert not ctx.view_fold_status(net.slot)
+    on, off, f32, folded = _three_ways(N, net, x)
+    assert not folded and np.array_equal(on, off)
+    # (no bars here: W_v[:, :W] 2^-64 below the gamma(dir) block of its rows is the within-row limit of the fp16-pair
+    # arithmetic - the unfolded kernel loses the colours, rms 0.33 on an MI355X, and counts nothing: DESIGN 8)
+    print(f"B, not folded: {ctx.precision_status(reset=True)} loose-bound events on 3 x 512 rows")
+    net.load_state_dict(sd_c)
+    assert ctx.view_fold_status(net.slot)
+    on, off, f32, folded = _three_ways(N, net, x)
+    want = _forward_fp64(sd_c, x, 8, [4], True)
+    assert folded and np.array_equal(on[:, 3], off[:, 3]) and not np.array_equal(on[:, :3], off[:, :3])
+    _assert_bars("C after A and B", on, f32, want)
+    stale, ref = _errors(rows_a, want), _errors(f32, want)
+    assert stale[0] > 1.25 * ref[0] + 1e-8 and stale[1] > 2.0 * ref[1] + 1e-7, (stale, ref)
+    ctx.precision_status(reset=True)
+
+
+@pytest.mark.parametrize("ask_first", [True, False], ids=["status first", "launch first"])
+def test_deferred_refresh(N, rows, ask_first):
+    """Weights loaded under set_precision("f32"), then back to f16x2: the first fp16-pair launch reads a fold of the new
+    weights, whether view_fold_status refreshed it on the null stream beforehand or the launch does on its own stream."""
+    ctx = N.get_context()
+    x = rows[:512]
+    sd_a, sd_d = R.bench_pair()[1], R.reload_state_dict("D")
+    net = make_net(N, sd_a)
+    rows_a = cpu(net(x))
+    try:
+        ctx.set_precision("f32")
+        net.load_state_dict(sd_d)
+        f32_first = cpu(net(x))
+    finally:
+        ctx.set_precision("f16x2")
+    if ask_first:
+        assert ctx.view_fold_status(net.slot)
+    first = cpu(net(x))
+    on, off, f32, folded = _three_ways(N, net, x)
+    want = _forward_fp64(sd_d, x, 8, [4], True)
+    assert folded and np.array_equal(first, on) and np.array_equal(f32_first, f32)
+    assert np.array_equal(on[:, 3], off[:, 3]) and not np.array_equal(on[:, :3], off[:, :3])
+    _assert_bars("D after a load under f32", first, f32, want)
+    stale, ref = _errors(rows_a, want), _errors(f32, want)
+    assert stale[0] > 1.25 * ref[0] + 1e-8 and stale[1] > 2.0 * ref[1] + 1e-7, (stale, ref)
+    ctx.precision_status(reset=True)
+
+
+# ---- 7. the folded kernel's own event --------------------------------------------------------------------------------------
+
+def test_feature_bound_event_is_counted_per_point(N):
+    """An eligible network whose feature_linear bound is infinite on every row while the trunk output is finite
+    (view_fold_rule.event_network: max|h| in [2^73, 2^75), the threshold at 2^68.6; tests/test_view_fold_cpu.py shows why no
+    wider margin exists). Guard off: the folded kernel counts one event per point more than the unfolded one - 64 and 96
+    rows, so that a count per wavefront or per half-wave shows - and sigma is finite and the same bits. Through
+    batchify_rays' guard the rays come back from the fp32 kernel, with the warning, colours NaN as the reference's.
+    MI355X: 64 and 96 events with the fold on, 0 with it off (before the event line asked for a live lane: 128 for 64 rows)."""
+    import warnings
+    ctx = N.get_context()
+    sd, margin = R.event_network()
+    assert R.verdict(sd, R.BENCH) == "eligible" and margin >= 4
+    net = make_net(N, sd)
+    assert ctx.view_fold_status(net.slot)
+    rows = R.event_rows()
+    for n in (64, 96):
+        x = gpu(rows[:n])
+        ctx.precision_status(reset=True)
+
+        def run():
+            out = cpu(net(x))
+            return out, ctx.precision_status(reset=True)
+
+        (on, ev_on), (off, ev_off) = _on_off(ctx, run)
+        print(f"n = {n}: loose-bound events with the fold on {ev_on}, off {ev_off}")
+        assert ev_on - ev_off == n, (n, ev_on, ev_off)
+        assert np.isfinite(on[:, 3]).all() and np.array_equal(on[:, 3], off[:, 3])
+        # the kernels that form the feature vector return the reference's NaN colours (NeRF.forward in fp32 on the CPU)
+        want32 = _forward_fp64(sd, x, 8, [4], True, dtype=torch.float32)
+        assert np.isnan(want32[:, :3]).all() and np.isfinite(want32[:, 3]).all()
+        for out in (off, _f32(ctx, lambda: cpu(net(x)))):
+            assert np.array_equal(~np.isfinite(want32), ~np.isfinite(out))
+    q = _query(N)
+    rays = gpu(load_golden("render_rays_lego")["rays"][:64])
+    kw = dict(network_fn=net, network_query_fn=q, N_samples=16, white_bkgd=True, retraw=True)
+    ctx.precision_status(reset=True)
+    try:
+        want = _f32(ctx, lambda: npd(N.batchify_rays(rays, 32, **kw)))
+        with pytest.warns(RuntimeWarning, match="rendered again with the fp32 kernel"):
+            got = npd(N.batchify_rays(rays, 32, **kw))
+        assert ctx.get_precision() == "f16x2"
+        for k in want:
+            assert np.array_equal(got[k], want[k], equal_nan=True), k
+        assert np.isnan(got["rgb_map"]).any() and np.isnan(got["raw"][..., :3]).any()
+        assert np.isfinite(got["raw"][..., 3]).all() and np.isfinite(got["acc_map"]).all()
+    finally:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            ctx.precision_status(reset=True)
+            ctx.precision_peek()

@@ -54,10 +54,15 @@ def group(at, ot, t4, col):
     return g.reshape(-1)
 
 
-@pytest.mark.parametrize("D,W,skips", [(8, 256, (4,)), (2, 100, ()), (3, 128, (0,))])
-def test_folded_tables_gather_the_fold(driver, tmp_path, D, W, skips):
+@pytest.mark.parametrize("D,W,skips,input_ch,n_dir", [(8, 256, (4,), 63, 27), (2, 100, (), 63, 27), (3, 128, (0,), 63, 27),
+                                                       (8, 256, (4,), 39, 15), (6, 256, (1, 3), 63, 3), (2, 64, (), 3, 3)],
+                         ids=["8-256-skips0", "2-100-skips1", "3-128-skips2", "8-256-skips0-39-15", "6-256-skips13-63-3",
+                              "2-64-noskip-3-3"])
+def test_folded_tables_gather_the_fold(driver, tmp_path, D, W, skips, input_ch, n_dir):
+    """Every width of gamma(x) and gamma(dir) the packer pads differently: the gamma(dir) chunk has W_v[:, W + c] at encoding
+    column c < n_dir and zero beyond."""
     out = tmp_path / "fold.bin"
-    r = subprocess.run([driver, str(D), str(W), "63", "27", str(len(skips)), *map(str, skips), str(out)],
+    r = subprocess.run([driver, str(D), str(W), str(input_ch), str(n_dir), str(len(skips)), *map(str, skips), str(out)],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     raw = np.fromfile(out, dtype=np.float32)
@@ -72,7 +77,7 @@ def test_folded_tables_gather_the_fold(driver, tmp_path, D, W, skips):
     assert np.array_equal(fstream[:n_trunk * CHUNK], stream[:n_trunk * CHUNK])       # the trunk as in the plain stream
     assert np.array_equal(ids[:n_trunk], np.repeat(np.arange(D), [(2 if (i == 0 or (i - 1) in skips) else 0) + (8 if i else 0)
                                                                   for i in range(D)]))
-    nv, n_dir = W // 2, 27
+    nv = W // 2
     tail = nv * W + nv
     tables = [(t.astype(np.int64) - 1) for t in (fstream, fbias)]
     assert all(t.max() < n_params + tail and t.min() >= -1 for t in tables)
@@ -80,7 +85,7 @@ def test_folded_tables_gather_the_fold(driver, tmp_path, D, W, skips):
     # parameters and a fold made here, gathered through the tables
     rng = np.random.default_rng(3)
     params = rng.standard_normal(n_params).astype(np.float32)
-    trunk_in = [63 if i == 0 else (W + 63 if (i - 1) in skips else W) for i in range(D)]
+    trunk_in = [input_ch if i == 0 else (W + input_ch if (i - 1) in skips else W) for i in range(D)]
     off = sum(W * n + W for n in trunk_in)
     wv = params[off:off + nv * (W + n_dir)].reshape(nv, W + n_dir)
     bv = params[off + nv * (W + n_dir):off + nv * (W + n_dir) + nv]
@@ -113,3 +118,123 @@ def test_folded_tables_gather_the_fold(driver, tmp_path, D, W, skips):
     assert np.array_equal(got_b[:v0], plain_b[:v0]) and np.array_equal(got_b[v1:], plain_b[v1:])
     want = [b_vf[hidden_col(ot, r, h)] if hidden_col(ot, r, h) < nv else 0.0 for ot in range(4) for h in range(2) for r in range(16)]
     assert np.array_equal(got_b[v0:v1], np.asarray(want, dtype=np.float32))
+
+
+# ---- the decision restated on the host (tests/view_fold_rule.py) ------------------------------------------------------------
+
+import view_fold_rule as R  # noqa: E402
+
+
+def _named_networks():
+    """Every network a GPU test asserts a decision on, with the decision it asserts."""
+    for tag, sd, arch, folds in R.edge_networks():
+        yield tag, sd, arch, folds
+    for tag, sd in zip(("bench coarse", "bench fine"), R.bench_pair()):
+        yield tag, sd, R.BENCH, True
+        yield tag + ", unfoldable twin", R.unfoldable_twin(sd), R.BENCH, False
+    for tag, seed, arch, *_ in R.VARIANTS:
+        yield "variant " + tag, R.variant_state_dict(seed, arch), arch, True
+    yield "reload B, unfoldable twin", R.unfoldable_twin(R.reload_state_dict("B")), R.BENCH, False
+    yield "reload C", R.reload_state_dict("C"), R.BENCH, True
+    yield "reload D", R.reload_state_dict("D"), R.BENCH, True
+    for name, sd in R.eligibility_networks().items():
+        yield "test_eligibility: " + name, sd, R.BENCH, False
+    yield "event network", R.event_network()[0], R.BENCH, True
+
+
+def test_rule_decides_every_named_network():
+    """No decision assertion on an undetermined network: every network the GPU tests name is "eligible" or "not eligible"
+    as they assert it, the equalised copy (row_exponents_kernel restated) moves g and r by no more than the slack, and the
+    rule applied to that copy - what the device does - gives the same answer."""
+    for tag, sd, arch, folds in _named_networks():
+        v = R.verdict(sd, arch)
+        finite, g, r = R.fold_rule(sd, arch)
+        fin_eq, g_eq, r_eq, folded = R.equalised_rule(sd, arch)
+        show = lambda x: "None" if x is None else f"{x:+.2f}"
+        print(f"{tag}: {v}; g {show(g)} (equalised {show(g_eq)}), r {show(r)} (equalised {show(r_eq)})")
+        assert v == ("eligible" if folds else "not eligible"), tag
+        assert folded == folds and fin_eq == finite, tag
+        if finite:
+            assert abs(g_eq - g) <= R.GAIN_SLACK, tag
+            assert (r is None) == (r_eq is None) and (r is None or abs(r_eq - r) <= R.RATIO_SLACK), tag
+
+
+def test_rule_on_the_hostile_networks():
+    """test_hostile_folds_against_fp64 asserts no decision (its networks may sit inside the slack); here what the rule says
+    of each, and that the equalised copy never contradicts a determined verdict."""
+    want = {"1/8 of the feature rows x2^13": "eligible", "W_f x1e3, W_v[:, :W] x1e-3": "eligible",
+            "gamma(dir) columns x2^-10": "not eligible", "W=128": "eligible", "W=100": "eligible", "default init": "eligible"}
+    for case in R.HOSTILE:
+        sd, arch = R.hostile(case)
+        v = R.verdict(sd, arch)
+        _, g, r = R.fold_rule(sd, arch)
+        _, g_eq, r_eq, folded = R.equalised_rule(sd, arch)
+        print(f"{case}: {v}; g {g:.2f} (equalised {g_eq:.2f}), r {r:+.2f} (equalised {r_eq:+.2f}); device folds: {folded}")
+        assert v == want[case], case
+        assert folded == (v == "eligible"), case
+
+
+def test_boundary_networks_land_on_their_side():
+    for W in (256, 100):
+        nets = {tag.split(" ", 1)[1]: (sd, arch) for tag, sd, arch, _ in R.boundary_networks(W)}
+        g = {k: R.fold_rule(*nets[k])[1] for k in ("g=124", "g=132")}
+        assert 123 < g["g=124"] <= 124 and 132 <= g["g=132"] < 133, g
+        r = {k: R.fold_rule(*nets[k])[2] for k in ("r=+5", "r=-5", "r=+11", "r=-11")}
+        assert 4 < r["r=+5"] <= 5 and -5 <= r["r=-5"] < -4 and 11 <= r["r=+11"] < 12 and -12 < r["r=-11"] <= -11, r
+        assert all(R.fold_rule(*nets[k])[2] is None for k in ("W_v[:, W:] = 0", "W_v[:, :W] = 0"))
+        # the overflow scaling is the same function: powers of two on W_f, b_f and, inverted, on the columns that read them
+        sd0, arch = R.base(W)
+        for k in ("g=124", "g=132"):
+            sd = nets[k][0]
+            a = np.log2(sd["feature_linear.bias"][0] / sd0["feature_linear.bias"][0])
+            assert a == int(a)
+            assert np.array_equal(sd["feature_linear.weight"], sd0["feature_linear.weight"] * np.float32(2.0 ** a))
+            assert np.array_equal(sd["views_linears.0.weight"][:, :W], sd0["views_linears.0.weight"][:, :W] * np.float32(2.0 ** -a))
+            assert np.array_equal(sd["views_linears.0.weight"][:, W:], sd0["views_linears.0.weight"][:, W:])
+
+
+def test_rule_sees_one_bad_entry_anywhere():
+    """The restatement itself: a single non-finite entry in any of the four tensors, first or last element."""
+    sd0, arch = R.base(256)
+    assert R.verdict(sd0, arch) == "eligible"
+    for key in ("feature_linear.weight", "feature_linear.bias", "views_linears.0.weight", "views_linears.0.bias"):
+        for at in (0, -1):
+            sd = R._copy(sd0)
+            sd[key].reshape(-1)[at] = np.inf
+            assert R.verdict(sd, arch) == "not eligible", (key, at)
+    # a product that overflows fp32 from finite factors
+    sd = R._copy(sd0)
+    sd["feature_linear.weight"] *= np.float32(1e20)
+    sd["views_linears.0.weight"] *= np.float32(1e20)
+    assert not R.fold_rule(sd, arch)[0]
+
+
+def test_event_window():
+    """The folded kernel's feature_linear event is reachable on an eligible network only for trunk outputs in [2^68, 2^76):
+    with g <= 124 the a-priori bound is infinite from 2^(128 - (g - 64)) >= 2^68 on, and the fp16-pair kernel represents no
+    activation of 2^76 or more. A margin of 2^8 on every point leaves no room; the event network takes what the window admits
+    and every one of its rows is beyond the threshold, below the range's end, and NaN in the reference's fp32 colours."""
+    import torch
+    sd, margin = R.event_network()
+    assert R.verdict(sd, R.BENCH) == "eligible"
+    _, g, _ = R.fold_rule(sd, R.BENCH)
+    threshold = R.EVENT_THRESHOLD_LOG2 - (g - 64)
+    assert g <= R.GAIN_LIMIT - R.GAIN_SLACK and threshold >= 68
+    assert threshold + 8 >= R.EVENT_RANGE_LOG2            # the margin the window cannot hold
+    m = np.log2(R.trunk_max(sd, R.BENCH, R.event_rows()))
+    print(f"g {g:.2f}: threshold 2^{threshold:.2f}; max|h| of the rows 2^{m.min():.2f} .. 2^{m.max():.2f}; margin 2^{margin:.2f}")
+    assert m.max() < R.EVENT_RANGE_LOG2 - 1 and margin >= 4 and np.isclose(m.min() - threshold, margin)
+    # the reference (fp32, NeRF.forward): feature_linear overflows on every row, the colours are NaN, sigma is finite
+    t = lambda k: torch.as_tensor(sd[k])
+    x = torch.as_tensor(R.event_rows())
+    h = x[:, :63]
+    for i in range(8):
+        h = torch.relu(h @ t(f"pts_linears.{i}.weight").T + t(f"pts_linears.{i}.bias"))
+        if i == 4:
+            h = torch.cat([x[:, :63], h], -1)
+    feat = h @ t("feature_linear.weight").T + t("feature_linear.bias")
+    hv = torch.relu(torch.cat([feat, x[:, 63:]], -1) @ t("views_linears.0.weight").T + t("views_linears.0.bias"))
+    rgb = hv @ t("rgb_linear.weight").T + t("rgb_linear.bias")
+    sigma = h @ t("alpha_linear.weight").T + t("alpha_linear.bias")
+    assert torch.isfinite(h).all() and torch.isinf(feat).any(1).all()
+    assert torch.isnan(rgb).all() and torch.isfinite(sigma).all()
