@@ -1008,6 +1008,49 @@ int nerf_grid_components_keep(nerf_ctx* ctx, const int32_t* links, const int32_t
                               int64_t count, uint8_t* mask, void* stream);
 int nerf_grid_copy_rows(nerf_ctx* ctx, const nerf_grid_copy_rows_args* args);
 
+/* Sparse voxel grid: depth and ray lengths ----------------------------------------------------------
+ * How far a ray goes before it ends: svox2's volume_render_depth (trace_ray_expected_term and trace_ray_sigma_thresh of
+ * render_lerp_kernel_cuvol.cu) and the ray length of its PyTorch renderer (return_raylen). All three modes use the ray set-up
+ * and the sample lattice of nerf_grid_render_rays, operation by operation: the same o, d, delta_scale, tmin (near_clip
+ * applied) and tmax, the same fp32 additions of t, the same skip rule, the same stall rule. Directions need not be unit.
+ * background_brightness is not read. With world_step = step_size * delta_scale (the length of a step in world units):
+ *
+ * NERF_GRID_DEPTH_EXPECTED: depth = 0, log_T = 0; at every sample with sigma > opt.sigma_thresh, with a and log_T as in the
+ *   render:  weight = exp(log_T) (1 - exp(a));  depth += (weight * (t / step_size)) * world_step;  log_T += a;
+ *   if exp(log_T) < opt.stop_thresh: log_T = -1e3, stop.  Each fp32 operation rounded, in that order. The value is the
+ *   expected length along the ray in world units (not z-depth) and is NOT divided by the accumulated opacity 1 - exp(log_T):
+ *   log_transmit returns log_T (bit for bit what the render returns under the same options) so that callers can normalise.
+ * NERF_GRID_DEPTH_THRESHOLD: depth = (t / step_size) * world_step at the first lattice sample whose interpolated density
+ *   strictly exceeds sigma_thresh, 0 if there is none. opt.sigma_thresh and opt.stop_thresh are not read. sigma_thresh < 0
+ *   or NaN is NERF_E_INVALID: the skip data is only valid when an all-empty cell (sigma == 0 exactly) can never be a hit.
+ * NERF_GRID_DEPTH_RAYLEN: depth = tmax - tmin, in GRID units, negative for a ray that misses the box (svox2.py
+ *   _volume_render_gradcheck_lerp(return_raylen=True)). Nothing is marched; skip data is not read.
+ * A ray that misses the box gives depth 0 and log_T 0. A ray whose set-up is not finite (a zero direction, a NaN or an
+ * infinity in origin or direction) gives depth 0 and log_T 0, and ray length NaN. log_transmit may only be asked for in the
+ * expected mode. Stream-ordered, nothing is synchronised or allocated; one lane per ray, no atomics: two calls give
+ * identical bits, with and without skip data. At most 2^26 rays or pixels per call. */
+#define NERF_GRID_DEPTH_EXPECTED 0
+#define NERF_GRID_DEPTH_THRESHOLD 1
+#define NERF_GRID_DEPTH_RAYLEN 2
+
+typedef struct nerf_grid_depth_args {
+    size_t struct_size;
+    int32_t mode;               /* NERF_GRID_DEPTH_*                                                                */
+    float sigma_thresh;         /* NERF_GRID_DEPTH_THRESHOLD: >= 0, not NaN; otherwise not read                     */
+    const float* origins;       /* [dev] [n_rays, 3]       (nerf_grid_depth_rays only)                              */
+    const float* dirs;          /* [dev] [n_rays, 3], need not be unit                                              */
+    int64_t n_rays;             /* nerf_grid_depth_image: ignored, width * height rays in row-major pixel order     */
+    float* depth;               /* [dev] [n_rays]                                                                   */
+    float* log_transmit;        /* [dev] [n_rays] or NULL; NERF_GRID_DEPTH_EXPECTED only                            */
+    int32_t use_skip;           /* 1: use the skip data if nerf_grid_accelerate made it; 0: plain march             */
+    void* stream;
+} nerf_grid_depth_args;
+
+int nerf_grid_depth_rays(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_depth_args* args);
+/* the rays of `cam` made inside the launch (as nerf_grid_render_image makes them): one call per frame */
+int nerf_grid_depth_image(nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_render_options* opt,
+                          const nerf_grid_depth_args* args);
+
 #ifdef __cplusplus
 }
 #endif

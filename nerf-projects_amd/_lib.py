@@ -32,6 +32,7 @@ EXPORTS = (
     "nerf_grid_compact_workspace", "nerf_grid_compact", "nerf_grid_gather",
     "nerf_grid_components_occupancy", "nerf_grid_components_workspace", "nerf_grid_components_label",
     "nerf_grid_components_finish", "nerf_grid_components_volumes", "nerf_grid_components_keep", "nerf_grid_copy_rows",
+    "nerf_grid_depth_rays", "nerf_grid_depth_image",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -39,6 +40,7 @@ NERF_GUARD_OFF, NERF_GUARD_REPORT, NERF_GUARD_FALLBACK = 0, 1, 2
 NERF_OCC_EVALUATE, NERF_OCC_EMPTY = 0, 1
 NERF_GRID_TV_DENSITY, NERF_GRID_TV_SH = 0, 1
 NERF_GRID_OPTIM_RMSPROP, NERF_GRID_OPTIM_SGD = 0, 1
+NERF_GRID_DEPTH_EXPECTED, NERF_GRID_DEPTH_THRESHOLD, NERF_GRID_DEPTH_RAYLEN = 0, 1, 2
 
 
 class NerfArch(C.Structure):
@@ -222,6 +224,11 @@ class GridCopyRowsArgs(_Sized):
                 ("src_row", _FP), ("density", _FP), ("sh", _FP), ("stream", C.c_void_p)]
 
 
+class GridDepthArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("mode", C.c_int32), ("sigma_thresh", C.c_float), ("origins", _FP), ("dirs", _FP),
+                ("n_rays", C.c_int64), ("depth", _FP), ("log_transmit", _FP), ("use_skip", C.c_int32), ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -396,6 +403,10 @@ def load():
     lib.nerf_grid_components_keep.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp]
     lib.nerf_grid_copy_rows.restype = i32
     lib.nerf_grid_copy_rows.argtypes = [vp, C.POINTER(GridCopyRowsArgs)]
+    lib.nerf_grid_depth_rays.restype = i32
+    lib.nerf_grid_depth_rays.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridDepthArgs)]
+    lib.nerf_grid_depth_image.restype = i32
+    lib.nerf_grid_depth_image.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridRenderOptions), C.POINTER(GridDepthArgs)]
     _lib = lib
     return lib
 

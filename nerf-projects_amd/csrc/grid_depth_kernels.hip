@@ -1,0 +1,135 @@
+// Sparse voxel grid: depth maps and ray lengths (svox2's volume_render_depth and return_raylen).
+// Semantics: include/nerf_mi355x.h, "Sparse voxel grid: depth and ray lengths". Design and measurements: DESIGN.md section 7g.
+//
+// Mapping: one lane per ray. A depth march reads densities only - per sample one skip byte, 8 links and at most 8 floats, no
+// SH rows - so there is nothing for the render kernel's lanes-per-coefficient to share out: a lane walks its ray alone with the
+// device functions of grid_device.h (the same set-up, the same additions of t, the same skip rule, so the sample lattice is
+// the render's, bit for bit). No LDS, no scratch, no atomics, no shuffles: every result depends on its own ray only.
+// The image form makes its rays in the launch. A wavefront takes an 8 x 8 tile of pixels (lane = 8 * row + column in the
+// tile) rather than 64 pixels of a row: the rays of a tile stay within a few cells of one another for the whole march, so the
+// wavefront's 64 link and density loads fall on fewer cache lines, and its rays end at more nearly the same sample (less of
+// the wavefront idles behind its longest ray). The stores are 8 runs of 32 bytes. -DNERF_ABLATE_DEPTH_ROWS builds the
+// row mapping for the A/B of DESIGN.md.
+#include "grid_device.h"
+
+namespace nerf {
+namespace {
+
+constexpr int kTile = 8;      // pixels per side of a wavefront's tile: kTile * kTile = 64 lanes
+
+// the pixel of this thread in row-major order, or -1 outside the image
+__device__ __forceinline__ int64_t depth_pixel(const GridCam& cam) {
+    const int64_t tid = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
+#ifdef NERF_ABLATE_DEPTH_ROWS
+    return tid < (int64_t)cam.width * cam.height ? tid : -1;
+#else
+    const int64_t tile = tid / (kTile * kTile);
+    const int lane = (int)(tid % (kTile * kTile));
+    const int tiles_x = (cam.width + kTile - 1) / kTile;
+    const int64_t px = (tile % tiles_x) * kTile + lane % kTile;
+    const int64_t py = (tile / tiles_x) * kTile + lane / kTile;
+    return px < cam.width && py < cam.height ? py * cam.width + px : -1;
+#endif
+}
+
+int64_t depth_image_threads(const GridCam& cam) {
+#ifdef NERF_ABLATE_DEPTH_ROWS
+    return (int64_t)cam.width * cam.height;
+#else
+    return (int64_t)((cam.width + kTile - 1) / kTile) * ((cam.height + kTile - 1) / kTile) * (kTile * kTile);
+#endif
+}
+
+template <int MODE, bool IMAGE, bool SKIP>
+__global__ __launch_bounds__(kGridThreads) void grid_depth_kernel(GridDev g, GridRenderOpt opt, GridDepth r) {
+    int64_t ray;
+    GridRay rs;
+    if (IMAGE) {
+        ray = depth_pixel(r.cam);
+        if (ray < 0) return;
+        camera_ray(r.cam, ray, rs.o, rs.d);
+    } else {
+        ray = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
+        if (ray >= r.n_rays) return;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            rs.o[i] = r.origins[ray * 3 + i];
+            rs.d[i] = r.dirs[ray * 3 + i];
+        }
+    }
+    setup_ray<SKIP>(g, opt, rs);
+    if (MODE == NERF_GRID_DEPTH_RAYLEN) {
+        r.depth[ray] = rs.ok ? sub(rs.tmax, rs.tmin) : __builtin_nanf("");
+        return;
+    }
+
+    float depth = 0.0f, log_t = 0.0f;
+    if (rs.ok && rs.tmin <= rs.tmax) {
+        const float world_step = mul(opt.step_size, rs.delta_scale);
+        const float neg_step = -opt.step_size;
+        float t = rs.tmin;
+        while (t <= rs.tmax) {
+            // the render's stall rule: every pass advances t, a ray whose t no longer changes is left
+            const float t_next = add(t, opt.step_size);
+            if (!(t_next > t)) break;
+            float wa[3], wb[3];
+            const int base = march_cell(g, rs, t, wa, wb);
+            if (SKIP) {
+                const int sv = rs.skip_ok ? g.skip[base] : 0;
+                if (sv > 0) {
+                    t = skip_jump(t, t_next, sv, opt.step_size);
+                    continue;
+                }
+            }
+            int lk[8];
+            load_links(g, base, lk);
+            const float sigma = sample_sigma(g, lk, wa, wb);
+            if (MODE == NERF_GRID_DEPTH_THRESHOLD) {
+                if (sigma > r.sigma_thresh) {
+                    depth = mul(t / opt.step_size, world_step);
+                    break;
+                }
+            } else if (sigma > opt.sigma_thresh) {
+                const float a = mul(mul(neg_step, sigma), rs.delta_scale);
+                const float weight = mul(expf(log_t), sub(1.0f, expf(a)));
+                depth = add(depth, mul(mul(weight, t / opt.step_size), world_step));
+                log_t = add(log_t, a);
+                if (expf(log_t) < opt.stop_thresh) {
+                    log_t = -1e3f;
+                    break;
+                }
+            }
+            t = t_next;
+        }
+    }
+    r.depth[ray] = depth;
+    if (MODE == NERF_GRID_DEPTH_EXPECTED && r.log_transmit) r.log_transmit[ray] = log_t;
+}
+
+template <int MODE, bool SKIP>
+hipError_t launch_depth_mode(const GridDev& g, const GridRenderOpt& o, const GridDepth& r, hipStream_t s) {
+    if (r.origins == nullptr)
+        grid_depth_kernel<MODE, true, SKIP><<<blocks_for(depth_image_threads(r.cam)), kGridThreads, 0, s>>>(g, o, r);
+    else
+        grid_depth_kernel<MODE, false, SKIP><<<blocks_for(r.n_rays), kGridThreads, 0, s>>>(g, o, r);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_grid_depth(const GridDev& g, const GridRenderOpt& o, const GridDepth& r, hipStream_t s) {
+    if (r.n_rays <= 0) return hipSuccess;
+    const bool skip = g.skip != nullptr;
+    switch (r.mode) {
+        case NERF_GRID_DEPTH_EXPECTED:
+            return skip ? launch_depth_mode<NERF_GRID_DEPTH_EXPECTED, true>(g, o, r, s)
+                        : launch_depth_mode<NERF_GRID_DEPTH_EXPECTED, false>(g, o, r, s);
+        case NERF_GRID_DEPTH_THRESHOLD:
+            return skip ? launch_depth_mode<NERF_GRID_DEPTH_THRESHOLD, true>(g, o, r, s)
+                        : launch_depth_mode<NERF_GRID_DEPTH_THRESHOLD, false>(g, o, r, s);
+        case NERF_GRID_DEPTH_RAYLEN: return launch_depth_mode<NERF_GRID_DEPTH_RAYLEN, false>(g, o, r, s);      // nothing is marched
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace nerf

@@ -3,6 +3,7 @@
 //   grid_train_api.cpp      fused backward, TV gradient, optimiser step
 //   grid_resample_api.cpp   lattice density, weight render, threshold, dilate, compact, gather
 //   grid_components_api.cpp occupancy, labelling, volumes, keep mask, row copy
+//   grid_depth_api.cpp      expected depth, threshold depth, ray length
 //   grid_*_kernels.hip      the kernels of each, on grid_device.h (sampling, rays) and compact_device.h (compaction)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -159,6 +160,20 @@ hipError_t launch_grid_label_volumes(const int32_t* labels, int64_t n, int64_t c
 hipError_t launch_grid_keep_mask(const int32_t* links, const int32_t* labels, int64_t n, const uint8_t* floater, int64_t count,
                                  uint8_t* mask, hipStream_t s);
 hipError_t launch_grid_copy_rows(const GridCopyRows& a, hipStream_t s);
+
+// ---- depth and ray lengths (grid_depth_kernels.hip) ----
+struct GridDepth {
+    const float* origins;              // nullptr: the rays of `cam`
+    const float* dirs;
+    GridCam cam;
+    int64_t n_rays;
+    int32_t mode;                      // NERF_GRID_DEPTH_*
+    float sigma_thresh;                // of the threshold mode
+    float* depth;                      // [n_rays]
+    float* log_transmit;               // [n_rays] or nullptr (expected mode)
+};
+
+hipError_t launch_grid_depth(const GridDev& g, const GridRenderOpt& o, const GridDepth& r, hipStream_t s);
 
 // ---- argument checks (grid_api.cpp): NERF_OK, or NERF_E_INVALID with last_error set. None needs a device or reads a handle. ----
 void set_error(const char* fmt, ...);

@@ -1,11 +1,12 @@
 """Sparse voxel grid (Plenoxels): render a scene from a lattice of densities and spherical-harmonic colours, no network.
 
 ``SparseGrid``, ``Rays``, ``Camera`` and ``RenderOptions`` carry the names, argument order and defaults of ``svox2`` for the
-forward (inference) side: ``volume_render``, ``volume_render_image``, ``sample``, ``accelerate``, ``save`` / ``load`` in the
-``.npz`` layout of Plenoxels checkpoints. ``SparseGrid.from_nerf`` bakes one of this package's ``NeRF`` models into a grid.
+forward (inference) side: ``volume_render``, ``volume_render_image``, ``volume_render_depth``, ``volume_render_depth_image``,
+``sample``, ``accelerate``, ``save`` / ``load`` in the ``.npz`` layout of Plenoxels checkpoints. ``SparseGrid.from_nerf`` bakes
+one of this package's ``NeRF`` models into a grid.
 The semantics of every call are stated in include/nerf_mi355x.h, "Sparse voxel grid"; everything runs in HIP kernels
-(csrc/grid_kernels.hip) and, as everywhere in this package, there is no CPU or PyTorch fallback. What svox2 has and this
-module does not (background layers, learned bases, the other backends) raises ``NotImplementedError``; so do the svox2-named
+(csrc/grid_kernels.hip, csrc/grid_depth_kernels.hip) and, as everywhere in this package, there is no CPU or PyTorch fallback.
+What svox2 has and this module does not (background layers, learned bases, the other backends) raises ``NotImplementedError``; so do the svox2-named
 training methods on ``SparseGrid`` - training a grid is ``grid_train.GridTrainer``, under names of its own.
 """
 import ctypes as C
@@ -16,7 +17,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (GridCamera, GridProjectArgs, GridRenderArgs, GridRenderOptions, GridSampleArgs, SparseGridDesc, check)
+from ._lib import (GridCamera, GridDepthArgs, GridProjectArgs, GridRenderArgs, GridRenderOptions, GridSampleArgs, SparseGridDesc,
+                   check)
 from .host import NeRF, get_context, get_embedder, run_network
 from .mesh import _axes, density_grid
 from .occupancy import OccupancyGrid
@@ -507,25 +509,82 @@ class SparseGrid:
             check(self.ctx.lib.nerf_grid_render_rays(h, C.byref(opt), C.byref(a)))
         return (rgb, logt) if return_log_transmit else rgb
 
+    def _depth(self, cam, rays, mode, sigma_thresh=0.0, return_log_transmit=False, randomize=False):
+        """One call of nerf_grid_depth_rays / nerf_grid_depth_image: ``depth [n]`` (and ``log_transmit [n]``)."""
+        opt = self.opt._to_c(randomize)
+        h = self._handle()
+        a = GridDepthArgs()
+        a.mode, a.sigma_thresh = mode, sigma_thresh
+        if cam is not None:
+            c = cam._to_c()
+            n = cam.width * cam.height
+        else:
+            o = self._rays_arg(rays.origins, "rays.origins")
+            d = self._rays_arg(rays.dirs, "rays.dirs", o.shape[0])
+            n = o.shape[0]
+            a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), n
+        depth = torch.empty((n,), device=self.ctx.device, dtype=torch.float32)
+        logt = torch.empty((n,), device=self.ctx.device, dtype=torch.float32) if return_log_transmit else None
+        a.depth = depth.data_ptr()
+        a.log_transmit = 0 if logt is None else logt.data_ptr()
+        a.use_skip = 1
+        a.stream = self.ctx.stream().value
+        if cam is not None:
+            check(self.ctx.lib.nerf_grid_depth_image(h, C.byref(c), C.byref(opt), C.byref(a)))
+        else:
+            check(self.ctx.lib.nerf_grid_depth_rays(h, C.byref(opt), C.byref(a)))
+        return (depth, logt) if return_log_transmit else depth
+
+    @staticmethod
+    def _depth_mode(sigma_thresh, return_log_transmit=False):
+        if sigma_thresh is None:
+            return _lib.NERF_GRID_DEPTH_EXPECTED, 0.0
+        x = float(sigma_thresh)
+        if not x >= 0.0:
+            raise ValueError(f"sigma_thresh = {sigma_thresh!r} must be >= 0 and not NaN: the empty-space skip is only valid when "
+                             "an empty cell (sigma == 0) can never be a hit")
+        if return_log_transmit:
+            raise ValueError("return_log_transmit belongs to the expected termination (sigma_thresh=None)")
+        return _lib.NERF_GRID_DEPTH_THRESHOLD, x
+
     def volume_render(self, rays: Rays, use_kernel: bool = True, randomize: bool = False, return_raylen: bool = False,
                       return_log_transmit: bool = False):
         """``[N, 3]`` colours of ``rays`` (``dirs`` need not be unit) under ``self.opt``; with ``return_log_transmit`` also the
-        log of the transmittance left at the end of every ray (exactly -1e3 where the ray stopped at ``stop_thresh``)."""
+        log of the transmittance left at the end of every ray (exactly -1e3 where the ray stopped at ``stop_thresh``).
+        With ``return_raylen`` nothing is rendered: ``[N]``, the length ``tmax - tmin`` of every ray inside the box in grid
+        units (``near_clip`` applied; negative for a miss, NaN for a ray that is not finite), as svox2's PyTorch renderer."""
         if not use_kernel:
             raise NotImplementedError("use_kernel=False (the PyTorch renderer) does not exist here: HIP kernels only")
         if return_raylen:
-            raise NotImplementedError("return_raylen is not built")
+            if return_log_transmit:
+                raise ValueError("return_raylen marches nothing: there is no log_transmit to return")
+            return self._depth(None, rays, _lib.NERF_GRID_DEPTH_RAYLEN, randomize=randomize)
         return self._render(None, rays, randomize, return_log_transmit, None)
 
     def volume_render_image(self, camera: Camera, use_kernel: bool = True, randomize: bool = False, batch_size: int = 5000,
                             return_raylen: bool = False):
         """``[H, W, 3]``: the rays of ``camera`` are made inside the render launch, a frame is one C call (``batch_size`` is
-        accepted for the call surface)."""
+        accepted for the call surface). With ``return_raylen``: ``[H, W, 1]``, the ray lengths of :meth:`volume_render`."""
         if not use_kernel:
             raise NotImplementedError("use_kernel=False (the PyTorch renderer) does not exist here: HIP kernels only")
         if return_raylen:
-            raise NotImplementedError("return_raylen is not built")
+            return self._depth(camera, None, _lib.NERF_GRID_DEPTH_RAYLEN, randomize=randomize).view(camera.height, camera.width, 1)
         return self._render(camera, None, randomize, False, None).view(camera.height, camera.width, 3)
+
+    def volume_render_depth(self, rays: Rays, sigma_thresh: Optional[float] = None, return_log_transmit: bool = False):
+        """``[N]`` depths of ``rays`` in world units along the ray (not z-depth), on the sample lattice of :meth:`volume_render`.
+        ``sigma_thresh=None``: the expected termination ``sum_i weight_i t_i`` under ``self.opt`` - not divided by the
+        accumulated opacity; with ``return_log_transmit`` also ``log_transmit [N]`` (the render's, bit for bit), so that
+        ``depth / (1 - exp(log_transmit))`` normalises it. ``sigma_thresh=x`` (``x >= 0``): the distance of the first
+        sample whose density strictly exceeds ``x``. 0 where nothing is hit."""
+        mode, x = self._depth_mode(sigma_thresh, return_log_transmit)
+        return self._depth(None, rays, mode, x, return_log_transmit)
+
+    def volume_render_depth_image(self, camera: Camera, sigma_thresh: Optional[float] = None, batch_size: int = 5000):
+        """``[H, W]``: :meth:`volume_render_depth` of the rays of ``camera``, made inside the launch; a frame is one C call
+        (``batch_size`` is accepted for the call surface)."""
+        mode, x = self._depth_mode(sigma_thresh)
+        return self._depth(camera, None, mode, x).view(camera.height, camera.width)
 
     def count_samples(self, camera=None, rays=None):
         """``(visited, shaded)`` samples of a render, counted in an instrumented launch of its own (atomics; waits)."""
@@ -615,8 +674,6 @@ class SparseGrid:
         return f
 
     volume_render_fused = _not_built("volume_render_fused", "grid training (fused backward)")
-    volume_render_depth = _not_built("volume_render_depth", "depth rendering")
-    volume_render_depth_image = _not_built("volume_render_depth_image", "depth rendering")
     resample = _not_built("resample", "resampling / upsampling")
     sparsify_background = _not_built("sparsify_background", "background MSI layers")
     tv = _not_built("tv", "grid training (total-variation loss)")
