@@ -833,6 +833,76 @@ int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_opti
 int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* args);
 int nerf_grid_optim_step(nerf_ctx* ctx, const nerf_grid_optim_args* args);
 
+/* Sparse voxel grid: gradients for autograd -------------------------------------------------------
+ * The two halves of nerf_grid_fused_backward as calls of their own, with the cotangent d loss / d rgb supplied by the caller
+ * between them, and the transpose of nerf_grid_sample: what a torch.autograd.Function needs to differentiate a render or a
+ * sample with respect to density_data and sh_data under any loss. All three are stream-ordered, synchronise nothing and
+ * return a status with nerf_last_error(). Gradients ACCUMULATE, as in the training section: the caller zeroes them.
+ *
+ * nerf_grid_render_rays_taped is nerf_grid_render_rays (rgb_out and log_transmit bit-identical to it, with and without skip
+ * data) and also writes the tape, tape[ray, c] in fp64: the colour of channel c once more as the fp64 sum of the exact
+ * products weight * max(0, raw_c) of all shaded samples plus exp(log_T) * background_brightness - the starting value of
+ * `remaining_c` in the training section. 24 bytes per ray; nothing else is kept between forward and backward.
+ *
+ * nerf_grid_render_backward marches every ray once more over the same sample lattice under the same options (the same fp32
+ * additions of t, sigma_thresh and stop rules, skip data) and adds the gradients of sum_ray,c grad_rgb[ray, c] * rgb[ray, c]
+ * to grad_density and grad_sh: the statement of nerf_grid_fused_backward operation for operation - dot, the fp64 remaining
+ * (started from tape[ray, c]), accum, d_sigma, d_coef, the corner weights (w_x * w_y) * w_z, zero terms not added, the
+ * mask at every kept corner of every shaded sample - with g_c = grad_rgb[ray, c] instead of the MSE's. origins, dirs, the
+ * options, use_skip and the grid's tables must be those of the taped render. A ray that misses the box or whose set-up is
+ * not finite contributes nothing. grad_density, grad_sh and mask may each be NULL: that table's adds (the mask's stores) are
+ * not issued. The adds are float atomics (one hardware add each, no compare-and-swap): two calls agree to rounding of the
+ * sums, not bit for bit.
+ *
+ * nerf_grid_sample_backward: for every point p (cell, weights and world-to-grid transform exactly those of
+ * nerf_grid_sample) and every column j (0 = density, 1.. = sh; with want_colors = 0 the density column only), at each of
+ * the 8 corners whose link is kept:
+ *   table[row, j] += ((w_x * grad_out[p, j]) * w_y) * w_z        (fp32, each product rounded, in this order: the
+ *                                                                 reference's; a product that is zero is not added)
+ * A NULL grad_density or grad_sh skips that table. There is no gradient with respect to the points. */
+typedef struct nerf_grid_render_taped_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]                                                                */
+    const float* dirs;          /* [dev] [n_rays, 3], need not be unit                                              */
+    int64_t n_rays;             /* 0: nothing is done                                                               */
+    float* rgb_out;             /* [dev] [n_rays, 3]                                                                */
+    float* log_transmit;        /* [dev] [n_rays] or NULL                                                           */
+    double* tape;               /* [dev] [n_rays, 3]                                                                */
+    int32_t use_skip;           /* 1: use the skip data if nerf_grid_accelerate made it                             */
+    void* stream;
+} nerf_grid_render_taped_args;
+
+typedef struct nerf_grid_render_backward_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]       (those of the taped render)                              */
+    const float* dirs;          /* [dev] [n_rays, 3]                                                                */
+    int64_t n_rays;             /* 0: nothing is done                                                               */
+    const float* grad_rgb;      /* [dev] [n_rays, 3] d loss / d rgb_out, contiguous                                 */
+    const double* tape;         /* [dev] [n_rays, 3] as nerf_grid_render_rays_taped wrote it                        */
+    float* grad_density;        /* [dev] [capacity, 1], added to; or NULL                                           */
+    float* grad_sh;             /* [dev] [capacity, 3 * basis_dim], added to; or NULL                               */
+    uint8_t* mask;              /* [dev] [capacity] or NULL                                                         */
+    int32_t use_skip;
+    void* stream;
+} nerf_grid_render_backward_args;
+
+typedef struct nerf_grid_sample_backward_args {
+    size_t struct_size;
+    const float* points;        /* [dev] [n, 3] world coordinates, or grid coordinates with grid_coords              */
+    int64_t n;                  /* 0: nothing is done                                                               */
+    int32_t grid_coords;
+    int32_t want_colors;
+    const float* grad_out_density; /* [dev] [n, 1]                                                                  */
+    const float* grad_out_sh;   /* [dev] [n, 3 * basis_dim]; may be NULL without want_colors or without grad_sh      */
+    float* grad_density;        /* [dev] [capacity, 1], added to; or NULL                                           */
+    float* grad_sh;             /* [dev] [capacity, 3 * basis_dim], added to; or NULL                               */
+    void* stream;
+} nerf_grid_sample_backward_args;
+
+int nerf_grid_render_rays_taped(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_render_taped_args* args);
+int nerf_grid_render_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_render_backward_args* args);
+int nerf_grid_sample_backward(nerf_sparse_grid* grid, const nerf_grid_sample_backward_args* args);
+
 /* Sparse voxel grid: resampling -------------------------------------------------------------------
  * The stages of svox2's SparseGrid.resample (coarse-to-fine training: sample the grid on another lattice, drop the nodes that
  * matter to no camera or hold no density, rebuild links). Every stage is stream-ordered and synchronises nothing; the caller

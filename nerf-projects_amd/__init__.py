@@ -20,6 +20,8 @@ from . import grid  # noqa: F401
 from .grid import Camera, Rays, RenderOptions, SparseGrid  # noqa: F401
 from . import grid_train  # noqa: F401
 from .grid_train import GridTrainer  # noqa: F401
+from . import grid_autograd  # noqa: F401
+from .grid_autograd import GridModule  # noqa: F401
 from . import grid_resample  # noqa: F401
 from .grid_resample import dilate_mask, resample_grid, weight_render  # noqa: F401
 from . import grid_components  # noqa: F401

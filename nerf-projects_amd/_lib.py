@@ -33,6 +33,7 @@ EXPORTS = (
     "nerf_grid_components_occupancy", "nerf_grid_components_workspace", "nerf_grid_components_label",
     "nerf_grid_components_finish", "nerf_grid_components_volumes", "nerf_grid_components_keep", "nerf_grid_copy_rows",
     "nerf_grid_depth_rays", "nerf_grid_depth_image",
+    "nerf_grid_render_rays_taped", "nerf_grid_render_backward", "nerf_grid_sample_backward",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -184,6 +185,23 @@ class GridOptimArgs(_Sized):
     _fields_ = [("struct_size", C.c_size_t), ("data", _FP), ("rms", _FP), ("grad", _FP), ("mask", _FP), ("rows", C.c_int64),
                 ("cols", C.c_int32), ("kind", C.c_int32), ("beta", C.c_float), ("lr", C.c_float), ("eps", C.c_float),
                 ("minval", C.c_float), ("stream", C.c_void_p)]
+
+
+class GridRenderTapedArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("rgb_out", _FP),
+                ("log_transmit", _FP), ("tape", _FP), ("use_skip", C.c_int32), ("stream", C.c_void_p)]
+
+
+class GridRenderBackwardArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("grad_rgb", _FP),
+                ("tape", _FP), ("grad_density", _FP), ("grad_sh", _FP), ("mask", _FP), ("use_skip", C.c_int32),
+                ("stream", C.c_void_p)]
+
+
+class GridSampleBackwardArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("points", _FP), ("n", C.c_int64), ("grid_coords", C.c_int32),
+                ("want_colors", C.c_int32), ("grad_out_density", _FP), ("grad_out_sh", _FP), ("grad_density", _FP),
+                ("grad_sh", _FP), ("stream", C.c_void_p)]
 
 
 class GridLatticeArgs(_Sized):
@@ -407,6 +425,12 @@ def load():
     lib.nerf_grid_depth_rays.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridDepthArgs)]
     lib.nerf_grid_depth_image.restype = i32
     lib.nerf_grid_depth_image.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridRenderOptions), C.POINTER(GridDepthArgs)]
+    lib.nerf_grid_render_rays_taped.restype = i32
+    lib.nerf_grid_render_rays_taped.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridRenderTapedArgs)]
+    lib.nerf_grid_render_backward.restype = i32
+    lib.nerf_grid_render_backward.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridRenderBackwardArgs)]
+    lib.nerf_grid_sample_backward.restype = i32
+    lib.nerf_grid_sample_backward.argtypes = [vp, C.POINTER(GridSampleBackwardArgs)]
     _lib = lib
     return lib
 

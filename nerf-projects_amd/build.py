@@ -19,7 +19,8 @@ SOURCES = ["api.cpp", "train_api.cpp", "pack_weights.cpp", "mlp_kernel.hip", "ml
            "grid_api.cpp", "grid_kernels.hip", "grid_train_api.cpp", "grid_train_kernels.hip",
            "grid_resample_api.cpp", "grid_resample_kernels.hip",
            "grid_components_api.cpp", "grid_components_kernels.hip",
-           "grid_depth_api.cpp", "grid_depth_kernels.hip"]
+           "grid_depth_api.cpp", "grid_depth_kernels.hip",
+           "grid_autograd_api.cpp", "grid_autograd_kernels.hip"]
 HEADERS = [os.path.join(CSRC, "nerf_internal.h"), os.path.join(CSRC, "ctx_internal.h"),
            os.path.join(CSRC, "mlp_inputs.h"), os.path.join(CSRC, "mlp_pair_common.h"), os.path.join(CSRC, "mlp_kernel_h2_body.inc"), os.path.join(CSRC, "ray_device.h"), os.path.join(CSRC, "grid_internal.h"), os.path.join(CSRC, "grid_device.h"), os.path.join(CSRC, "compact_device.h"),
            os.path.join(ROOT, "include", "nerf_mi355x.h")]

@@ -1,6 +1,7 @@
 // Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what the host and the device side of the grid share.
 //   grid_api.cpp            create / render / sample / accelerate, and the argument checks every grid_*_api.cpp uses (below)
 //   grid_train_api.cpp      fused backward, TV gradient, optimiser step
+//   grid_autograd_api.cpp   taped render, render backward with a caller's cotangent, sample backward
 //   grid_resample_api.cpp   lattice density, weight render, threshold, dilate, compact, gather
 //   grid_components_api.cpp occupancy, labelling, volumes, keep mask, row copy
 //   grid_depth_api.cpp      expected depth, threshold depth, ray length
@@ -92,6 +93,41 @@ struct GridOptim {
 hipError_t launch_grid_fused(const GridDev& g, const GridRenderOpt& o, const GridFused& r, hipStream_t s);
 hipError_t launch_grid_tv_grad(const GridDev& g, const GridTv& a, hipStream_t s);
 hipError_t launch_grid_optim_step(const GridOptim& a, int rmsprop, hipStream_t s);
+
+// ---- gradients for autograd (grid_autograd_kernels.hip) ----
+struct GridTaped {
+    const float* origins;
+    const float* dirs;
+    int64_t n_rays;
+    float* rgb;
+    float* log_transmit;               // or nullptr
+    double* tape;                      // [n_rays, 3]: the colour as the fp64 sum of its exact terms
+};
+
+struct GridRenderBwd {
+    const float* origins;
+    const float* dirs;
+    int64_t n_rays;
+    const float* grad_rgb;             // [n_rays, 3]
+    const double* tape;
+    float* grad_density;               // added to; each of the three may be nullptr: nothing is issued for it
+    float* grad_sh;
+    uint8_t* mask;
+};
+
+struct GridSampleBwd {
+    const float* points;
+    int64_t n;
+    int32_t grid_coords, want_colors;
+    const float* grad_out_density;     // [n, 1]
+    const float* grad_out_sh;          // [n, 3 B]
+    float* grad_density;               // added to, or nullptr
+    float* grad_sh;
+};
+
+hipError_t launch_grid_render_taped(const GridDev& g, const GridRenderOpt& o, const GridTaped& r, hipStream_t s);
+hipError_t launch_grid_render_bwd(const GridDev& g, const GridRenderOpt& o, const GridRenderBwd& r, hipStream_t s);
+hipError_t launch_grid_sample_bwd(const GridDev& g, const GridSampleBwd& a, hipStream_t s);
 
 // ---- resampling (grid_resample_kernels.hip) ----
 constexpr int64_t kGridMaxLattice = (int64_t)1 << 30;   // nodes of a resampling lattice: 1024^3

@@ -1,0 +1,193 @@
+"""``loss.backward()`` through a sparse voxel grid: ``GridModule(grid)`` is a ``torch.nn.Module`` whose parameters are the
+grid's own ``density_data`` and ``sh_data``, and whose ``volume_render``, ``volume_render_image`` and ``sample`` are
+differentiable with respect to them - any loss, any torch optimiser::
+
+    m = GridModule(grid)
+    adam = torch.optim.Adam(m.parameters(), lr=1e-2)
+    rgb = m.volume_render(rays); loss = anything(rgb); loss.backward(); adam.step()
+
+It is the counterpart of svox2's ``SparseGrid`` as an ``nn.Module`` (``volume_render`` / ``sample`` under autograd), beside
+``SparseGrid`` and not on it: a ``SparseGrid`` itself still refuses tensors that require gradients. Everything runs in the HIP
+kernels of csrc/grid_autograd_kernels.hip; the semantics are stated in include/nerf_mi355x.h, "Sparse voxel grid: gradients
+for autograd". The forward keeps 24 bytes per ray (the tape) for the backward; the backward marches every ray once.
+Not built: gradients with respect to rays, points or the camera, of depth or ``log_transmit``, double backward, sparse
+gradient tensors.
+"""
+import ctypes as C
+from dataclasses import replace
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from ._lib import GridRenderBackwardArgs, GridRenderTapedArgs, GridSampleBackwardArgs, check
+from .grid import Camera, Rays, SparseGrid
+
+__all__ = ["GridModule"]
+
+
+def _points_arg(t, name, device, n=None):
+    """``t`` as a contiguous fp32 ``[N, 3]`` tensor on ``device``, refused in ``SparseGrid``'s vocabulary."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} is on the CPU: GridModule has no CPU fallback")
+    if t.requires_grad:
+        raise NotImplementedError(f"{name} requires a gradient: gradients with respect to rays and points are not built")
+    if t.dim() != 2 or t.shape[1] != 3 or (n is not None and t.shape[0] != n):
+        raise ValueError(f"{name} must be [N, 3], got {tuple(t.shape)}")
+    return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _zeros_like_or_none(t, wanted):
+    return torch.zeros_like(t, memory_format=torch.contiguous_format) if wanted else None
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def _same_tables(module, density, sh):
+    """The kernels read the tables through the grid's handle: they must still be the tensors autograd saved."""
+    g = module.grid
+    if g.density_data.data_ptr() != density.data_ptr() or g.sh_data.data_ptr() != sh.data_ptr():
+        raise RuntimeError("the grid's tables were replaced between forward and backward: run the forward again after rebind()")
+    return g._handle()
+
+
+class _VolumeRender(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, density, sh, module, o, d):
+        g = module.grid
+        opt = replace(g.opt)
+        h = g._handle()
+        n = o.shape[0]
+        rgb = torch.empty((n, 3), device=o.device, dtype=torch.float32)
+        tape = torch.empty((n, 3), device=o.device, dtype=torch.float64)
+        a = GridRenderTapedArgs()
+        a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), n
+        a.rgb_out, a.log_transmit, a.tape = rgb.data_ptr(), 0, tape.data_ptr()
+        a.use_skip = 1
+        a.stream = g.ctx.stream().value
+        check(g.ctx.lib.nerf_grid_render_rays_taped(h, C.byref(opt._to_c()), C.byref(a)))
+        ctx.save_for_backward(density, sh, o, d, tape)      # the parameters too: torch refuses a backward after an in-place step
+        ctx.module, ctx.opt = module, opt
+        return rgb
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_rgb):
+        density, sh, o, d, tape = ctx.saved_tensors
+        g = ctx.module.grid
+        h = _same_tables(ctx.module, density, sh)
+        grad_rgb = grad_rgb.to(dtype=torch.float32).contiguous()      # (rgb.sum().backward() hands in a stride-0 expansion)
+        gd = _zeros_like_or_none(density, ctx.needs_input_grad[0])
+        gs = _zeros_like_or_none(sh, ctx.needs_input_grad[1])
+        a = GridRenderBackwardArgs()
+        a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]
+        a.grad_rgb, a.tape = grad_rgb.data_ptr(), tape.data_ptr()
+        a.grad_density, a.grad_sh, a.mask = _ptr(gd), _ptr(gs), 0
+        a.use_skip = 1
+        a.stream = g.ctx.stream().value
+        check(g.ctx.lib.nerf_grid_render_backward(h, C.byref(ctx.opt._to_c()), C.byref(a)))
+        return gd, gs, None, None, None
+
+
+class _Sample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, density, sh, module, p, grid_coords, want_colors):
+        out_density, out_sh = module.grid.sample(p, grid_coords=grid_coords, want_colors=want_colors)
+        ctx.save_for_backward(density, sh, p)
+        ctx.module, ctx.grid_coords, ctx.want_colors = module, grid_coords, want_colors
+        if not want_colors:
+            ctx.mark_non_differentiable(out_sh)
+        return out_density, out_sh
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_density_out, grad_sh_out):
+        density, sh, p = ctx.saved_tensors
+        g = ctx.module.grid
+        h = _same_tables(ctx.module, density, sh)
+        gd = _zeros_like_or_none(density, ctx.needs_input_grad[0])
+        gs = _zeros_like_or_none(sh, ctx.needs_input_grad[1] and ctx.want_colors)
+        go_d = grad_density_out.to(dtype=torch.float32).contiguous()
+        go_s = grad_sh_out.to(dtype=torch.float32).contiguous() if ctx.want_colors else None
+        a = GridSampleBackwardArgs()
+        a.points, a.n = p.data_ptr(), p.shape[0]
+        a.grid_coords, a.want_colors = int(ctx.grid_coords), int(ctx.want_colors)
+        a.grad_out_density, a.grad_out_sh = go_d.data_ptr(), _ptr(go_s)
+        a.grad_density, a.grad_sh = _ptr(gd), _ptr(gs)
+        a.stream = g.ctx.stream().value
+        check(g.ctx.lib.nerf_grid_sample_backward(h, C.byref(a)))
+        return gd, gs, None, None, None, None      # (without want_colors sh_data takes no part: no gradient)
+
+
+class GridModule(torch.nn.Module):
+    """``density_data`` and ``sh_data`` are ``nn.Parameter`` views of the grid's own tensors: the same storage and the same
+    version counter, so an optimiser that steps them in place is seen by ``grid.volume_render_image`` at once - the grid's
+    handle stays, and so does its skip data, which depends on ``links`` only. The grid's attributes stay plain tensors.
+
+    If the grid's tables are replaced (``GridTrainer.resample`` / ``remove_floaters``, or assignment) the next call raises a
+    ``RuntimeError`` that names :meth:`rebind`, which makes new parameters; optimiser state built on the old ones is the
+    caller's business. ``self.grid.opt`` are the render options, read at every forward.
+
+    Under ``torch.no_grad()``, or with both parameters frozen, the methods call the plain kernels and keep no tape."""
+
+    def __init__(self, grid: SparseGrid):
+        super().__init__()
+        if not isinstance(grid, SparseGrid):
+            raise TypeError("GridModule needs a SparseGrid")
+        self.grid = grid
+        self.rebind()
+
+    def rebind(self):
+        """Make ``density_data`` / ``sh_data`` anew from the grid's current tensors (``requires_grad`` as before, or True)."""
+        g = self.grid
+        g._handle()      # validates the tensors
+        old = [getattr(self, name, None) for name in ("density_data", "sh_data")]
+        self._bound = (g.density_data, g.sh_data)
+        self.density_data = torch.nn.Parameter(g.density_data, requires_grad=old[0] is None or old[0].requires_grad)
+        self.sh_data = torch.nn.Parameter(g.sh_data, requires_grad=old[1] is None or old[1].requires_grad)
+        return self
+
+    def _check_bound(self):
+        g = self.grid
+        pairs = ((g.density_data, self._bound[0], self.density_data), (g.sh_data, self._bound[1], self.sh_data))
+        for now, bound, param in pairs:
+            if now is not bound or param.data_ptr() != now.data_ptr() or param.shape != now.shape:
+                raise RuntimeError("the grid's density_data / sh_data are no longer the tensors this GridModule's parameters "
+                                   "were made from: call rebind() (and make the optimiser anew)")
+
+    def _differentiate(self):
+        return torch.is_grad_enabled() and (self.density_data.requires_grad or self.sh_data.requires_grad)
+
+    def volume_render(self, rays: Rays, use_kernel: bool = True):
+        """``[N, 3]``, bit-identical to ``grid.volume_render(rays)``, differentiable with respect to the parameters."""
+        if not use_kernel:
+            raise NotImplementedError("use_kernel=False (the PyTorch renderer) does not exist here: HIP kernels only")
+        self._check_bound()
+        dev = self.grid.ctx.device
+        o = _points_arg(rays.origins, "rays.origins", dev)
+        d = _points_arg(rays.dirs, "rays.dirs", dev, o.shape[0])
+        if not self._differentiate():
+            return self.grid.volume_render(Rays(o, d))
+        return _VolumeRender.apply(self.density_data, self.sh_data, self, o, d)
+
+    def volume_render_image(self, camera: Camera, use_kernel: bool = True):
+        """``[H, W, 3]``: :meth:`volume_render` of ``camera.gen_rays()``, bit-identical to ``grid.volume_render_image``."""
+        if not use_kernel:
+            raise NotImplementedError("use_kernel=False (the PyTorch renderer) does not exist here: HIP kernels only")
+        return self.volume_render(camera.gen_rays(self.grid.ctx.device)).view(camera.height, camera.width, 3)
+
+    def sample(self, points: torch.Tensor, use_kernel: bool = True, grid_coords: bool = False, want_colors: bool = True):
+        """``(density [N, 1], sh [N, 3 * basis_dim])`` as ``grid.sample``, differentiable with respect to the parameters."""
+        if not use_kernel:
+            raise NotImplementedError("use_kernel=False (the PyTorch sampler) does not exist here: HIP kernels only")
+        self._check_bound()
+        p = _points_arg(points, "points", self.grid.ctx.device)
+        if not self._differentiate():
+            return self.grid.sample(p, grid_coords=grid_coords, want_colors=want_colors)
+        return _Sample.apply(self.density_data, self.sh_data, self, p, bool(grid_coords), bool(want_colors))
+
+    def forward(self, rays: Rays):
+        return self.volume_render(rays)

@@ -1,0 +1,254 @@
+"""Gradients through the sparse voxel grid for autograd, the parts that need no GPU: the numpy restatement
+(tests/grid_autograd_oracle.py) against the reference's recorded gradients (tests/golden/grid_autograd.npz: the render's
+vector-Jacobian product, a Charbonnier loss, the sampler's transpose) and against the fused MSE restatement, the C ABI of
+the three entry points, what the module refuses, and the generated code of csrc/grid_autograd_kernels.hip."""
+import ctypes as C
+import functools
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import grid_autograd_oracle as GA  # noqa: E402
+import grid_oracle as GO  # noqa: E402
+import grid_train_oracle as GT  # noqa: E402
+from grid_testlib import assert_structs_match_c_header, compile_kernels_to_asm  # noqa: E402
+
+RENDER = os.path.join(ROOT, "tests", "golden", "grid_render.npz")
+TRAIN = os.path.join(ROOT, "tests", "golden", "grid_train.npz")
+AUTOGRAD = os.path.join(ROOT, "tests", "golden", "grid_autograd.npz")
+GRIDS = ("a", "b", "c", "d")
+BACKGROUNDS = (("bg1", 1.0), ("bg0", 0.0))
+
+
+def fixture_grid(z, name):
+    return {"links": z[f"{name}_links"], "density_data": z[f"{name}_density"], "sh_data": z[f"{name}_sh"],
+            "radius": z[f"{name}_radius"], "center": z[f"{name}_center"]}
+
+
+def golden_key(name, tag, kind, key):
+    """The SH gradient of the vector-Jacobian product does not depend on the background and is stored once."""
+    if kind == "sample":
+        return f"{name}_sample_grad_{key}"
+    if kind == "vjp" and key == "sh":
+        return f"{name}_vjp_grad_sh"
+    return f"{name}_{tag}_{kind}_grad_{key}"
+
+
+def grad_bar(a, name, tag, kind, key):
+    """(fp64 gradient, bar): 3x the reference's own fp32 - fp64 distance, and no tighter than 1e-5 of the largest entry"""
+    k = golden_key(name, tag, kind, key)
+    want = a[k + "64"].astype(np.float64)
+    return want, max(3.0 * float(a[k + "_d_ref"]), 1e-5 * float(np.abs(want).max()))
+
+
+def charbonnier_cotangent(rgb, gt, eps):
+    """d mean(sqrt((rgb - gt)^2 + eps)) / d rgb in fp32"""
+    diff = (rgb - gt).astype(np.float32)
+    return (diff / np.sqrt((diff * diff).astype(np.float32) + np.float32(eps)).astype(np.float32) / np.float32(diff.size)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_render_case(name, tag, kind):
+    """(rgb, grad_density, grad_sh, mask) of the restatement for golden (i) ``vjp`` or (ii) ``charb`` at the PyTorch
+    statement's setting (sigma_thresh = 0, stop_thresh = 0); computed once, read only"""
+    z, t, a = np.load(RENDER), np.load(TRAIN), np.load(AUTOGRAD)
+    bg = dict(BACKGROUNDS)[tag]
+    if kind == "vjp":
+        cot = a[f"{name}_vjp_w"]
+    else:
+        gt, eps = t[f"{name}_rgb_gt"], float(a["charb_eps"])
+        cot = lambda rgb: charbonnier_cotangent(rgb, gt, eps)      # noqa: E731
+    out = GA.render_vjp(fixture_grid(z, name), z[f"{name}_origins"], z[f"{name}_dirs"], cot, background_brightness=bg,
+                        sigma_thresh=0.0, stop_thresh=0.0)
+    for arr in out:
+        arr.setflags(write=False)
+    return out
+
+
+def test_fixture_holds_arrays_only_and_is_small():
+    assert os.path.getsize(AUTOGRAD) < 1 << 20
+    a, z = np.load(AUTOGRAD), np.load(RENDER)      # (allow_pickle is off: arrays only)
+    want = {"charb_eps"}
+    for name in GRIDS:
+        want |= {f"{name}_vjp_w", f"{name}_sample_cd", f"{name}_sample_cs"}
+        kinds = [(name, tag, kind) for tag, _ in BACKGROUNDS for kind in ("vjp", "charb")] + [(name, "", "sample")]
+        for n, tag, kind in kinds:
+            for key in ("density", "sh"):
+                k = golden_key(n, tag, kind, key)
+                want |= {k + "64", k + "_d_ref"}
+                shape = z[f"{name}_density"].shape if key == "density" else z[f"{name}_sh"].shape
+                assert a[k + "64"].shape == shape and a[k + "64"].dtype == np.float32 and a[k + "_d_ref"].dtype == np.float64
+        assert a[f"{name}_vjp_w"].shape == (1024, 3)
+        assert a[f"{name}_sample_cd"].shape == (512, 1) and a[f"{name}_sample_cs"].shape == (512, z[f"{name}_sh"].shape[1])
+    assert set(a.files) == want
+    assert float(a["charb_eps"]) == 1e-3
+
+
+@pytest.mark.parametrize("kind", ("vjp", "charb"))
+@pytest.mark.parametrize("name", GRIDS)
+def test_oracle_render_backward_matches_the_reference_autograd(name, kind):
+    z, a = np.load(RENDER), np.load(AUTOGRAD)
+    g = fixture_grid(z, name)
+    for tag, bg in BACKGROUNDS:
+        rgb, gd, gs, mask = oracle_render_case(name, tag, kind)
+        fwd, _ = GO.render(g, z[f"{name}_origins"], z[f"{name}_dirs"], sigma_thresh=0.0, stop_thresh=0.0, background_brightness=bg)
+        assert np.array_equal(rgb, fwd)      # the taped render is the render
+        for key, got in (("density", gd), ("sh", gs)):
+            want, tol = grad_bar(a, name, tag, kind, key)
+            err = np.abs(got.astype(np.float64) - want)
+            print(f"grid {name} {tag} {kind} d/d{key}: restatement vs fp64 autograd max {err.max():.3e} (bar {tol:.3e}, max |g| {np.abs(want).max():.3e})")
+            assert err.max() <= tol, (name, tag, kind, key, int(err.argmax()), err.max(), tol)      # every entry
+        assert mask.any() and not gd[mask == 0].any() and not gs[mask == 0].any()
+
+
+@pytest.mark.parametrize("name", GRIDS)
+def test_oracle_sample_backward_matches_the_reference_autograd(name):
+    z, a = np.load(RENDER), np.load(AUTOGRAD)
+    g = fixture_grid(z, name)
+    gd, gs = GA.sample_backward(g, z[f"{name}_pts_grid"], a[f"{name}_sample_cd"], a[f"{name}_sample_cs"], grid_coords=True)
+    for key, got in (("density", gd), ("sh", gs)):
+        want, tol = grad_bar(a, name, "", "sample", key)
+        err = np.abs(got.astype(np.float64) - want)
+        print(f"grid {name} sample d/d{key}: restatement vs fp64 autograd max {err.max():.3e} (bar {tol:.3e}), rows != 0 {int((want != 0).any(-1).sum())}")
+        assert err.max() <= tol, (name, key, int(err.argmax()), err.max(), tol)
+    gd1, gs1 = GA.sample_backward(g, z[f"{name}_pts_grid"], a[f"{name}_sample_cd"], None, grid_coords=True, want_colors=False)
+    assert np.array_equal(gd1, gd) and not gs1.any()
+    # the transpose: <sample(x), c> = <x, sample_backward(c)> with the tables as x
+    dens, sh = GO.sample(g, z[f"{name}_pts_grid"], grid_coords=True)
+    lhs = (dens.astype(np.float64) * a[f"{name}_sample_cd"]).sum() + (sh.astype(np.float64) * a[f"{name}_sample_cs"]).sum()
+    rhs = (g["density_data"].astype(np.float64) * gd).sum() + (g["sh_data"].astype(np.float64) * gs).sum()
+    assert abs(lhs - rhs) <= 1e-5 * max(1.0, abs(lhs))
+
+
+@pytest.mark.parametrize("name", ("b", "c", "d"))
+def test_oracle_with_the_mse_cotangent_is_the_fused_restatement(name):
+    """With g_c = (rgb_c - gt_c) * 2 / (3 n) the backward is the second march of the fused statement, operation for operation."""
+    z, t = np.load(RENDER), np.load(TRAIN)
+    g = fixture_grid(z, name)
+    o, d, gt = z[f"{name}_origins"], z[f"{name}_dirs"], t[f"{name}_rgb_gt"]
+    skip = GO.skip_distances(g["links"])
+    n = np.float32(o.shape[0])
+    cot = lambda rgb: ((rgb - gt).astype(np.float32) * (np.float32(2.0) / (np.float32(3.0) * n))).astype(np.float32)      # noqa: E731
+    for kw in ({}, {"skip": skip}, {"step_size": 0.3, "near_clip": 2.0, "sigma_thresh": 0.5, "stop_thresh": 1e-2}):
+        rgb, gd, gs, mask = GA.render_vjp(g, o, d, cot, background_brightness=0.5, **kw)
+        rgb_f, gd_f, gs_f, mask_f = GT.fused(g, o, d, gt, background_brightness=0.5, **kw)
+        assert np.array_equal(rgb, rgb_f) and np.array_equal(mask, mask_f)
+        assert np.array_equal(gd, gd_f) and np.array_equal(gs, gs_f)
+        assert mask.any()
+
+
+# ---- C ABI ------------------------------------------------------------------------------------------------------------
+NEW_STRUCTS = {"nerf_grid_render_taped_args": "GridRenderTapedArgs", "nerf_grid_render_backward_args": "GridRenderBackwardArgs",
+               "nerf_grid_sample_backward_args": "GridSampleBackwardArgs"}
+NEW_SYMBOLS = ("nerf_grid_render_rays_taped", "nerf_grid_render_backward", "nerf_grid_sample_backward")
+
+
+def test_autograd_structs_match_a_c_compile_of_the_header(tmp_path):
+    assert_structs_match_c_header(tmp_path, NEW_STRUCTS)
+
+
+def test_autograd_calls_refuse_bad_arguments_before_any_device_call():
+    """Every refusal here comes before a handle is dereferenced: the grid pointer is a fake."""
+    import nerf_projects_amd  # noqa: F401
+    from nerf_projects_amd import _lib
+    lib = _lib.load()
+    for s in NEW_SYMBOLS:
+        assert hasattr(lib, s) and s in _lib.EXPORTS
+    fake = C.c_void_p(0x1000)
+    err = lambda: lib.nerf_last_error().decode()      # noqa: E731
+
+    def options():
+        opt = _lib.GridRenderOptions()
+        opt.step_size, opt.background_brightness = 0.5, 1.0
+        return opt
+
+    for fn, cls in ((lib.nerf_grid_render_rays_taped, _lib.GridRenderTapedArgs),
+                    (lib.nerf_grid_render_backward, _lib.GridRenderBackwardArgs)):
+        opt, a = options(), cls()
+        assert fn(None, C.byref(opt), C.byref(a)) == -1 and "NULL grid" in err()
+        assert fn(fake, None, C.byref(a)) == -1 and "NULL" in err()
+        assert fn(fake, C.byref(opt), None) == -1 and "NULL" in err()
+        a.struct_size -= 8
+        assert fn(fake, C.byref(opt), C.byref(a)) == -1 and "struct_size" in err()
+        a = cls()
+        opt.struct_size += 4
+        assert fn(fake, C.byref(opt), C.byref(a)) == -1 and "struct_size" in err()
+        for field in ("last_sample_opaque", "randomize"):
+            opt = options()
+            setattr(opt, field, 1)
+            assert fn(fake, C.byref(opt), C.byref(a)) == -1 and field in err() and "not built" in err(), field
+        for step in (0.0, -0.5, float("nan")):
+            opt = options()
+            opt.step_size = step
+            assert fn(fake, C.byref(opt), C.byref(a)) == -1 and "step_size" in err(), step
+        opt = options()
+        a.n_rays = 4      # and no pointers
+        assert fn(fake, C.byref(opt), C.byref(a)) == -1 and "required" in err()
+        a.n_rays = -1
+        assert fn(fake, C.byref(opt), C.byref(a)) == -1 and "n_rays" in err()
+        a.n_rays = (1 << 26) + 1
+        assert fn(fake, C.byref(opt), C.byref(a)) == -1 and "n_rays" in err()
+        a.n_rays = 0
+        assert fn(fake, C.byref(opt), C.byref(a)) == 0      # zero rays: nothing is done
+    a = _lib.GridRenderBackwardArgs()
+    a.n_rays = 4
+    buf = (C.c_float * 12)()
+    a.origins = a.dirs = a.grad_rgb = C.addressof(buf)      # everything but the tape
+    assert lib.nerf_grid_render_backward(fake, C.byref(options()), C.byref(a)) == -1 and "tape" in err()
+
+    s = _lib.GridSampleBackwardArgs()
+    assert lib.nerf_grid_sample_backward(None, C.byref(s)) == -1 and "NULL grid" in err()
+    assert lib.nerf_grid_sample_backward(fake, None) == -1 and "NULL" in err()
+    s.struct_size = 0
+    assert lib.nerf_grid_sample_backward(fake, C.byref(s)) == -1 and "struct_size" in err()
+    s = _lib.GridSampleBackwardArgs()
+    s.n = 5      # and no pointers
+    assert lib.nerf_grid_sample_backward(fake, C.byref(s)) == -1 and "required" in err()
+    s.points = s.grad_out_density = s.grad_sh = C.addressof(buf)
+    s.want_colors = 1      # the SH table is wanted and its cotangent is missing
+    assert lib.nerf_grid_sample_backward(fake, C.byref(s)) == -1 and "grad_out_sh" in err()
+    s.n = -1
+    assert lib.nerf_grid_sample_backward(fake, C.byref(s)) == -1 and "n = -1" in err()
+    s.n = 0
+    assert lib.nerf_grid_sample_backward(fake, C.byref(s)) == 0
+
+
+def test_module_refuses_cpu_tensors_and_what_is_not_a_grid():
+    import nerf_projects_amd as N
+    from nerf_projects_amd import grid_autograd
+    assert N.GridModule is grid_autograd.GridModule and issubclass(N.GridModule, torch.nn.Module)
+    with pytest.raises(TypeError, match="SparseGrid"):
+        N.GridModule(object())
+    with pytest.raises(RuntimeError, match="CPU"):
+        grid_autograd._points_arg(torch.zeros(4, 3), "rays.origins", torch.device("cuda"))
+    with pytest.raises(TypeError):
+        grid_autograd._points_arg(np.zeros((4, 3)), "points", torch.device("cuda"))
+
+
+def test_grid_autograd_kernels_use_no_scratch_no_inline_assembly_and_no_compare_and_swap(tmp_path):
+    text, asm, build = compile_kernels_to_asm(tmp_path, "grid_autograd_kernels.hip")
+    assert "grid_autograd_kernels.hip" in build.SOURCES and "grid_autograd_api.cpp" in build.SOURCES
+    assert not re.search(r"\basm\b|__asm", text)
+    kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", asm, re.M)
+    # taped render and render backward: B in {9, 4, 1} x skip; one sample backward
+    assert sum("grid_taped_kernel" in k for k in kernels) == 6 and sum("grid_render_bwd_kernel" in k for k in kernels) == 6
+    assert sum("grid_sample_bwd_kernel" in k for k in kernels) == 1 and len(kernels) == 13, kernels
+    sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", asm)
+    assert len(sizes) == len(kernels) and all(int(s) == 0 for s in sizes), sizes
+    assert not re.search(r"\bscratch_(load|store)", asm)
+    assert "cmpswap" not in asm                                   # float adds are one hardware atomic each, no CAS loop
+    assert len(re.findall(r"\bglobal_atomic_add_f32\b", asm)) > 0
+    assert not re.search(r"global_atomic_add_f32[^\n]*\bsc0\b", asm)      # none returns the old value
+    lds = re.findall(r"\.group_segment_fixed_size:\s*(\d+)", asm)
+    assert all(int(s) == 0 for s in lds), lds
+    vgprs = dict(zip(kernels, (int(v) for v in re.findall(r"\.vgpr_count:\s*(\d+)", asm))))
+    print("vgprs per kernel:", vgprs)
+    # the backward allocates no more registers than the fused kernel, 80 at basis_dim 9: 6 waves per SIMD
+    assert max(v for k, v in vgprs.items() if "grid_render_bwd_kernel" in k) <= 80
+    assert max(vgprs.values()) <= 80
