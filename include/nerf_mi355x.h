@@ -58,7 +58,9 @@ typedef struct nerf_ctx nerf_ctx;
 /* Constructor arguments of the reference NeRF module (nerf/nerf.py:9). */
 typedef struct nerf_arch {
     int32_t D;                  /* trunk depth, netdepth                          */
-    int32_t W;                  /* trunk width, netwidth (this build: 256 only)   */
+    int32_t W;                  /* trunk width, netwidth: 2..256. Inference runs a narrower network zero-padded to 256
+                                   (the same function, at the 256-wide cost); a narrower network trains too, layer by
+                                   layer and not on the fused fp16-pair kernels */
     int32_t input_ch;           /* 3 + 6*multires (63), or 3 for i_embed == -1    */
     int32_t input_ch_views;     /* 3 + 6*multires_views (27), or 3                */
     int32_t output_ch;          /* 4, or 5 when N_importance > 0 (nerf.ipynb:885) */

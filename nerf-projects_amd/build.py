@@ -21,9 +21,8 @@ SOURCES = ["api.cpp", "train_api.cpp", "pack_weights.cpp", "mlp_kernel.hip", "ml
            "grid_components_api.cpp", "grid_components_kernels.hip",
            "grid_depth_api.cpp", "grid_depth_kernels.hip",
            "grid_autograd_api.cpp", "grid_autograd_kernels.hip"]
-HEADERS = [os.path.join(CSRC, "nerf_internal.h"), os.path.join(CSRC, "ctx_internal.h"),
-           os.path.join(CSRC, "mlp_inputs.h"), os.path.join(CSRC, "mlp_pair_common.h"), os.path.join(CSRC, "mlp_kernel_h2_body.inc"), os.path.join(CSRC, "ray_device.h"), os.path.join(CSRC, "grid_internal.h"), os.path.join(CSRC, "grid_device.h"), os.path.join(CSRC, "compact_device.h"),
-           os.path.join(ROOT, "include", "nerf_mi355x.h")]
+# every header of csrc/ (a new one is a dependency of up_to_date() without being listed) and the public one
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(ROOT, "include", "nerf_mi355x.h")]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17",
     "-ffp-contract=off",          # PyTorch's op boundaries are rounding boundaries; fmaf is explicit where wanted
@@ -65,7 +64,6 @@ def build(force=False, keep_temps=False, verbose=True):
         if only and src not in only.split(",") and os.path.exists(obj):
             return obj
         cmd = [hipcc()] + FLAGS + EXTRA.get(src, VGPR_FORM) + ["-I", os.path.join(ROOT, "include"), "-I", CSRC]
-        cmd += os.environ.get("NERF_EXTRA_FLAGS", "").split()       # ablation builds (-DNERF_ABLATE_...)
         if keep_temps:
             cmd += ["-save-temps=cwd", "-Rpass-analysis=kernel-resource-usage"]
         cmd += ["-c", os.path.join(CSRC, src), "-o", obj]
@@ -76,7 +74,7 @@ def build(force=False, keep_temps=False, verbose=True):
 
     with ThreadPoolExecutor(max_workers=4) as pool:
         objs = list(pool.map(compile_one, SOURCES))
-    out = os.environ.get("NERF_LIB_OUT", LIB)                       # ablation builds go next to the real library
+    out = os.environ.get("NERF_LIB_OUT", LIB)                       # a second build (an A/B against the parent, say) goes next to the real library
     link = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out + ".tmp"]
     if verbose:
         print(" ".join(link), flush=True)

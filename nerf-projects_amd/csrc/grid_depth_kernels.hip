@@ -8,8 +8,8 @@
 // The image form makes its rays in the launch. A wavefront takes an 8 x 8 tile of pixels (lane = 8 * row + column in the
 // tile) rather than 64 pixels of a row: the rays of a tile stay within a few cells of one another for the whole march, so the
 // wavefront's 64 link and density loads fall on fewer cache lines, and its rays end at more nearly the same sample (less of
-// the wavefront idles behind its longest ray). The stores are 8 runs of 32 bytes. -DNERF_ABLATE_DEPTH_ROWS builds the
-// row mapping for the A/B of DESIGN.md.
+// the wavefront idles behind its longest ray). The stores are 8 runs of 32 bytes. (DESIGN.md has the A/B against
+// the row mapping.)
 #include "grid_device.h"
 
 namespace nerf {
@@ -20,24 +20,16 @@ constexpr int kTile = 8;      // pixels per side of a wavefront's tile: kTile * 
 // the pixel of this thread in row-major order, or -1 outside the image
 __device__ __forceinline__ int64_t depth_pixel(const GridCam& cam) {
     const int64_t tid = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
-#ifdef NERF_ABLATE_DEPTH_ROWS
-    return tid < (int64_t)cam.width * cam.height ? tid : -1;
-#else
     const int64_t tile = tid / (kTile * kTile);
     const int lane = (int)(tid % (kTile * kTile));
     const int tiles_x = (cam.width + kTile - 1) / kTile;
     const int64_t px = (tile % tiles_x) * kTile + lane % kTile;
     const int64_t py = (tile / tiles_x) * kTile + lane / kTile;
     return px < cam.width && py < cam.height ? py * cam.width + px : -1;
-#endif
 }
 
 int64_t depth_image_threads(const GridCam& cam) {
-#ifdef NERF_ABLATE_DEPTH_ROWS
-    return (int64_t)cam.width * cam.height;
-#else
     return (int64_t)((cam.width + kTile - 1) / kTile) * ((cam.height + kTile - 1) / kTile) * (kTile * kTile);
-#endif
 }
 
 template <int MODE, bool IMAGE, bool SKIP>

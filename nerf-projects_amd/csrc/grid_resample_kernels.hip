@@ -38,22 +38,17 @@ __global__ __launch_bounds__(kGridThreads) void grid_lattice_density_kernel(Grid
 // weight >= 0, so the order of the floats is the order of their bits: one integer maximum, whose result does not depend on
 // the order of arrival. The 8 entries are first read with plain global loads issued together (one wait for all of them), and
 // an entry already >= weight needs no atomic; a stale (smaller) value read costs one atomic that changes nothing, never a
-// missed update, because entries only grow. -DNERF_ABLATE_WEIGHT_PRELOAD builds the form without the loads.
+// missed update, because entries only grow. (DESIGN.md 7e has the A/B against the form without the loads.)
 __device__ __forceinline__ void raise_corners(float* p, int64_t s0, int64_t s1, float weight) {
     float* q[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) q[c] = p + ((c >> 2) & 1) * s0 + ((c >> 1) & 1) * s1 + (c & 1);
-#ifndef NERF_ABLATE_WEIGHT_PRELOAD
     float cur[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) cur[c] = *q[c];
 #pragma unroll
     for (int c = 0; c < 8; ++c)
         if (!(cur[c] >= weight)) atomicMax(reinterpret_cast<unsigned int*>(q[c]), __float_as_uint(weight));
-#else
-#pragma unroll
-    for (int c = 0; c < 8; ++c) atomicMax(reinterpret_cast<unsigned int*>(q[c]), __float_as_uint(weight));
-#endif
 }
 
 __global__ __launch_bounds__(kGridThreads) void grid_weight_render_kernel(GridWeight a) {

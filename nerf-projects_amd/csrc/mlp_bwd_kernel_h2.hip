@@ -25,10 +25,11 @@
 // ReLU masks. The reference's autograd keeps the post-ReLU activations; the forward kernel keeps them too (the weight
 // gradients need them) but the mask is one BIT of each: it writes 16 bytes per point, half-wave and layer (MlpStore::mask)
 // and this kernel reads those - by LDS-DMA a whole layer ahead, no registers in flight - instead of a kilobyte.
-#define NERF_FRAG_VGPR      // this kernel has the vector registers the forward kernel gives to the encoded inputs: A fragments there
 #include "mlp_pair_common.h"
 
 namespace nerf {
+
+using BwdPipe = PipeH<true>;      // this kernel has the vector registers the forward kernel gives to the encoded inputs: A fragments there
 
 struct PendingB {
     float c;        // raw sum -> gradient, in the equalised network's units: descale * 2^-t_in (per point)
@@ -69,7 +70,7 @@ __device__ __forceinline__ void next_tile_pair(PendingB& pd) {
     if constexpr (BLK) pd.keep_base += 2048;
 }
 template <int CONV, bool FIRST, bool BLK>
-__device__ __forceinline__ void chunk_bwd(PipeH& p, Frag4& cur, f32x16 (&acc)[8], const XT& x, XT (&hid)[8],
+__device__ __forceinline__ void chunk_bwd(BwdPipe& p, Frag4& cur, f32x16 (&acc)[8], const XT& x, XT (&hid)[8],
                                           const f32x16 (&pend)[8], PendingB& pd) {
     constexpr int C0 = CONV < 0 ? 0 : CONV;
     ConvTmp t;
@@ -136,7 +137,7 @@ void nerf_mlp_bwd_h2_kernel(const MlpBwdLaunch b) {
     const int h = lane >> 5;
     const int D = __builtin_amdgcn_readfirstlane(b.D);      // (explicitly scalar: it indexes the launch record)
 
-    PipeH pipe{(const char*)b.stream_h2, ring_lds, 0, 0, b.n_chunks, wave, lane, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
+    BwdPipe pipe{(const char*)b.stream_h2, ring_lds, 0, wave, lane, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
     pipe_start(pipe);
     for (int k = 0; k < 2; ++k) {
         prefetch_pieces<0, 4>(piece_src(pipe, k), piece_dst(pipe, k));
@@ -180,17 +181,13 @@ void nerf_mlp_bwd_h2_kernel(const MlpBwdLaunch b) {
     Frag4 cur;
     {
         const unsigned fr0 = lds_byte_addr(ring_lds) + lane * 16;
-        frag_issue<0>(cur.q[0], fr0);
-        frag_issue<1024>(cur.q[1], fr0);
-        frag_issue<2048>(cur.q[2], fr0);
-        frag_issue<3072>(cur.q[3], fr0);
+        frag_issue<0>(pipe, cur.q[0], fr0);
+        frag_issue<1024>(pipe, cur.q[1], fr0);
+        frag_issue<2048>(pipe, cur.q[2], fr0);
+        frag_issue<3072>(pipe, cur.q[3], fr0);
     }
     const unsigned rgb0 = lds_addr(rgb_lds) + 64 * h;   // this half-wave's entries of tile 0 of row 0 (row c, tile t: + 128 (4 c + t))
 
-#ifdef NERF_EXP_STAGGER      // timing experiment (profiles/r04_ab_notes.txt): workgroups out of phase with each other, so that the chip's
-    // thousand waves do not issue their stores (and their weight-stream loads) in the same instants
-    for (int k = 0; k < (int)((blockIdx.x >> 3) & 7); ++k) __builtin_amdgcn_s_sleep(NERF_EXP_STAGGER);
-#endif
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         pipe_tile_start(pipe);
         const int64_t pt = point_of(tile);
@@ -309,11 +306,7 @@ void nerf_mlp_bwd_h2_kernel(const MlpBwdLaunch b) {
             // Into LDS (a per-lane atomic on eight global addresses, a quarter of all lanes firing, queued in the memory pipe
             // the weight ring's counted waits look at: it doubled the kernel's time); the workgroup adds its sums at the end.
             if (m_grp > 0.0f && slack >= 12 && pd.t_out > -60) {
-#ifdef NERF_LOOSE_BY_LAYER      // diagnostic build (tools/gpu/loose_probe.py): events of >= 2^24 by the slot they close, others in bucket 1
-                const int bucket = slack >= 24 ? 2 + (slot == kBwdMaxFeat ? 0 : (slot >= 6 ? 1 : (slot >= 3 ? 2 : (slot >= 1 ? 3 : 4)))) : 1;
-#else
                 const int bucket = 1 + (slack >= 24 ? 6 : (slack - 12) >> 1);
-#endif
                 const unsigned one = 1u;
                 asm volatile("ds_add_u32 %0, %1" : : "v"(lds_byte_addr(loose_hist + bucket)), "v"(one) : "memory");
                 if (slack >= kLooseBwdGuard) asm volatile("ds_add_u32 %0, %1" : : "v"(lds_byte_addr(loose_hist)), "v"(one) : "memory");

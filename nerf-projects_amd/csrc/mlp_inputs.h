@@ -27,11 +27,7 @@ __device__ __forceinline__ void encode_point(const float (&p)[3], const float (&
 #pragma unroll
         for (int j = 0; j < 15; ++j) {
             float sn, cs;
-#ifdef NERF_ABLATE_PE
-            sn = q[j % 3] * (float)(1 << (j / 3)); cs = sn + 1.0f;
-#else
             sincosf(q[j % 3] * (float)(1 << (j / 3)), &sn, &cs);
-#endif
             const float own = h ? cs : sn;
             const float other = __shfl_xor(h ? sn : cs, 32);
             x0[j] = own;                                   // slot j
@@ -47,11 +43,7 @@ __device__ __forceinline__ void encode_point(const float (&p)[3], const float (&
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
                 float sn, cs;
-#ifdef NERF_ABLATE_PE
-                sn = q[j % 3] * (float)(1 << (j / 3)); cs = sn + 1.0f;
-#else
                 sincosf(q[j % 3] * (float)(1 << (j / 3)), &sn, &cs);
-#endif
                 dd[j] = h ? cs : sn;
                 dd[j + 6] = __shfl_xor(h ? sn : cs, 32);
             }

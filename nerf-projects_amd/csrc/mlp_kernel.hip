@@ -154,9 +154,7 @@ __device__ __forceinline__ void run_steps(Pipe& p, Frag16& cur, const f32x4* fr,
         __builtin_amdgcn_sched_barrier(0);
         cur = nxt;
         if constexpr (S == NSTEP / 2 - 1) {
-#ifndef NERF_ABLATE_BARRIER
             __syncthreads();
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
         run_steps<S + 1, NSTEP>(p, cur, fr, fr_next, body, post);
@@ -240,15 +238,11 @@ __device__ __forceinline__ float activate(f32x16 (&dst)[8], const f32x16 (&src)[
 #pragma unroll
     for (int t = 0; t < N; ++t)
 #pragma unroll
-#ifdef NERF_ABLATE_RELU
-        for (int r = 0; r < 16; ++r) dst[t][r] = (r == 0 && t == 0) ? src[t][r] : dst[t][r];
-#else
         for (int r = 0; r < 16; r += 2) {
             dst[t][r] = RELU ? fmaxf(src[t][r], 0.0f) : src[t][r];
             dst[t][r + 1] = RELU ? fmaxf(src[t][r + 1], 0.0f) : src[t][r + 1];
             top = fmaxf(fmaxf(top, fabsf(dst[t][r])), fabsf(dst[t][r + 1]));
         }
-#endif
     return top;
 }
 

@@ -33,6 +33,8 @@
 
 namespace nerf {
 
+using FwdPipe = PipeH<false>;      // A fragments into the accumulator half: the vector registers hold the encoded inputs
+
 // multiply a split tile by 2^d (exact while nothing leaves the fp16 range)
 __device__ __forceinline__ void rescale_tile(XT& x, int d) {
     const _Float16 f = (_Float16)pow2f(d < -30 ? -30 : (d > 15 ? 15 : d));
@@ -103,14 +105,10 @@ __device__ __forceinline__ void keep_pair(const Pending& pd, float y0, float y1)
 template <int T, int Q, int STORE>
 __device__ __forceinline__ void keep_pairs(const Pending& pd, const f32x2& even, float y0, float y1) {
     const f32x4 v = {even[0], even[1], y0, y1};
-#ifdef NERF_EXP_NOSTORE      // timing experiments (profiles/r02_kernel_ab.md)
-    asm volatile("" ::"v"(v));
-    return;
-#endif
     // (s_nop 1: a store of more than 8 bytes reads its data registers late - two wait states before a vector instruction
     // may overwrite them on gfx950; hipcc's hazard recogniser does not look inside inline asm)
     if constexpr (STORE == 2) {
-        asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 " NERF_STORE_BITS "\n\ts_nop 1"
+        asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 nt\n\ts_nop 1"
                      :
                      : "v"(pd.keep_off), "v"(v), "s"(pd.keep_base), "n"(1024 * Q - ((T & 1) ? 0 : 4096))
                      : "memory");
@@ -128,10 +126,6 @@ __device__ __forceinline__ void next_tile_pair(Pending& pd) {
 }
 template <int P, int STORE = 0, int T = 0>
 __device__ __forceinline__ void convert_pair(XT& dst, const f32x16& src, Pending& pd, const f32x2& b) {
-#ifdef NERF_ABLATE_CONV
-    if (P == 0) dst.hi[0][0] = __float_as_uint(src[0] + b[0]);
-    return;
-#endif
     const float y0 = fmaxf(fmaf(src[2 * P], pd.c, b[0]), pd.floor);
     const float y1 = fmaxf(fmaf(src[2 * P + 1], pd.c, b[1]), pd.floor);
     if constexpr (STORE) {
@@ -147,7 +141,6 @@ __device__ __forceinline__ void convert_pair(XT& dst, const f32x16& src, Pending
     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(a1));
     dst.hi[P >> 2][P & 3] = hi;
     dst.lo[P >> 2][P & 3] = lo;
-#ifndef NERF_ABLATE_MASKS
     if constexpr (STORE) {
         pd.maskw = mask_push(pd.maskw, hi);
         if constexpr (P == 7 && (T & 1) == 1) {      // tiles 2w, 2w + 1 done: word w of the record
@@ -155,7 +148,6 @@ __device__ __forceinline__ void convert_pair(XT& dst, const f32x16& src, Pending
             pd.maskw = 0u;
         }
     }
-#endif
 }
 
 // a whole tile at once (not hidden: tile 0 at the start of a layer)
@@ -183,17 +175,10 @@ __device__ __forceinline__ void convert_tile0_with(XT& dst, const f32x16& src, P
 // convert_pair cut into the three slices that ride behind MFMAs 1, 2 and 3 of a step
 template <int P>
 __device__ __forceinline__ void conv_slice0(ConvTmp& t, const f32x16& src, const Pending& pd, const f32x2& b) {
-#ifdef NERF_ABLATE_CONV   // timing-only build: one instruction keeps the operands alive
-    t.y0 = src[2 * P] + b[0]; t.y1 = 0.0f;
-    return;
-#endif
     t.y0 = fmaxf(fmaf(src[2 * P], pd.c, b[0]), pd.floor);
     t.y1 = fmaxf(fmaf(src[2 * P + 1], pd.c, b[1]), pd.floor);
 }
 __device__ __forceinline__ void conv_slice1(ConvTmp& t, Pending& pd) {
-#ifdef NERF_ABLATE_CONV
-    return;
-#endif
     pd.m = fmaxf(fmaxf(pd.m, fabsf(t.y0)), fabsf(t.y1));
     t.a0 = t.y0 * pd.sc;
     t.a1 = t.y1 * pd.sc;
@@ -202,7 +187,7 @@ __device__ __forceinline__ void conv_slice1(ConvTmp& t, Pending& pd) {
 // convert_stream_h2 below). CONV >= 0: while the chunk runs, step s converts register pair s of pending tile CONV;
 // its two bias entries are requested one step earlier.
 template <int CONV, bool FIRST, int STORE = 0>
-__device__ __forceinline__ void chunk_ktile8(PipeH& p, Frag4& cur, f32x16 (&acc)[8], const XT& x, XT (&hid)[8],
+__device__ __forceinline__ void chunk_ktile8(FwdPipe& p, Frag4& cur, f32x16 (&acc)[8], const XT& x, XT (&hid)[8],
                                              const f32x16 (&pend)[8], Pending& pd) {
     constexpr int C0 = CONV < 0 ? 0 : CONV;
     f32x2 r;
@@ -223,7 +208,6 @@ __device__ __forceinline__ void chunk_ktile8(PipeH& p, Frag4& cur, f32x16 (&acc)
             else if constexpr (pt == 13) conv_slice2<s>(hid[C0], t);
             else if constexpr (pt == 14) {
                 if constexpr (s < 7) r = lds_pair_issue<128 * C0 + 8 * (s + 1)>(pd.bias_addr);
-#ifndef NERF_ABLATE_MASKS
                 if constexpr (STORE) {      // the pair's ReLU flags (MlpStore::mask)
                     pd.maskw = mask_push(pd.maskw, hid[C0].hi[s >> 2][s & 3]);
                     if constexpr (s == 7 && (C0 & 1) == 1) {
@@ -231,19 +215,18 @@ __device__ __forceinline__ void chunk_ktile8(PipeH& p, Frag4& cur, f32x16 (&acc)
                         pd.maskw = 0u;
                     }
                 }
-#endif
             }
         }
     });
 }
-__device__ __forceinline__ void chunk_ktile4(PipeH& p, Frag4& cur, f32x16 (&acc)[8], const XT& x) {
+__device__ __forceinline__ void chunk_ktile4(FwdPipe& p, Frag4& cur, f32x16 (&acc)[8], const XT& x) {
     consume_chunk<4, 0>(p, cur, [&](auto tag, auto part, const Frag4& f) {
         constexpr int s = decltype(tag)::value, pt = decltype(part)::value;
         if constexpr (pt < 6) mma_one<pt, false>(acc[s], f, x);
     });
 }
 template <int CONV, bool FIRST, int STORE = 0>
-__device__ __forceinline__ void chunk_pair4(PipeH& p, Frag4& cur, f32x16 (&acc)[8], const XT& x0, const XT& x1,
+__device__ __forceinline__ void chunk_pair4(FwdPipe& p, Frag4& cur, f32x16 (&acc)[8], const XT& x0, const XT& x1,
                                             XT (&hid)[8], const f32x16 (&pend)[8], Pending& pd) {
     constexpr int C0 = CONV < 0 ? 0 : CONV;
     f32x2 r0, r1;
@@ -284,7 +267,7 @@ __device__ __forceinline__ void chunk_pair4(PipeH& p, Frag4& cur, f32x16 (&acc)[
         }
     });
 }
-__device__ __forceinline__ void chunk_row8(PipeH& p, Frag4& cur, f32x16& acc, const XT (&x)[8]) {
+__device__ __forceinline__ void chunk_row8(FwdPipe& p, Frag4& cur, f32x16& acc, const XT (&x)[8]) {
     consume_chunk<8, 0>(p, cur, [&](auto tag, auto part, const Frag4& f) {
         constexpr int s = decltype(tag)::value, pt = decltype(part)::value;
         if constexpr (pt < 6) {
@@ -598,15 +581,7 @@ struct EqualiseBatch {
     EqualiseRefs refs[2];
     unsigned* flags[2];      // row_exponents_layers_kernel: the mailbox [kMaxLinears][256] per network: (epoch << 8) | (e_j + 128)
     unsigned epoch;
-#ifdef NERF_ROWEXP_STAMPS      // profiles/microbench/row_exponents_bench.hip: wall_clock64() samples of thread 0 per phase
-    unsigned long long* stamps;
-#endif
 };
-#ifdef NERF_ROWEXP_STAMPS
-#define ROWEXP_STAMP() if (threadIdx.x == 0 && blockIdx.x == 0) batch.stamps[n_stamp++] = wall_clock64()
-#else
-#define ROWEXP_STAMP()
-#endif
 constexpr int kRowExpThreads = 1024;
 __global__ __launch_bounds__(kRowExpThreads) void row_exponents_kernel(const EqualiseBatch batch) {
     const float* params = batch.params[blockIdx.x];
@@ -619,11 +594,7 @@ __global__ __launch_bounds__(kRowExpThreads) void row_exponents_kernel(const Equ
     __shared__ int median_exp, n_valid;
     // (wave: known to be uniform, so that what it indexes - rows, offsets - stays in scalar registers)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n_waves = kRowExpThreads >> 6;
-#ifdef NERF_ROWEXP_STAMPS
-    int n_stamp = 0;
-#endif
     for (int idx = 0; idx < r.n; ++idx) {
-        ROWEXP_STAMP();
         const int k = r.order[idx];
         const int n_out = r.out[k], n_in = r.in[k], src = r.col_src[k], c0 = r.hid_col0[k], c1 = c0 + r.n_hid[k];
         if (r.scale_rows[k]) {
@@ -696,9 +667,7 @@ __global__ __launch_bounds__(kRowExpThreads) void row_exponents_kernel(const Equ
                 const bool valid = m1 > 0.0 && m1 < (double)__builtin_inff() * (double)__builtin_inff();
                 if ((lane & (64 / kRows - 1)) == 0 && j0 + my_row < n_out) row_exp[j0 + my_row] = valid ? (e2 + 1) >> 1 : -1000;
             }
-            ROWEXP_STAMP();
             __syncthreads();
-            ROWEXP_STAMP();
             // towards the MEDIAN binade, not the largest: the ordinary units keep their scale - a skip layer concatenates
             // them with gamma(x), whose entries are not scaled, and one huge row must not push 255 others 2^20 above those
             // (a histogram over the binades a float's norm can have)
@@ -709,7 +678,6 @@ __global__ __launch_bounds__(kRowExpThreads) void row_exponents_kernel(const Equ
                     atomicAdd(&n_valid, 1);
                 }
             __syncthreads();
-            ROWEXP_STAMP();
             if (wave == 0) {
                 // the smallest binade with more than half of the rows at or below it: lane l owns bins 5 l .. 5 l + 4
                 int own = 0;
@@ -732,7 +700,6 @@ __global__ __launch_bounds__(kRowExpThreads) void row_exponents_kernel(const Equ
                 if (over == 0ull && lane == 0) median_exp = 0;      // (no valid row)
             }
             __syncthreads();
-            ROWEXP_STAMP();
             for (int j = threadIdx.x; j < 256; j += blockDim.x) {
                 int e = (j < n_out && row_exp[j] > -1000) ? median_exp - row_exp[j] : 0;
                 e = e > 30 ? 30 : (e < -30 ? -30 : e);      // a unit 2^30 off the median is not brought all the way

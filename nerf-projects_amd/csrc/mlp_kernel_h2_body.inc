@@ -17,11 +17,8 @@
     const float* const bias_src = fold ? a.bias_fold : a.bias;
     const float* const descale_src = fold ? a.descale_fold : a.descale;
 
-    PipeH pipe{(const char*)(fold ? a.stream_fold : a.stream_h2), ring_lds, 0, 0, a.n_chunks, wave, lane, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
+    FwdPipe pipe{(const char*)(fold ? a.stream_fold : a.stream_h2), ring_lds, 0, wave, lane, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
     pipe_start(pipe);
-#ifdef NERF_STAMPS
-    pipe.st = Stamper{a.stamps, 0, -1, 0, blockIdx.x == 0 && wave == 0 && a.stamps != nullptr};
-#endif
     for (int k = 0; k < 2; ++k) {
         prefetch_pieces<0, 4>(piece_src(pipe, k), piece_dst(pipe, k));
         prefetch_pieces<0, 4>(piece_src(pipe, k) + 4096, piece_dst(pipe, k) + 4096);
@@ -41,10 +38,10 @@
     Frag4 cur;
     {
         const unsigned fr0 = lds_byte_addr(ring_lds) + lane * 16;
-        frag_issue<0>(cur.q[0], fr0);
-        frag_issue<1024>(cur.q[1], fr0);
-        frag_issue<2048>(cur.q[2], fr0);
-        frag_issue<3072>(cur.q[3], fr0);
+        frag_issue<0>(pipe, cur.q[0], fr0);
+        frag_issue<1024>(pipe, cur.q[1], fr0);
+        frag_issue<2048>(pipe, cur.q[2], fr0);
+        frag_issue<3072>(pipe, cur.q[3], fr0);
     }
 
     const unsigned bias0 = lds_addr(bias_lds) + 64 * h;   // this half-wave's entries of bias-block tile 0
@@ -54,15 +51,8 @@
     if constexpr (MODE == kInputRaysIndexed) n_live = __builtin_amdgcn_readfirstlane(*a.index_count);
     if (idle) n_live = 0;      // the launch belongs to this kernel's twin
     const int64_t n_tiles = (n_live + kPointsPerGroup - 1) / kPointsPerGroup;
-#ifdef NERF_EXP_STAGGER      // timing experiment (profiles/r04_ab_notes.txt): workgroups out of phase with each other, so that the chip's
-    // thousand waves do not issue their stores (and their weight-stream loads) in the same instants
-    for (int k = 0; k < (int)((blockIdx.x >> 3) & 7); ++k) __builtin_amdgcn_s_sleep(NERF_EXP_STAGGER);
-#endif
     const int n_layers = (a.use_viewdirs && !fold) ? a.D + 1 : a.D;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-#ifdef NERF_STAMPS
-        pipe.c = 0;
-#endif
         pipe_tile_start(pipe);
         const int64_t tile0 = tile * kPointsPerGroup + wave * kPointsPerWave;
         const int64_t pt_raw = tile0 + (lane & 31);
@@ -321,10 +311,6 @@
                 }
             }
         }
-#ifdef NERF_STAMPS
-        STAMP(pipe, 0x7fffff00);
-        pipe.st.on = false;   // first tile only
-#endif
     }   // tile loop
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if constexpr (STORE) {

@@ -14,32 +14,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 struct XT {
     u32x4 hi[2], lo[2];
 };
-#ifdef NERF_STAMPS
-// diagnostic build: wave 0 of workgroup 0 records (tag, s_memtime) through its first tile. A sample is taken at the
-// start of a step and stored at the start of the NEXT one, so that reading the counter (an SMEM return) adds no wait
-// of its own.
-struct Stamper {
-    unsigned long long* buf;
-    unsigned long long t_prev;
-    int tag_prev;
-    int n;
-    bool on;
-};
-__device__ __forceinline__ void stamp(Stamper& st, int tag) {
-    if (st.on) {
-        if (st.n < 4090 && (threadIdx.x & 63) == 0) {
-            st.buf[2 * st.n] = (unsigned long long)st.tag_prev;
-            st.buf[2 * st.n + 1] = st.t_prev;
-        }
-        ++st.n;
-        st.t_prev = __builtin_amdgcn_s_memtime();
-        st.tag_prev = tag;
-    }
-}
-#define STAMP(p, tag) stamp((p).st, (tag))
-#else
-#define STAMP(p, tag) do {} while (0)
-#endif
 
 // ---- weight-stream pipeline -------------------------------------------------------------
 // Four 32 KiB LDS buffers form a ring: while chunk c is consumed, chunk c+1 is resident, chunk c+2 half issued and
@@ -50,10 +24,13 @@ __device__ __forceinline__ void stamp(Stamper& st, int tag) {
 //   s_barrier -> every wave's share has, and every wave has finished chunk c-1, whose buffer chunk c+3 takes.
 constexpr int kRingH = 4;
 
+// FRAG_VGPR: where frag_issue puts the A fragments. The forward kernels give their vector registers to the encoded inputs
+// and take the accumulator half; the backward-data kernel has the vector registers free.
+template <bool FRAG_VGPR>
 struct PipeH {
     const char* stream;
     char* lds;
-    int c, b, n, wave, lane;
+    int b, wave, lane;
     const char* g_first;
     const char* g_second;
     char* l_first;
@@ -65,20 +42,18 @@ struct PipeH {
     const char* g2;         // this lane's source of chunk c + 2 and of chunk c + 3 (middle of the wave's share)
     const char* g3;         // the stream is followed by a copy of its first three chunks (launch_convert_stream_h2): within a
                             // tile the positions only advance, into the head of the next tile's stream; a tile resets them
-    int c3;
-#ifdef NERF_STAMPS
-    Stamper st;
-#endif
 };
 
 __device__ __forceinline__ int ringh_next(int b, int k) {
     b += k;
     return b >= kRingH ? b - kRingH : b;
 }
-__device__ __forceinline__ const char* piece_src(const PipeH& p, int chunk) {
+template <bool V>
+__device__ __forceinline__ const char* piece_src(const PipeH<V>& p, int chunk) {
     return p.stream + (size_t)chunk * kChunkBytes + p.wave * 8192 + p.lane * 16;
 }
-__device__ __forceinline__ char* piece_dst(const PipeH& p, int slot) { return p.lds + slot * kChunkBytes + p.wave * 8192; }
+template <bool V>
+__device__ __forceinline__ char* piece_dst(const PipeH<V>& p, int slot) { return p.lds + slot * kChunkBytes + p.wave * 8192; }
 
 template <int J>
 __device__ __forceinline__ void prefetch_piece(const char* g, char* l) {
@@ -109,15 +84,15 @@ struct Frag4 {
 // A count that is too small only waits longer; the pattern is kept across chunk boundaries (a chunk's last step issues
 // no bias read, the next chunk issues its first ones before its step 0), and everything else that reads LDS between
 // chunks waits for lgkmcnt(0).
-template <int OFF>
-__device__ __forceinline__ void frag_issue(f32x4& q, unsigned addr) {
-#ifdef NERF_FRAG_VGPR
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(q) : "v"(addr), "n"(OFF) : "memory");
-#else
-    // into the accumulator half of the register file: an MFMA takes its A operand from there as well, and the 32
-    // registers of the double-buffered fragments are 32 vector registers the conversion does not have to fight for
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&a"(q) : "v"(addr), "n"(OFF) : "memory");
-#endif
+template <int OFF, bool V>
+__device__ __forceinline__ void frag_issue(const PipeH<V>&, f32x4& q, unsigned addr) {
+    if constexpr (V) {
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(q) : "v"(addr), "n"(OFF) : "memory");
+    } else {
+        // into the accumulator half of the register file: an MFMA takes its A operand from there as well, and the 32
+        // registers of the double-buffered fragments are 32 vector registers the conversion does not have to fight for
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&a"(q) : "v"(addr), "n"(OFF) : "memory");
+    }
 }
 template <int N>
 __device__ __forceinline__ void lgkm_wait() {
@@ -136,8 +111,8 @@ struct PartTag {
 
 // body(step, part, frags): part 0..5 = that MFMA pair; part 11, 12, 13 = the vector work placed behind pairs 1, 2, 3;
 // part 14 = the bias requests for the next step, behind pair 4
-template <int S, int NSTEP, int NB, class Body>
-__device__ __forceinline__ void run_steps(PipeH& p, Frag4& cur, unsigned fr, unsigned fr_next, Body& body) {
+template <int S, int NSTEP, int NB, bool V, class Body>
+__device__ __forceinline__ void run_steps(PipeH<V>& p, Frag4& cur, unsigned fr, unsigned fr_next, Body& body) {
     if constexpr (S < NSTEP) {
         constexpr bool last = S + 1 == NSTEP;
         constexpr int G = last ? 0 : (S + 1) * 4;
@@ -148,15 +123,12 @@ __device__ __forceinline__ void run_steps(PipeH& p, Frag4& cur, unsigned fr, uns
         NERF_FENCE();
         body(StepTag<S>{}, PartTag<0>{}, cur);
         NERF_FENCE();
-        STAMP(p, (p.c << 8) | (S << 4) | NB);
-        frag_issue<(G + 0) * 1024>(nxt.q[0], ad);
-#ifndef NERF_ABLATE_DMA
+        frag_issue<(G + 0) * 1024>(p, nxt.q[0], ad);
         {
             constexpr int per = 8 / NSTEP;
             if constexpr (S < NSTEP / 2) prefetch_pieces<S * per, (S + 1) * per>(p.g_first, p.l_first);
             else prefetch_pieces<(S - NSTEP / 2) * per - 4, (S - NSTEP / 2 + 1) * per - 4>(p.g_second, p.l_second);
         }
-#endif
         NERF_FENCE();
         body(StepTag<S>{}, PartTag<1>{}, cur);
         NERF_FENCE();
@@ -165,12 +137,12 @@ __device__ __forceinline__ void run_steps(PipeH& p, Frag4& cur, unsigned fr, uns
             NERF_FENCE();
         }
         body(StepTag<S>{}, PartTag<11>{}, cur);
-        frag_issue<(G + 1) * 1024>(nxt.q[1], ad);
+        frag_issue<(G + 1) * 1024>(p, nxt.q[1], ad);
         NERF_FENCE();
         body(StepTag<S>{}, PartTag<2>{}, cur);
         NERF_FENCE();
         body(StepTag<S>{}, PartTag<12>{}, cur);
-        frag_issue<(G + 2) * 1024>(nxt.q[2], ad);
+        frag_issue<(G + 2) * 1024>(p, nxt.q[2], ad);
         NERF_FENCE();
         if constexpr (NB == 0) {
             lgkm_wait<3>();
@@ -179,7 +151,7 @@ __device__ __forceinline__ void run_steps(PipeH& p, Frag4& cur, unsigned fr, uns
         body(StepTag<S>{}, PartTag<3>{}, cur);
         NERF_FENCE();
         body(StepTag<S>{}, PartTag<13>{}, cur);
-        frag_issue<(G + 3) * 1024>(nxt.q[3], ad);
+        frag_issue<(G + 3) * 1024>(p, nxt.q[3], ad);
         NERF_FENCE();
         body(StepTag<S>{}, PartTag<4>{}, cur);
         NERF_FENCE();
@@ -189,22 +161,7 @@ __device__ __forceinline__ void run_steps(PipeH& p, Frag4& cur, unsigned fr, uns
         NERF_FENCE();
         cur = nxt;
         if constexpr (S == NSTEP / 2 - 1) {
-#if defined(NERF_ABLATE_BARRIER)      // timing-only builds: what the chunk's synchronisation costs (profiles/r02_kernel_ab.md)
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#elif defined(NERF_ABLATE_VMWAIT)
-            asm volatile("s_barrier" ::: "memory");
-#else
-#ifdef NERF_EXP_VMCNT      // timing experiment only (profiles/r02_kernel_ab.md): UNSAFE for the ring
-#ifdef NERF_EXP_VMCNT_ALL
-            if constexpr (true)
-#else
-            if constexpr (NB > 0)
-#endif
-                asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(NERF_EXP_VMCNT) : "memory");
-            else
-#endif
             asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
-#endif
             NERF_FENCE();
         }
         run_steps<S + 1, NSTEP, NB>(p, cur, fr, fr_next, body);
@@ -215,18 +172,20 @@ __device__ __forceinline__ unsigned lds_byte_addr(const void* p) {
     return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
 }
 
-__device__ __forceinline__ void pipe_tile_start(PipeH& p) {
+template <bool V>
+__device__ __forceinline__ void pipe_tile_start(PipeH<V>& p) {
     p.g2 = piece_src(p, 2) + 4096;      // (biased by half a wave's share: see consume_chunk)
     p.g3 = piece_src(p, 3) + 4096;
 }
-__device__ __forceinline__ void pipe_start(PipeH& p) {
+template <bool V>
+__device__ __forceinline__ void pipe_start(PipeH<V>& p) {
     static_assert(kRingH == 4, "ring slots are advanced with & 3");
     p.b = 0;
     p.fr = lds_byte_addr(p.lds) + p.lane * 16;
     pipe_tile_start(p);
 }
-template <int NSTEP, int NB, class Body>
-__device__ __forceinline__ void consume_chunk(PipeH& p, Frag4& cur, Body body) {
+template <int NSTEP, int NB, bool V, class Body>
+__device__ __forceinline__ void consume_chunk(PipeH<V>& p, Frag4& cur, Body body) {
     const int b1 = (p.b + 1) & 3, b2 = (p.b + 2) & 3, b3 = (p.b + 3) & 3;
     const unsigned fr = p.fr;
     const unsigned fr_next = lds_byte_addr(p.lds) + p.lane * 16 + b1 * kChunkBytes;
@@ -237,9 +196,6 @@ __device__ __forceinline__ void consume_chunk(PipeH& p, Frag4& cur, Body body) {
     p.g_second = p.g3;
     p.l_second = piece_dst(p, b3) + 4096;
     run_steps<0, NSTEP, NB>(p, cur, fr, fr_next, body);
-#ifdef NERF_STAMPS
-    ++p.c;
-#endif
     p.b = b1;
     p.fr = fr_next;
     p.g2 = p.g3;
@@ -329,10 +285,6 @@ struct ConvTmp {
 };
 template <int P>
 __device__ __forceinline__ void conv_slice2(XT& dst, const ConvTmp& t) {
-#ifdef NERF_ABLATE_CONV
-    if (P == 0) dst.hi[0][0] = __float_as_uint(t.y0);
-    return;
-#endif
     unsigned hi, lo;
     asm("v_cvt_pk_f16_f32 %0, %2, %3\n\t"
         "v_fma_mixlo_f16 %1, %0, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
@@ -352,14 +304,8 @@ __device__ __forceinline__ f32x16 mma(const f32x4& a, const u32x4& b, f32x16 c) 
 // MFMA K (0..5) of a step, small terms first
 template <int K, bool FIRST>
 __device__ __forceinline__ void mma_one(f32x16& acc, const Frag4& f, const XT& x) {
-#ifdef NERF_MMA_SHARED_OPERANDS
-    // neighbours share an operand: (q0,lo0) (q0,hi0) (q1,hi0) | (q3,hi1) (q2,hi1) (q2,lo1)
-    constexpr int A[6] = {0, 0, 1, 3, 2, 2};
-    constexpr bool LO[6] = {true, false, false, false, false, true};
-#else
     constexpr int A[6] = {1, 0, 0, 3, 2, 2};
     constexpr bool LO[6] = {false, true, false, false, true, false};
-#endif
     constexpr int s = K / 3;
     const u32x4& b = LO[K] ? x.lo[s] : x.hi[s];
     if constexpr (K == 0 && FIRST) {
@@ -426,9 +372,6 @@ __device__ __forceinline__ P* wave_uniform(P* p) {
 // scalar cache (6 % of the pass: all of it in the open at a layer boundary); the same with a C++ atomicMax on a
 // reconstructed pointer (a FLAT atomic behind s_waitcnt vmcnt(0): the weight ring drained at every boundary, 2x).
 __device__ __forceinline__ void enter_max(unsigned* record_lds, float m_point) {
-#ifdef NERF_ABLATE_ENTER_MAX
-    return;
-#endif
     asm volatile("ds_max_u32 %0, %1" : : "v"(lds_byte_addr(record_lds)), "v"(__float_as_uint(m_point)) : "memory");
 }
 // at the end of the kernel, behind a barrier: thread t enters record t
@@ -449,26 +392,10 @@ template <int IMM>
 __device__ __forceinline__ void keep_quad(float* base, unsigned off, const f32x4& v) {
     asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" : : "v"(off), "v"(v), "s"(base), "n"(IMM) : "memory");
 }
-// cache-policy bits of the blocked layout's stores (timing experiments set others: profiles/r04_ab_notes.txt)
-#if defined(NERF_STORE_BITS_SEL) && NERF_STORE_BITS_SEL == 1
-#define NERF_STORE_BITS "sc1 nt"
-#elif defined(NERF_STORE_BITS_SEL) && NERF_STORE_BITS_SEL == 2
-#define NERF_STORE_BITS "sc0 nt"
-#elif defined(NERF_STORE_BITS_SEL) && NERF_STORE_BITS_SEL == 3
-#define NERF_STORE_BITS "sc1"
-#elif defined(NERF_STORE_BITS_SEL) && NERF_STORE_BITS_SEL == 4
-#define NERF_STORE_BITS "sc0 sc1 nt"
-#else
-#define NERF_STORE_BITS "nt"
-#endif
 // the same with the nt bit, for stores that write whole lines of data nobody reads soon (the layout blocked by 32 points)
 template <int IMM>
 __device__ __forceinline__ void keep_quad_nt(float* base, unsigned off, const f32x4& v) {
-#ifdef NERF_EXP_NOSTORE      // timing experiments (profiles/r04_ab_notes.txt)
-    asm volatile("" ::"v"(v), "v"(off), "s"(base));
-    return;
-#endif
-    asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 " NERF_STORE_BITS "\n\ts_nop 1" : : "v"(off), "v"(v), "s"(base), "n"(IMM) : "memory");
+    asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 nt\n\ts_nop 1" : : "v"(off), "v"(v), "s"(base), "n"(IMM) : "memory");
 }
 template <int IMM>
 __device__ __forceinline__ void keep_word(unsigned* base, unsigned off, unsigned v) {

@@ -185,7 +185,7 @@ struct MlpLaunch {
     const float* descale;
     const float* gain;
     unsigned* loose;             // counter of (wave, layer) events where the a-priori output bound was >= 2^12 x too wide
-    unsigned long long* stamps;   // -DNERF_STAMPS builds only: s_memtime samples of one wave (profiles/microbench/stamps.py)
+    unsigned long long* reserved;   // unused (was `stamps`). Without it the f16x2 frame rate left the parent's spread: 0.04 % ABOVE it, within noise; kept by the rule of that change (profiles/switch_removal_ab.md)
     const float* bias;
     int n_chunks;
     int n_bias_tiles;

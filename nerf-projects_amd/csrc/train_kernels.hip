@@ -260,21 +260,13 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(GemmTN g) {
 #pragma unroll
             for (int it = 0; it < 32; ++it) {
                 const int64_t p = p0 + it;
-#ifdef NERF_ABLATE_TN_LOADS
-                ra[it] = (float)(p & 7);
-#else
                 ra[it] = (p < p_end && ptid < g.Mo) ? g.A[p * g.lda + ptid] : 0.0f;
-#endif
             }
 #pragma unroll
             for (int it = 0; it < 16; ++it) {
                 const int64_t p = p0 + bp0 + it;
                 const int n = n0 + bn;
-#ifdef NERF_ABLATE_TN_LOADS
-                rb[it] = (float)((p + n) & 7);
-#else
                 rb[it] = (p < p_end && n < g.No) ? g.B[p * g.ldb + n] : 0.0f;
-#endif
             }
         };
         auto deposit = [&](int buf, const float (&ra)[32], const float (&rb)[16]) {
@@ -338,10 +330,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(GemmTN g) {
             F16 nxt = cur;
             if (c + 1 < 4) nxt = frag_at(bs, 32 * (c + 1) + j, h);
             FENCE();
-#ifndef NERF_ABLATE_TN_MFMA
             mma_frag<1, 16>(acc[0][c], a0, cur);
             mma_frag<0, 16>(acc[1][c], a1, cur);
-#endif
             FENCE();
             cur = nxt;
         }

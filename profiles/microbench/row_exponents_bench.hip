@@ -1,6 +1,8 @@
 // microbenchmark (round 3): where row_exponents_kernel's 0.18 ms per optimiser step go. Includes the kernel's own source and
-// launches it on an 8 x 256 network with view directions, wall_clock64() samples of thread 0 per phase and layer.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I nerf-projects_amd/csrc -DNERF_ROWEXP_STAMPS \
+// launches it on an 8 x 256 network with view directions, wall_clock64() samples of thread 0 per phase and layer. The
+// samples are not in the shipped kernel: profiles/microbench/rowexp_stamps.patch adds them (and EqualiseBatch::stamps).
+//   git apply profiles/microbench/rowexp_stamps.patch
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I nerf-projects_amd/csrc \
 //       profiles/microbench/row_exponents_bench.hip -o row_exponents_bench && ./row_exponents_bench
 #include "mlp_kernel_h2.hip"
 

@@ -1,6 +1,8 @@
-"""Per-step cycle timeline of one wave of the fp16-pair MLP kernel (diagnostic build -DNERF_STAMPS).
+"""Per-step cycle timeline of one wave of the fp16-pair inference kernel. The instrumentation is not in the shipped sources:
+profiles/microbench/stamps.patch adds it (to a copy of the tree, or take it out again afterwards).
 
-    NERF_EXTRA_FLAGS=-DNERF_STAMPS NERF_LIB_OUT=$PWD/nerf-projects_amd/libnerf_stamps.so python nerf-projects_amd/build.py --force
+    git apply profiles/microbench/stamps.patch
+    NERF_LIB_OUT=$PWD/nerf-projects_amd/libnerf_stamps.so python nerf-projects_amd/build.py --force
     NERF_MI355X_LIB=.../libnerf_stamps.so NERF_STAMPS_FILE=/tmp/stamps.bin python bench.py --steps 1 --warmup 0 --no-cpu-baseline
     python profiles/microbench/stamps.py /tmp/stamps.bin
 

@@ -1,3 +1,5 @@
+"""Loose-bound events of the backward-data kernel over 40 training steps (precision_detail). For the events of >= 2^24 by the
+layer they close, build the library with profiles/microbench/loose_by_layer.patch applied: it changes what the buckets mean."""
 import sys, os
 sys.path.insert(0, os.getcwd())
 import numpy as np, torch
