@@ -1123,6 +1123,73 @@ int nerf_grid_depth_rays(nerf_sparse_grid* grid, const nerf_grid_render_options*
 int nerf_grid_depth_image(nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_render_options* opt,
                           const nerf_grid_depth_args* args);
 
+/* Sparse voxel grid: gradients of depth and log_transmit for autograd -------------------------------
+ * The expected depth (NERF_GRID_DEPTH_EXPECTED) and log_T of the section above as a forward that leaves a tape and a backward
+ * that takes a cotangent for each: what a torch.autograd.Function needs to differentiate depth maps, silhouettes and opacity
+ * regularisers with respect to density_data under any loss. Both depend on density_data alone: sh_data is not read and has
+ * no gradient. Both calls are stream-ordered, synchronise and allocate nothing and return a status with nerf_last_error().
+ * Gradients ACCUMULATE, as in the sections on training and on autograd: the caller zeroes them. At most 2^26 rays per call.
+ * The threshold depth is piecewise constant and the ray length does not depend on the tables: neither has a backward.
+ *
+ * nerf_grid_depth_rays_taped is nerf_grid_depth_rays in mode NERF_GRID_DEPTH_EXPECTED (depth and log_transmit bit-identical
+ * to it, with and without skip data) and also writes the tape, tape[ray] in fp64: the ray's depth once more, as the fp64 sum
+ * of the very fp32 terms  term = (weight * (t / step_size)) * world_step  that the forward adds in fp32 (0 for a ray that is
+ * not marched). 8 bytes per ray; nothing else is kept between forward and backward.
+ *
+ * nerf_grid_depth_backward marches every ray once more over the same sample lattice under the same options (the same fp32
+ * additions of t, the same sigma_thresh and stop rules, the same skip rule, the same stall rule) and adds to grad_density
+ * the gradient of  sum_ray grad_depth[ray] * depth[ray] + grad_log_transmit[ray] * log_transmit[ray].  origins, dirs, the
+ * options, use_skip and the grid's tables must be those of the taped forward. Per ray: g_d = grad_depth[ray] and
+ * g_T = grad_log_transmit[ray], each 0 where the pointer is NULL; step_ds = step_size * delta_scale (= world_step);
+ * neg_step = -step_size; remaining = tape[ray] (fp64; 0 without a tape); log_T = 0. At every sample with
+ * sigma > opt.sigma_thresh, in march order, fp32 with each operation rounded, in this order:
+ *   a      = (neg_step * sigma) * delta_scale
+ *   weight = exp(log_T) * (1 - exp(a))
+ *   tau    = t / step_size
+ *   term   = (weight * tau) * world_step                       (the forward's term, bit for bit)
+ *   remaining = remaining - (double)term                       (fp64: what the later samples still add to the depth)
+ *   log_T  = log_T + a
+ *   lead   = (exp(log_T) * tau) * world_step
+ *   d_sigma = step_ds * (g_d * (lead - (float)remaining)) - g_T * step_ds
+ *   at each of the 8 corners (x, y, z bits) whose link is kept:  v = ((w_x * w_y) * w_z) * d_sigma;
+ *     grad_density[row] += v  unless v == 0 (a zero term is not added)
+ *   if exp(log_T) < opt.stop_thresh: stop (after the adds of this sample)
+ * This is  d depth / d sigma_i = step_ds (T_{i+1} tau_i world_step - sum_{j > i} term_j)  and  d log_T / d sigma_i = -step_ds.
+ * A ray that stops at stop_thresh returned the constant log_T = -1e3: for such a ray g_T is taken as 0 at every sample (the
+ * call finds out whether a ray with g_T != 0 stops by marching it once without adds before the march that adds), and g_d
+ * contributes at the samples up to and including the stopping one, with log_T as it stood before the reset. A ray that
+ * misses the box or whose set-up is not finite contributes nothing, whatever its cotangents hold. n_rays = 0 does nothing.
+ * grad_depth and grad_log_transmit may each be NULL, not both (NERF_E_INVALID); tape may be NULL if and only if grad_depth
+ * is. The adds are float atomics (one hardware add each, no compare-and-swap): two calls agree to rounding of the sums,
+ * not bit for bit. */
+typedef struct nerf_grid_depth_taped_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]                                                                */
+    const float* dirs;          /* [dev] [n_rays, 3], need not be unit                                              */
+    int64_t n_rays;             /* 0: nothing is done                                                               */
+    float* depth;               /* [dev] [n_rays]                                                                   */
+    float* log_transmit;        /* [dev] [n_rays] or NULL                                                           */
+    double* tape;               /* [dev] [n_rays]                                                                   */
+    int32_t use_skip;           /* 1: use the skip data if nerf_grid_accelerate made it                             */
+    void* stream;
+} nerf_grid_depth_taped_args;
+
+typedef struct nerf_grid_depth_backward_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]       (those of the taped forward)                             */
+    const float* dirs;          /* [dev] [n_rays, 3]                                                                */
+    int64_t n_rays;             /* 0: nothing is done                                                               */
+    const float* grad_depth;    /* [dev] [n_rays] d loss / d depth, or NULL                                         */
+    const float* grad_log_transmit; /* [dev] [n_rays] d loss / d log_transmit, or NULL                              */
+    const double* tape;         /* [dev] [n_rays] as nerf_grid_depth_rays_taped wrote it; NULL iff grad_depth is    */
+    float* grad_density;        /* [dev] [capacity, 1], added to                                                    */
+    int32_t use_skip;
+    void* stream;
+} nerf_grid_depth_backward_args;
+
+int nerf_grid_depth_rays_taped(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_depth_taped_args* args);
+int nerf_grid_depth_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_depth_backward_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ EXPORTS = (
     "nerf_grid_components_finish", "nerf_grid_components_volumes", "nerf_grid_components_keep", "nerf_grid_copy_rows",
     "nerf_grid_depth_rays", "nerf_grid_depth_image",
     "nerf_grid_render_rays_taped", "nerf_grid_render_backward", "nerf_grid_sample_backward",
+    "nerf_grid_depth_rays_taped", "nerf_grid_depth_backward",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -247,6 +248,17 @@ class GridDepthArgs(_Sized):
                 ("n_rays", C.c_int64), ("depth", _FP), ("log_transmit", _FP), ("use_skip", C.c_int32), ("stream", C.c_void_p)]
 
 
+class GridDepthTapedArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("depth", _FP),
+                ("log_transmit", _FP), ("tape", _FP), ("use_skip", C.c_int32), ("stream", C.c_void_p)]
+
+
+class GridDepthBackwardArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("grad_depth", _FP),
+                ("grad_log_transmit", _FP), ("tape", _FP), ("grad_density", _FP), ("use_skip", C.c_int32),
+                ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -431,6 +443,10 @@ def load():
     lib.nerf_grid_render_backward.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridRenderBackwardArgs)]
     lib.nerf_grid_sample_backward.restype = i32
     lib.nerf_grid_sample_backward.argtypes = [vp, C.POINTER(GridSampleBackwardArgs)]
+    lib.nerf_grid_depth_rays_taped.restype = i32
+    lib.nerf_grid_depth_rays_taped.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridDepthTapedArgs)]
+    lib.nerf_grid_depth_backward.restype = i32
+    lib.nerf_grid_depth_backward.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridDepthBackwardArgs)]
     _lib = lib
     return lib
 

@@ -5,6 +5,7 @@
 //   grid_resample_api.cpp   lattice density, weight render, threshold, dilate, compact, gather
 //   grid_components_api.cpp occupancy, labelling, volumes, keep mask, row copy
 //   grid_depth_api.cpp      expected depth, threshold depth, ray length
+//   grid_depth_autograd_api.cpp   taped expected depth, backward with cotangents for depth and log_transmit
 //   grid_*_kernels.hip      the kernels of each, on grid_device.h (sampling, rays) and compact_device.h (compaction)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -210,6 +211,29 @@ struct GridDepth {
 };
 
 hipError_t launch_grid_depth(const GridDev& g, const GridRenderOpt& o, const GridDepth& r, hipStream_t s);
+
+// ---- gradients of depth and log_transmit (grid_depth_autograd_kernels.hip) ----
+struct GridDepthTaped {
+    const float* origins;
+    const float* dirs;
+    int64_t n_rays;
+    float* depth;                      // [n_rays]
+    float* log_transmit;               // or nullptr
+    double* tape;                      // [n_rays]: the depth as the fp64 sum of its fp32 terms
+};
+
+struct GridDepthBwd {
+    const float* origins;
+    const float* dirs;
+    int64_t n_rays;
+    const float* grad_depth;           // [n_rays] or nullptr
+    const float* grad_log_transmit;    // [n_rays] or nullptr
+    const double* tape;                // nullptr iff grad_depth is
+    float* grad_density;               // [capacity, 1], added to
+};
+
+hipError_t launch_grid_depth_taped(const GridDev& g, const GridRenderOpt& o, const GridDepthTaped& r, hipStream_t s);
+hipError_t launch_grid_depth_bwd(const GridDev& g, const GridRenderOpt& o, const GridDepthBwd& r, hipStream_t s);
 
 // ---- argument checks (grid_api.cpp): NERF_OK, or NERF_E_INVALID with last_error set. None needs a device or reads a handle. ----
 void set_error(const char* fmt, ...);

@@ -1,17 +1,22 @@
 """``loss.backward()`` through a sparse voxel grid: ``GridModule(grid)`` is a ``torch.nn.Module`` whose parameters are the
-grid's own ``density_data`` and ``sh_data``, and whose ``volume_render``, ``volume_render_image`` and ``sample`` are
-differentiable with respect to them - any loss, any torch optimiser::
+grid's own ``density_data`` and ``sh_data``, and whose ``volume_render``, ``volume_render_image``, ``sample``,
+``volume_render_depth`` and ``volume_render_depth_image`` are differentiable with respect to them - any loss, any torch
+optimiser::
 
     m = GridModule(grid)
     adam = torch.optim.Adam(m.parameters(), lr=1e-2)
     rgb = m.volume_render(rays); loss = anything(rgb); loss.backward(); adam.step()
+    depth, log_t = m.volume_render_depth(rays, return_log_transmit=True)      # depth supervision, silhouettes, T (1 - T), ...
 
 It is the counterpart of svox2's ``SparseGrid`` as an ``nn.Module`` (``volume_render`` / ``sample`` under autograd), beside
 ``SparseGrid`` and not on it: a ``SparseGrid`` itself still refuses tensors that require gradients. Everything runs in the HIP
-kernels of csrc/grid_autograd_kernels.hip; the semantics are stated in include/nerf_mi355x.h, "Sparse voxel grid: gradients
-for autograd". The forward keeps 24 bytes per ray (the tape) for the backward; the backward marches every ray once.
-Not built: gradients with respect to rays, points or the camera, of depth or ``log_transmit``, double backward, sparse
-gradient tensors.
+kernels of csrc/grid_autograd_kernels.hip and csrc/grid_depth_autograd_kernels.hip; the semantics are stated in
+include/nerf_mi355x.h, "Sparse voxel grid: gradients for autograd" and "Sparse voxel grid: gradients of depth and
+log_transmit for autograd". The forward keeps 24 bytes per ray (the tape; 8 for a depth) for the backward; the backward
+marches every ray once. The expected depth and ``log_transmit`` depend on ``density_data`` alone: ``sh_data`` gets no
+gradient from them.
+Not built: gradients with respect to rays, points or the camera, of the threshold depth (piecewise constant) or the ray
+length, double backward, sparse gradient tensors.
 """
 import ctypes as C
 from dataclasses import replace
@@ -19,7 +24,8 @@ from dataclasses import replace
 import torch
 from torch.autograd.function import once_differentiable
 
-from ._lib import GridRenderBackwardArgs, GridRenderTapedArgs, GridSampleBackwardArgs, check
+from ._lib import (NERF_GRID_DEPTH_EXPECTED, GridDepthBackwardArgs, GridDepthTapedArgs, GridRenderBackwardArgs,
+                   GridRenderTapedArgs, GridSampleBackwardArgs, check)
 from .grid import Camera, Rays, SparseGrid
 
 __all__ = ["GridModule"]
@@ -46,50 +52,106 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
-def _same_tables(module, density, sh):
+def _same_tables(module, density, sh=None):
     """The kernels read the tables through the grid's handle: they must still be the tensors autograd saved."""
     g = module.grid
-    if g.density_data.data_ptr() != density.data_ptr() or g.sh_data.data_ptr() != sh.data_ptr():
+    if g.density_data.data_ptr() != density.data_ptr() or (sh is not None and g.sh_data.data_ptr() != sh.data_ptr()):
         raise RuntimeError("the grid's tables were replaced between forward and backward: run the forward again after rebind()")
     return g._handle()
 
 
 class _VolumeRender(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, density, sh, module, o, d):
+    def forward(ctx, density, sh, module, o, d, want_log_transmit=False):
         g = module.grid
         opt = replace(g.opt)
         h = g._handle()
         n = o.shape[0]
         rgb = torch.empty((n, 3), device=o.device, dtype=torch.float32)
+        logt = torch.empty((n if want_log_transmit else 0,), device=o.device, dtype=torch.float32)
         tape = torch.empty((n, 3), device=o.device, dtype=torch.float64)
         a = GridRenderTapedArgs()
         a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), n
-        a.rgb_out, a.log_transmit, a.tape = rgb.data_ptr(), 0, tape.data_ptr()
+        a.rgb_out, a.log_transmit, a.tape = rgb.data_ptr(), logt.data_ptr() if want_log_transmit else 0, tape.data_ptr()
         a.use_skip = 1
         a.stream = g.ctx.stream().value
         check(g.ctx.lib.nerf_grid_render_rays_taped(h, C.byref(opt._to_c()), C.byref(a)))
         ctx.save_for_backward(density, sh, o, d, tape)      # the parameters too: torch refuses a backward after an in-place step
-        ctx.module, ctx.opt = module, opt
-        return rgb
+        ctx.module, ctx.opt, ctx.want_log_transmit = module, opt, want_log_transmit
+        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None: its launch is not issued
+        if not want_log_transmit:
+            ctx.mark_non_differentiable(logt)
+        return rgb, logt
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, grad_rgb):
+    def backward(ctx, grad_rgb, grad_logt):
         density, sh, o, d, tape = ctx.saved_tensors
         g = ctx.module.grid
         h = _same_tables(ctx.module, density, sh)
-        grad_rgb = grad_rgb.to(dtype=torch.float32).contiguous()      # (rgb.sum().backward() hands in a stride-0 expansion)
         gd = _zeros_like_or_none(density, ctx.needs_input_grad[0])
         gs = _zeros_like_or_none(sh, ctx.needs_input_grad[1])
-        a = GridRenderBackwardArgs()
-        a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]
-        a.grad_rgb, a.tape = grad_rgb.data_ptr(), tape.data_ptr()
-        a.grad_density, a.grad_sh, a.mask = _ptr(gd), _ptr(gs), 0
+        if grad_rgb is not None:
+            grad_rgb = grad_rgb.to(dtype=torch.float32).contiguous()      # (rgb.sum().backward() hands in a stride-0 expansion)
+            a = GridRenderBackwardArgs()
+            a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]
+            a.grad_rgb, a.tape = grad_rgb.data_ptr(), tape.data_ptr()
+            a.grad_density, a.grad_sh, a.mask = _ptr(gd), _ptr(gs), 0
+            a.use_skip = 1
+            a.stream = g.ctx.stream().value
+            check(g.ctx.lib.nerf_grid_render_backward(h, C.byref(ctx.opt._to_c()), C.byref(a)))
+        if grad_logt is not None and ctx.want_log_transmit and gd is not None:
+            _depth_backward(g, h, ctx.opt, o, d, None, grad_logt, None, gd)      # log_transmit depends on density_data alone
+        return gd, gs, None, None, None, None
+
+
+def _depth_backward(g, h, opt, o, d, grad_depth, grad_logt, tape, gd):
+    """One nerf_grid_depth_backward launch that takes both cotangents (either may be None) and adds to ``gd``."""
+    if o.shape[0] == 0:      # (an empty tensor has no address to hand over)
+        return
+    grad_depth = None if grad_depth is None else grad_depth.to(dtype=torch.float32).contiguous()
+    grad_logt = None if grad_logt is None else grad_logt.to(dtype=torch.float32).contiguous()
+    a = GridDepthBackwardArgs()
+    a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]
+    a.grad_depth, a.grad_log_transmit = _ptr(grad_depth), _ptr(grad_logt)
+    a.tape = 0 if grad_depth is None else tape.data_ptr()
+    a.grad_density = gd.data_ptr()
+    a.use_skip = 1
+    a.stream = g.ctx.stream().value
+    check(g.ctx.lib.nerf_grid_depth_backward(h, C.byref(opt._to_c()), C.byref(a)))
+
+
+class _VolumeRenderDepth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, density, module, o, d):
+        g = module.grid
+        opt = replace(g.opt)
+        h = g._handle()
+        n = o.shape[0]
+        depth = torch.empty((n,), device=o.device, dtype=torch.float32)
+        logt = torch.empty((n,), device=o.device, dtype=torch.float32)
+        tape = torch.empty((n,), device=o.device, dtype=torch.float64)
+        a = GridDepthTapedArgs()
+        a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), n
+        a.depth, a.log_transmit, a.tape = depth.data_ptr(), logt.data_ptr(), tape.data_ptr()
         a.use_skip = 1
         a.stream = g.ctx.stream().value
-        check(g.ctx.lib.nerf_grid_render_backward(h, C.byref(ctx.opt._to_c()), C.byref(a)))
-        return gd, gs, None, None, None
+        check(g.ctx.lib.nerf_grid_depth_rays_taped(h, C.byref(opt._to_c()), C.byref(a)))
+        ctx.save_for_backward(density, o, d, tape)
+        ctx.module, ctx.opt = module, opt
+        ctx.set_materialize_grads(False)
+        return depth, logt
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_depth, grad_logt):
+        density, o, d, tape = ctx.saved_tensors
+        g = ctx.module.grid
+        h = _same_tables(ctx.module, density)
+        gd = torch.zeros_like(density, memory_format=torch.contiguous_format)
+        if grad_depth is not None or grad_logt is not None:
+            _depth_backward(g, h, ctx.opt, o, d, grad_depth, grad_logt, tape, gd)
+        return gd, None, None, None
 
 
 class _Sample(torch.autograd.Function):
@@ -131,7 +193,8 @@ class GridModule(torch.nn.Module):
     ``RuntimeError`` that names :meth:`rebind`, which makes new parameters; optimiser state built on the old ones is the
     caller's business. ``self.grid.opt`` are the render options, read at every forward.
 
-    Under ``torch.no_grad()``, or with both parameters frozen, the methods call the plain kernels and keep no tape."""
+    Under ``torch.no_grad()``, or with both parameters frozen (for a depth: with ``density_data`` frozen), the methods call
+    the plain kernels and keep no tape."""
 
     def __init__(self, grid: SparseGrid):
         super().__init__()
@@ -161,8 +224,10 @@ class GridModule(torch.nn.Module):
     def _differentiate(self):
         return torch.is_grad_enabled() and (self.density_data.requires_grad or self.sh_data.requires_grad)
 
-    def volume_render(self, rays: Rays, use_kernel: bool = True):
-        """``[N, 3]``, bit-identical to ``grid.volume_render(rays)``, differentiable with respect to the parameters."""
+    def volume_render(self, rays: Rays, use_kernel: bool = True, return_log_transmit: bool = False):
+        """``[N, 3]``, bit-identical to ``grid.volume_render(rays)``, differentiable with respect to the parameters. With
+        ``return_log_transmit``: ``(rgb, log_transmit [N])``, both differentiable (``log_transmit`` with respect to
+        ``density_data``; exactly -1e3, with no gradient, where a ray stopped at ``stop_thresh``)."""
         if not use_kernel:
             raise NotImplementedError("use_kernel=False (the PyTorch renderer) does not exist here: HIP kernels only")
         self._check_bound()
@@ -170,8 +235,33 @@ class GridModule(torch.nn.Module):
         o = _points_arg(rays.origins, "rays.origins", dev)
         d = _points_arg(rays.dirs, "rays.dirs", dev, o.shape[0])
         if not self._differentiate():
-            return self.grid.volume_render(Rays(o, d))
-        return _VolumeRender.apply(self.density_data, self.sh_data, self, o, d)
+            return self.grid.volume_render(Rays(o, d), return_log_transmit=return_log_transmit)
+        rgb, logt = _VolumeRender.apply(self.density_data, self.sh_data, self, o, d, bool(return_log_transmit))
+        return (rgb, logt) if return_log_transmit else rgb
+
+    def volume_render_depth(self, rays: Rays, sigma_thresh=None, return_log_transmit: bool = False):
+        """``[N]`` as ``grid.volume_render_depth``, bit for bit. The expected termination (``sigma_thresh=None``) and, with
+        ``return_log_transmit``, ``log_transmit [N]`` are differentiable with respect to ``density_data``: one backward
+        launch takes both cotangents; ``sh_data`` takes no part. The threshold depth (``sigma_thresh=x``) is piecewise
+        constant: the plain kernel's result, which does not require grad."""
+        mode, _ = SparseGrid._depth_mode(sigma_thresh, return_log_transmit)
+        self._check_bound()
+        dev = self.grid.ctx.device
+        o = _points_arg(rays.origins, "rays.origins", dev)
+        d = _points_arg(rays.dirs, "rays.dirs", dev, o.shape[0])
+        if mode != NERF_GRID_DEPTH_EXPECTED or not (torch.is_grad_enabled() and self.density_data.requires_grad):
+            return self.grid.volume_render_depth(Rays(o, d), sigma_thresh=sigma_thresh, return_log_transmit=return_log_transmit)
+        depth, logt = _VolumeRenderDepth.apply(self.density_data, self, o, d)
+        return (depth, logt) if return_log_transmit else depth
+
+    def volume_render_depth_image(self, camera: Camera, sigma_thresh=None, return_log_transmit: bool = False):
+        """``[H, W]`` (with ``return_log_transmit`` a pair of them): :meth:`volume_render_depth` of ``camera.gen_rays()``,
+        bit-identical to ``grid.volume_render_depth_image``."""
+        SparseGrid._depth_mode(sigma_thresh, return_log_transmit)      # a bad threshold is refused before anything else
+        out = self.volume_render_depth(camera.gen_rays(self.grid.ctx.device), sigma_thresh, return_log_transmit)
+        if return_log_transmit:
+            return tuple(t.view(camera.height, camera.width) for t in out)
+        return out.view(camera.height, camera.width)
 
     def volume_render_image(self, camera: Camera, use_kernel: bool = True):
         """``[H, W, 3]``: :meth:`volume_render` of ``camera.gen_rays()``, bit-identical to ``grid.volume_render_image``."""
