@@ -139,6 +139,13 @@ int nerf_set_render_precision(nerf_ctx* ctx, int precision);
  * nerf_view_fold_status: *folded = 1 if deterministic fp16-pair inference launches of `slot` use the fold (0: not eligible, no
  * view branch, or switched off). Synchronises the device. */
 int nerf_set_view_fold(nerf_ctx* ctx, int on);
+/* Per-ray view bias: in a folded render of ray records with a multiple of 32 samples per ray (nerf_render_rays /
+ * nerf_render_frame, with or without an occupancy grid) what the view layer adds for gamma(dir) is formed once per ray -
+ * b_vf + W_v[:, W:] gamma(dir), accumulated in fp64, rounded once - and the kernel neither encodes the direction per point nor
+ * runs its chunk. Without a grid every wavefront of 32 points lies on one ray and takes its ray's row through LDS; with a grid
+ * each point reads its own ray's row, the same values: an all-occupied grid still gives the dense render bit for bit. sigma is bit for bit the folded kernel's; the colours differ by the rounding of that term.
+ * on (default) / off for the following launches of this context; every other launch is what it was. */
+int nerf_set_ray_view_bias(nerf_ctx* ctx, int on);
 int nerf_view_fold_status(nerf_ctx* ctx, int slot, int* folded);
 /* NERF_PRECISION_F16X2 chooses a layer's per-point output scale from an a-priori bound (largest row sum of |W| x
  * largest |input| + largest |bias|). A bound 2^12 or more above a point's real outputs starts to cost low-order

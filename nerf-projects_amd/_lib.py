@@ -21,7 +21,7 @@ EXPORTS = (
     "nerf_get_precision", "nerf_precision_status", "nerf_get_adam_state", "nerf_set_adam_state",
     "nerf_shard_bounds", "nerf_render_shard", "nerf_precision_peek", "nerf_precision_check",
     "nerf_precision_detail", "nerf_profile_read_train", "nerf_set_render_precision",
-    "nerf_set_view_fold", "nerf_view_fold_status",
+    "nerf_set_view_fold", "nerf_view_fold_status", "nerf_set_ray_view_bias",
     "nerf_pack_rays", "nerf_density_grid", "nerf_marching_cubes", "nerf_train_forward", "nerf_train_backward",
     "nerf_zero_grad", "nerf_adam_step", "nerf_occupancy_create", "nerf_occupancy_destroy", "nerf_occupancy_cells",
     "nerf_occupancy_stats", "nerf_render_rays_occ", "nerf_render_frame_occ",
@@ -347,6 +347,8 @@ def load():
     lib.nerf_set_render_precision.argtypes = [vp, i32]
     lib.nerf_set_view_fold.restype = i32
     lib.nerf_set_view_fold.argtypes = [vp, i32]
+    lib.nerf_set_ray_view_bias.restype = i32
+    lib.nerf_set_ray_view_bias.argtypes = [vp, i32]
     lib.nerf_view_fold_status.restype = i32
     lib.nerf_view_fold_status.argtypes = [vp, i32, C.POINTER(i32)]
     lib.nerf_get_precision.restype = i32

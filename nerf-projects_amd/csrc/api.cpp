@@ -66,6 +66,34 @@ int run_mlp(nerf_ctx* c, MlpLaunch& a, const PackedNet& net_in, int mode, hipStr
     a.stream_fold = net.d_stream_fold;
     a.bias_fold = net.d_bias_fold;
     a.descale_fold = net.d_descale_fold;
+    // The per-ray view bias: where the fold is allowed on ray records of whole rays with a multiple of 32 samples each (dense,
+    // every wavefront then lies on one ray, or through an occupancy grid's list, which must give the dense render's bits where
+    // it names every point), the folded twin of the pair is nerf_mlp_h2_fold_ray_kernel. The table is filled
+    // whether or not the network's word then names that kernel: the host does not know the word.
+    a.ray_bias = nullptr;
+    a.stream_ray = nullptr;
+    if (may_fold && c->ray_view_bias && (mode == kInputRays || mode == kInputRaysIndexed) && net.arch.use_viewdirs && net.d_stream_ray && a.rays && a.ray_ld >= 11 &&
+        a.samples_per_ray > 0 && a.samples_per_ray % kPointsPerWave == 0 && a.n_points > 0 && a.n_points % a.samples_per_ray == 0) {
+        const int64_t n_rays = a.n_points / a.samples_per_ray;
+        const size_t want = (size_t)n_rays * kRayBiasRow;
+        if (want > c->ray_bias_floats) {
+            if (c->ray_bias) {
+                HIP_TRY(hipDeviceSynchronize());
+                HIP_TRY(hipFree(c->ray_bias));
+                c->ray_bias = nullptr;
+                c->ray_bias_floats = 0;
+            }
+            HIP_TRY(hipMalloc((void**)&c->ray_bias, want * sizeof(float)));
+            c->ray_bias_floats = want;
+        }
+        const int D = net.arch.D, W = net.arch.W;
+        const LinearDesc &views = net.linears[D], &feature = net.linears[D + 1];
+        const ViewFoldRefs refs{(unsigned)views.w_off, (unsigned)views.b_off, (unsigned)feature.w_off, (unsigned)feature.b_off,
+                                (unsigned)net.n_params, W, views.out, views.in - W};
+        HIP_TRY(launch_ray_view_bias(net.d_params_eq, refs, a.rays, a.ray_ld, n_rays, c->ray_bias, s));
+        a.ray_bias = c->ray_bias;
+        a.stream_ray = net.d_stream_ray;
+    }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->profiling) {
         for (hipEvent_t* e : {&e0, &e1}) {
@@ -197,6 +225,11 @@ int refresh_fold(PackedNet& net, hipStream_t s) {
                                      net.d_stream_fold, net.d_descale_fold, s));
     // (the folded stream ends with four view chunks, the alpha_linear tile and the gamma(dir) chunk)
     HIP_TRY(launch_view_fold_eligible(net.d_gain, D, net.d_chunk_max_fold, net.n_chunks_fold - 6, net.d_fold_word, s));
+    // the same stream without its gamma(dir) chunk, its own head behind it (PackedNet::d_stream_ray)
+    const size_t n_ray = (size_t)net.n_chunks_fold - 1;
+    HIP_TRY(hipMemcpyAsync(net.d_stream_ray, net.d_stream_fold, n_ray * kChunkBytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(net.d_stream_ray + n_ray * kChunkFloats, net.d_stream_fold, (size_t)kStreamTailChunks * kChunkBytes,
+                           hipMemcpyDeviceToDevice, s));
     return NERF_OK;
 }
 
@@ -229,7 +262,7 @@ void free_net(PackedNet& n) {
                     (void*)n.d_row_exp, (void*)n.d_eq_flags, (void*)n.train.d_stream_bwd_h2, (void*)n.train.d_descale_bwd, (void*)n.train.d_gain_bwd,
                     (void*)n.train.d_chunk_layer_bwd, (void*)n.train.d_chunk_max_bwd, (void*)n.d_fold_stream_table,
                     (void*)n.d_fold_bias_table, (void*)n.d_stream_eq_fold, (void*)n.d_stream_fold, (void*)n.d_bias_fold,
-                    (void*)n.d_descale_fold, (void*)n.d_chunk_layer_fold, (void*)n.d_chunk_max_fold, (void*)n.d_fold_word})
+                    (void*)n.d_descale_fold, (void*)n.d_chunk_layer_fold, (void*)n.d_chunk_max_fold, (void*)n.d_fold_word, (void*)n.d_stream_ray})
         if (p) (void)hipFree(p);
     n = PackedNet{};
 }
@@ -346,6 +379,7 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     if (c->ws) (void)hipFree(c->ws);
     if (c->tape_mem) (void)hipFree(c->tape_mem);
     if (c->frame_rays) (void)hipFree(c->frame_rays);
+    if (c->ray_bias) (void)hipFree(c->ray_bias);
     if (c->d_loose) (void)hipFree(c->d_loose);
     if (c->h_loose) (void)hipHostFree(c->h_loose);
     if (c->scratch_done) (void)hipEventDestroy(c->scratch_done);
@@ -389,6 +423,15 @@ int nerf_set_view_fold(nerf_ctx* c, int on) {
         return NERF_E_INVALID;
     }
     c->view_fold = on != 0;
+    return NERF_OK;
+}
+
+int nerf_set_ray_view_bias(nerf_ctx* c, int on) {
+    if (!c) {
+        set_error("nerf_set_ray_view_bias: ctx is NULL");
+        return NERF_E_INVALID;
+    }
+    c->ray_view_bias = on != 0;
     return NERF_OK;
 }
 
@@ -563,6 +606,7 @@ int nerf_load_weights(nerf_ctx* c, int slot, const nerf_arch* arch, const float*
         up((void**)&net.d_chunk_layer_fold, fold_layer_of.data(), (size_t)fnc * sizeof(int));
         up((void**)&net.d_stream_eq_fold, nullptr, (size_t)fnc * kChunkBytes);
         up((void**)&net.d_stream_fold, nullptr, (size_t)(fnc + kStreamTailChunks) * kChunkBytes);
+        up((void**)&net.d_stream_ray, nullptr, (size_t)(fnc - 1 + kStreamTailChunks) * kChunkBytes);
         up((void**)&net.d_bias_fold, nullptr, (size_t)nbt * kBiasTileFloats * sizeof(float));
         up((void**)&net.d_descale_fold, nullptr, (kMaxDepth + 3) * sizeof(float));
         up((void**)&net.d_chunk_max_fold, nullptr, (size_t)fnc * sizeof(float));

@@ -53,6 +53,11 @@ struct nerf_ctx {
     size_t ws_bytes = 0;
     float* frame_rays = nullptr;   // ray record of the chunk being rendered by nerf_render_frame
     size_t frame_rays_floats = 0;
+    // nerf_set_ray_view_bias, and the table of the per-ray view bias (MlpLaunch::ray_bias): [rays of the launch][kRayBiasRow],
+    // filled before each launch that uses it and reused in stream order like the scratch below; grows, never shrinks
+    bool ray_view_bias = true;
+    float* ray_bias = nullptr;
+    size_t ray_bias_floats = 0;
     // The scratch above is shared by every call on this context (nerf_render_rays, nerf_render_frame, nerf_train_step,
     // nerf_image_metrics). Calls are asynchronous, so two calls may only reuse it in stream order: ScratchScope
     // (below) serialises host threads with `scratch_mutex` and, when a call arrives on another stream than the one

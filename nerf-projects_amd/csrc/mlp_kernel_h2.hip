@@ -289,6 +289,20 @@ __device__ __forceinline__ void finish_views(f32x16 (&y)[4], const f32x16 (&acc)
     }
 }
 
+// the same with the four bias tiles read from memory: `row` is this lane's half-wave's 16 entries of tile 0 of a row in the bias
+// tiles' order (MlpLaunch::ray_bias, the indexed ray mode: a lane's point has its own ray). Plain loads at the end of the tile,
+// beside the re-read of the raw inputs: the wait hipcc puts in front of their use also retires the ring's pieces in flight.
+__device__ __forceinline__ void finish_views_row(f32x16 (&y)[4], const f32x16 (&acc)[8], const float* row, float c) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        f32x4 b[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) b[q] = *(const f32x4*)(row + 32 * t + 4 * q);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) y[t][r] = fmaxf(fmaf(acc[t][r], c, b[r >> 2][r & 3]), 0.0f);
+    }
+}
+
 // the mask word of two fp32 tiles (values >= 0) in mask_push's bit order: value 2s of the first tile at bit 15 - s, 2s + 1
 // at bit 31 - s, the second tile's eight places lower
 __device__ __forceinline__ unsigned relu_mask_word(const f32x16& t0, const f32x16& t1) {
@@ -348,7 +362,7 @@ __device__ __forceinline__ float row_dot4(const f32x16 (&x)[4], unsigned w_addr)
 template <int MODE, int STORE = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void nerf_mlp_h2_kernel(const MlpLaunch a) {
-    constexpr bool fold = false;
+    constexpr bool fold = false, ray_bias = false;
     bool idle = false;      // the network is folded: this launch is nerf_mlp_h2_fold_kernel's
     if constexpr (STORE == 0) idle = a.fold_word != nullptr && __builtin_amdgcn_readfirstlane(*a.fold_word) != 0u;
 #include "mlp_kernel_h2_body.inc"
@@ -357,7 +371,25 @@ void nerf_mlp_h2_kernel(const MlpLaunch a) {
 template <int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void nerf_mlp_h2_fold_kernel(const MlpLaunch a) {
-    constexpr bool fold = true;
+    constexpr bool fold = true, ray_bias = false;
+    constexpr int STORE = 0;
+    const bool idle = __builtin_amdgcn_readfirstlane(*a.fold_word) == 0u;      // not eligible: nerf_mlp_h2_kernel's launch
+#include "mlp_kernel_h2_body.inc"
+}
+
+// The folded kernel for ray records with a multiple of 32 samples per ray (MlpLaunch::ray_bias): what the view layer adds for
+// gamma(dir) is a function of the ray and the weights alone, so it is formed once per ray (ray_view_bias_kernel,
+// refresh_kernels.hip) and read here where the folded kernel reads b_vf - in kInputRays, where a wavefront lies on ONE ray,
+// through a per-wave LDS slot; in kInputRaysIndexed per lane from the table, with the same values: a list that names every
+// point gives the dense render's bits (tests/test_occupancy.py), which is why the indexed mode has this twin at all. Gone from the tile: six
+// accurate sincosf per lane, the split of gamma(dir), its chunk (4 steps, 24 MFMAs), the third fetch of the ray record and its
+// wave_max. A kernel of its own name, not a second parameter of nerf_mlp_h2_fold_kernel: the five folded instantiations keep
+// their symbols and their code.
+template <int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void nerf_mlp_h2_fold_ray_kernel(const MlpLaunch a) {
+    static_assert(MODE == kInputRays || MODE == kInputRaysIndexed, "ray records only");
+    constexpr bool fold = true, ray_bias = true;
     constexpr int STORE = 0;
     const bool idle = __builtin_amdgcn_readfirstlane(*a.fold_word) == 0u;      // not eligible: nerf_mlp_h2_kernel's launch
 #include "mlp_kernel_h2_body.inc"
@@ -379,7 +411,7 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
         if (n_cu[dev] <= 0) n_cu[dev] = 256;
     }
     const dim3 grid((unsigned)(tiles < n_cu[dev] ? tiles : n_cu[dev])), block(256);
-    const size_t lds = kRingH * kChunkBytes;   // + 20.5 KiB static (bias block, layer scales)
+    const size_t lds = kRingH * kChunkBytes;   // + 20.5 KiB static (bias block, layer scales; + 4 KiB in the per-ray-bias kernel)
     static bool raised[64][5] = {};
     if (mode < 0 || mode > 4) return hipErrorInvalidValue;
     if (mode == kInputRaysIndexed && (a.store || !a.index || !a.index_count)) return hipErrorInvalidValue;
@@ -423,6 +455,28 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
     if (a.fold_word) {
         // the folded twin, first: whichever of the two the network's word does not name returns at once (see the kernels)
         if (!a.stream_fold || !a.bias_fold || !a.descale_fold || !a.use_viewdirs) return hipErrorInvalidValue;
+        if (a.ray_bias || a.stream_ray) {
+            // the per-ray view bias: a wavefront's 32 points on one ray, or the launch is not this kernel's
+            if (!a.ray_bias || !a.stream_ray || (mode != kInputRays && mode != kInputRaysIndexed) || a.samples_per_ray <= 0 || a.samples_per_ray % kPointsPerWave ||
+                a.n_points % a.samples_per_ray)
+                return hipErrorInvalidValue;
+            static bool raised_ray[64][2] = {};
+            const int idx = mode == kInputRaysIndexed ? 1 : 0;
+            if (!raised_ray[dev][idx]) {
+                e = hipFuncSetAttribute(idx ? (const void*)nerf_mlp_h2_fold_ray_kernel<kInputRaysIndexed>
+                                            : (const void*)nerf_mlp_h2_fold_ray_kernel<kInputRays>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) return e;
+                raised_ray[dev][idx] = true;
+            }
+            if (idx) hipLaunchKernelGGL(nerf_mlp_h2_fold_ray_kernel<kInputRaysIndexed>, grid, block, lds, s, a);
+            else hipLaunchKernelGGL(nerf_mlp_h2_fold_ray_kernel<kInputRays>, grid, block, lds, s, a);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            if (idx) hipLaunchKernelGGL(nerf_mlp_h2_kernel<kInputRaysIndexed>, grid, block, lds, s, a);
+            else hipLaunchKernelGGL(nerf_mlp_h2_kernel<kInputRays>, grid, block, lds, s, a);
+            return hipGetLastError();
+        }
         static bool raised_fold[64][5] = {};
         const void* fn = mode == kInputEmbedded ? (const void*)nerf_mlp_h2_fold_kernel<kInputEmbedded>
                          : mode == kInputPoints ? (const void*)nerf_mlp_h2_fold_kernel<kInputPoints>

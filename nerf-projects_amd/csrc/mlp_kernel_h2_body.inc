@@ -3,6 +3,10 @@
 // belongs to the other kernel (no tile is run then). fold: the view fold
 // (nerf_internal.h, PackedNet::d_stream_fold) - feature_linear is not evaluated: the launch reads the folded stream, bias block
 // and scales, the trunk's last layer is the pending layer of the view section, and alpha_linear's tile follows the view chunks.
+// ray_bias (nerf_mlp_h2_fold_ray_kernel; fold, ray records with a multiple of 32 samples per ray): the view layer's gamma(dir)
+// term comes per ray from MlpLaunch::ray_bias instead of being computed per point. kInputRays: a wavefront's 32 points lie on
+// one ray, whose row travels through a per-wave LDS slot - see the tile start and the view section. kInputRaysIndexed: the
+// listed points of a wavefront lie on any rays, and each lane reads its own ray's entries from the table in the view section.
 // (Text, not a function: the static LDS arrays have to be the kernel's own, and with the body behind a function's reference
 // and pointer parameters hipcc spilled some hundred registers per lane to scratch.)
     // The ring is the dynamic LDS allocation; the bias block and the small per-layer tables are static.
@@ -10,6 +14,7 @@
     __shared__ __attribute__((aligned(16))) float bias_lds[kBiasLdsBytes / 4];
     __shared__ __attribute__((aligned(16))) float layer_tab[4 * (kMaxDepth + 3)];   // per layer [descale, gain, max|b|, -]
     __shared__ unsigned max_record[kBwdMaxSlots];      // STORE: enter_max's records
+    __shared__ __attribute__((aligned(16))) float ray_lds[kWavesPerGroup * 256];      // ray_bias: a KiB per wave, its ray's row in front
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5;
@@ -17,7 +22,7 @@
     const float* const bias_src = fold ? a.bias_fold : a.bias;
     const float* const descale_src = fold ? a.descale_fold : a.descale;
 
-    FwdPipe pipe{(const char*)(fold ? a.stream_fold : a.stream_h2), ring_lds, 0, wave, lane, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+    FwdPipe pipe{(const char*)(ray_bias ? a.stream_ray : fold ? a.stream_fold : a.stream_h2), ring_lds, 0, wave, lane, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
     pipe_start(pipe);
     for (int k = 0; k < 2; ++k) {
         prefetch_pieces<0, 4>(piece_src(pipe, k), piece_dst(pipe, k));
@@ -58,6 +63,15 @@
         const int64_t pt_raw = tile0 + (lane & 31);
         int64_t pt = pt_raw < n_live ? pt_raw : n_live - 1;
         if constexpr (MODE == kInputRaysIndexed) pt = a.index[pt];      // the listed point replaces the slot: inputs, output row
+        if constexpr (ray_bias && MODE == kInputRays) {
+            // This wave's ray (a wave behind the batch's end: the last ray) -> its row of the table into the wave's slot, one
+            // LDS-DMA of 64 x 16 bytes (the row has 33 pieces: the lanes behind fetch the last one again). Issued before the
+            // tile's first ring piece, so every counted vmcnt(8) of the tile retires it with the pieces before it; the view
+            // section, the only reader, is sixty chunks away, and the wave's reads of the previous tile's row have returned
+            // (lgkmcnt(0) behind each of them).
+            const float* row = a.ray_bias + (pt / a.samples_per_ray) * kRayBiasRow + 4 * (lane < 32 ? lane : 32);
+            __builtin_amdgcn_global_load_lds(GLB_PTR(row), LDS_PTR(ray_lds + wave * 256), 16, 0, 0);
+        }
 
         XT xp0, xp1;
         float m_pe;
@@ -102,7 +116,11 @@
             pd.floor = is_feature ? -__builtin_inff() : 0.0f;
             float bound = fmaf(tab[1], m_in, tab[2]) * 1.001f;
             // the next layer may concatenate these outputs with inputs that must fit the same scale
-            if (joins_dir) {
+            if (joins_dir && ray_bias && MODE == kInputRays) {
+                // the same number per ray: max(|d|, 1) travels behind the ray's row (kRayBiasMax). It keeps the scale of the trunk
+                // output, and with it sigma, bit for bit the folded kernel's.
+                bound = fmaxf(bound, lds_scalar(ray_lds + wave * 256 + kRayBiasMax));
+            } else if (joins_dir) {
                 // range of gamma(dir), which the view layer concatenates: re-read from the ray record here (once per
                 // tile) rather than kept in a register through the trunk
                 f32x16 x0, x1, dd;
@@ -234,20 +252,28 @@
                 const float feat_bound = fmaf(lds_scalar(layer_tab + 4 * a.D + 1), m_prev, lds_scalar(layer_tab + 4 * a.D + 2));
                 if (h == 0 && live && !rgb_poisoned && !(feat_bound < __builtin_inff()) && a.loose) atomicAdd(a.loose, 1u);
             }
-            XT xd;
-            {
-                f32x16 x0, x1, dd;
-                load_inputs<MODE, false, true>(a, pt, h, x0, x1, dd);
-                split_tile(xd, dd, pd.sc);
+            if constexpr (!ray_bias) {      // (ray_bias: the term is in the ray's row, the stream has no gamma(dir) chunk)
+                XT xd;
+                {
+                    f32x16 x0, x1, dd;
+                    load_inputs<MODE, false, true>(a, pt, h, x0, x1, dd);
+                    split_tile(xd, dd, pd.sc);
+                }
+                chunk_ktile4(pipe, cur, accB, xd);
             }
-            chunk_ktile4(pipe, cur, accB, xd);
             unsigned bad;     // raw inputs re-read (a value kept across the view layer costs the step a register): requested
             {                 // here, behind the last MFMA chunk, so that the round trip runs under the colour head's arithmetic
                 f32x16 x0, x1, dd;
                 load_inputs<MODE, false, false>(a, pt, h, x0, x1, dd, nullptr, &bad);
             }
             f32x16 y[4];
-            finish_views(y, accB, bias0 + 128 * (8 * a.D + 9), lds_scalar(layer_tab + 4 * (a.D + 1)) * pow2f(-pd.t_out));
+            // (ray_bias: b_vf + W_v[:, W:] gamma(dir) of the wave's ray, in the order of the bias tiles it stands in for)
+            if constexpr (ray_bias && MODE == kInputRaysIndexed)      // (the same entries, each lane's from its own ray's row)
+                finish_views_row(y, accB, a.ray_bias + (pt / a.samples_per_ray) * kRayBiasRow + 16 * h,
+                                 lds_scalar(layer_tab + 4 * (a.D + 1)) * pow2f(-pd.t_out));
+            else
+                finish_views(y, accB, ray_bias ? lds_addr(ray_lds + wave * 256) + 64 * h : bias0 + 128 * (8 * a.D + 9),
+                             lds_scalar(layer_tab + 4 * (a.D + 1)) * pow2f(-pd.t_out));
             if constexpr (STORE) {
                 const unsigned off = 4u * ((unsigned)pt * (unsigned)a.st.hv_ld + 4u * (unsigned)h);
                 keep_tiles4<0>(a.st.hv, off, y);

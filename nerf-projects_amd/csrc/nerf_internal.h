@@ -26,6 +26,12 @@ constexpr int kBwdMaxOutRows = 8;           // output_linear rows the fused back
 constexpr int kPointsPerWave = 32;
 constexpr int kWavesPerGroup = 4;
 constexpr int kPointsPerGroup = kPointsPerWave * kWavesPerGroup;
+// Per-ray view bias (ray_view_bias_kernel -> nerf_mlp_h2_fold_ray_kernel): a ray's row of the table is the 128 entries of
+// u = b_vf + W_v[:, W:] gamma(dir) in the view layer's bias-block order [tile(4)][h(2)][16], then max(|d_x|, |d_y|, |d_z|, 1)
+// and three zeros: 33 pieces of 16 bytes.
+constexpr int kRayBiasEntries = 128;             // the view layer's units: the entries of u
+constexpr int kRayBiasMax = kRayBiasEntries;     // where max(|d|, 1) stands in a row
+constexpr int kRayBiasRow = kRayBiasEntries + 4;
 
 // ---- slot maps of the encoded tiles (kernel input side: mlp_inputs.h; weight side: pack_weights.cpp) ----------
 // Column of gamma(xyz) (nerf/embedder.py:28-65: [x y z | sin f0 xyz | cos f0 xyz | ...], 63 wide) held by slot
@@ -130,6 +136,11 @@ struct PackedNet {
     unsigned* d_fold_word = nullptr;
     int n_chunks_fold = 0;
     bool fold_dirty = false;
+    // The folded stream once more WITHOUT its last chunk, the gamma(dir) chunk, for nerf_mlp_h2_fold_ray_kernel (the per-ray view
+    // bias, MlpLaunch::ray_bias): chunks 0 .. n_chunks_fold - 2 of d_stream_fold as converted - the same fp16 pairs at the same
+    // scales, so the bias block and d_descale_fold serve both - followed by its own copy of its first kStreamTailChunks chunks.
+    // Cut on the device by refresh_fold.
+    uint32_t* d_stream_ray = nullptr;
     int n_chunks = 0;
     int n_bias_tiles = 0;
     uint32_t skip_in_mask = 0;   // bit i: trunk layer i reads [input_pts, h]
@@ -228,6 +239,11 @@ struct MlpLaunch {
     // jitter, density noise): those are training-time renders, which nerf_train_forward / nerf_train_step reproduce bit for
     // bit with kernels that keep feature_linear for the backward pass and so never fold.
     bool no_fold;
+    // The per-ray view bias (run_mlp sets both or neither; kInputRays, samples_per_ray and n_points multiples of 32, fold_word
+    // set): the folded twin of this launch is nerf_mlp_h2_fold_ray_kernel, which reads stream_ray (PackedNet::d_stream_ray) and
+    // takes row pt / samples_per_ray of ray_bias [n_rays][kRayBiasRow] in place of the view layer's bias tiles and gamma(dir) chunk.
+    const float* ray_bias;
+    const uint32_t* stream_ray;
 };
 
 // Fused backward-data pass (nerf_mlp_bwd_kernel): from d raw to the gradient at every pre-activation, one launch.
@@ -329,6 +345,10 @@ struct ViewFoldRefs {      // offsets into the (equalised) parameters; tail_off:
 hipError_t launch_view_fold(const float* params_eq, float* tail, const ViewFoldRefs& r, unsigned* word, hipStream_t s);
 hipError_t launch_view_fold_eligible(const float* gain, int D, const float* chunk_max, int first_view, unsigned* word,
                                      hipStream_t s);
+// table [n_rays][kRayBiasRow] of the per-ray view bias from the equalised parameters and their fold tail (refresh_kernels.hip);
+// the direction is the last three floats of a ray record
+hipError_t launch_ray_view_bias(const float* params_eq, const ViewFoldRefs& r, const float* rays, int ray_ld, int64_t n_rays,
+                                float* table, hipStream_t s);
 // the fp32 kernels' stream and bias block, likewise
 int refresh_f32(PackedNet& net, hipStream_t s);
 hipError_t launch_convert_stream_h2(const float* stream, const int* chunk_layer, int n_chunks, float* chunk_max,

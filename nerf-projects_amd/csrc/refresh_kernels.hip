@@ -294,6 +294,67 @@ __global__ void view_fold_eligible_kernel(const float* gain, int D, const float*
     word[0] = ok ? 1u : 0u;
 }
 
+// ---- the per-ray view bias (MlpLaunch::ray_bias) ------------------------------------------------------------------------
+// In ray mode with a multiple of 32 samples per ray a wavefront's 32 points share one ray, so the view layer's gamma(dir) term
+// is the same for all of them: u = b_vf + W_v[:, W:] gamma(dir) is formed here once per ray, from the equalised parameters and
+// their fold tail, and nerf_mlp_h2_fold_ray_kernel reads it where the folded kernel reads b_vf and runs the gamma(dir) chunk.
+// gamma(dir) is the encoder's (encode_point, mlp_inputs.h: the accurate sincosf of d * 2^k, d * 2^k exact); every entry is
+// accumulated in fp64 from b_vf over the encoding columns in index order and rounded once to fp32, so a ray's row depends on
+// nothing but the ray and the weights. A thread owns one entry of the row ([tile(4)][h(2)][16]: the view layer's bias-block
+// order) and keeps its 27 weights in registers; a workgroup walks its rays eight at a time, their encodings shared through LDS.
+constexpr int kRayBiasBatch = 8, kRayBiasPerBlock = 64;
+__global__ __launch_bounds__(kRayBiasEntries) void ray_view_bias_kernel(const float* params, const ViewFoldRefs refs, const float* rays,
+                                                                    int ray_ld, int64_t n_rays, float* table) {
+    __shared__ float g[kRayBiasBatch][32];      // gamma(dir) by encoding column (0 beyond n_dir); [27]: max(|d|, 1)
+    const int i = threadIdx.x;
+    const int feat = 32 * (i >> 5) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * ((i >> 4) & 1);      // acc_feature (pack_weights.cpp)
+    const int ld = refs.W + refs.n_dir;
+    const bool unit = feat < refs.n_view;      // (a narrower network's missing units: zero, as in its bias tiles)
+    float w[27];
+#pragma unroll
+    for (int c = 0; c < 27; ++c) w[c] = (unit && c < refs.n_dir) ? params[refs.wv_off + (size_t)feat * ld + refs.W + c] : 0.0f;
+    const float b = unit ? params[refs.tail_off + (size_t)refs.n_view * refs.W + feat] : 0.0f;
+    for (int q = i; q < kRayBiasBatch * 32; q += kRayBiasEntries) g[q >> 5][q & 31] = 0.0f;
+    const int64_t first = (int64_t)blockIdx.x * kRayBiasPerBlock;
+    const int64_t end = first + kRayBiasPerBlock < n_rays ? first + kRayBiasPerBlock : n_rays;
+    for (int64_t base = first; base < end; base += kRayBiasBatch) {
+        __syncthreads();      // the batch before has been read (first round: the zeros are in place)
+        if (i < kRayBiasBatch * 12) {
+            const int r = i / 12, k = (i % 12) / 3, c = i % 3;
+            const int64_t ray = base + r < end ? base + r : end - 1;
+            const float* d = rays + ray * ray_ld + ray_ld - 3;
+            if (3 + 6 * k + c < refs.n_dir) {
+                float sn, cs;
+                sincosf(d[c] * (float)(1 << k), &sn, &cs);
+                g[r][3 + 6 * k + c] = sn;
+                g[r][3 + 6 * k + 3 + c] = cs;
+            }
+            if (k == 0) g[r][c] = d[c];
+            // the bound load_inputs gives for |gamma(dir)| (v_max_f32 passes over a NaN component, there as here)
+            if (i % 12 == 0) g[r][27] = fmaxf(fmaxf(fabsf(d[0]), fabsf(d[1])), fmaxf(fabsf(d[2]), 1.0f));
+        }
+        __syncthreads();
+        for (int r = 0; r < kRayBiasBatch && base + r < end; ++r) {
+            double acc = (double)b;
+#pragma unroll
+            for (int c = 0; c < 27; ++c) acc = fma((double)w[c], (double)g[r][c], acc);
+            float* row = table + (base + r) * kRayBiasRow;
+            row[i] = (float)acc;
+            if (i < kRayBiasRow - kRayBiasEntries) row[kRayBiasMax + i] = i == 0 ? g[r][27] : 0.0f;
+        }
+    }
+}
+
+hipError_t launch_ray_view_bias(const float* params_eq, const ViewFoldRefs& r, const float* rays, int ray_ld, int64_t n_rays,
+                                float* table, hipStream_t s) {
+    if (n_rays <= 0) return hipSuccess;
+    if (!params_eq || !rays || !table || ray_ld < 11 || r.n_dir < 3 || r.n_dir > 27 || r.n_view < 1 || r.n_view > kRayBiasEntries)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ray_view_bias_kernel, dim3((unsigned)((n_rays + kRayBiasPerBlock - 1) / kRayBiasPerBlock)), dim3(kRayBiasEntries),
+                       0, s, params_eq, r, rays, ray_ld, n_rays, table);
+    return hipGetLastError();
+}
+
 hipError_t launch_view_fold(const float* params_eq, float* tail, const ViewFoldRefs& r, unsigned* word, hipStream_t s) {
     if (!params_eq || !tail || !word || r.W < 2 || r.W > kWidth || r.n_view < 1 || r.n_dir < 0) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(word, 0, 2 * sizeof(unsigned), s);

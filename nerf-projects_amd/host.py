@@ -69,6 +69,11 @@ class Context:
         feature_linear into views_linears.0, nerf_set_view_fold). On by default; results are valid either way."""
         check(self.lib.nerf_set_view_fold(self.handle, int(bool(on))))
 
+    def set_ray_view_bias(self, on=True):
+        """Whether folded renders of ray records with a multiple of 32 samples per ray take the view layer's gamma(dir) term
+        per ray instead of per point (nerf_set_ray_view_bias). On by default; sigma is the same bits either way."""
+        check(self.lib.nerf_set_ray_view_bias(self.handle, int(bool(on))))
+
     def view_fold_status(self, slot):
         """True if the next fp16-pair inference launch of the network in ``slot`` uses the view fold
         (nerf_view_fold_status). Synchronises."""
