@@ -1197,6 +1197,83 @@ typedef struct nerf_grid_depth_backward_args {
 int nerf_grid_depth_rays_taped(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_depth_taped_args* args);
 int nerf_grid_depth_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_depth_backward_args* args);
 
+/* Sparse voxel grid: floater views ------------------------------------------------------------------
+ * The labelled nodes of the connected components (section "connected components") projected into a camera: what svox2's
+ * opt/util/floater_visualization.py computes in Python loops on the host. Both calls scan the label tensor, one thread per
+ * node, and take the node's entry in a per-label table built by the caller: table[label] for 1 <= label <= n_labels, and 0
+ * (ignore) for label 0, a label outside that range or an entry of 0. Both are stream-ordered, allocate and synchronise
+ * nothing and return a status with nerf_last_error(). NDC cameras do not exist in nerf_grid_camera. At most 2^26 pixels.
+ *
+ * The projection of node (i, j, k), fp32, every operation rounded separately, no fused multiply-add, per axis a:
+ *   p_a = ((idx_a / reso_a) * 2 - 1) * radius_a + center_a
+ * This is the reference's formula and NOT grid2world: it has no + 0.5, so it is the voxel's lower corner, half a voxel from
+ * the node the renderer samples. It is kept, so that the images are the reference's.
+ *   q_r = ((w2c[r][0] p_0 + w2c[r][1] p_1) + w2c[r][2] p_2) + w2c[r][3]      r = 0, 1, 2;  w2c row-major [3, 4]
+ *   x = (q_0 / q_2) * fx + cx,  y = (q_1 / q_2) * fy + cy                    fx, fy, cx, cy: the camera's, rounded to fp32
+ * The node is VALID iff q_2 > 0, 0 <= x < width and 0 <= y < height (a NaN fails); (xi, yi) is the truncation of (x, y).
+ * The camera's c2w is checked and not read: the caller passes w2c, the inverse of the 4 x 4 c2w rounded to fp32.
+ *
+ * nerf_grid_floater_heatmap (project_floaters_to_view). For every node with a non-zero table entry:
+ *   rho = density_data[link] if 0 <= link < capacity, else 0; with min_density > 0 the node is dropped unless
+ *     rho >= min_density                                                      counters[0] += 1 for every node kept ("dense")
+ *   it must be valid and inside the heatmap: xi < out_width, yi < out_height  counters[1] += 1 ("in view")
+ *   with filter_occluded, d = depth[yi * width + xi] on the camera's [height, width] map; the node is visible iff
+ *     q_2 < d + 0.05 or d < 0.01. The reference compares the camera-space z with a length along the ray; that is kept.
+ *                                                                             counters[2] += 1 ("visible")
+ *   counts[yi * out_width + xi] += 1
+ * Then heatmap = the maximum of counts over the 3 x 3 neighbours that lie inside the image (cv2.dilate with its default
+ * border), as float. The reference dilates only if some count is non-zero; the maximum over an all-zero image is that image,
+ * so nothing has to be decided and nothing goes to the host. counts, counters and counter_slots are zeroed by the call;
+ * counter_slots is where the wavefronts add their sums, spread over 256 cache lines, before the second kernel adds them up
+ * into counters.
+ *
+ * nerf_grid_component_view (create_multi_object_voxel_overlay's far-to-near painter with its depth test, without the random
+ * subsampling to max_points_per_object that the reference has for speed only). The table holds the slot >= 1 to draw a label
+ * with. Every valid node with a slot covers the 21 pixels (xi + dx, yi + dy), dx^2 + dy^2 <= 5, that lie inside the camera's
+ * image: the disc is fixed here and not read from OpenCV's circle raster. slots[pixel] is the slot of the covering node
+ * with the smallest q_2, among equal q_2 the smallest slot, and 0 where no node covers the pixel. keys is a workspace of one
+ * uint64 per pixel, set to all ones by the call and lowered with (bits(q_2) << 32) | slot: q_2 > 0, so the bit pattern
+ * orders as the float does.
+ *
+ * Every atomic is an integer one (add on int32, min on uint64), so every result is deterministic: two calls give identical
+ * bits. */
+#define NERF_GRID_FLOATER_COUNTER_INTS 8192
+
+typedef struct nerf_grid_floater_heatmap_args {
+    size_t struct_size;
+    const int32_t* labels;      /* [dev] [X, Y, Z] of the grid                                                      */
+    const int32_t* table;       /* [dev] [n_labels + 1]: non-zero = a floater                                        */
+    int64_t n_labels;
+    float radius[3];            /* of the grid (positive, finite)                                                   */
+    float center[3];
+    float w2c[12];              /* [3, 4] row-major                                                                 */
+    float min_density;          /* <= 0: no density filter                                                          */
+    int32_t filter_occluded;
+    const float* depth;         /* [dev] [height, width] of the camera; may be NULL without filter_occluded         */
+    int32_t out_width, out_height; /* the heatmap's size (render_size), the camera's by default                      */
+    int32_t* counts;            /* [dev] [out_height, out_width] workspace: the counts before the dilation           */
+    int32_t* counters;          /* [dev] [3]: dense, in view, visible                                                */
+    int32_t* counter_slots;     /* [dev] [NERF_GRID_FLOATER_COUNTER_INTS] workspace                                  */
+    float* heatmap;             /* [dev] [out_height, out_width]                                                    */
+    void* stream;
+} nerf_grid_floater_heatmap_args;
+
+typedef struct nerf_grid_component_view_args {
+    size_t struct_size;
+    const int32_t* labels;      /* [dev] [X, Y, Z] of the grid                                                      */
+    const int32_t* table;       /* [dev] [n_labels + 1]: the slot >= 1 of a label, 0 = not drawn                     */
+    int64_t n_labels;
+    float radius[3];
+    float center[3];
+    float w2c[12];
+    uint64_t* keys;             /* [dev] [height, width] workspace                                                  */
+    int32_t* slots;             /* [dev] [height, width]                                                            */
+    void* stream;
+} nerf_grid_component_view_args;
+
+int nerf_grid_floater_heatmap(nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_floater_heatmap_args* args);
+int nerf_grid_component_view(nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_component_view_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,5 +27,8 @@ from .grid_resample import dilate_mask, resample_grid, weight_render  # noqa: F4
 from . import grid_components  # noqa: F401
 from .grid_components import (compute_all_advanced_metrics, compute_FDR, compute_MCQ, label_components,  # noqa: F401
                               remove_floaters)
+from . import grid_floater_views  # noqa: F401
+from .grid_floater_views import (component_view, floater_overlay_on_render, main_object_overlay, multi_object_overlay,  # noqa: F401
+                                 project_floaters_to_view)
 
 __version__ = "0.1.0"

@@ -35,6 +35,7 @@ EXPORTS = (
     "nerf_grid_depth_rays", "nerf_grid_depth_image",
     "nerf_grid_render_rays_taped", "nerf_grid_render_backward", "nerf_grid_sample_backward",
     "nerf_grid_depth_rays_taped", "nerf_grid_depth_backward",
+    "nerf_grid_floater_heatmap", "nerf_grid_component_view",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -43,6 +44,7 @@ NERF_OCC_EVALUATE, NERF_OCC_EMPTY = 0, 1
 NERF_GRID_TV_DENSITY, NERF_GRID_TV_SH = 0, 1
 NERF_GRID_OPTIM_RMSPROP, NERF_GRID_OPTIM_SGD = 0, 1
 NERF_GRID_DEPTH_EXPECTED, NERF_GRID_DEPTH_THRESHOLD, NERF_GRID_DEPTH_RAYLEN = 0, 1, 2
+NERF_GRID_FLOATER_COUNTER_INTS = 8192
 
 
 class NerfArch(C.Structure):
@@ -259,6 +261,18 @@ class GridDepthBackwardArgs(_Sized):
                 ("stream", C.c_void_p)]
 
 
+class GridFloaterHeatmapArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("labels", _FP), ("table", _FP), ("n_labels", C.c_int64), ("radius", C.c_float * 3),
+                ("center", C.c_float * 3), ("w2c", C.c_float * 12), ("min_density", C.c_float), ("filter_occluded", C.c_int32),
+                ("depth", _FP), ("out_width", C.c_int32), ("out_height", C.c_int32), ("counts", _FP), ("counters", _FP),
+                ("counter_slots", _FP), ("heatmap", _FP), ("stream", C.c_void_p)]
+
+
+class GridComponentViewArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("labels", _FP), ("table", _FP), ("n_labels", C.c_int64), ("radius", C.c_float * 3),
+                ("center", C.c_float * 3), ("w2c", C.c_float * 12), ("keys", _FP), ("slots", _FP), ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -449,6 +463,10 @@ def load():
     lib.nerf_grid_depth_rays_taped.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridDepthTapedArgs)]
     lib.nerf_grid_depth_backward.restype = i32
     lib.nerf_grid_depth_backward.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridDepthBackwardArgs)]
+    lib.nerf_grid_floater_heatmap.restype = i32
+    lib.nerf_grid_floater_heatmap.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridFloaterHeatmapArgs)]
+    lib.nerf_grid_component_view.restype = i32
+    lib.nerf_grid_component_view.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridComponentViewArgs)]
     _lib = lib
     return lib
 
