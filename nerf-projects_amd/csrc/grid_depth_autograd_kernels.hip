@@ -3,9 +3,9 @@
 // results. Semantics: include/nerf_mi355x.h, "Sparse voxel grid: gradients of depth and log_transmit for autograd". Design,
 // generated-code figures and measurements: DESIGN.md section 7i.
 //
-// All three marches here (taped forward, the backward's look-ahead for the stop, the backward itself) are one function,
-// depth_march, on the device functions of grid_device.h: the set-up, the additions of t, the skip rule, the stall rule, the
-// links and the interpolated density are the forward's, so the sample lattice is the forward's by construction.
+// All three marches here (taped forward, the backward's look-ahead for the stop, the backward itself) are grid_march of
+// grid_device.h, the function grid_depth_kernel calls: setup_ray, the additions of t and the stall rule, march_cell, the skip
+// byte and skip_jump, load_links and sample_sigma are there once, so the sample lattice is the forward's by construction.
 // Mapping: a ray owns a group of kRayLanes = 32 adjacent lanes in both kernels. Every lane of the group walks the ray - the
 // same addresses, so a group's loads are one request, and control flow is uniform inside a group - and in the backward lane c
 // of the group's first 8 issues the add of corner c. A batch of a few thousand rays is bound by the latency of its longest
@@ -23,46 +23,6 @@ namespace {
 
 constexpr int kRayLanes = 32;     // adjacent lanes that walk one ray together; the backward's lanes 0..7 add one corner each
 
-// weight of corner c (x, y, z bits) = (wx * wy) * wz, in that order
-__device__ __forceinline__ float corner_weight(int c, const float wa[3], const float wb[3]) {
-    return mul(mul((c & 4) ? wb[0] : wa[0], (c & 2) ? wb[1] : wa[1]), (c & 1) ? wb[2] : wa[2]);
-}
-
-// The march of grid_depth_kernel in its expected mode, operation for operation, for a ray that is marched
-// (rs.ok && rs.tmin <= rs.tmax): at(t, lk, wa, wb, sigma) is called at every sample with sigma > opt.sigma_thresh, in march
-// order, and returns true where the ray stops.
-template <bool SKIP, class F>
-__device__ __forceinline__ void depth_march(const GridDev& g, const GridRenderOpt& opt, const GridRay& rs, F&& at) {
-    float t = rs.tmin;
-    while (t <= rs.tmax) {
-        // the render's stall rule: every pass advances t, a ray whose t no longer changes is left
-        const float t_next = add(t, opt.step_size);
-        if (!(t_next > t)) break;
-        float wa[3], wb[3];
-        const int base = march_cell(g, rs, t, wa, wb);
-        if (SKIP) {
-            const int sv = rs.skip_ok ? g.skip[base] : 0;
-            if (sv > 0) {
-                t = skip_jump(t, t_next, sv, opt.step_size);
-                continue;
-            }
-        }
-        int lk[8];
-        load_links(g, base, lk);
-        const float sigma = sample_sigma(g, lk, wa, wb);
-        if (sigma > opt.sigma_thresh && at(t, lk, wa, wb, sigma)) break;
-        t = t_next;
-    }
-}
-
-__device__ __forceinline__ void load_ray(const float* origins, const float* dirs, int64_t ray, GridRay& rs) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        rs.o[i] = origins[ray * 3 + i];
-        rs.d[i] = dirs[ray * 3 + i];
-    }
-}
-
 template <int GL, bool SKIP>
 __global__ __launch_bounds__(kGridThreads) void grid_depth_taped_kernel(GridDev g, GridRenderOpt opt, GridDepthTaped r) {
     const int64_t tid = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
@@ -77,7 +37,8 @@ __global__ __launch_bounds__(kGridThreads) void grid_depth_taped_kernel(GridDev 
     if (rs.ok && rs.tmin <= rs.tmax) {
         const float world_step = mul(opt.step_size, rs.delta_scale);
         const float neg_step = -opt.step_size;
-        depth_march<SKIP>(g, opt, rs, [&](float t, const int*, const float*, const float*, float sigma) {
+        grid_march<SKIP>(g, opt, rs, [&](float t, const int*, const float*, const float*, float sigma) {
+            if (!(sigma > opt.sigma_thresh)) return false;
             const float a = mul(mul(neg_step, sigma), rs.delta_scale);
             const float weight = mul(expf(log_t), sub(1.0f, expf(a)));
             const float term = mul(mul(weight, t / opt.step_size), world_step);
@@ -116,7 +77,8 @@ __global__ __launch_bounds__(kGridThreads) void grid_depth_bwd_kernel(GridDev g,
         // its end, so such a ray is walked once without adds first.
         float log_t = 0.0f;
         bool stopped = false;
-        depth_march<SKIP>(g, opt, rs, [&](float, const int*, const float*, const float*, float sigma) {
+        grid_march<SKIP>(g, opt, rs, [&](float, const int*, const float*, const float*, float sigma) {
+            if (!(sigma > opt.sigma_thresh)) return false;
             log_t = add(log_t, mul(mul(neg_step, sigma), rs.delta_scale));
             stopped = expf(log_t) < opt.stop_thresh;
             return stopped;
@@ -131,7 +93,8 @@ __global__ __launch_bounds__(kGridThreads) void grid_depth_bwd_kernel(GridDev g,
     const float world_step = mul(opt.step_size, rs.delta_scale);
     const float step_ds = world_step;
     float log_t = 0.0f;
-    depth_march<SKIP>(g, opt, rs, [&](float t, const int* lk, const float* wa, const float* wb, float sigma) {
+    grid_march<SKIP>(g, opt, rs, [&](float t, const int* lk, const float* wa, const float* wb, float sigma) {
+        if (!(sigma > opt.sigma_thresh)) return false;
         const float a = mul(mul(neg_step, sigma), rs.delta_scale);
         const float weight = mul(expf(log_t), sub(1.0f, expf(a)));
         const float tau = t / opt.step_size;

@@ -2,9 +2,10 @@
 // Semantics: include/nerf_mi355x.h, "Sparse voxel grid: depth and ray lengths". Design and measurements: DESIGN.md section 7g.
 //
 // Mapping: one lane per ray. A depth march reads densities only - per sample one skip byte, 8 links and at most 8 floats, no
-// SH rows - so there is nothing for the render kernel's lanes-per-coefficient to share out: a lane walks its ray alone with the
-// device functions of grid_device.h (the same set-up, the same additions of t, the same skip rule, so the sample lattice is
-// the render's, bit for bit). No LDS, no scratch, no atomics, no shuffles: every result depends on its own ray only.
+// SH rows - so there is nothing for the render kernel's lanes-per-coefficient to share out: a lane walks its ray alone with
+// setup_ray and grid_march of grid_device.h, the functions the render kernel calls (the additions of t and the stall rule,
+// march_cell, the skip byte and skip_jump, load_links and sample_sigma are there once, so the sample lattice is the render's,
+// bit for bit). No LDS, no scratch, no atomics, no shuffles: every result depends on its own ray only.
 // The image form makes its rays in the launch. A wavefront takes an 8 x 8 tile of pixels (lane = 8 * row + column in the
 // tile) rather than 64 pixels of a row: the rays of a tile stay within a few cells of one another for the whole march, so the
 // wavefront's 64 link and density loads fall on fewer cache lines, and its rays end at more nearly the same sample (less of
@@ -43,11 +44,7 @@ __global__ __launch_bounds__(kGridThreads) void grid_depth_kernel(GridDev g, Gri
     } else {
         ray = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
         if (ray >= r.n_rays) return;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            rs.o[i] = r.origins[ray * 3 + i];
-            rs.d[i] = r.dirs[ray * 3 + i];
-        }
+        load_ray(r.origins, r.dirs, ray, rs);
     }
     setup_ray<SKIP>(g, opt, rs);
     if (MODE == NERF_GRID_DEPTH_RAYLEN) {
@@ -59,40 +56,23 @@ __global__ __launch_bounds__(kGridThreads) void grid_depth_kernel(GridDev g, Gri
     if (rs.ok && rs.tmin <= rs.tmax) {
         const float world_step = mul(opt.step_size, rs.delta_scale);
         const float neg_step = -opt.step_size;
-        float t = rs.tmin;
-        while (t <= rs.tmax) {
-            // the render's stall rule: every pass advances t, a ray whose t no longer changes is left
-            const float t_next = add(t, opt.step_size);
-            if (!(t_next > t)) break;
-            float wa[3], wb[3];
-            const int base = march_cell(g, rs, t, wa, wb);
-            if (SKIP) {
-                const int sv = rs.skip_ok ? g.skip[base] : 0;
-                if (sv > 0) {
-                    t = skip_jump(t, t_next, sv, opt.step_size);
-                    continue;
-                }
-            }
-            int lk[8];
-            load_links(g, base, lk);
-            const float sigma = sample_sigma(g, lk, wa, wb);
+        grid_march<SKIP>(g, opt, rs, [&](float t, const int*, const float*, const float*, float sigma) {
             if (MODE == NERF_GRID_DEPTH_THRESHOLD) {
-                if (sigma > r.sigma_thresh) {
-                    depth = mul(t / opt.step_size, world_step);
-                    break;
-                }
-            } else if (sigma > opt.sigma_thresh) {
-                const float a = mul(mul(neg_step, sigma), rs.delta_scale);
-                const float weight = mul(expf(log_t), sub(1.0f, expf(a)));
-                depth = add(depth, mul(mul(weight, t / opt.step_size), world_step));
-                log_t = add(log_t, a);
-                if (expf(log_t) < opt.stop_thresh) {
-                    log_t = -1e3f;
-                    break;
-                }
+                if (!(sigma > r.sigma_thresh)) return false;
+                depth = mul(t / opt.step_size, world_step);
+                return true;
             }
-            t = t_next;
-        }
+            if (!(sigma > opt.sigma_thresh)) return false;
+            const float a = mul(mul(neg_step, sigma), rs.delta_scale);
+            const float weight = mul(expf(log_t), sub(1.0f, expf(a)));
+            depth = add(depth, mul(mul(weight, t / opt.step_size), world_step));
+            log_t = add(log_t, a);
+            if (expf(log_t) < opt.stop_thresh) {
+                log_t = -1e3f;
+                return true;
+            }
+            return false;
+        });
     }
     r.depth[ray] = depth;
     if (MODE == NERF_GRID_DEPTH_EXPECTED && r.log_transmit) r.log_transmit[ray] = log_t;

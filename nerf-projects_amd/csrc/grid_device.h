@@ -1,7 +1,10 @@
 // Sparse voxel grid: the device functions the grid kernels (rendering, training, resampling, components) share, so that all
 // walk the same sample lattice with the same fp32 operations: rounded arithmetic, the SH basis, the trilinear set-up, the ray
-// set-up and the steps of the march including the skip rule. Semantics: include/nerf_mi355x.h, "Sparse voxel grid".
+// set-up, the one march (grid_march: the stall rule, the cell, the skip rule, the links, the density) and, on it, the colour
+// march forward (march_colour) and backward (march_colour_bwd). Semantics: include/nerf_mi355x.h, "Sparse voxel grid".
 #pragma once
+#include <type_traits>
+
 #include "grid_internal.h"
 
 namespace nerf {
@@ -10,6 +13,17 @@ namespace {
 constexpr int kGridThreads = 256;
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kGridThreads - 1) / kGridThreads); }      // one thread per item
+
+// f(std::integral_constant<int, B>) for the basis_dim B the kernels are built for
+template <class F>
+hipError_t dispatch_basis(int basis_dim, F&& f) {
+    switch (basis_dim) {
+        case 9: return f(std::integral_constant<int, 9>());
+        case 4: return f(std::integral_constant<int, 4>());
+        case 1: return f(std::integral_constant<int, 1>());
+    }
+    return hipErrorInvalidValue;
+}
 
 // flat C-order index of a node (z fastest) -> its coordinates
 __device__ __forceinline__ void node_to_xyz(int64_t idx, const int32_t size[3], int& ix, int& iy, int& iz) {
@@ -24,6 +38,25 @@ __device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b);
 
 // lanes of a wavefront that walk one ray: one SH coefficient per lane
 template <int B> struct GroupLanes { static constexpr int value = B == 9 ? 32 : (B == 4 ? 16 : 4); };
+
+// this thread in that layout; a whole group has the same ray (and leaves together where ray >= n_rays)
+struct GroupLane {
+    int64_t ray;
+    int lane;      // of the group
+    bool busy;     // lane < 3 B: it owns coefficient k of channel col / B
+    int col, k;    // idle lanes of a group read column 0 and contribute nothing
+};
+template <int B>
+__device__ __forceinline__ GroupLane group_lane() {
+    const int64_t tid = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
+    GroupLane gl;
+    gl.ray = tid / GroupLanes<B>::value;
+    gl.lane = (int)(tid % GroupLanes<B>::value);
+    gl.busy = gl.lane < 3 * B;
+    gl.col = gl.busy ? gl.lane : 0;
+    gl.k = gl.col % B;
+    return gl;
+}
 
 // svox2 utils.eval_sh_bases, fp32, the reference's operation order
 __device__ __forceinline__ float sh_basis(int k, float x, float y, float z) {
@@ -56,6 +89,22 @@ __device__ __forceinline__ float trilerp(const float v[8], const float wa[3], co
     const float c0 = add(mul(c00, wa[1]), mul(c01, wb[1]));
     const float c1 = add(mul(c10, wa[1]), mul(c11, wb[1]));
     return add(mul(c0, wa[0]), mul(c1, wb[0]));
+}
+
+// base cell (returned: its index into links / skip) and trilinear weights of a point in grid coordinates
+__device__ __forceinline__ int point_cell(const GridDev& g, const float x[3], float wa[3], float wb[3]) {
+    int l[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        cell_of(x[i], g.size[i], l[i], wb[i]);
+        wa[i] = sub(1.0f, wb[i]);
+    }
+    return (l[0] * g.size[1] + l[1]) * g.size[2] + l[2];
+}
+
+// weight of corner c (x, y, z bits) = (wx * wy) * wz, in that order
+__device__ __forceinline__ float corner_weight(int c, const float wa[3], const float wb[3]) {
+    return mul(mul((c & 4) ? wb[0] : wa[0], (c & 2) ? wb[1] : wa[1]), (c & 1) ? wb[2] : wa[2]);
 }
 
 // the 8 links of base cell `base` (corner order 000, 001, 010, ..., 111 = x, y, z bits); anything outside [0, capacity) is -1
@@ -93,6 +142,14 @@ struct GridRay {
     bool ok;               // the set-up is finite: the ray is marched (if tmin <= tmax)
     bool skip_ok;          // skip data may be used (positions exact to 1/16)
 };
+
+__device__ __forceinline__ void load_ray(const float* origins, const float* dirs, int64_t ray, GridRay& rs) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        rs.o[i] = origins[ray * 3 + i];
+        rs.d[i] = dirs[ray * 3 + i];
+    }
+}
 
 // in: r.o, r.d = world origin and direction (need not be unit)
 template <bool SKIP>
@@ -137,15 +194,10 @@ __device__ __forceinline__ void setup_ray(const GridDev& g, const GridRenderOpt&
     r.skip_ok = SKIP && reach_o < kGridSkipMaxT && fabsf(tmin) < kGridSkipMaxT && fabsf(tmax) < kGridSkipMaxT;
 }
 
-// the sample at t: base cell (returned: its index into links / skip) and trilinear weights
+// the sample at t: its point_cell
 __device__ __forceinline__ int march_cell(const GridDev& g, const GridRay& r, float t, float wa[3], float wb[3]) {
-    int l[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        cell_of(add(r.o[i], mul(t, r.d[i])), g.size[i], l[i], wb[i]);
-        wa[i] = sub(1.0f, wb[i]);
-    }
-    return (l[0] * g.size[1] + l[1]) * g.size[2] + l[2];
+    const float x[3] = {add(r.o[0], mul(t, r.d[0])), add(r.o[1], mul(t, r.d[1])), add(r.o[2], mul(t, r.d[2]))};
+    return point_cell(g, x, wa, wb);
 }
 
 // The skip rule at a sample t0 in a cell of skip value sv > 0: every node within sv - 1 cells of this cell's corners is
@@ -185,6 +237,136 @@ __device__ __forceinline__ float shade_channel(const GridDev& g, const int lk[8]
         if (k + off < B) part = add(part, up);
     }
     return part;
+}
+
+// ---- the one march --------------------------------------------------------------------------------------------------------
+// Every kernel that walks a ray walks it here, so all of them visit the same samples, bit for bit. For a ray that is marched
+// (rs.ok && rs.tmin <= rs.tmax): at(t, lk, wa, wb, sigma) is called at every sample whose links are loaded - every sample
+// the skip rule does not pass over - in march order. The callback applies its own density threshold and returns true where
+// the ray ends. The first sample needs no test against tmax (the precondition is that test), so the loop tests at its end:
+// written with the test at its head, the same march cost the plain render 2 % (profiles/grid_march_ab.md).
+template <bool SKIP, class F>
+__device__ __forceinline__ void grid_march(const GridDev& g, const GridRenderOpt& opt, const GridRay& rs, F&& at) {
+    float t = rs.tmin;
+    do {
+        // the march ends unconditionally: every pass through this loop advances t by at least one addition of step_size,
+        // and a ray whose t no longer changes under that addition (t so large that step_size is below half an ulp) is left
+        // at once
+        const float t_next = add(t, opt.step_size);
+        if (!(t_next > t)) break;
+        float wa[3], wb[3];
+        const int base = march_cell(g, rs, t, wa, wb);
+        if (SKIP) {
+            const int sv = rs.skip_ok ? g.skip[base] : 0;
+            if (sv > 0) {
+                t = skip_jump(t, t_next, sv, opt.step_size);
+                continue;
+            }
+        }
+        int lk[8];
+        load_links(g, base, lk);
+        if (at(t, lk, wa, wb, sample_sigma(g, lk, wa, wb))) break;
+        t = t_next;
+    } while (t <= rs.tmax);
+}
+
+// ---- the colour march, forward --------------------------------------------------------------------------------------------
+// what lane (channel, coefficient) of a ray's group holds after it; outv and tot are complete in the lanes with k == 0
+struct Colour {
+    float outv = 0.0f, log_t = 0.0f;      // the channel with its background term; log_transmit (-1e3 where the ray stopped)
+    double tot = 0.0;                      // TAPE: the channel once more, as the fp64 sum of its exact terms
+    // COUNT: samples whose links were loaded / that were shaded. 32 bits hold a ray's: t advances only while step_size is
+    // above half an ulp of t, |t| < 2^24 step_size, by at least half a step_size per sample: fewer than 2^26 samples
+    unsigned visited = 0, shaded = 0;
+};
+
+// grid_render_kernel, grid_taped_kernel and the first march of grid_fused_kernel: at every sample above sigma_thresh the
+// channel is shaded, weighted and accumulated, and the ray stops below stop_thresh. A ray that is not marched is background.
+template <int B, bool SKIP, bool TAPE, bool COUNT>
+__device__ __forceinline__ Colour march_colour(const GridDev& g, const GridRenderOpt& opt, const GridRay& rs, const GroupLane& gl,
+                                               float yk) {
+    Colour c;
+    if (rs.ok && rs.tmin <= rs.tmax) {
+        const float neg_step = -opt.step_size;
+        grid_march<SKIP>(g, opt, rs, [&](float, const int* lk, const float* wa, const float* wb, float sigma) {
+            if (COUNT) ++c.visited;
+            if (!(sigma > opt.sigma_thresh)) return false;
+            if (COUNT) ++c.shaded;
+            const float part = shade_channel<B>(g, lk, wa, wb, gl.col, gl.k, yk);
+            const float a = mul(mul(neg_step, sigma), rs.delta_scale);
+            const float weight = mul(expf(c.log_t), sub(1.0f, expf(a)));
+            const float colour = fmaxf(add(part, 0.5f), 0.0f);
+            c.outv = add(c.outv, mul(weight, colour));
+            if (TAPE) c.tot += (double)weight * (double)colour;      // (a product of two floats is exact in a double)
+            c.log_t = add(c.log_t, a);
+            if (expf(c.log_t) < opt.stop_thresh) {
+                c.log_t = -1e3f;
+                return true;
+            }
+            return false;
+        });
+    }
+    c.outv = add(c.outv, mul(expf(c.log_t), opt.background_brightness));
+    if (TAPE) c.tot += (double)expf(c.log_t) * (double)opt.background_brightness;
+    return c;
+}
+
+// ---- the colour march, backward -------------------------------------------------------------------------------------------
+// grid_render_bwd_kernel and the second march of grid_fused_kernel, for a ray that is marched: the same lattice, and at every
+// shaded sample the gradients are scattered into the 8 corner rows. gc[c] = d loss / d rgb[c]. r.grad_sh, r.grad_density and
+// r.mask are written where want_sh (false in idle lanes), want_density and want_mask say so.
+// remaining[c] = what the samples not yet passed, and the background, still add to channel c; it starts as the forward's
+// `tot`. It is the one quantity of the backward that is a difference of large, nearly equal sums (the colour minus what the
+// passed samples gave); in fp32 its rounding, 6e-8 of the whole colour, is a relative 1e-3 of the small density gradients
+// behind a bright sample, which RMSProp's g / (sqrt(rms) + eps) turns into density errors of 1e-3. Kept in fp64, built from
+// and reduced by the very same exact products, it is exact to 1e-16 of the colour; everything else is fp32.
+template <int B, bool SKIP, class R>
+__device__ __forceinline__ void march_colour_bwd(const GridDev& g, const GridRenderOpt& opt, const GridRay& rs, const GroupLane& gl,
+                                                 float yk, const float gc[3], double remaining[3], const R& r, bool want_sh,
+                                                 bool want_density, bool want_mask) {
+    constexpr int GL = GroupLanes<B>::value;
+    constexpr int DL = GL < 8 ? GL : 8;      // lanes of a group that share the 8 density adds
+    const float g_own = gl.col / B == 0 ? gc[0] : (gl.col / B == 1 ? gc[1] : gc[2]);
+    const float step_ds = mul(opt.step_size, rs.delta_scale);
+    const float neg_step = -opt.step_size;
+    float log_t = 0.0f;
+    grid_march<SKIP>(g, opt, rs, [&](float, const int* lk, const float* wa, const float* wb, float sigma) {
+        if (!(sigma > opt.sigma_thresh)) return false;
+        const float part = shade_channel<B>(g, lk, wa, wb, gl.col, gl.k, yk);
+        const float raw = add(part, 0.5f);      // complete in the lanes with k == 0
+        const float a = mul(mul(neg_step, sigma), rs.delta_scale);
+        const float weight = mul(expf(log_t), sub(1.0f, expf(a)));
+        log_t = add(log_t, a);
+        float dot = 0.0f, raw_own = 0.0f;
+        double accum64 = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float rc = __shfl(raw, c * B, GL);
+            const float colour = fmaxf(rc, 0.0f);
+            dot = add(dot, mul(colour, gc[c]));
+            remaining[c] -= (double)weight * (double)colour;
+            accum64 += remaining[c] * (double)gc[c];
+            if (gl.col / B == c) raw_own = rc;
+        }
+        const float accum = (float)accum64;
+        const float d_sigma = mul(step_ds, sub(mul(expf(log_t), dot), accum));
+        // max(0, .) passes the gradient where its argument is >= 0 (torch.clamp_min)
+        const float d_coef = raw_own >= 0.0f ? mul(mul(weight, yk), g_own) : 0.0f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            if (lk[c] < 0) continue;
+            const float w8 = corner_weight(c, wa, wb);
+            if (want_sh) {
+                const float v = mul(w8, d_coef);
+                if (v != 0.0f) atomicAdd(&r.grad_sh[(int64_t)lk[c] * (3 * B) + gl.col], v);
+            }
+            if (gl.lane == c % DL) {
+                if (want_density) atomicAdd(&r.grad_density[lk[c]], mul(w8, d_sigma));
+                if (want_mask) r.mask[lk[c]] = 1;
+            }
+        }
+        return expf(log_t) < opt.stop_thresh;
+    });
 }
 
 }  // namespace

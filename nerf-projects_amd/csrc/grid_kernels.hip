@@ -9,7 +9,9 @@
 // 12 B * B row is one contiguous read by the group - interpolates it, multiplies by Y_k and the B lanes of a channel are
 // summed with __shfl_down inside the group. All control flow is uniform inside a group, so a shuffle only ever reads lanes
 // that execute it. Groups of a wavefront diverge (rays end at different t, samples are shaded or not): the lanes of a
-// finished or unshaded ray are masked off by EXEC while the other group works. No LDS, no scratch, no atomics (except in the
+// finished or unshaded ray are masked off by EXEC while the other group works. The lane decode (group_lane), the march
+// (grid_march) and the colour accumulated along it (march_colour) are grid_device.h's, shared with the taped, fused, depth
+// and backward kernels: all of them visit the same samples. No LDS, no scratch, no atomics (except in the
 // instrumented launch that counts samples), 256-thread workgroups and few registers so that every SIMD holds its 8 waves:
 // the kernel is bound by the dependent link -> row loads, and waves in flight are what hides them.
 #include <algorithm>
@@ -34,94 +36,34 @@ __global__ __launch_bounds__(kGridThreads) void grid_gen_rays_kernel(GridCam cam
 
 template <int B, bool IMAGE, bool SKIP, bool COUNT>
 __global__ __launch_bounds__(kGridThreads) void grid_render_kernel(GridDev g, GridRenderOpt opt, GridRender r) {
-    constexpr int GL = GroupLanes<B>::value;
-    const int64_t tid = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
-    const int64_t ray = tid / GL;
-    const int lane = (int)(tid % GL);
-    if (ray >= r.n_rays) return;      // (a whole group leaves together)
-    const bool busy = lane < 3 * B;
-    const int col = busy ? lane : 0;  // idle lanes of a group read column 0 and contribute nothing
-    const int k = col % B;
-
+    const GroupLane gl = group_lane<B>();
+    if (gl.ray >= r.n_rays) return;
     GridRay rs;
-    if (IMAGE) {
-        camera_ray(r.cam, ray, rs.o, rs.d);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            rs.o[i] = r.origins[ray * 3 + i];
-            rs.d[i] = r.dirs[ray * 3 + i];
-        }
-    }
+    if (IMAGE)
+        camera_ray(r.cam, gl.ray, rs.o, rs.d);
+    else
+        load_ray(r.origins, r.dirs, gl.ray, rs);
     setup_ray<SKIP>(g, opt, rs);
-    const float yk = busy ? sh_basis(k, rs.v[0], rs.v[1], rs.v[2]) : 0.0f;
-
-    float outv = 0.0f, log_t = 0.0f;
-    unsigned long long visited = 0, shaded = 0;
-    if (rs.ok && rs.tmin <= rs.tmax) {
-        const float neg_step = -opt.step_size;
-        float t = rs.tmin;
-        while (t <= rs.tmax) {
-            // the march ends unconditionally: every pass through this loop advances t by at least one addition of
-            // step_size, and a ray whose t no longer changes under that addition (t so large that step_size is below half
-            // an ulp) is left at once
-            const float t_next = add(t, opt.step_size);
-            if (!(t_next > t)) break;
-            float wa[3], wb[3];
-            const int base = march_cell(g, rs, t, wa, wb);
-            if (SKIP) {
-                const int sv = rs.skip_ok ? g.skip[base] : 0;
-                if (sv > 0) {
-                    t = skip_jump(t, t_next, sv, opt.step_size);
-                    continue;
-                }
-            }
-            if (COUNT) ++visited;      // samples whose links are loaded
-            int lk[8];
-            load_links(g, base, lk);
-            const float sigma = sample_sigma(g, lk, wa, wb);
-            if (sigma > opt.sigma_thresh) {
-                if (COUNT) ++shaded;
-                const float part = shade_channel<B>(g, lk, wa, wb, col, k, yk);
-                const float a = mul(mul(neg_step, sigma), rs.delta_scale);
-                const float weight = mul(expf(log_t), sub(1.0f, expf(a)));
-                outv = add(outv, mul(weight, fmaxf(add(part, 0.5f), 0.0f)));
-                log_t = add(log_t, a);
-                if (expf(log_t) < opt.stop_thresh) {
-                    log_t = -1e3f;
-                    break;
-                }
-            }
-            t = t_next;
-        }
-    }
-    outv = add(outv, mul(expf(log_t), opt.background_brightness));
-    if (busy && k == 0) r.rgb[ray * 3 + col / B] = outv;
-    if (lane == 0) {
-        if (r.log_transmit) r.log_transmit[ray] = log_t;
+    const float yk = gl.busy ? sh_basis(gl.k, rs.v[0], rs.v[1], rs.v[2]) : 0.0f;
+    const Colour c = march_colour<B, SKIP, false, COUNT>(g, opt, rs, gl, yk);
+    if (gl.busy && gl.k == 0) r.rgb[gl.ray * 3 + gl.col / B] = c.outv;
+    if (gl.lane == 0) {
+        if (r.log_transmit) r.log_transmit[gl.ray] = c.log_t;
         if (COUNT) {
-            atomicAdd(&r.counters[0], visited);
-            atomicAdd(&r.counters[1], shaded);
+            atomicAdd(&r.counters[0], (unsigned long long)c.visited);
+            atomicAdd(&r.counters[1], (unsigned long long)c.shaded);
         }
     }
 }
 
 template <int B, bool IMAGE, bool SKIP>
 hipError_t launch_render_b(const GridDev& g, const GridRenderOpt& o, const GridRender& r, hipStream_t s) {
-    const int64_t threads = r.n_rays * GroupLanes<B>::value;
-    const unsigned blocks = (unsigned)((threads + kGridThreads - 1) / kGridThreads);
+    const unsigned blocks = blocks_for(r.n_rays * GroupLanes<B>::value);
     if (r.counters)
         grid_render_kernel<B, IMAGE, SKIP, true><<<blocks, kGridThreads, 0, s>>>(g, o, r);
     else
         grid_render_kernel<B, IMAGE, SKIP, false><<<blocks, kGridThreads, 0, s>>>(g, o, r);
     return hipGetLastError();
-}
-
-template <int B>
-hipError_t launch_render_basis(const GridDev& g, const GridRenderOpt& o, const GridRender& r, hipStream_t s) {
-    const bool image = r.origins == nullptr, skip = g.skip != nullptr;
-    if (image) return skip ? launch_render_b<B, true, true>(g, o, r, s) : launch_render_b<B, true, false>(g, o, r, s);
-    return skip ? launch_render_b<B, false, true>(g, o, r, s) : launch_render_b<B, false, false>(g, o, r, s);
 }
 
 // one thread per (point, output column): column 0 = density, 1 + j = SH column j
@@ -132,17 +74,14 @@ __global__ __launch_bounds__(kGridThreads) void grid_sample_kernel(GridDev g, co
     const int64_t p = tid / cols;
     const int j = (int)(tid % cols);
     if (p >= n) return;
-    int l[3];
-    float wa[3], wb[3];
+    float x[3], wa[3], wb[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        float x = points[p * 3 + i];
-        if (!grid_coords) x = add(g.offset[i], mul(x, g.scaling[i]));
-        cell_of(x, g.size[i], l[i], wb[i]);
-        wa[i] = sub(1.0f, wb[i]);
+        x[i] = points[p * 3 + i];
+        if (!grid_coords) x[i] = add(g.offset[i], mul(x[i], g.scaling[i]));
     }
     int lk[8];
-    load_links(g, (l[0] * g.size[1] + l[1]) * g.size[2] + l[2], lk);
+    load_links(g, point_cell(g, x, wa, wb), lk);
     float cv[8];
     const int row = 3 * g.basis_dim;
 #pragma unroll
@@ -162,7 +101,8 @@ __global__ __launch_bounds__(kGridThreads) void grid_skip_init_kernel(GridDev g,
     const int64_t n = (int64_t)g.size[0] * g.size[1] * g.size[2];
     const int64_t idx = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
     if (idx >= n) return;
-    const int kz = (int)(idx % g.size[2]), jy = (int)((idx / g.size[2]) % g.size[1]), ix = (int)(idx / ((int64_t)g.size[2] * g.size[1]));
+    int ix, jy, kz;
+    node_to_xyz(idx, g.size, ix, jy, kz);
     uint8_t v = 0;
     if (ix < g.size[0] - 1 && jy < g.size[1] - 1 && kz < g.size[2] - 1) {
         int lk[8];
@@ -183,6 +123,7 @@ __global__ __launch_bounds__(kGridThreads) void grid_skip_grow_kernel(GridDev g,
     if (idx >= n) return;
     if (skip[idx] != r) return;
     const int sz = g.size[2], sy = g.size[1];
+    // (node_to_xyz spelt out on sz, sy: through the function the 31 rounds of accelerate() measured 15 % slower)
     const int kz = (int)(idx % sz), jy = (int)((idx / sz) % sy), ix = (int)(idx / ((int64_t)sz * sy));
     bool all = true;
     for (int a = -1; a <= 1; ++a)
@@ -230,12 +171,12 @@ __global__ __launch_bounds__(kGridThreads) void grid_project_sh_kernel(const flo
 
 hipError_t launch_grid_render(const GridDev& g, const GridRenderOpt& o, const GridRender& r, hipStream_t s) {
     if (r.n_rays <= 0) return hipSuccess;
-    switch (g.basis_dim) {
-        case 9: return launch_render_basis<9>(g, o, r, s);
-        case 4: return launch_render_basis<4>(g, o, r, s);
-        case 1: return launch_render_basis<1>(g, o, r, s);
-    }
-    return hipErrorInvalidValue;
+    const bool image = r.origins == nullptr, skip = g.skip != nullptr;
+    return dispatch_basis(g.basis_dim, [&](auto b) {
+        constexpr int B = decltype(b)::value;
+        if (image) return skip ? launch_render_b<B, true, true>(g, o, r, s) : launch_render_b<B, true, false>(g, o, r, s);
+        return skip ? launch_render_b<B, false, true>(g, o, r, s) : launch_render_b<B, false, false>(g, o, r, s);
+    });
 }
 
 hipError_t launch_grid_gen_rays(const GridCam& cam, float* origins, float* dirs, hipStream_t s) {

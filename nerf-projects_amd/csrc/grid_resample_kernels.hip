@@ -22,15 +22,9 @@ __global__ __launch_bounds__(kGridThreads) void grid_lattice_density_kernel(Grid
     int ix, iy, iz;
     node_to_xyz(idx, a.size, ix, iy, iz);
     const float p[3] = {a.axis[0][ix], a.axis[1][iy], a.axis[2][iz]};
-    int l[3];
     float wa[3], wb[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        cell_of(p[i], g.size[i], l[i], wb[i]);
-        wa[i] = sub(1.0f, wb[i]);
-    }
     int lk[8];
-    load_links(g, (l[0] * g.size[1] + l[1]) * g.size[2] + l[2], lk);
+    load_links(g, point_cell(g, p, wa, wb), lk);
     a.density[idx] = sample_sigma(g, lk, wa, wb);
 }
 
@@ -198,15 +192,9 @@ __global__ __launch_bounds__(kGridThreads) void grid_gather_kernel(GridDev g, Gr
     int ix, iy, iz;
     node_to_xyz(node, a.size, ix, iy, iz);
     const float p[3] = {a.axis[0][ix], a.axis[1][iy], a.axis[2][iz]};
-    int l[3];
     float wa[3], wb[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        cell_of(p[i], g.size[i], l[i], wb[i]);
-        wa[i] = sub(1.0f, wb[i]);
-    }
     int lk[8];
-    load_links(g, (l[0] * g.size[1] + l[1]) * g.size[2] + l[2], lk);
+    load_links(g, point_cell(g, p, wa, wb), lk);
     float cv[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) cv[c] = lk[c] >= 0 ? g.sh[(int64_t)lk[c] * cols + j] : 0.0f;

@@ -252,3 +252,5 @@ def test_grid_autograd_kernels_use_no_scratch_no_inline_assembly_and_no_compare_
     # the backward allocates no more registers than the fused kernel, 80 at basis_dim 9: 6 waves per SIMD
     assert max(v for k, v in vgprs.items() if "grid_render_bwd_kernel" in k) <= 80
     assert max(vgprs.values()) <= 80
+    # the taped render is the render plus one fp64 sum: like the render, 8 waves per SIMD
+    assert max(v for k, v in vgprs.items() if "grid_taped_kernel" in k) <= 64

@@ -160,6 +160,28 @@ def test_grid_kernels_use_no_scratch_and_no_inline_assembly(tmp_path):
     sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", asm)
     assert len(sizes) == len(kernels) and all(int(s) == 0 for s in sizes), sizes
     assert not re.search(r"\bscratch_(load|store)", asm)
+    vgprs = dict(zip(kernels, (int(v) for v in re.findall(r"\.vgpr_count:\s*(\d+)", asm))))
+    print("vgprs per kernel:", vgprs)
+    # 8 waves per SIMD, the instrumented launches included: waves in flight are what hides the link -> row load chain
+    assert len(vgprs) == 30 and max(v for k, v in vgprs.items() if "grid_render_kernel" in k) <= 64
+
+
+def test_the_march_is_written_once():
+    """Every kernel that walks a ray visits the same samples because all of them call grid_march of grid_device.h: the loop
+    head and the call of skip_jump occur once in the grid sources, corner_weight is defined once, and depth_march, the copy
+    that was local to one file, is gone. (grid_weight_render_kernel marches a dense lattice from t = 0: `while (t <= tmax)`.)"""
+    csrc = os.path.join(ROOT, "nerf-projects_amd", "csrc")
+    names = ["grid_device.h"] + sorted(f for f in os.listdir(csrc) if re.fullmatch(r"grid_\w+\.hip", f))
+    assert len(names) >= 9, names
+    # code only: the comments may speak of the march
+    text = {f: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read()) for f in names}
+    count = lambda pattern: {f: len(re.findall(pattern, t)) for f, t in text.items() if re.search(pattern, t)}
+    assert count(r"while \(t <= rs\.tmax\)") == {"grid_device.h": 1}
+    assert count(r"\bskip_jump\(") == {"grid_device.h": 2}      # the definition and the one call
+    assert count(r"=\s*skip_jump\(") == {"grid_device.h": 1}
+    assert count(r"\bfloat corner_weight\(") == {"grid_device.h": 1}
+    assert count(r"\bdepth_march\b") == {}
+    assert count(r"\bgrid_march<") == {"grid_device.h": 2, "grid_depth_kernels.hip": 1, "grid_depth_autograd_kernels.hip": 3}
 
 
 # ---- .npz layout --------------------------------------------------------------------------------------------------------

@@ -396,4 +396,4 @@ def test_grid_train_kernels_use_no_scratch_no_inline_assembly_and_no_compare_and
     assert all(int(s) == 0 for s in lds), lds
     vgprs = [int(v) for v in re.findall(r"\.vgpr_count:\s*(\d+)", asm)]
     print("vgprs per kernel:", dict(zip(kernels, vgprs)))
-    assert max(vgprs) <= 128      # at least 4 waves per SIMD
+    assert max(vgprs) <= 80      # 6 waves per SIMD at basis_dim 9, 7 at 4 and 1
