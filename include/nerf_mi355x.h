@@ -1274,6 +1274,76 @@ typedef struct nerf_grid_component_view_args {
 int nerf_grid_floater_heatmap(nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_floater_heatmap_args* args);
 int nerf_grid_component_view(nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_component_view_args* args);
 
+/* Sparse voxel grid: half-precision colours ---------------------------------------------------------
+ * An inference-side grid whose SH table lives on the device in fp16, as a Plenoxels checkpoint stores it (svox2's
+ * SparseGrid.save writes sh_data.astype(float16)). Density, links and skip data are those of section "Sparse voxel grid".
+ *
+ * The packed table is uint16 [capacity, nerf_grid_half_row_halfs(basis_dim)], IEEE binary16 bit patterns. One row:
+ *   channel-major like sh_data; channel c starts at slot c * S with S = 10 / 4 / 1 at basis_dim 9 / 4 / 1 (basis_dim rounded
+ *   up to even, so that coefficients (2 j, 2 j + 1) of a channel share an aligned 32-bit word), coefficient k of channel c is
+ *   slot c * S + k; every other slot is zero. The row has 32 / 16 / 4 halfs = 64 / 32 / 8 bytes (fp32: 108 / 48 / 12), a
+ *   power of two, so a row never straddles a 64-byte line. The table must be 4-byte aligned.
+ * Only nerf_grid_pack_half, nerf_grid_unpack_half and the render / sample kernels know this layout; everything else goes
+ * through them.
+ *
+ * nerf_grid_pack_half converts fp32 rows [rows, 3 * basis_dim] into rows [row0, row0 + rows) of the packed table - row0 lets a
+ * loader pack in chunks and never hold a whole fp32 table. A coefficient x becomes half(clamp(x, -65504, 65504)) rounded to
+ * nearest even: one that would overflow becomes the largest half and not an infinity (which would turn a sample of weight
+ * zero into NaN); NaN stays NaN; signed zeros and subnormals convert as IEEE 754 does. `clamped` [dev] (or NULL) is
+ * INCREMENTED by the number of entries with |x| > 65504; the caller zeroes it. nerf_grid_unpack_half is the exact widening
+ * of rows [0, rows) back to fp32 [rows, 3 * basis_dim]. Both are stream-ordered and synchronise nothing.
+ *
+ * nerf_grid_create_half is nerf_grid_create with the packed table in place of sh_data: the same link check (it synchronises
+ * `stream`), the same borrowed-pointer rules, the same opaque handle, destroyed by nerf_grid_destroy. On such a handle
+ *   - nerf_grid_render_rays, nerf_grid_render_image (also with `counters`) and nerf_grid_sample read the halves. A half is
+ *     widened to fp32 when it is loaded and everything after that is the fp32 arithmetic of section "Sparse voxel grid" in
+ *     the same order and association, so the results are, bit for bit, those of a nerf_grid_create handle on the table of
+ *     nerf_grid_unpack_half. For a grid that came from a checkpoint that is a lossless render.
+ *   - every entry point that reads links and density only works unchanged: accelerate / drop_skip / has_skip, depth rays and
+ *     image in all modes, depth taped / backward, lattice density, components occupancy, floater heatmap, component view.
+ *   - every entry point that reads or writes an fp32 SH table through the handle returns NERF_E_INVALID and names the
+ *     half-precision grid, before any launch: nerf_grid_fused_backward, nerf_grid_render_rays_taped,
+ *     nerf_grid_render_backward, nerf_grid_sample_backward, nerf_grid_tv_grad with NERF_GRID_TV_SH, nerf_grid_gather.
+ * lanes chooses the lane mapping of the render kernel; the results do not depend on it.
+ *   NERF_GRID_HALF_LANES_SINGLE  one coefficient per lane, the mapping of the fp32 kernel: 2 / 4 / 16 rays per wavefront
+ *   NERF_GRID_HALF_LANES_PAIR    two coefficients per lane from one 32-bit load: 4 / 8 rays per wavefront at basis_dim 9 / 4
+ *                                (basis_dim 1 has no pairs: SINGLE)
+ *   NERF_GRID_HALF_LANES_DEFAULT the faster of the two as measured on the MI355X (profiles/grid_half_ab.md) */
+#define NERF_GRID_HALF_LANES_DEFAULT 0
+#define NERF_GRID_HALF_LANES_SINGLE 1
+#define NERF_GRID_HALF_LANES_PAIR 2
+
+typedef struct nerf_grid_half_desc {
+    size_t struct_size;         /* sizeof(nerf_grid_half_desc), checked                                             */
+    int32_t reso[3];            /* nodes per axis, each in [2, 1024]                                                */
+    int32_t basis_dim;          /* 1, 4 or 9                                                                        */
+    float radius[3];            /* > 0                                                                              */
+    float center[3];
+    int64_t capacity;           /* rows of density_data / sh_half, >= 0                                             */
+    const int32_t* links;       /* [dev] [X, Y, Z]                                                                  */
+    const float* density_data;  /* [dev] [capacity, 1]          (may be NULL when capacity == 0)                    */
+    const uint16_t* sh_half;    /* [dev] [capacity, nerf_grid_half_row_halfs(basis_dim)], as nerf_grid_pack_half writes it */
+    int32_t lanes;              /* NERF_GRID_HALF_LANES_*                                                           */
+    void* stream;
+} nerf_grid_half_desc;
+
+typedef struct nerf_grid_pack_half_args {
+    size_t struct_size;
+    int32_t basis_dim;          /* 1, 4 or 9                                                                        */
+    int64_t capacity;           /* rows of the packed table                                                         */
+    int64_t row0, rows;         /* rows [row0, row0 + rows) of it are written; 0 <= row0, 0 <= rows, row0 + rows <= capacity */
+    const float* sh_data;       /* [dev] [rows, 3 * basis_dim]                                                      */
+    uint16_t* sh_half;          /* [dev] [capacity, nerf_grid_half_row_halfs(basis_dim)]                            */
+    unsigned long long* clamped; /* [dev] [1] or NULL: += entries with |x| > 65504                                  */
+    void* stream;
+} nerf_grid_pack_half_args;
+
+/* halfs in one packed row: 32 / 16 / 4; NERF_E_INVALID (negative) for a basis_dim other than 9 / 4 / 1. Needs no device. */
+int nerf_grid_half_row_halfs(int32_t basis_dim);
+int nerf_grid_pack_half(nerf_ctx* ctx, const nerf_grid_pack_half_args* args);
+int nerf_grid_unpack_half(nerf_ctx* ctx, const uint16_t* sh_half, int64_t rows, int32_t basis_dim, float* sh_data, void* stream);
+int nerf_grid_create_half(nerf_ctx* ctx, const nerf_grid_half_desc* desc, nerf_sparse_grid** out);
+
 #ifdef __cplusplus
 }
 #endif

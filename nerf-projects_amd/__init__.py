@@ -18,6 +18,8 @@ from .mesh import density_grid, marching_cubes, marching_cubes_volume, save_obj 
 from .occupancy import OccupancyGrid  # noqa: F401
 from . import grid  # noqa: F401
 from .grid import Camera, Rays, RenderOptions, SparseGrid  # noqa: F401
+from . import grid_half  # noqa: F401
+from .grid_half import HalfGrid  # noqa: F401
 from . import grid_train  # noqa: F401
 from .grid_train import GridTrainer  # noqa: F401
 from . import grid_autograd  # noqa: F401

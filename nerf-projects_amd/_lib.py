@@ -36,6 +36,7 @@ EXPORTS = (
     "nerf_grid_render_rays_taped", "nerf_grid_render_backward", "nerf_grid_sample_backward",
     "nerf_grid_depth_rays_taped", "nerf_grid_depth_backward",
     "nerf_grid_floater_heatmap", "nerf_grid_component_view",
+    "nerf_grid_half_row_halfs", "nerf_grid_pack_half", "nerf_grid_unpack_half", "nerf_grid_create_half",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -45,6 +46,7 @@ NERF_GRID_TV_DENSITY, NERF_GRID_TV_SH = 0, 1
 NERF_GRID_OPTIM_RMSPROP, NERF_GRID_OPTIM_SGD = 0, 1
 NERF_GRID_DEPTH_EXPECTED, NERF_GRID_DEPTH_THRESHOLD, NERF_GRID_DEPTH_RAYLEN = 0, 1, 2
 NERF_GRID_FLOATER_COUNTER_INTS = 8192
+NERF_GRID_HALF_LANES_DEFAULT, NERF_GRID_HALF_LANES_SINGLE, NERF_GRID_HALF_LANES_PAIR = 0, 1, 2
 
 
 class NerfArch(C.Structure):
@@ -273,6 +275,17 @@ class GridComponentViewArgs(_Sized):
                 ("center", C.c_float * 3), ("w2c", C.c_float * 12), ("keys", _FP), ("slots", _FP), ("stream", C.c_void_p)]
 
 
+class GridHalfDesc(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("reso", C.c_int32 * 3), ("basis_dim", C.c_int32), ("radius", C.c_float * 3),
+                ("center", C.c_float * 3), ("capacity", C.c_int64), ("links", _FP), ("density_data", _FP), ("sh_half", _FP),
+                ("lanes", C.c_int32), ("stream", C.c_void_p)]
+
+
+class GridPackHalfArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("basis_dim", C.c_int32), ("capacity", C.c_int64), ("row0", C.c_int64),
+                ("rows", C.c_int64), ("sh_data", _FP), ("sh_half", _FP), ("clamped", _FP), ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -467,6 +480,14 @@ def load():
     lib.nerf_grid_floater_heatmap.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridFloaterHeatmapArgs)]
     lib.nerf_grid_component_view.restype = i32
     lib.nerf_grid_component_view.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridComponentViewArgs)]
+    lib.nerf_grid_half_row_halfs.restype = i32
+    lib.nerf_grid_half_row_halfs.argtypes = [C.c_int32]
+    lib.nerf_grid_pack_half.restype = i32
+    lib.nerf_grid_pack_half.argtypes = [vp, C.POINTER(GridPackHalfArgs)]
+    lib.nerf_grid_unpack_half.restype = i32
+    lib.nerf_grid_unpack_half.argtypes = [vp, vp, i64, C.c_int32, vp, vp]
+    lib.nerf_grid_create_half.restype = i32
+    lib.nerf_grid_create_half.argtypes = [vp, C.POINTER(GridHalfDesc), C.POINTER(vp)]
     _lib = lib
     return lib
 

@@ -21,6 +21,32 @@ int nerf::require_grid(const char* fn, const nerf_sparse_grid* grid) {
     return NERF_E_INVALID;
 }
 
+int nerf::refuse_half_grid(const char* fn, const nerf_sparse_grid* grid) {
+    if (!grid->half) return NERF_OK;
+    set_error("%s: a half-precision grid (nerf_grid_create_half) has no fp32 SH table to read or write: widen it with "
+              "nerf_grid_unpack_half and use a grid of nerf_grid_create", fn);
+    return NERF_E_INVALID;
+}
+
+int nerf::check_grid_links(const char* fn, const int32_t* links, int64_t n, int64_t capacity, hipStream_t s) {
+    int* d_bad = nullptr;
+    int bad = 0;
+    HIP_TRY(hipMalloc((void**)&d_bad, sizeof(int)));
+    hipError_t e = launch_grid_check_links(links, n, capacity, d_bad, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_bad);
+    if (e != hipSuccess) {
+        set_error("%s: %s", fn, hipGetErrorString(e));
+        return NERF_E_HIP;
+    }
+    if (bad) {
+        set_error("%s: links holds a value >= capacity = %lld", fn, (long long)capacity);
+        return NERF_E_INVALID;
+    }
+    return NERF_OK;
+}
+
 int nerf::check_grid_reso(const char* fn, const int32_t* reso, int64_t* nodes) {
     if (!reso) {
         set_error("%s: reso is NULL", fn);
@@ -108,7 +134,10 @@ int render(const char* fn, nerf_sparse_grid* grid, const nerf_grid_camera* cam, 
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;
     DeviceGuard dg(grid->ctx->device);
-    HIP_TRY(launch_grid_render(g, o, r, (hipStream_t)a->stream));
+    if (grid->half)
+        HIP_TRY(launch_grid_half_render(g, o, r, grid->half_pair, (hipStream_t)a->stream));
+    else
+        HIP_TRY(launch_grid_render(g, o, r, (hipStream_t)a->stream));
     return NERF_OK;
 }
 
@@ -149,22 +178,8 @@ int nerf_grid_create(nerf_ctx* c, const nerf_sparse_grid_desc* d, nerf_sparse_gr
         return NERF_E_INVALID;
     }
     DeviceGuard dg(c->device);
-    hipStream_t s = (hipStream_t)d->stream;
-    int* d_bad = nullptr;
-    int bad = 0;
-    HIP_TRY(hipMalloc((void**)&d_bad, sizeof(int)));
-    hipError_t e = launch_grid_check_links(d->links, n, d->capacity, d_bad, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_bad);
-    if (e != hipSuccess) {
-        set_error("nerf_grid_create: %s", hipGetErrorString(e));
-        return NERF_E_HIP;
-    }
-    if (bad) {
-        set_error("nerf_grid_create: links holds a value >= capacity = %lld", (long long)d->capacity);
-        return NERF_E_INVALID;
-    }
+    rc = check_grid_links(fn, d->links, n, d->capacity, (hipStream_t)d->stream);
+    if (rc != NERF_OK) return rc;
     nerf_sparse_grid* grid = new (std::nothrow) nerf_sparse_grid();
     if (!grid) return NERF_E_NOMEM;
     grid->ctx = c;
@@ -172,6 +187,7 @@ int nerf_grid_create(nerf_ctx* c, const nerf_sparse_grid_desc* d, nerf_sparse_gr
     g.links = d->links;
     g.density = d->density_data;
     g.sh = d->sh_data;
+    g.sh_half = nullptr;
     g.skip = nullptr;
     g.basis_dim = d->basis_dim;
     g.capacity = d->capacity;
@@ -219,7 +235,11 @@ int nerf_grid_sample(nerf_sparse_grid* grid, const nerf_grid_sample_args* a) {
         return NERF_E_INVALID;
     }
     DeviceGuard dg(grid->ctx->device);
-    HIP_TRY(launch_grid_sample(grid->g, a->points, a->n, a->grid_coords, a->want_colors, a->density, a->sh, (hipStream_t)a->stream));
+    if (grid->half)
+        HIP_TRY(launch_grid_half_sample(grid->g, a->points, a->n, a->grid_coords, a->want_colors, a->density, a->sh,
+                                        (hipStream_t)a->stream));
+    else
+        HIP_TRY(launch_grid_sample(grid->g, a->points, a->n, a->grid_coords, a->want_colors, a->density, a->sh, (hipStream_t)a->stream));
     return NERF_OK;
 }
 

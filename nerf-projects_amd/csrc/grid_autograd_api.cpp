@@ -33,6 +33,8 @@ int nerf_grid_render_rays_taped(nerf_sparse_grid* grid, const nerf_grid_render_o
     }
     if (a->n_rays == 0) return NERF_OK;
     GridTaped r{a->origins, a->dirs, a->n_rays, a->rgb_out, a->log_transmit, a->tape};
+    rc = refuse_half_grid(fn, grid);      // (the first read of the handle)
+    if (rc != NERF_OK) return rc;
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;
     DeviceGuard dg(grid->ctx->device);
@@ -56,6 +58,8 @@ int nerf_grid_render_backward(nerf_sparse_grid* grid, const nerf_grid_render_opt
     }
     if (a->n_rays == 0 || (!a->grad_density && !a->grad_sh && !a->mask)) return NERF_OK;
     GridRenderBwd r{a->origins, a->dirs, a->n_rays, a->grad_rgb, a->tape, a->grad_density, a->grad_sh, a->mask};
+    rc = refuse_half_grid(fn, grid);      // (the first read of the handle)
+    if (rc != NERF_OK) return rc;
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;
     DeviceGuard dg(grid->ctx->device);
@@ -65,7 +69,7 @@ int nerf_grid_render_backward(nerf_sparse_grid* grid, const nerf_grid_render_opt
 
 int nerf_grid_sample_backward(nerf_sparse_grid* grid, const nerf_grid_sample_backward_args* a) {
     const char* fn = "nerf_grid_sample_backward";
-    const int rc = require_grid(fn, grid);
+    int rc = require_grid(fn, grid);
     if (rc != NERF_OK) return rc;
     NERF_CHECK_STRUCT(fn, a, nerf_grid_sample_backward_args);
     if (a->n < 0 || a->n > kGridMaxItems) {
@@ -79,6 +83,8 @@ int nerf_grid_sample_backward(nerf_sparse_grid* grid, const nerf_grid_sample_bac
     if (a->n == 0 || (!a->grad_density && !(a->want_colors && a->grad_sh))) return NERF_OK;
     GridSampleBwd p{a->points, a->n, a->grid_coords, a->want_colors, a->grad_out_density, a->grad_out_sh, a->grad_density,
                     a->grad_sh};
+    rc = refuse_half_grid(fn, grid);      // (the first read of the handle)
+    if (rc != NERF_OK) return rc;
     DeviceGuard dg(grid->ctx->device);
     HIP_TRY(launch_grid_sample_bwd(grid->g, p, (hipStream_t)a->stream));
     return NERF_OK;

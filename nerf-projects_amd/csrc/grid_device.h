@@ -222,14 +222,20 @@ __device__ __forceinline__ float sample_sigma(const GridDev& g, const int lk[8],
     return trilerp(cv, wa, wb);
 }
 
+// how shade_channel fetches column `col` of row `link`: here from the fp32 table; grid_half_kernels.hip widens a packed half
+template <int B>
+struct FetchFloat {
+    static __device__ __forceinline__ float at(const GridDev& g, int link, int col) { return g.sh[(int64_t)link * (3 * B) + col]; }
+};
+
 // lane (channel c, coefficient k = col % B): Y_k times the interpolated coefficient, summed over the B lanes of the channel;
 // the sum is complete in the lane with k == 0
-template <int B>
+template <int B, class Fetch = FetchFloat<B>>
 __device__ __forceinline__ float shade_channel(const GridDev& g, const int lk[8], const float wa[3], const float wb[3], int col,
                                                int k, float yk) {
     float cv[8];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) cv[c] = lk[c] >= 0 ? g.sh[(int64_t)lk[c] * (3 * B) + col] : 0.0f;
+    for (int c = 0; c < 8; ++c) cv[c] = lk[c] >= 0 ? Fetch::at(g, lk[c], col) : 0.0f;
     float part = mul(yk, trilerp(cv, wa, wb));
 #pragma unroll
     for (int off = 1; off < B; off <<= 1) {
@@ -238,6 +244,16 @@ __device__ __forceinline__ float shade_channel(const GridDev& g, const int lk[8]
     }
     return part;
 }
+
+// how march_colour shades a sample: a callable (g, lk, wa, wb, gl, yk) -> the channel's sum, complete in the lanes with k == 0.
+// This one is shade_channel on the fp32 table; the half-precision kernels pass their own.
+template <int B>
+struct ShadeFloat {
+    __device__ __forceinline__ float operator()(const GridDev& g, const int lk[8], const float wa[3], const float wb[3],
+                                                const GroupLane& gl, float yk) const {
+        return shade_channel<B>(g, lk, wa, wb, gl.col, gl.k, yk);
+    }
+};
 
 // ---- the one march --------------------------------------------------------------------------------------------------------
 // Every kernel that walks a ray walks it here, so all of them visit the same samples, bit for bit. For a ray that is marched
@@ -282,9 +298,9 @@ struct Colour {
 
 // grid_render_kernel, grid_taped_kernel and the first march of grid_fused_kernel: at every sample above sigma_thresh the
 // channel is shaded, weighted and accumulated, and the ray stops below stop_thresh. A ray that is not marched is background.
-template <int B, bool SKIP, bool TAPE, bool COUNT>
+template <int B, bool SKIP, bool TAPE, bool COUNT, class Shade = ShadeFloat<B>>
 __device__ __forceinline__ Colour march_colour(const GridDev& g, const GridRenderOpt& opt, const GridRay& rs, const GroupLane& gl,
-                                               float yk) {
+                                               float yk, const Shade& shade = Shade()) {
     Colour c;
     if (rs.ok && rs.tmin <= rs.tmax) {
         const float neg_step = -opt.step_size;
@@ -292,7 +308,7 @@ __device__ __forceinline__ Colour march_colour(const GridDev& g, const GridRende
             if (COUNT) ++c.visited;
             if (!(sigma > opt.sigma_thresh)) return false;
             if (COUNT) ++c.shaded;
-            const float part = shade_channel<B>(g, lk, wa, wb, gl.col, gl.k, yk);
+            const float part = shade(g, lk, wa, wb, gl, yk);
             const float a = mul(mul(neg_step, sigma), rs.delta_scale);
             const float weight = mul(expf(c.log_t), sub(1.0f, expf(a)));
             const float colour = fmaxf(add(part, 0.5f), 0.0f);

@@ -6,6 +6,7 @@
 //   grid_components_api.cpp occupancy, labelling, volumes, keep mask, row copy
 //   grid_depth_api.cpp      expected depth, threshold depth, ray length
 //   grid_depth_autograd_api.cpp   taped expected depth, backward with cotangents for depth and log_transmit
+//   grid_half_api.cpp       half-precision colours: pack / unpack, create; render and sample are dispatched from grid_api.cpp
 //   grid_*_kernels.hip      the kernels of each, on grid_device.h (sampling, rays) and compact_device.h (compaction)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,7 +28,8 @@ constexpr int64_t kGridMaxItems = (int64_t)1 << 26;   // rays / points / nodes p
 struct GridDev {
     const int32_t* links;
     const float* density;
-    const float* sh;
+    const float* sh;                   // [capacity, 3 B], or nullptr on a half-precision grid
+    const uint16_t* sh_half;           // [capacity, grid_half_row_halfs(B)] packed fp16 rows (grid_half_kernels.hip), or nullptr
     const uint8_t* skip;               // [X, Y, Z] bytes indexed like links (base cell = its lowest node), or nullptr
     int32_t size[3];
     int32_t basis_dim;
@@ -239,6 +241,10 @@ hipError_t launch_grid_depth_bwd(const GridDev& g, const GridRenderOpt& o, const
 void set_error(const char* fmt, ...);
 int require_ctx(const char* fn, const nerf_ctx* c);                      // "NULL context"
 int require_grid(const char* fn, const nerf_sparse_grid* grid);          // "NULL grid"
+// for the entry points that read or write an fp32 SH table through the handle: a grid of nerf_grid_create_half is refused
+int refuse_half_grid(const char* fn, const nerf_sparse_grid* grid);
+// the link check of nerf_grid_create / nerf_grid_create_half: synchronises `s`; NERF_E_INVALID for a link >= capacity
+int check_grid_links(const char* fn, const int32_t* links, int64_t n, int64_t capacity, hipStream_t s);
 // reso not NULL, every side in [2, 1024] (so that a cell exists on every axis), at most 2^30 nodes
 int check_grid_reso(const char* fn, const int32_t* reso, int64_t* nodes);
 // a public camera (struct_size, size, intrinsics) / the public render options (struct_size, what is not built, ranges), converted
@@ -276,10 +282,34 @@ hipError_t launch_grid_check_links(const int32_t* links, int64_t n, int64_t capa
 hipError_t launch_grid_project_sh(const float* raw, int64_t m, int n_dirs, int basis_dim, const float* P, float* sh_out,
                                   int64_t row0, hipStream_t s);
 
+// ---- half-precision colours (grid_half_kernels.hip) ----
+// One packed row: channel-major like sh_data, a channel in kGridHalfChannel slots (B rounded up to even, so that coefficients
+// (2 j, 2 j + 1) of a channel share an aligned 32-bit word; 1 at B = 1), the row zero-padded to a power of two of halfs.
+constexpr int grid_half_channel_halfs(int B) { return B == 1 ? 1 : (B + 1) / 2 * 2; }       // 10 / 4 / 1
+constexpr int grid_half_row_halfs(int B) { return B == 9 ? 32 : (B == 4 ? 16 : 4); }        // 64 / 32 / 8 bytes
+
+struct GridHalfPack {
+    const float* sh;                   // [rows, 3 B]
+    uint16_t* sh_half;                 // the whole packed table; rows [row0, row0 + rows) are written
+    int64_t rows, row0;
+    int32_t basis_dim;
+    unsigned long long* clamped;       // += entries beyond +-65504, or nullptr
+};
+
+hipError_t launch_grid_pack_half(const GridHalfPack& a, hipStream_t s);
+hipError_t launch_grid_unpack_half(const uint16_t* sh_half, int64_t rows, int basis_dim, float* sh, hipStream_t s);
+// on a GridDev with sh_half: the half twins of launch_grid_render / launch_grid_sample (same arguments, same results as the
+// fp32 kernels give on the widened table, bit for bit). pair: two coefficients per lane (NERF_GRID_HALF_LANES_PAIR), else one.
+hipError_t launch_grid_half_render(const GridDev& g, const GridRenderOpt& o, const GridRender& r, bool pair, hipStream_t s);
+hipError_t launch_grid_half_sample(const GridDev& g, const float* points, int64_t n, int grid_coords, int want_colors,
+                                   float* density, float* sh, hipStream_t s);
+
 }  // namespace nerf
 
 struct nerf_sparse_grid {
     nerf_ctx* ctx = nullptr;
     nerf::GridDev g{};
     uint8_t* d_skip = nullptr;
+    bool half = false;                 // made by nerf_grid_create_half: g.sh_half is the colour table, g.sh is nullptr
+    bool half_pair = false;            // ... and it renders with two coefficients per lane
 };

@@ -156,6 +156,8 @@ int nerf_grid_gather(nerf_sparse_grid* grid, const nerf_grid_gather_args* a) {
     t.density_data = a->density_data;
     t.sh_data = a->sh_data;
     // ---- from here on the handle is read ----
+    rc = refuse_half_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
     GridDev g = grid->g;
     g.skip = nullptr;
     DeviceGuard dg(grid->ctx->device);

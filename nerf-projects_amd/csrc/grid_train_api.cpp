@@ -49,6 +49,8 @@ int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_opti
     r.grad_density = a->grad_density;
     r.grad_sh = a->grad_sh;
     r.mask = a->mask;
+    rc = refuse_half_grid(fn, grid);      // (the first read of the handle)
+    if (rc != NERF_OK) return rc;
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;
     DeviceGuard dg(grid->ctx->device);
@@ -78,6 +80,10 @@ int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* a) {
         return NERF_E_INVALID;
     }
     // ---- from here on the handle is read ----
+    if (a->target == NERF_GRID_TV_SH) {
+        rc = refuse_half_grid(fn, grid);
+        if (rc != NERF_OK) return rc;
+    }
     const GridDev& g = grid->g;
     const int64_t n = (int64_t)g.size[0] * g.size[1] * g.size[2];
     const int cols = a->target == NERF_GRID_TV_DENSITY ? 1 : 3 * g.basis_dim;

@@ -8,6 +8,7 @@ The semantics of every call are stated in include/nerf_mi355x.h, "Sparse voxel g
 (csrc/grid_kernels.hip, csrc/grid_depth_kernels.hip) and, as everywhere in this package, there is no CPU or PyTorch fallback.
 What svox2 has and this module does not (background layers, learned bases, the other backends) raises ``NotImplementedError``; so do the svox2-named
 training methods on ``SparseGrid`` - training a grid is ``grid_train.GridTrainer``, under names of its own.
+``SparseGrid.to_half()`` gives the inference twin with fp16 colours on the device, ``grid_half.HalfGrid``.
 """
 import ctypes as C
 from dataclasses import dataclass, replace
@@ -232,6 +233,12 @@ def _volume_arg(t, name, dtype, ctx=None):
         raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
     _reso3(list(t.shape), name + ".shape")
     return t.detach().contiguous()
+
+
+def _refuse_half(grid, who):
+    """``TypeError`` for a ``grid_half.HalfGrid`` where the fp32 SH table of a grid is read or written."""
+    if getattr(grid, "is_half", False):
+        raise TypeError(f"{who} reads or writes the fp32 SH table of a SparseGrid and a HalfGrid has none: pass grid.to_float()")
 
 
 def _as_u8(mask):
@@ -614,6 +621,11 @@ class SparseGrid:
         return self.sample(points, use_kernel=use_kernel)
 
     __call__ = forward
+
+    def to_half(self, lanes=None):
+        """``grid_half.HalfGrid.from_grid(self)``: the inference twin of this grid with its colours in fp16 on the device."""
+        from .grid_half import HalfGrid
+        return HalfGrid.from_grid(self, lanes=lanes)
 
     def accelerate(self):
         """Build the empty-space skip data on the device from the CURRENT links (a separate array; ``links`` is not written)."""

@@ -26,7 +26,7 @@ from torch.autograd.function import once_differentiable
 
 from ._lib import (NERF_GRID_DEPTH_EXPECTED, GridDepthBackwardArgs, GridDepthTapedArgs, GridRenderBackwardArgs,
                    GridRenderTapedArgs, GridSampleBackwardArgs, check)
-from .grid import Camera, Rays, SparseGrid
+from .grid import Camera, Rays, SparseGrid, _refuse_half
 
 __all__ = ["GridModule"]
 
@@ -198,6 +198,7 @@ class GridModule(torch.nn.Module):
 
     def __init__(self, grid: SparseGrid):
         super().__init__()
+        _refuse_half(grid, "GridModule")
         if not isinstance(grid, SparseGrid):
             raise TypeError("GridModule needs a SparseGrid")
         self.grid = grid

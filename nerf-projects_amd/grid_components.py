@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ._lib import GridCopyRowsArgs, GridLabelArgs, GridOccupancyArgs, check
-from .grid import SparseGrid, _as_u8, _reso3, _volume_arg
+from .grid import SparseGrid, _as_u8, _refuse_half, _reso3, _volume_arg
 from .grid_resample import compact_mask
 from .host import get_context
 
@@ -231,6 +231,7 @@ def _copy_rows(grid, new_links, rows):
 
 def _without_floaters(grid, fdr_kwargs):
     """``(links, density_data, sh_data, result)`` of ``grid`` without the components ``compute_FDR`` calls floaters."""
+    _refuse_half(grid, "remove_floaters")
     _check_grid(grid, "remove_floaters")
     result = compute_FDR(grid, **fdr_kwargs)      # every argument is checked in here, before anything is made
     ctx = grid.ctx

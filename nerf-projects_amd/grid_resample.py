@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ._lib import GridCompactArgs, GridGatherArgs, GridLatticeArgs, GridWeightArgs, check
-from .grid import Camera, SparseGrid, _as_u8, _reso3, _three, _volume_arg
+from .grid import Camera, SparseGrid, _as_u8, _refuse_half, _reso3, _three, _volume_arg
 from .host import get_context
 
 __all__ = ["resample_grid", "lattice_axes", "lattice_density", "weight_render", "threshold_mask", "dilate_mask", "compact_mask"]
@@ -160,6 +160,7 @@ def _gather(grid, axes, links, volume, rows):
 
 def _check_resample_args(grid, reso, sigma_thresh, weight_thresh, dilate, cameras, weight_render_stop_thresh, max_elements):
     """Everything that can be refused is refused here, before anything is launched or changed."""
+    _refuse_half(grid, "resample_grid")
     if not isinstance(grid, SparseGrid):
         raise TypeError("resample_grid needs a SparseGrid")
     reso = _reso3(reso)

@@ -22,7 +22,7 @@ import torch
 
 from ._lib import (NERF_GRID_OPTIM_RMSPROP, NERF_GRID_OPTIM_SGD, NERF_GRID_TV_DENSITY, NERF_GRID_TV_SH, GridFusedArgs,
                    GridOptimArgs, GridTvArgs, check)
-from .grid import Rays, SparseGrid
+from .grid import Rays, SparseGrid, _refuse_half
 
 __all__ = ["GridTrainer"]
 
@@ -38,6 +38,7 @@ class GridTrainer:
     ``generator``: a CPU ``torch.Generator`` from which :meth:`add_tv_grad` draws the start of its cell range."""
 
     def __init__(self, grid: SparseGrid, generator: torch.Generator = None):
+        _refuse_half(grid, "GridTrainer")
         if not isinstance(grid, SparseGrid):
             raise TypeError("GridTrainer needs a SparseGrid")
         self.grid = grid
