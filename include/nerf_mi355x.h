@@ -1344,6 +1344,121 @@ int nerf_grid_pack_half(nerf_ctx* ctx, const nerf_grid_pack_half_args* args);
 int nerf_grid_unpack_half(nerf_ctx* ctx, const uint16_t* sh_half, int64_t rows, int32_t basis_dim, float* sh_data, void* stream);
 int nerf_grid_create_half(nerf_ctx* ctx, const nerf_grid_half_desc* desc, nerf_sparse_grid** out);
 
+/* Sparse voxel grid: background layers --------------------------------------------------------------
+ * svox2's multi-sphere-image background (background_nlayers > 0), forward side: L = nlayers concentric spheres around the
+ * grid's centre, radius 1 (the unit sphere of the normalised box) outwards to infinity, each an equirectangular image of
+ * 2R x R texels (R = reso) holding (r, g, b, sigma).
+ *   links [dev] int32 [2R, R], C order: >= 0 = row of `data`; a negative link, or one >= capacity, reads as zeros.
+ *   data  [dev] float [capacity, L, 4]: channels 0..2 colour, 3 sigma; 16-byte aligned.
+ * Both are BORROWED under the rules of section "Sparse voxel grid". nerf_grid_set_background attaches them to a grid of
+ * nerf_grid_create (a half-precision handle is NERF_E_INVALID), checks every link against capacity on the device and
+ * synchronises `stream`, as nerf_grid_create does; desc == NULL detaches. nerf_grid_has_background: 1 / 0.
+ *
+ * The reference states the background twice and the statements differ: its PyTorch renderer samples between consecutive
+ * sphere hits and attenuates by world distance, its CUDA kernel (render_background_forward) samples ON the spheres and
+ * attenuates by the difference of inverse radii. Checkpoints are trained and rendered with the CUDA kernel, so that one is
+ * followed. Everything below is fp32 with every operation rounded (no fused multiply-add) unless it says fp64;
+ * dot(a, b) = (a_x b_x + a_y b_y) + a_z b_z, |a| = sqrt(dot(a, a)), lerp(a, b, w) = a + w (b - a).
+ *
+ * The pass runs AFTER the foreground: nerf_grid_background_rays / _image take rgb [n, 3] and log_transmit [n] as the
+ * foreground left them (render with background_brightness = 0 and log_transmit requested; its "+ exp(log_T) * 0" leaves the
+ * colour unchanged bit for bit) and update both in place, on the same stream. Per ray, with o, d (grid-coordinate origin,
+ * unit grid direction), delta_scale and the finiteness rule of the foreground's set-up, and log_T = log_transmit[ray]:
+ *   if log_T < -25: the ray is left alone - nothing is read further, nothing is written, no brightness term.
+ *   if the set-up is not finite (the foreground's miss rule): rgb_c += exp(log_T) * background_brightness, log_transmit
+ *     is not written; no layers.
+ *   Set-up, per axis a:  s_a = 2 / reso_a;  O_a = ((o_a + 0.5) * s_a) - 1;  D_a = d_a * s_a;  then
+ *     inorm = 1 / |D|;  D_a = D_a * inorm;  world_step = delta_scale * inorm   (no step_size factor);
+ *     q2a = 2 * dot(D, D);  qb = 2 * dot(O, D);  f = qb * qb - (2 * q2a) * dot(O, O);
+ *     C = O x D (C_x = O_y * D_z - O_z * D_y, cyclic);  inner = max(|C| + 1e-3, 1);  invr_last = 1 / inner.
+ *   Steps: n = (int)((float)L / step_size) + 2. For i = 0 .. n - 1:
+ *     r = (float)((double)n / ((double)(n - i) - 0.5))                                       (fp64, rounded once)
+ *     skip the step if r < inner;  det = f + ((2 * q2a) * r) * r;  skip the step if det < 0
+ *     t = (-qb + sqrt(det)) / q2a           (the far hit; its sign is NOT tested, as in the reference: a ray that starts
+ *                                            outside a sphere and points away from it is sampled behind its origin)
+ *     P_a = O_a + t * D_a;  invr = 1 / |P|;  u_a = P_a * invr;  lat = asinf(u_y);  lon = atan2f(u_x, u_z)
+ *     x = (float)(2R * (0.5 + ((double)lon * 0.5) * (1 / pi)));  y = (float)(R * (0.5 - (double)lat * (1 / pi)))   (fp64,
+ *                                            1 / pi = 0.318309886183790671538, each rounded to fp32 once)
+ *     z = fminf(fmaxf(((1 - invr) * L) - 0.5, 0), L - 1)
+ *     l = (int)(x, y, z) (truncation; a NaN gives 0), each clamped to [0, (2R - 1, R - 1, L - 2)];  w = (x, y, z) - l
+ *     nx = l_x + 1, or 0 at l_x = 2R - 1;  ny = l_y + 1, or 0 at l_y = R - 1   (both axes wrap)
+ *     texel (X, Y) has link links[X * R + Y]; its value for channel c is
+ *       lerp(data[(link * L + l_z) * 4 + c], data[(link * L + l_z + 1) * 4 + c], w_z), or 0 without a row   (z first)
+ *     v_c = lerp(lerp(texel(l_x, l_y), texel(l_x, ny), w_y), lerp(texel(nx, l_y), texel(nx, ny), w_y), w_x)   (y, then x)
+ *     if v_3 > 0 (sigma):  p = ((invr_last - invr) * world_step) * v_3;  weight = exp(log_T) * (1 - exp(-p));
+ *       log_T = log_T - p;  out_c = out_c + weight * max(0, (v_c * 0.28209479177387814) + 0.5)  for c = 0..2;
+ *       if exp(log_T) < stop_thresh: leave the loop (this step's invr_last is no longer needed)
+ *     invr_last = invr                      (on every step that was not skipped, also where sigma <= 0)
+ *   rgb_c = rgb_c + (out_c + exp(log_T) * background_brightness);  log_transmit[ray] = log_T.
+ * sigma_thresh and near_clip are not read. Termination is unconditional: n <= L / 1e-3 + 2 with L <= 1024 and
+ * step_size >= 1e-3. One lane per ray, no atomics: two calls on the same input give identical bits. The image form makes
+ * the rays of `cam` inside the launch as nerf_grid_render_image does. At most 2^26 rays or pixels per call; n_rays = 0 does
+ * nothing. Stream-ordered, nothing is synchronised or allocated.
+ *
+ * Thinning (svox2 sparsify_background), in two calls with one host read of *count between them:
+ * nerf_grid_background_sparsify_plan: mask[X, Y, z] = texel (X, Y) has a row and data[link, z, 3] >= sigma_thresh (a NaN is
+ *   not), dilated `dilate` times over the [2R, R, L] volume by the 27-neighbourhood clamped at the faces (svox2's dilate: no
+ *   wrap); a texel is kept iff it has a row and any of its L mask bytes is set; new_links[2R, R] = the rank of a kept texel
+ *   among the kept ones in C order, else -1; *count [dev] = the kept texels. (svox2 pairs the i-th texel that has a row with
+ *   row i; here the texel's own link is followed, which is the same wherever svox2's pairing is valid.)
+ * nerf_grid_background_gather: new_data[new_links[t]] = data[links[t]] for every kept texel t, rows of [L, 4].
+ * The caller then installs new_links / new_data with nerf_grid_set_background. Deterministic; no atomics. */
+typedef struct nerf_grid_background_desc {
+    size_t struct_size;
+    int32_t nlayers;            /* L in [2, 1024]                                                                   */
+    int32_t reso;               /* R in [2, 1024]: 2R x R texels per layer                                          */
+    int64_t capacity;           /* rows of data, in [0, 2^31)                                                       */
+    const int32_t* links;       /* [dev] [2R, R]                                                                    */
+    const float* data;          /* [dev] [capacity, L, 4], 16-byte aligned (may be NULL when capacity == 0)         */
+    void* stream;
+} nerf_grid_background_desc;
+
+typedef struct nerf_grid_background_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]       (nerf_grid_background_rays only)                         */
+    const float* dirs;          /* [dev] [n_rays, 3], need not be unit                                              */
+    int64_t n_rays;             /* nerf_grid_background_image: ignored, width * height rays in row-major order      */
+    float* rgb;                 /* [dev] [n_rays, 3] in / out                                                       */
+    float* log_transmit;        /* [dev] [n_rays] in / out                                                          */
+    void* stream;
+} nerf_grid_background_args;
+
+typedef struct nerf_grid_background_sparsify_args {
+    size_t struct_size;
+    int32_t nlayers, reso;      /* as in nerf_grid_background_desc                                                  */
+    int64_t capacity;
+    const int32_t* links;       /* [dev] [2R, R]                                                                    */
+    const float* data;          /* [dev] [capacity, L, 4]                                                           */
+    float sigma_thresh;         /* not NaN                                                                          */
+    int32_t dilate;             /* >= 0                                                                             */
+    uint8_t* mask;              /* [dev] [2, 2R, R, L] workspace (the volume and its dilation, alternating)         */
+    uint8_t* keep;              /* [dev] [2R, R] workspace                                                          */
+    int32_t* block_offsets;     /* [dev] [nerf_grid_compact_workspace(2 R R)] workspace                             */
+    int32_t* new_links;         /* [dev] [2R, R] out                                                                */
+    int32_t* count;             /* [dev] [1] out                                                                    */
+    void* stream;
+} nerf_grid_background_sparsify_args;
+
+typedef struct nerf_grid_background_gather_args {
+    size_t struct_size;
+    int32_t nlayers, reso;
+    int64_t capacity;           /* rows of data                                                                     */
+    const int32_t* links;       /* [dev] [2R, R]: the old links                                                     */
+    const float* data;          /* [dev] [capacity, L, 4]                                                           */
+    const int32_t* new_links;   /* [dev] [2R, R] of nerf_grid_background_sparsify_plan                              */
+    int64_t new_capacity;       /* *count of the plan                                                               */
+    float* new_data;            /* [dev] [new_capacity, L, 4], not overlapping data                                 */
+    void* stream;
+} nerf_grid_background_gather_args;
+
+int nerf_grid_set_background(nerf_sparse_grid* grid, const nerf_grid_background_desc* desc);
+int nerf_grid_has_background(const nerf_sparse_grid* grid);
+int nerf_grid_background_rays(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_background_args* args);
+int nerf_grid_background_image(nerf_sparse_grid* grid, const nerf_grid_camera* cam, const nerf_grid_render_options* opt,
+                               const nerf_grid_background_args* args);
+int nerf_grid_background_sparsify_plan(nerf_ctx* ctx, const nerf_grid_background_sparsify_args* args);
+int nerf_grid_background_gather(nerf_ctx* ctx, const nerf_grid_background_gather_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,8 @@ EXPORTS = (
     "nerf_grid_depth_rays_taped", "nerf_grid_depth_backward",
     "nerf_grid_floater_heatmap", "nerf_grid_component_view",
     "nerf_grid_half_row_halfs", "nerf_grid_pack_half", "nerf_grid_unpack_half", "nerf_grid_create_half",
+    "nerf_grid_set_background", "nerf_grid_has_background", "nerf_grid_background_rays", "nerf_grid_background_image",
+    "nerf_grid_background_sparsify_plan", "nerf_grid_background_gather",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -286,6 +288,28 @@ class GridPackHalfArgs(_Sized):
                 ("rows", C.c_int64), ("sh_data", _FP), ("sh_half", _FP), ("clamped", _FP), ("stream", C.c_void_p)]
 
 
+class GridBackgroundDesc(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("nlayers", C.c_int32), ("reso", C.c_int32), ("capacity", C.c_int64),
+                ("links", _FP), ("data", _FP), ("stream", C.c_void_p)]
+
+
+class GridBackgroundArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("rgb", _FP),
+                ("log_transmit", _FP), ("stream", C.c_void_p)]
+
+
+class GridBackgroundSparsifyArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("nlayers", C.c_int32), ("reso", C.c_int32), ("capacity", C.c_int64),
+                ("links", _FP), ("data", _FP), ("sigma_thresh", C.c_float), ("dilate", C.c_int32), ("mask", _FP), ("keep", _FP),
+                ("block_offsets", _FP), ("new_links", _FP), ("count", _FP), ("stream", C.c_void_p)]
+
+
+class GridBackgroundGatherArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("nlayers", C.c_int32), ("reso", C.c_int32), ("capacity", C.c_int64),
+                ("links", _FP), ("data", _FP), ("new_links", _FP), ("new_capacity", C.c_int64), ("new_data", _FP),
+                ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -488,6 +512,19 @@ def load():
     lib.nerf_grid_unpack_half.argtypes = [vp, vp, i64, C.c_int32, vp, vp]
     lib.nerf_grid_create_half.restype = i32
     lib.nerf_grid_create_half.argtypes = [vp, C.POINTER(GridHalfDesc), C.POINTER(vp)]
+    lib.nerf_grid_set_background.restype = i32
+    lib.nerf_grid_set_background.argtypes = [vp, C.POINTER(GridBackgroundDesc)]
+    lib.nerf_grid_has_background.restype = i32
+    lib.nerf_grid_has_background.argtypes = [vp]
+    lib.nerf_grid_background_rays.restype = i32
+    lib.nerf_grid_background_rays.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridBackgroundArgs)]
+    lib.nerf_grid_background_image.restype = i32
+    lib.nerf_grid_background_image.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridRenderOptions),
+                                               C.POINTER(GridBackgroundArgs)]
+    lib.nerf_grid_background_sparsify_plan.restype = i32
+    lib.nerf_grid_background_sparsify_plan.argtypes = [vp, C.POINTER(GridBackgroundSparsifyArgs)]
+    lib.nerf_grid_background_gather.restype = i32
+    lib.nerf_grid_background_gather.argtypes = [vp, C.POINTER(GridBackgroundGatherArgs)]
     _lib = lib
     return lib
 

@@ -7,6 +7,7 @@
 //   grid_depth_api.cpp      expected depth, threshold depth, ray length
 //   grid_depth_autograd_api.cpp   taped expected depth, backward with cotangents for depth and log_transmit
 //   grid_half_api.cpp       half-precision colours: pack / unpack, create; render and sample are dispatched from grid_api.cpp
+//   grid_background_api.cpp background layers: attach / detach, the background pass, the two calls of the thinning
 //   grid_*_kernels.hip      the kernels of each, on grid_device.h (sampling, rays) and compact_device.h (compaction)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -304,6 +305,39 @@ hipError_t launch_grid_half_render(const GridDev& g, const GridRenderOpt& o, con
 hipError_t launch_grid_half_sample(const GridDev& g, const float* points, int64_t n, int grid_coords, int want_colors,
                                    float* density, float* sh, hipStream_t s);
 
+// ---- background layers (grid_background_kernels.hip) ----
+struct GridBg {
+    const int32_t* links;              // [2 reso, reso], or nullptr: no background attached
+    const float* data;                 // [capacity, nlayers, 4]
+    int32_t nlayers, reso;
+    int64_t capacity;
+};
+
+struct GridBgRender {
+    const float* origins;              // nullptr: the rays of `cam`
+    const float* dirs;
+    GridCam cam;
+    int64_t n_rays;
+    float* rgb;                        // [n_rays, 3] in / out
+    float* log_transmit;               // [n_rays] in / out
+};
+
+struct GridBgSparsify {
+    GridBg bg;
+    float sigma_thresh;
+    int32_t dilate;
+    uint8_t* mask;                     // [2, 2 reso, reso, nlayers]
+    uint8_t* keep;                     // [2 reso, reso]
+    int32_t* block_offsets;
+    int32_t* new_links;
+    int32_t* count;
+};
+
+hipError_t launch_grid_background(const GridDev& g, const GridBg& bg, const GridRenderOpt& o, const GridBgRender& r, hipStream_t s);
+hipError_t launch_grid_background_plan(const GridBgSparsify& a, hipStream_t s);
+hipError_t launch_grid_background_gather(const GridBg& bg, const int32_t* new_links, int64_t new_capacity, float* new_data,
+                                         hipStream_t s);
+
 }  // namespace nerf
 
 struct nerf_sparse_grid {
@@ -312,4 +346,5 @@ struct nerf_sparse_grid {
     uint8_t* d_skip = nullptr;
     bool half = false;                 // made by nerf_grid_create_half: g.sh_half is the colour table, g.sh is nullptr
     bool half_pair = false;            // ... and it renders with two coefficients per lane
+    nerf::GridBg bg{};                 // nerf_grid_set_background; bg.links == nullptr: none
 };

@@ -6,7 +6,8 @@ forward (inference) side: ``volume_render``, ``volume_render_image``, ``volume_r
 one of this package's ``NeRF`` models into a grid.
 The semantics of every call are stated in include/nerf_mi355x.h, "Sparse voxel grid"; everything runs in HIP kernels
 (csrc/grid_kernels.hip, csrc/grid_depth_kernels.hip) and, as everywhere in this package, there is no CPU or PyTorch fallback.
-What svox2 has and this module does not (background layers, learned bases, the other backends) raises ``NotImplementedError``; so do the svox2-named
+What svox2 has and this module does not (learned bases, the other backends) raises ``NotImplementedError``, and so do background
+layers on ``SparseGrid`` itself: a grid with them is ``grid_background.BackgroundGrid``. So do the svox2-named
 training methods on ``SparseGrid`` - training a grid is ``grid_train.GridTrainer``, under names of its own.
 ``SparseGrid.to_half()`` gives the inference twin with fp16 colours on the device, ``grid_half.HalfGrid``.
 """
@@ -236,9 +237,13 @@ def _volume_arg(t, name, dtype, ctx=None):
 
 
 def _refuse_half(grid, who):
-    """``TypeError`` for a ``grid_half.HalfGrid`` where the fp32 SH table of a grid is read or written."""
+    """``TypeError`` for a ``grid_half.HalfGrid`` where the fp32 SH table of a grid is read or written, and
+    ``NotImplementedError`` for a ``grid_background.BackgroundGrid`` where only a foreground is handled."""
     if getattr(grid, "is_half", False):
         raise TypeError(f"{who} reads or writes the fp32 SH table of a SparseGrid and a HalfGrid has none: pass grid.to_float()")
+    if getattr(grid, "use_background", False):
+        raise NotImplementedError(f"{who} is built for the foreground only (training, resampling and pruning a background are "
+                                  "not): pass grid.foreground(), the SparseGrid on the same tensors")
 
 
 def _as_u8(mask):
@@ -312,7 +317,7 @@ class SparseGrid:
         if basis_dim not in (1, 4, 9):
             raise ValueError(f"basis_dim {basis_dim}: spherical harmonics of 1, 4 or 9 coefficients are built")
         if background_nlayers:
-            raise NotImplementedError("background MSI layers are not built")
+            raise NotImplementedError("background MSI layers are not built into SparseGrid: grid_background.BackgroundGrid has them")
         if torch.device(device).type != "cuda":
             raise RuntimeError(f"device {device} is not a GPU: SparseGrid has no CPU fallback")
         self.ctx = get_context(device)
@@ -653,7 +658,8 @@ class SparseGrid:
         not built (background layers, learned bases)."""
         z = np.load(path)
         if "background_data" in z.files:
-            raise NotImplementedError("background MSI layers are not built")
+            raise NotImplementedError("background MSI layers are not built into SparseGrid: grid_background.load_grid / "
+                                      "BackgroundGrid.load open this file")
         basis_type = int(z["basis_type"].item()) if "basis_type" in z.files else BASIS_TYPE_SH
         if basis_type != BASIS_TYPE_SH or "basis_data" in z.files:
             raise NotImplementedError("only spherical harmonics (BASIS_TYPE_SH) are built, not learned bases")

@@ -118,6 +118,9 @@ class HalfGrid(SparseGrid):
             return g
         if not isinstance(grid, SparseGrid):
             raise TypeError("HalfGrid.from_grid needs a SparseGrid")
+        if grid.use_background:
+            raise NotImplementedError("HalfGrid.from_grid: half-precision colours with background layers are not built: pass "
+                                      "grid.foreground()")
         grid._handle()      # validates the tensors
         ctx = grid.ctx
         sh_half = torch.empty((grid.capacity, row_halfs(grid.basis_dim)), dtype=torch.float16, device=ctx.device)
