@@ -1459,6 +1459,115 @@ int nerf_grid_background_image(nerf_sparse_grid* grid, const nerf_grid_camera* c
 int nerf_grid_background_sparsify_plan(nerf_ctx* ctx, const nerf_grid_background_sparsify_args* args);
 int nerf_grid_background_gather(nerf_ctx* ctx, const nerf_grid_background_gather_args* args);
 
+/* Sparse voxel grid: background layers, training ------------------------------------------------------
+ * What svox2's optimisation loop does to the background: the background pass of volume_render_fused with a tape,
+ * render_background_backward, inplace_tv_background_grad (msi_tv_grad_sparse_kernel) and optim_background_step. All four are
+ * stream-ordered and synchronise nothing. Gradients ACCUMULATE: the caller zeroes grad_background [capacity, L, 4] and
+ * mask_background [capacity, L] (bytes) when a new step begins. fp32, every operation rounded (no fused multiply-add),
+ * unless fp64 is said. Row indices are 64-bit. The march - set-up, steps, cell, fetch, p, weight, log_T, the skip, sigma > 0
+ * and stop rules - is that of section "Sparse voxel grid: background layers", the same device code.
+ *
+ * nerf_grid_background_rays_taped is nerf_grid_background_rays: rgb (in / out) and the new log_transmit are bit-identical to
+ * that call's. It reads the foreground's log_transmit and writes the new one to log_transmit_out, so that the backward still
+ * has the incoming value (the two may not be the same array). `tape` [n, 3] fp64 comes from nerf_grid_render_rays_taped of the
+ * foreground, rendered with background_brightness = 0. Per ray:
+ *   tape_background_c = the fp64 sum of the exact products weight * max(0, col_c) over all shaded steps, plus
+ *                       (double)exp(log_T) * (double)background_brightness, with col_c = (v_c * 0.28209479177387814) + 0.5:
+ *                       the background's colour without the rounding of its fp32 sum
+ *   tape_c = tape_c + tape_background_c
+ *   a ray left alone (log_T < -25): tape_background_c = 0, tape and rgb untouched, log_transmit_out = log_T
+ *   a ray whose set-up is not finite: tape_background_c = (double)exp(log_T) * (double)background_brightness, added to tape_c
+ *     too; log_transmit_out = log_T
+ * The combined tape makes the foreground's nerf_grid_render_backward complete without any change to it: started from it,
+ * `remaining` after a ray's last foreground sample is the background's colour (svox2's accum carried from the foreground
+ * kernel into the background one).
+ *
+ * nerf_grid_background_backward marches every ray once more from the foreground's log_transmit, with g_c = grad_rgb[ray, c]
+ * and remaining_c = tape_background[ray, c] (fp64, for the reason given in the training section). At every shaded step
+ * (v_3 > 0), with p, weight, log_T as in the forward:
+ *   dot = (max(0, col_0) g_0 + max(0, col_1) g_1) + max(0, col_2) g_2
+ *   remaining_c -= weight * max(0, col_c)   (fp64, exact products);   accum = fp32(sum_c remaining_c g_c)   (c = 0, 1, 2)
+ *   d_3 = ((invr_last - invr) * world_step) * (exp(log_T after the step) * dot - accum)                      (sigma)
+ *   d_c = (0.28209479177387814 * weight) * g_c  where col_c > 0 (strict, as the reference), else 0           (colours)
+ *   for each of the 4 texels (X, Y) in {l_x, nx} x {l_y, ny} that has a row, and every channel c = 0..3:
+ *     xo = (1 - w_x) * d_c at X = l_x, w_x * d_c at X = nx;   val = (1 - w_y) * xo at Y = l_y, w_y * xo at Y = ny
+ *     grad[(link * L + l_z) * 4 + c] += val * (1 - w_z);   grad[(link * L + l_z + 1) * 4 + c] += val * w_z
+ *     (a term that is zero is not added);  mask[link * L + l_z] = mask[link * L + l_z + 1] = 1, whatever the terms
+ * A ray left alone and a ray whose set-up is not finite contribute nothing; a ray that misses the box still crosses the
+ * layers and does contribute. The adds are float atomics (one hardware add each, no compare-and-swap): two calls agree to
+ * rounding of the sums, not bit for bit. mask_background may be NULL. sparsity_loss and beta_loss are not built
+ * (NERF_E_INVALID naming the feature), randomize is refused with the options.
+ *
+ * nerf_grid_background_tv_grad: for the `count` cells (start + i) mod (2R * R * L), i < count, of the [2R, R, L] volume (z
+ * fastest) and each of the 4 channels c, on the background attached to the grid:
+ *   v00 = the cell's value, v10 that of (nx, y, z), v01 that of (x, ny, z): both axes wrap; a texel without a row reads 0 and
+ *   receives nothing. v_nxl = the value of layer z + 1 of the same texel; at the last layer, or without a row, it is 0 for
+ *   sigma (c = 3) and v00 for the colours, and nothing is added at z + 1.
+ *   dx = v10 - v00, dy = v01 - v00, dz = v_nxl - v00;  idelta = scale_c / sqrt(((1e-9 + dx dx) + dy dy) + dz dz), scale_c =
+ *   scale_sigma for c = 3, else scale_color (the caller passes scaling / count);  dx *= 2R / 256, dy *= R / 256, dz *= L / 256
+ *   grad[v00] += -((dx + dy) + dz) * idelta, grad[v_nxl] += dz * idelta, grad[v01] += dy * idelta, grad[v10] += dx * idelta
+ * each only if the value added is not zero, and then the mask byte of that (row, layer) is set.
+ *
+ * nerf_grid_background_optim_step: nerf_grid_optim_step's arithmetic element for element (the same device function: its
+ * NaN, subnormal, -0 and minval rules) over data [rows, 4], rows = capacity * L, in the rows whose mask byte is set, with
+ * lr = lr_color for the columns 0..2 and lr_sigma for column 3 (svox2's lr_last). */
+typedef struct nerf_grid_background_taped_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]                                                                */
+    const float* dirs;          /* [dev] [n_rays, 3], need not be unit                                              */
+    int64_t n_rays;             /* 0: nothing is done                                                               */
+    float* rgb;                 /* [dev] [n_rays, 3] in / out                                                       */
+    const float* log_transmit;  /* [dev] [n_rays]: the foreground's, not written                                    */
+    float* log_transmit_out;    /* [dev] [n_rays] out, another array than log_transmit                              */
+    double* tape;               /* [dev] [n_rays, 3] in / out: the foreground's tape                                */
+    double* tape_background;    /* [dev] [n_rays, 3] out                                                            */
+    void* stream;
+} nerf_grid_background_taped_args;
+
+typedef struct nerf_grid_background_backward_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]       (those of the taped pass)                                */
+    const float* dirs;          /* [dev] [n_rays, 3]                                                                */
+    int64_t n_rays;             /* 0: nothing is done                                                               */
+    const float* grad_rgb;      /* [dev] [n_rays, 3] d loss / d rgb, contiguous                                     */
+    const float* log_transmit;  /* [dev] [n_rays]: the foreground's, as the taped pass read it                      */
+    const double* tape_background; /* [dev] [n_rays, 3] as the taped pass wrote it                                  */
+    float* grad_background;     /* [dev] [capacity, L, 4], added to                                                 */
+    uint8_t* mask_background;   /* [dev] [capacity, L] or NULL                                                      */
+    float sparsity_loss;        /* must be 0 (not built)                                                            */
+    float beta_loss;            /* must be 0 (not built)                                                            */
+    void* stream;
+} nerf_grid_background_backward_args;
+
+typedef struct nerf_grid_background_tv_args {
+    size_t struct_size;
+    int64_t start, count;       /* cells (start + i) mod 2R R L; 0 <= start < 2R R L, 0 <= count <= 2R R L           */
+    float scale_sigma;          /* finite                                                                           */
+    float scale_color;          /* finite                                                                           */
+    float* grad;                /* [dev] [capacity, L, 4], added to                                                 */
+    uint8_t* mask;              /* [dev] [capacity, L]                                                              */
+    void* stream;
+} nerf_grid_background_tv_args;
+
+typedef struct nerf_grid_background_optim_args {
+    size_t struct_size;
+    float* data;                /* [dev] [rows, 4], updated in place: background_data                               */
+    float* rms;                 /* [dev] [rows, 4] (RMSProp; may be NULL for SGD)                                   */
+    const float* grad;          /* [dev] [rows, 4]                                                                  */
+    const uint8_t* mask;        /* [dev] [rows]                                                                     */
+    int64_t rows;               /* capacity * L, in [0, 2^35]                                                       */
+    int32_t kind;               /* NERF_GRID_OPTIM_RMSPROP / NERF_GRID_OPTIM_SGD                                    */
+    float beta, lr_sigma, lr_color, eps, minval;
+    void* stream;
+} nerf_grid_background_optim_args;
+
+int nerf_grid_background_rays_taped(nerf_sparse_grid* grid, const nerf_grid_render_options* opt,
+                                    const nerf_grid_background_taped_args* args);
+int nerf_grid_background_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* opt,
+                                  const nerf_grid_background_backward_args* args);
+int nerf_grid_background_tv_grad(nerf_sparse_grid* grid, const nerf_grid_background_tv_args* args);
+int nerf_grid_background_optim_step(nerf_ctx* ctx, const nerf_grid_background_optim_args* args);
+
 #ifdef __cplusplus
 }
 #endif

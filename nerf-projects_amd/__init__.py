@@ -24,6 +24,8 @@ from . import grid_background  # noqa: F401
 from .grid_background import BackgroundGrid, load_grid  # noqa: F401
 from . import grid_train  # noqa: F401
 from .grid_train import GridTrainer  # noqa: F401
+from . import grid_background_train  # noqa: F401
+from .grid_background_train import BackgroundTrainer  # noqa: F401
 from . import grid_autograd  # noqa: F401
 from .grid_autograd import GridModule  # noqa: F401
 from . import grid_resample  # noqa: F401

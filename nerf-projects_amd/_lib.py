@@ -39,6 +39,8 @@ EXPORTS = (
     "nerf_grid_half_row_halfs", "nerf_grid_pack_half", "nerf_grid_unpack_half", "nerf_grid_create_half",
     "nerf_grid_set_background", "nerf_grid_has_background", "nerf_grid_background_rays", "nerf_grid_background_image",
     "nerf_grid_background_sparsify_plan", "nerf_grid_background_gather",
+    "nerf_grid_background_rays_taped", "nerf_grid_background_backward", "nerf_grid_background_tv_grad",
+    "nerf_grid_background_optim_step",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -310,6 +312,29 @@ class GridBackgroundGatherArgs(_Sized):
                 ("stream", C.c_void_p)]
 
 
+class GridBackgroundTapedArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("rgb", _FP),
+                ("log_transmit", _FP), ("log_transmit_out", _FP), ("tape", _FP), ("tape_background", _FP),
+                ("stream", C.c_void_p)]
+
+
+class GridBackgroundBackwardArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("grad_rgb", _FP),
+                ("log_transmit", _FP), ("tape_background", _FP), ("grad_background", _FP), ("mask_background", _FP),
+                ("sparsity_loss", C.c_float), ("beta_loss", C.c_float), ("stream", C.c_void_p)]
+
+
+class GridBackgroundTvArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("start", C.c_int64), ("count", C.c_int64), ("scale_sigma", C.c_float),
+                ("scale_color", C.c_float), ("grad", _FP), ("mask", _FP), ("stream", C.c_void_p)]
+
+
+class GridBackgroundOptimArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("data", _FP), ("rms", _FP), ("grad", _FP), ("mask", _FP), ("rows", C.c_int64),
+                ("kind", C.c_int32), ("beta", C.c_float), ("lr_sigma", C.c_float), ("lr_color", C.c_float), ("eps", C.c_float),
+                ("minval", C.c_float), ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -525,6 +550,14 @@ def load():
     lib.nerf_grid_background_sparsify_plan.argtypes = [vp, C.POINTER(GridBackgroundSparsifyArgs)]
     lib.nerf_grid_background_gather.restype = i32
     lib.nerf_grid_background_gather.argtypes = [vp, C.POINTER(GridBackgroundGatherArgs)]
+    lib.nerf_grid_background_rays_taped.restype = i32
+    lib.nerf_grid_background_rays_taped.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridBackgroundTapedArgs)]
+    lib.nerf_grid_background_backward.restype = i32
+    lib.nerf_grid_background_backward.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridBackgroundBackwardArgs)]
+    lib.nerf_grid_background_tv_grad.restype = i32
+    lib.nerf_grid_background_tv_grad.argtypes = [vp, C.POINTER(GridBackgroundTvArgs)]
+    lib.nerf_grid_background_optim_step.restype = i32
+    lib.nerf_grid_background_optim_step.argtypes = [vp, C.POINTER(GridBackgroundOptimArgs)]
     _lib = lib
     return lib
 

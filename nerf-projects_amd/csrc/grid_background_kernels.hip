@@ -7,11 +7,13 @@
 // corner are 32 contiguous bytes, so a step is 4 link loads and 8 float4 loads, all channels interpolated from the same
 // registers (the reference runs four scalar trilinear fetches per step, sigma and then each colour). Rows reach
 // capacity * nlayers * 4 floats, past 2^31 at 2048 x 1024 texels of 64 layers: every row index is int64_t.
+// The march itself (set-up, sphere hit, texel coordinates, fetch, stop rule) is background_march of grid_background_device.h,
+// which the taped pass and the backward of grid_background_train_kernels.hip walk too.
 // The image form makes its rays in the launch and, like grid_depth_kernels.hip, gives a wavefront an 8 x 8 tile of pixels
 // rather than 64 pixels of a row: neighbouring rays hit neighbouring texels on every sphere, so a tile's 64 loads fall on
 // fewer lines than a row's (DESIGN.md has the A/B). No LDS, no scratch, no atomics, no shuffles: a result depends on its own
 // ray only, two runs give the same bits.
-#include "grid_device.h"
+#include "grid_background_device.h"
 
 namespace nerf {
 namespace {
@@ -31,24 +33,6 @@ __device__ __forceinline__ int64_t background_pixel(const GridCam& cam) {
 
 int64_t background_image_threads(const GridCam& cam) {
     return (int64_t)((cam.width + kTile - 1) / kTile) * ((cam.height + kTile - 1) / kTile) * (kTile * kTile);
-}
-
-__device__ __forceinline__ float dot3(const float a[3], const float b[3]) {
-    return add(add(mul(a[0], b[0]), mul(a[1], b[1])), mul(a[2], b[2]));
-}
-
-__device__ __forceinline__ float lerp1(float a, float b, float w) { return add(a, mul(w, sub(b, a))); }
-
-__device__ __forceinline__ float4 lerp4(const float4& a, const float4& b, float w) {
-    return make_float4(lerp1(a.x, b.x, w), lerp1(a.y, b.y, w), lerp1(a.z, b.z, w), lerp1(a.w, b.w, w));
-}
-
-// texel (x, y) between layers lz and lz + 1: zeros without a row
-__device__ __forceinline__ float4 background_texel(const GridBg& bg, int x, int y, int lz, float wz) {
-    const int link = bg.links[x * bg.reso + y];
-    if (link < 0 || (int64_t)link >= bg.capacity) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    const float4* row = reinterpret_cast<const float4*>(bg.data) + ((int64_t)link * bg.nlayers + lz);
-    return lerp4(row[0], row[1], wz);
 }
 
 template <bool IMAGE>
@@ -75,67 +59,12 @@ __global__ __launch_bounds__(kGridThreads) void grid_background_kernel(GridDev g
         return;
     }
 
-    float O[3], D[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float s = 2.0f / (float)g.size[i];
-        O[i] = sub(mul(add(rs.o[i], 0.5f), s), 1.0f);
-        D[i] = mul(rs.d[i], s);
-    }
-    const float inorm = 1.0f / sqrtf(dot3(D, D));
-#pragma unroll
-    for (int i = 0; i < 3; ++i) D[i] = mul(D[i], inorm);
-    const float world_step = mul(rs.delta_scale, inorm);
-    const float q2a = mul(2.0f, dot3(D, D));
-    const float qb = mul(2.0f, dot3(O, D));
-    const float two_q2a = mul(2.0f, q2a);
-    const float f = sub(mul(qb, qb), mul(two_q2a, dot3(O, O)));
-    const float C[3] = {sub(mul(O[1], D[2]), mul(O[2], D[1])), sub(mul(O[2], D[0]), mul(O[0], D[2])),
-                        sub(mul(O[0], D[1]), mul(O[1], D[0]))};
-    const float inner = fmaxf(add(sqrtf(dot3(C, C)), 1e-3f), 1.0f);
-    float invr_last = 1.0f / inner;
-
-    const int L = bg.nlayers, R = bg.reso;
-    const float Lf = (float)L;
-    const int n = (int)(Lf / opt.step_size) + 2;      // <= 1024 / 1e-3 + 2: the loop ends unconditionally
-    constexpr double kInvPi = 0.318309886183790671538;
     float out[3] = {0.0f, 0.0f, 0.0f};
-    for (int i = 0; i < n; ++i) {
-        const float rad = (float)((double)n / ((double)(n - i) - 0.5));
-        if (rad < inner) continue;
-        const float det = add(f, mul(mul(two_q2a, rad), rad));
-        if (det < 0.0f) continue;
-        const float t = add(-qb, sqrtf(det)) / q2a;
-        const float P[3] = {add(O[0], mul(t, D[0])), add(O[1], mul(t, D[1])), add(O[2], mul(t, D[2]))};
-        const float invr = 1.0f / sqrtf(dot3(P, P));
-        const float lat = asinf(mul(P[1], invr));
-        const float lon = atan2f(mul(P[0], invr), mul(P[2], invr));
-        const float x = (float)((double)(2 * R) * (0.5 + ((double)lon * 0.5) * kInvPi));
-        const float y = (float)((double)R * (0.5 - (double)lat * kInvPi));
-        const float z = fminf(fmaxf(sub(mul(sub(1.0f, invr), Lf), 0.5f), 0.0f), (float)(L - 1));
-        // (a NaN coordinate is sent to texel 0 explicitly: nothing may index outside the tables)
-        const int lx = x == x ? max(0, min((int)x, 2 * R - 1)) : 0;
-        const int ly = y == y ? max(0, min((int)y, R - 1)) : 0;
-        const int lz = max(0, min((int)z, L - 2));
-        const float wx = sub(x, (float)lx), wy = sub(y, (float)ly), wz = sub(z, (float)lz);
-        const int nx = lx < 2 * R - 1 ? lx + 1 : 0;
-        const int ny = ly < R - 1 ? ly + 1 : 0;
-        const float4 v00 = background_texel(bg, lx, ly, lz, wz);
-        const float4 v01 = background_texel(bg, lx, ny, lz, wz);
-        const float4 v10 = background_texel(bg, nx, ly, lz, wz);
-        const float4 v11 = background_texel(bg, nx, ny, lz, wz);
-        const float4 v = lerp4(lerp4(v00, v01, wy), lerp4(v10, v11, wy), wx);
-        if (v.w > 0.0f) {
-            const float p = mul(mul(sub(invr_last, invr), world_step), v.w);
-            const float weight = mul(expf(log_t), sub(1.0f, expf(-p)));
-            log_t = sub(log_t, p);
-            out[0] = add(out[0], mul(weight, fmaxf(add(mul(v.x, 0.28209479177387814f), 0.5f), 0.0f)));
-            out[1] = add(out[1], mul(weight, fmaxf(add(mul(v.y, 0.28209479177387814f), 0.5f), 0.0f)));
-            out[2] = add(out[2], mul(weight, fmaxf(add(mul(v.z, 0.28209479177387814f), 0.5f), 0.0f)));
-            if (expf(log_t) < opt.stop_thresh) break;
-        }
-        invr_last = invr;
-    }
+    log_t = background_march(g, bg, opt, rs, log_t, [&](const BgSample&, const float4& v, float, float weight, float) {
+        out[0] = add(out[0], mul(weight, fmaxf(background_colour(v.x), 0.0f)));
+        out[1] = add(out[1], mul(weight, fmaxf(background_colour(v.y), 0.0f)));
+        out[2] = add(out[2], mul(weight, fmaxf(background_colour(v.z), 0.0f)));
+    });
     const float b = mul(expf(log_t), opt.background_brightness);
 #pragma unroll
     for (int c = 0; c < 3; ++c) rgb[c] = add(rgb[c], add(out[c], b));

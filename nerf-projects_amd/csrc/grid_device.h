@@ -385,5 +385,23 @@ __device__ __forceinline__ void march_colour_bwd(const GridDev& g, const GridRen
     });
 }
 
+// One element of svox2's rmsprop_mask_step_kernel / sgd_mask_step_kernel (include/nerf_mi355x.h, nerf_grid_optim_step): every
+// operation one rounded fp32 operation, in the order written; fmaxf drops a NaN, so a NaN update lands on minval. Shared by the
+// foreground's and the background's step kernels.
+template <bool RMSPROP>
+__device__ __forceinline__ void optim_element(float* data, float* rms, int64_t i, float gr, float beta, float lr, float eps,
+                                              float minval) {
+    if (RMSPROP) {
+        const float g2 = mul(gr, gr);
+        float r = rms[i];
+        r = r == 0.0f ? g2 : add(g2, mul(beta, sub(r, g2)));
+        rms[i] = r;
+        const float upd = mul(lr, gr) / add(sqrtf(r), eps);
+        data[i] = fmaxf(sub(data[i], upd), minval);
+    } else {
+        data[i] = fmaxf(sub(data[i], mul(lr, gr)), minval);
+    }
+}
+
 }  // namespace
 }  // namespace nerf

@@ -8,6 +8,7 @@
 //   grid_depth_autograd_api.cpp   taped expected depth, backward with cotangents for depth and log_transmit
 //   grid_half_api.cpp       half-precision colours: pack / unpack, create; render and sample are dispatched from grid_api.cpp
 //   grid_background_api.cpp background layers: attach / detach, the background pass, the two calls of the thinning
+//   grid_background_train_api.cpp   background layers, training: taped pass, backward, TV gradient, optimiser step
 //   grid_*_kernels.hip      the kernels of each, on grid_device.h (sampling, rays) and compact_device.h (compaction)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -337,6 +338,50 @@ hipError_t launch_grid_background(const GridDev& g, const GridBg& bg, const Grid
 hipError_t launch_grid_background_plan(const GridBgSparsify& a, hipStream_t s);
 hipError_t launch_grid_background_gather(const GridBg& bg, const int32_t* new_links, int64_t new_capacity, float* new_data,
                                          hipStream_t s);
+
+// ---- background layers, training (grid_background_train_kernels.hip) ----
+struct GridBgTaped {
+    const float* origins;
+    const float* dirs;
+    int64_t n_rays;
+    float* rgb;                        // [n_rays, 3] in / out
+    const float* log_transmit;         // [n_rays]: the foreground's
+    float* log_transmit_out;           // [n_rays]
+    double* tape;                      // [n_rays, 3] in / out
+    double* tape_background;           // [n_rays, 3] out
+};
+
+struct GridBgBwd {
+    const float* origins;
+    const float* dirs;
+    int64_t n_rays;
+    const float* grad_rgb;             // [n_rays, 3]
+    const float* log_transmit;         // [n_rays]: the foreground's
+    const double* tape_background;     // [n_rays, 3]
+    float* grad_background;            // [capacity, nlayers, 4], added to
+    uint8_t* mask_background;          // [capacity, nlayers], or nullptr
+};
+
+struct GridBgTv {
+    int64_t start, count;              // cells (start + i) mod 2R R L, i < count
+    float scale_sigma, scale_color;
+    float* grad;                       // [capacity, nlayers, 4], added to
+    uint8_t* mask;                     // [capacity, nlayers]
+};
+
+struct GridBgOptim {
+    float* data;                       // [rows, 4], rows = capacity * nlayers
+    float* rms;                        // RMSProp only
+    const float* grad;
+    const uint8_t* mask;               // [rows]
+    int64_t rows;
+    float beta, lr_sigma, lr_color, eps, minval;
+};
+
+hipError_t launch_grid_background_taped(const GridDev& g, const GridBg& bg, const GridRenderOpt& o, const GridBgTaped& r, hipStream_t s);
+hipError_t launch_grid_background_bwd(const GridDev& g, const GridBg& bg, const GridRenderOpt& o, const GridBgBwd& r, hipStream_t s);
+hipError_t launch_grid_background_tv(const GridBg& bg, const GridBgTv& a, hipStream_t s);
+hipError_t launch_grid_background_optim(const GridBgOptim& a, int rmsprop, hipStream_t s);
 
 }  // namespace nerf
 

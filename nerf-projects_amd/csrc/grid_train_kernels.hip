@@ -91,23 +91,13 @@ __global__ __launch_bounds__(kGridThreads) void grid_tv_grad_kernel(GridDev g, G
 }
 
 // svox2's rmsprop_mask_step_kernel / sgd_mask_step_kernel, one thread per element of the rows whose mask byte is set. Every
-// operation is one rounded fp32 operation, in the order written (include/nerf_mi355x.h states it).
+// operation is one rounded fp32 operation, in the order written (include/nerf_mi355x.h states it): optim_element of grid_device.h.
 template <bool RMSPROP>
 __global__ __launch_bounds__(kGridThreads) void grid_optim_step_kernel(GridOptim a) {
     const int64_t tid = (int64_t)blockIdx.x * kGridThreads + threadIdx.x;
     if (tid >= a.rows * a.cols) return;
     if (!a.mask[tid / a.cols]) return;
-    const float gr = a.grad[tid];
-    if (RMSPROP) {
-        const float g2 = mul(gr, gr);
-        float rms = a.rms[tid];
-        rms = rms == 0.0f ? g2 : add(g2, mul(a.beta, sub(rms, g2)));
-        a.rms[tid] = rms;
-        const float upd = mul(a.lr, gr) / add(sqrtf(rms), a.eps);
-        a.data[tid] = fmaxf(sub(a.data[tid], upd), a.minval);
-    } else {
-        a.data[tid] = fmaxf(sub(a.data[tid], mul(a.lr, gr)), a.minval);
-    }
+    optim_element<RMSPROP>(a.data, a.rms, tid, a.grad[tid], a.beta, a.lr, a.eps, a.minval);
 }
 
 }  // namespace

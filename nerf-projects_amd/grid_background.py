@@ -8,8 +8,9 @@ voxel grid: background layers": the semantics of the reference's CUDA kernel, no
 on the device with :meth:`BackgroundGrid.sparsify_background`. As everywhere in this package there is no CPU or PyTorch
 fallback.
 
-Forward and inference side only: ``GridTrainer``, ``GridModule``, ``resample_grid``, ``remove_floaters`` and ``to_half``
-raise a ``NotImplementedError`` that names :meth:`BackgroundGrid.foreground`, the ``SparseGrid`` on the same tensors.
+Training it is ``grid_background_train.BackgroundTrainer``. ``GridTrainer``, ``GridModule``, ``resample_grid``,
+``remove_floaters`` and ``to_half`` handle a foreground only and raise a ``NotImplementedError`` that names
+:meth:`BackgroundGrid.foreground`, the ``SparseGrid`` on the same tensors.
 """
 import ctypes as C
 from dataclasses import replace
