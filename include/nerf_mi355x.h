@@ -767,8 +767,8 @@ int nerf_grid_project_sh(nerf_ctx* ctx, const nerf_grid_project_args* args);
  *       mask[row] = 1 - for EVERY kept corner of EVERY shaded sample, whatever its weight (svox2's sparse_grad_indexer)
  * A ray that misses the box or whose set-up is not finite writes its rgb_out (the background) and no gradient.
  * The adds are float atomics (one hardware add each, no compare-and-swap): two calls on the same input agree to rounding of
- * the sums, not bit for bit. beta_loss, sparsity_loss, background layers, randomize and last_sample_opaque are not built:
- * NERF_E_INVALID naming the feature.
+ * the sums, not bit for bit. beta_loss, sparsity_loss, background layers, randomize and last_sample_opaque are not built
+ * in this call: NERF_E_INVALID naming the feature (nerf_grid_fused_backward_losses, below, has the two losses).
  *
  * nerf_grid_tv_grad: for the `count` nodes (start + i) mod X Y Z, i < count (svox2's contiguous random cells) and the columns
  * [start_dim, end_dim) of the density or the SH table, with v000 the node's value and v100, v010, v001 its +x, +y, +z
@@ -776,7 +776,8 @@ int nerf_grid_project_sh(nerf_ctx* ctx, const nerf_grid_project_args* args);
  *   dx = v100 - v000, dy, dz likewise;  idelta = scale / sqrt(((1e-9 + dx dx) + dy dy) + dz dz)
  *   dx *= X / 256, dy *= Y / 256, dz *= Z / 256
  *   grad[v100] += dx * idelta, grad[v010] += dy * idelta, grad[v001] += dz * idelta, grad[v000] += -((dx + dy) + dz) * idelta
- * each only if the value added is not zero, and then mask[row] = 1. ignore_edge, ignore_last_z and NDC are not built.
+ * each only if the value added is not zero, and then mask[row] = 1. ignore_edge, ignore_last_z and NDC are not built in this
+ * call (nerf_grid_tv_grad_edge, below, has ignore_edge).
  *
  * nerf_grid_optim_step: elementwise over data [rows, cols] in the rows whose mask byte is set; other rows, and their rms,
  * are not touched. fp32, each operation correctly rounded, in this order:
@@ -800,8 +801,8 @@ typedef struct nerf_grid_fused_args {
     float* grad_density;        /* [dev] [capacity, 1], added to                                                    */
     float* grad_sh;             /* [dev] [capacity, 3 * basis_dim], added to                                        */
     uint8_t* mask;              /* [dev] [capacity]                                                                 */
-    float beta_loss;            /* must be 0 (not built)                                                            */
-    float sparsity_loss;        /* must be 0 (not built)                                                            */
+    float beta_loss;            /* must be 0 (not built) except in nerf_grid_fused_backward_losses                  */
+    float sparsity_loss;        /* must be 0 (not built) except in nerf_grid_fused_backward_losses                  */
     int32_t background_nlayers; /* must be 0 (not built)                                                            */
     int32_t use_skip;           /* 1: use the skip data if nerf_grid_accelerate made it                             */
     void* stream;
@@ -815,7 +816,7 @@ typedef struct nerf_grid_tv_args {
     int32_t start_dim, end_dim; /* columns of that table                                                            */
     int64_t start, count;       /* nodes (start + i) mod X Y Z; 0 <= start < X Y Z, 0 <= count <= X Y Z              */
     float scale;
-    int32_t ignore_edge;        /* must be 0 (not built)                                                            */
+    int32_t ignore_edge;        /* must be 0 (not built) except in nerf_grid_tv_grad_edge: 0 or 1                   */
     int32_t ignore_last_z;      /* must be 0 (not built)                                                            */
     int32_t use_ndc;            /* must be 0 (not built)                                                            */
     float* grad;                /* [dev] shaped like the table, added to                                            */
@@ -841,6 +842,63 @@ typedef struct nerf_grid_optim_args {
 int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_fused_args* args);
 int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* args);
 int nerf_grid_optim_step(nerf_ctx* ctx, const nerf_grid_optim_args* args);
+
+/* Sparse voxel grid: training with the beta and sparsity losses -----------------------------------
+ * What svox2's published configurations add to the step above: the two regularisers its volume_render_cuvol_fused folds into
+ * the density gradient of the same march (lambda_beta, lambda_sparsity), and the edge rule its inplace_tv_color_grad always
+ * runs with (ignore_edge). The capability has entries of its own: nerf_grid_fused_backward, nerf_grid_render_backward,
+ * nerf_grid_tv_grad and nerf_grid_background_backward keep refusing these fields. The device code is shared; the terms are a
+ * compile-time variant of the same kernels, so the entries above launch the code they launched before. All three calls are
+ * stream-ordered, synchronise nothing, and ACCUMULATE as above.
+ *
+ * nerf_grid_fused_backward_losses is nerf_grid_fused_backward - the same struct, the same contract: rgb_out and log_transmit
+ * bit-identical to nerf_grid_render_rays, background_nlayers, randomize and last_sample_opaque refused, zero rays do nothing -
+ * and honours beta_loss and sparsity_loss, both finite and >= 0 (else NERF_E_INVALID naming the field); with both 0 it IS
+ * nerf_grid_fused_backward (the same kernel). For a ray that is marched, fp32, each operation rounded, in this order
+ * (trace_ray_cuvol_backward):
+ *   T_in   = exp(log_T_final)     the forward's final log_transmit of this ray (-1e3 where it stopped, so T_in = 0); in the
+ *                                 fused kernel it is the first march's own value, nothing goes through memory
+ *   c_beta = beta_loss * (1 - T_in / ((1 - T_in) + 1e-3))                        only if beta_loss > 0
+ *   at every shaded sample (sigma > sigma_thresh), after accum = fp32(sum_c remaining_c g_c) is formed as above:
+ *     accum'  = accum + c_beta                                                    only if beta_loss > 0
+ *     d_sigma = (step_size * delta_scale) * (exp(log_T after the sample) * dot - accum')
+ *     d_sigma = d_sigma + sparsity_loss * ((4 sigma) / (1 + 2 (sigma sigma)))     only if sparsity_loss > 0
+ * and everything else - d_coef, the corner weights, zero terms not added, the mask at every kept corner of every shaded
+ * sample - is as above: grad_sh and the set of touched rows do not depend on the two weights. c_beta is the derivative of
+ *   beta_loss * sum_ray [log_T + log((1 - exp(log_T)) + 1e-3)]
+ * with respect to the ray's final log_T, and the last line that of sparsity_loss * sum over shaded samples of
+ * log(1 + 2 sigma^2) with respect to the sample's sigma. beta_loss is applied as given: svox2 passes lambda_beta / n_rays
+ * to its kernel, and so does this project's Python.
+ *
+ * nerf_grid_render_backward_losses is nerf_grid_render_backward (args: that call's struct, every rule of it) and takes the
+ * terms in a struct of its own. T_in comes from losses->log_transmit[ray], the taped foreground render's log_transmit; it is
+ * required when beta_loss > 0. The terms touch grad_density only: a NULL grad_density together with a non-zero weight is
+ * NERF_E_INVALID. c_beta is no part of the tape: a background pass that continues from the tape never sees it (svox2 removes
+ * it from its accum_out again). With both weights 0 it is nerf_grid_render_backward (the same kernel).
+ *
+ * nerf_grid_tv_grad_edge is nerf_grid_tv_grad - the same struct, the same checks, target SH refused on a half-precision
+ * handle - and honours ignore_edge in {0, 1}; with 0 it IS nerf_grid_tv_grad (the same kernel). With 1
+ * (tv_grad_sparse_kernel with ignore_edge = true):
+ *   a cell whose own link is exactly row 0 does nothing (the reference's literal `*links_ptr == 0`, followed literally:
+ *     it is what its checkpoints were trained with);
+ *   v000 = the cell's own value, 0 where the cell itself is empty;
+ *   a neighbour that is empty or lies outside the lattice reads v000 instead of 0: its difference is 0 and it receives nothing;
+ *   so an empty cell still contributes the differences towards its kept neighbours, and a kept cell none towards empty ones;
+ *   idelta, the scales X / 256, Y / 256, Z / 256, zero terms not added and the mask are as in nerf_grid_tv_grad.
+ * ignore_last_z (it belongs to last_sample_opaque) and use_ndc are refused as there. */
+struct nerf_grid_render_backward_args;      /* "Sparse voxel grid: gradients for autograd", below */
+typedef struct nerf_grid_render_backward_losses_args {
+    size_t struct_size;
+    float beta_loss;            /* finite, >= 0; applied as given                                                   */
+    float sparsity_loss;        /* finite, >= 0                                                                     */
+    const float* log_transmit;  /* [dev] [n_rays] of the taped foreground render; required when beta_loss > 0       */
+} nerf_grid_render_backward_losses_args;
+
+int nerf_grid_fused_backward_losses(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_fused_args* args);
+int nerf_grid_render_backward_losses(nerf_sparse_grid* grid, const nerf_grid_render_options* opt,
+                                     const struct nerf_grid_render_backward_args* args,
+                                     const nerf_grid_render_backward_losses_args* losses);
+int nerf_grid_tv_grad_edge(nerf_sparse_grid* grid, const nerf_grid_tv_args* args);
 
 /* Sparse voxel grid: gradients for autograd -------------------------------------------------------
  * The two halves of nerf_grid_fused_backward as calls of their own, with the cotangent d loss / d rgb supplied by the caller
@@ -1496,7 +1554,8 @@ int nerf_grid_background_gather(nerf_ctx* ctx, const nerf_grid_background_gather
  * A ray left alone and a ray whose set-up is not finite contribute nothing; a ray that misses the box still crosses the
  * layers and does contribute. The adds are float atomics (one hardware add each, no compare-and-swap): two calls agree to
  * rounding of the sums, not bit for bit. mask_background may be NULL. sparsity_loss and beta_loss are not built
- * (NERF_E_INVALID naming the feature), randomize is refused with the options.
+ * here (NERF_E_INVALID naming the feature): the foreground's share of both is nerf_grid_render_backward_losses', the
+ * sparsity term of the background's own sigma samples exists nowhere. randomize is refused with the options.
  *
  * nerf_grid_background_tv_grad: for the `count` cells (start + i) mod (2R * R * L), i < count, of the [2R, R, L] volume (z
  * fastest) and each of the 4 channels c, on the background attached to the grid:

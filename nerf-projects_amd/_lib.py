@@ -28,6 +28,7 @@ EXPORTS = (
     "nerf_grid_create", "nerf_grid_destroy", "nerf_grid_render_rays", "nerf_grid_render_image", "nerf_grid_gen_rays",
     "nerf_grid_sample", "nerf_grid_accelerate", "nerf_grid_drop_skip", "nerf_grid_has_skip", "nerf_grid_project_sh",
     "nerf_grid_fused_backward", "nerf_grid_tv_grad", "nerf_grid_optim_step",
+    "nerf_grid_fused_backward_losses", "nerf_grid_render_backward_losses", "nerf_grid_tv_grad_edge",
     "nerf_grid_lattice_density", "nerf_grid_weight_render", "nerf_grid_threshold", "nerf_grid_dilate",
     "nerf_grid_compact_workspace", "nerf_grid_compact", "nerf_grid_gather",
     "nerf_grid_components_occupancy", "nerf_grid_components_workspace", "nerf_grid_components_label",
@@ -205,6 +206,10 @@ class GridRenderBackwardArgs(_Sized):
     _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("grad_rgb", _FP),
                 ("tape", _FP), ("grad_density", _FP), ("grad_sh", _FP), ("mask", _FP), ("use_skip", C.c_int32),
                 ("stream", C.c_void_p)]
+
+
+class GridRenderBackwardLossesArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("beta_loss", C.c_float), ("sparsity_loss", C.c_float), ("log_transmit", _FP)]
 
 
 class GridSampleBackwardArgs(_Sized):
@@ -483,6 +488,13 @@ def load():
     lib.nerf_grid_tv_grad.argtypes = [vp, C.POINTER(GridTvArgs)]
     lib.nerf_grid_optim_step.restype = i32
     lib.nerf_grid_optim_step.argtypes = [vp, C.POINTER(GridOptimArgs)]
+    lib.nerf_grid_fused_backward_losses.restype = i32
+    lib.nerf_grid_fused_backward_losses.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridFusedArgs)]
+    lib.nerf_grid_render_backward_losses.restype = i32
+    lib.nerf_grid_render_backward_losses.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridRenderBackwardArgs),
+                                                     C.POINTER(GridRenderBackwardLossesArgs)]
+    lib.nerf_grid_tv_grad_edge.restype = i32
+    lib.nerf_grid_tv_grad_edge.argtypes = [vp, C.POINTER(GridTvArgs)]
     lib.nerf_grid_lattice_density.restype = i32
     lib.nerf_grid_lattice_density.argtypes = [vp, C.POINTER(GridLatticeArgs)]
     lib.nerf_grid_weight_render.restype = i32

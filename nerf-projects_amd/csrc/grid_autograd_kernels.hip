@@ -13,7 +13,9 @@
 // pointer is NULL gets nothing: the test is uniform over the launch.
 // Float adds are atomicAdd(float*) = one global_atomic_add_f32 without return (no compare-and-swap loop); the mask is
 // written with plain byte stores (every writer stores 1). No LDS, no scratch.
-#include "grid_device.h"
+// grid_render_bwd_kernel is written in grid_train_device.h; this file instantiates it without the loss terms,
+// grid_train_losses_kernels.hip with.
+#include "grid_train_device.h"
 
 namespace nerf {
 namespace {
@@ -32,26 +34,6 @@ __global__ __launch_bounds__(kGridThreads) void grid_taped_kernel(GridDev g, Gri
         r.tape[gl.ray * 3 + gl.col / B] = c.tot;
     }
     if (gl.lane == 0 && r.log_transmit) r.log_transmit[gl.ray] = c.log_t;
-}
-
-template <int B, bool SKIP>
-__global__ __launch_bounds__(kGridThreads) void grid_render_bwd_kernel(GridDev g, GridRenderOpt opt, GridRenderBwd r) {
-    const GroupLane gl = group_lane<B>();
-    if (gl.ray >= r.n_rays) return;
-    GridRay rs;
-    load_ray(r.origins, r.dirs, gl.ray, rs);
-    setup_ray<SKIP>(g, opt, rs);
-    if (!(rs.ok && rs.tmin <= rs.tmax)) return;      // a miss or a non-finite set-up: nothing to differentiate
-    const float yk = gl.busy ? sh_basis(gl.k, rs.v[0], rs.v[1], rs.v[2]) : 0.0f;
-    float gc[3];
-    double remaining[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        gc[c] = r.grad_rgb[gl.ray * 3 + c];
-        remaining[c] = r.tape[gl.ray * 3 + c];
-    }
-    march_colour_bwd<B, SKIP>(g, opt, rs, gl, yk, gc, remaining, r, gl.busy && r.grad_sh != nullptr, r.grad_density != nullptr,
-                              r.mask != nullptr);
 }
 
 // The transpose of grid_sample_kernel: one thread per (point, column), column 0 = density. The cell, the weights and the
@@ -102,9 +84,9 @@ hipError_t launch_grid_render_bwd(const GridDev& g, const GridRenderOpt& o, cons
         constexpr int B = decltype(b)::value;
         const unsigned blocks = blocks_for(r.n_rays * GroupLanes<B>::value);
         if (g.skip)
-            grid_render_bwd_kernel<B, true><<<blocks, kGridThreads, 0, s>>>(g, o, r);
+            grid_render_bwd_kernel<B, true, false><<<blocks, kGridThreads, 0, s>>>(g, o, r);
         else
-            grid_render_bwd_kernel<B, false><<<blocks, kGridThreads, 0, s>>>(g, o, r);
+            grid_render_bwd_kernel<B, false, false><<<blocks, kGridThreads, 0, s>>>(g, o, r);
         return hipGetLastError();
     });
 }

@@ -336,18 +336,30 @@ __device__ __forceinline__ Colour march_colour(const GridDev& g, const GridRende
 // passed samples gave); in fp32 its rounding, 6e-8 of the whole colour, is a relative 1e-3 of the small density gradients
 // behind a bright sample, which RMSProp's g / (sqrt(rms) + eps) turns into density errors of 1e-3. Kept in fp64, built from
 // and reduced by the very same exact products, it is exact to 1e-16 of the colour; everything else is fp32.
-template <int B, bool SKIP, class R>
+// LOSSES (include/nerf_mi355x.h, "Sparse voxel grid: training with the beta and sparsity losses"): svox2's two regularisers
+// folded into d_sigma, from r.beta_loss, r.sparsity_loss and the forward's final log_transmit of this ray, log_t_final. A
+// compile-time variant: without it this is the code it was before the terms existed, and nothing of them is read.
+template <int B, bool SKIP, bool LOSSES = false, class R>
 __device__ __forceinline__ void march_colour_bwd(const GridDev& g, const GridRenderOpt& opt, const GridRay& rs, const GroupLane& gl,
                                                  float yk, const float gc[3], double remaining[3], const R& r, bool want_sh,
-                                                 bool want_density, bool want_mask) {
+                                                 bool want_density, bool want_mask, float log_t_final = 0.0f) {
     constexpr int GL = GroupLanes<B>::value;
     constexpr int DL = GL < 8 ? GL : 8;      // lanes of a group that share the 8 density adds
     const float g_own = gl.col / B == 0 ? gc[0] : (gl.col / B == 1 ? gc[1] : gc[2]);
     const float step_ds = mul(opt.step_size, rs.delta_scale);
     const float neg_step = -opt.step_size;
     float log_t = 0.0f;
+    float c_beta = 0.0f;      // d (beta term) / d log_T of the whole ray: the same at every sample
+    if (LOSSES && r.beta_loss > 0.0f) {
+        const float t_in = expf(log_t_final);
+        c_beta = mul(r.beta_loss, sub(1.0f, __fdiv_rn(t_in, add(sub(1.0f, t_in), 1e-3f))));
+    }
     grid_march<SKIP>(g, opt, rs, [&](float, const int* lk, const float* wa, const float* wb, float sigma) {
         if (!(sigma > opt.sigma_thresh)) return false;
+        // (formed here, while few values are live: at the end of the sample it costs a wave of occupancy at basis_dim 4)
+        float d_sparsity = 0.0f;
+        if (LOSSES && r.sparsity_loss > 0.0f)
+            d_sparsity = mul(r.sparsity_loss, __fdiv_rn(mul(4.0f, sigma), add(1.0f, mul(2.0f, mul(sigma, sigma)))));
         const float part = shade_channel<B>(g, lk, wa, wb, gl.col, gl.k, yk);
         const float raw = add(part, 0.5f);      // complete in the lanes with k == 0
         const float a = mul(mul(neg_step, sigma), rs.delta_scale);
@@ -364,8 +376,10 @@ __device__ __forceinline__ void march_colour_bwd(const GridDev& g, const GridRen
             accum64 += remaining[c] * (double)gc[c];
             if (gl.col / B == c) raw_own = rc;
         }
-        const float accum = (float)accum64;
-        const float d_sigma = mul(step_ds, sub(mul(expf(log_t), dot), accum));
+        float accum = (float)accum64;
+        if (LOSSES && r.beta_loss > 0.0f) accum = add(accum, c_beta);
+        float d_sigma = mul(step_ds, sub(mul(expf(log_t), dot), accum));
+        if (LOSSES && r.sparsity_loss > 0.0f) d_sigma = add(d_sigma, d_sparsity);
         // max(0, .) passes the gradient where its argument is >= 0 (torch.clamp_min)
         const float d_coef = raw_own >= 0.0f ? mul(mul(weight, yk), g_own) : 0.0f;
 #pragma unroll

@@ -1,7 +1,7 @@
 // Sparse voxel grid (nerf_mi355x.h, "Sparse voxel grid"): what the host and the device side of the grid share.
 //   grid_api.cpp            create / render / sample / accelerate, and the argument checks every grid_*_api.cpp uses (below)
-//   grid_train_api.cpp      fused backward, TV gradient, optimiser step
-//   grid_autograd_api.cpp   taped render, render backward with a caller's cotangent, sample backward
+//   grid_train_api.cpp      fused backward, TV gradient, optimiser step; the same with the loss terms and the edge rule
+//   grid_autograd_api.cpp   taped render, render backward with a caller's cotangent (and with the loss terms), sample backward
 //   grid_resample_api.cpp   lattice density, weight render, threshold, dilate, compact, gather
 //   grid_components_api.cpp occupancy, labelling, volumes, keep mask, row copy
 //   grid_depth_api.cpp      expected depth, threshold depth, ray length
@@ -73,6 +73,7 @@ struct GridFused {
     float* grad_density;               // [capacity, 1], added to
     float* grad_sh;                    // [capacity, 3 B], added to
     uint8_t* mask;                     // [capacity], 1 stored at every kept corner of every shaded sample
+    float beta_loss, sparsity_loss;    // read by the LOSSES instantiations only (grid_train_losses_kernels.hip)
 };
 
 struct GridTv {
@@ -98,6 +99,9 @@ struct GridOptim {
 hipError_t launch_grid_fused(const GridDev& g, const GridRenderOpt& o, const GridFused& r, hipStream_t s);
 hipError_t launch_grid_tv_grad(const GridDev& g, const GridTv& a, hipStream_t s);
 hipError_t launch_grid_optim_step(const GridOptim& a, int rmsprop, hipStream_t s);
+// grid_train_losses_kernels.hip: the same kernels (grid_train_device.h) with the loss terms / the edge rule compiled in
+hipError_t launch_grid_fused_losses(const GridDev& g, const GridRenderOpt& o, const GridFused& r, hipStream_t s);
+hipError_t launch_grid_tv_grad_edge(const GridDev& g, const GridTv& a, hipStream_t s);
 
 // ---- gradients for autograd (grid_autograd_kernels.hip) ----
 struct GridTaped {
@@ -118,6 +122,9 @@ struct GridRenderBwd {
     float* grad_density;               // added to; each of the three may be nullptr: nothing is issued for it
     float* grad_sh;
     uint8_t* mask;
+    // read by the LOSSES instantiations only (grid_train_losses_kernels.hip)
+    const float* log_transmit;         // [n_rays] the taped render's; may be nullptr where beta_loss is 0
+    float beta_loss, sparsity_loss;
 };
 
 struct GridSampleBwd {
@@ -133,6 +140,7 @@ struct GridSampleBwd {
 hipError_t launch_grid_render_taped(const GridDev& g, const GridRenderOpt& o, const GridTaped& r, hipStream_t s);
 hipError_t launch_grid_render_bwd(const GridDev& g, const GridRenderOpt& o, const GridRenderBwd& r, hipStream_t s);
 hipError_t launch_grid_sample_bwd(const GridDev& g, const GridSampleBwd& a, hipStream_t s);
+hipError_t launch_grid_render_bwd_losses(const GridDev& g, const GridRenderOpt& o, const GridRenderBwd& r, hipStream_t s);
 
 // ---- resampling (grid_resample_kernels.hip) ----
 constexpr int64_t kGridMaxLattice = (int64_t)1 << 30;   // nodes of a resampling lattice: 1024^3

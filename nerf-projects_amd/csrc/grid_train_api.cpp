@@ -1,5 +1,7 @@
-// C ABI of sparse voxel grid training (include/nerf_mi355x.h, "Sparse voxel grid: training"): argument checks and launches.
-// Every check that needs no device comes before the first dereference of a handle.
+// C ABI of sparse voxel grid training (include/nerf_mi355x.h, "Sparse voxel grid: training" and "Sparse voxel grid: training
+// with the beta and sparsity losses"): argument checks and launches. Every check that needs no device comes before the first
+// dereference of a handle. nerf_grid_fused_backward / nerf_grid_fused_backward_losses and nerf_grid_tv_grad /
+// nerf_grid_tv_grad_edge share one set of checks each: the older entry of a pair refuses what only the newer one has built.
 #include <cmath>
 
 #include "ctx_internal.h"
@@ -7,22 +9,31 @@
 
 using namespace nerf;
 
-extern "C" {
+namespace {
 
-int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* o, const nerf_grid_fused_args* a) {
-    const char* fn = "nerf_grid_fused_backward";
+// a loss weight of the *_losses entries: finite and >= 0
+int check_loss_weight(const char* fn, const char* field, float v) {
+    if (std::isfinite(v) && v >= 0.0f) return NERF_OK;
+    set_error("%s: %s = %g must be finite and >= 0", fn, field, v);
+    return NERF_E_INVALID;
+}
+
+int fused_backward(const char* fn, bool losses, nerf_sparse_grid* grid, const nerf_grid_render_options* o, const nerf_grid_fused_args* a) {
     int rc = require_grid(fn, grid);
     if (rc != NERF_OK) return rc;
     GridRenderOpt opt{};
     rc = check_grid_options(fn, o, &opt);
     if (rc != NERF_OK) return rc;
     NERF_CHECK_STRUCT(fn, a, nerf_grid_fused_args);
-    if (a->beta_loss != 0.0f) {
-        set_error("%s: beta_loss is not built", fn);
+    if (losses) {
+        rc = check_loss_weight(fn, "beta_loss", a->beta_loss);
+        if (rc == NERF_OK) rc = check_loss_weight(fn, "sparsity_loss", a->sparsity_loss);
+        if (rc != NERF_OK) return rc;
+    } else if (a->beta_loss != 0.0f) {
+        set_error("%s: beta_loss is not built here: nerf_grid_fused_backward_losses has it", fn);
         return NERF_E_INVALID;
-    }
-    if (a->sparsity_loss != 0.0f) {
-        set_error("%s: sparsity_loss is not built", fn);
+    } else if (a->sparsity_loss != 0.0f) {
+        set_error("%s: sparsity_loss is not built here: nerf_grid_fused_backward_losses has it", fn);
         return NERF_E_INVALID;
     }
     if (a->background_nlayers != 0) {
@@ -49,22 +60,36 @@ int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_opti
     r.grad_density = a->grad_density;
     r.grad_sh = a->grad_sh;
     r.mask = a->mask;
+    r.beta_loss = a->beta_loss;
+    r.sparsity_loss = a->sparsity_loss;
     rc = refuse_half_grid(fn, grid);      // (the first read of the handle)
     if (rc != NERF_OK) return rc;
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;
     DeviceGuard dg(grid->ctx->device);
-    HIP_TRY(launch_grid_fused(g, opt, r, (hipStream_t)a->stream));
+    // with both weights 0 the losses entry is the plain one: the same kernel
+    if (r.beta_loss > 0.0f || r.sparsity_loss > 0.0f)
+        HIP_TRY(launch_grid_fused_losses(g, opt, r, (hipStream_t)a->stream));
+    else
+        HIP_TRY(launch_grid_fused(g, opt, r, (hipStream_t)a->stream));
     return NERF_OK;
 }
 
-int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* a) {
-    const char* fn = "nerf_grid_tv_grad";
+int tv_grad(const char* fn, bool edge_entry, nerf_sparse_grid* grid, const nerf_grid_tv_args* a) {
     int rc = require_grid(fn, grid);
     if (rc != NERF_OK) return rc;
     NERF_CHECK_STRUCT(fn, a, nerf_grid_tv_args);
-    if (a->ignore_edge || a->ignore_last_z || a->use_ndc) {
-        set_error("%s: ignore_edge, ignore_last_z and NDC scaling are not built", fn);
+    if (edge_entry) {
+        if (a->ignore_edge != 0 && a->ignore_edge != 1) {
+            set_error("%s: ignore_edge = %d must be 0 or 1", fn, a->ignore_edge);
+            return NERF_E_INVALID;
+        }
+        if (a->ignore_last_z || a->use_ndc) {
+            set_error("%s: ignore_last_z and NDC scaling are not built", fn);
+            return NERF_E_INVALID;
+        }
+    } else if (a->ignore_edge || a->ignore_last_z || a->use_ndc) {
+        set_error("%s: ignore_edge, ignore_last_z and NDC scaling are not built here: nerf_grid_tv_grad_edge has ignore_edge", fn);
         return NERF_E_INVALID;
     }
     if (a->target != NERF_GRID_TV_DENSITY && a->target != NERF_GRID_TV_SH) {
@@ -109,9 +134,28 @@ int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* a) {
     t.scale = a->scale;
     for (int k = 0; k < 3; ++k) t.axis_scale[k] = (float)g.size[k] * (1.0f / 256.0f);
     DeviceGuard dg(grid->ctx->device);
-    HIP_TRY(launch_grid_tv_grad(g, t, (hipStream_t)a->stream));
+    if (a->ignore_edge)
+        HIP_TRY(launch_grid_tv_grad_edge(g, t, (hipStream_t)a->stream));
+    else
+        HIP_TRY(launch_grid_tv_grad(g, t, (hipStream_t)a->stream));
     return NERF_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int nerf_grid_fused_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* o, const nerf_grid_fused_args* a) {
+    return fused_backward("nerf_grid_fused_backward", false, grid, o, a);
+}
+
+int nerf_grid_fused_backward_losses(nerf_sparse_grid* grid, const nerf_grid_render_options* o, const nerf_grid_fused_args* a) {
+    return fused_backward("nerf_grid_fused_backward_losses", true, grid, o, a);
+}
+
+int nerf_grid_tv_grad(nerf_sparse_grid* grid, const nerf_grid_tv_args* a) { return tv_grad("nerf_grid_tv_grad", false, grid, a); }
+
+int nerf_grid_tv_grad_edge(nerf_sparse_grid* grid, const nerf_grid_tv_args* a) { return tv_grad("nerf_grid_tv_grad_edge", true, grid, a); }
 
 int nerf_grid_optim_step(nerf_ctx* c, const nerf_grid_optim_args* a) {
     const char* fn = "nerf_grid_optim_step";

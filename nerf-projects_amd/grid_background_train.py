@@ -5,7 +5,9 @@ in include/nerf_mi355x.h, "Sparse voxel grid: background layers, training". The 
 optimisation loop under names of their own::
 
     svox2                                                        here
-    grid.volume_render_fused(rays, rgb_gt, ...)                  trainer.forward_backward(rays, rgb_gt)
+    grid.volume_render_fused(rays, rgb_gt)                       trainer.forward_backward(rays, rgb_gt)
+    grid.volume_render_fused(rays, rgb_gt, beta_loss=...,        trainer.volume_render_fused(rays, rgb_gt, beta_loss=...,
+        sparsity_loss=...)                                           sparsity_loss=...)      (sparsity: foreground samples only)
     grid.inplace_tv_background_grad(grid.background_data.grad)   trainer.add_tv_grad("background", ...)
     grid.optim_background_step(lr_sigma_bg, lr_color_bg, ...)    trainer.step(..., lr_sigma_bg, lr_color_bg, ...)
     grid.sparsify_background(...)                                trainer.sparsify_background(...)
@@ -22,7 +24,8 @@ import numpy as np
 import torch
 
 from ._lib import (NERF_GRID_OPTIM_RMSPROP, NERF_GRID_OPTIM_SGD, GridBackgroundBackwardArgs, GridBackgroundOptimArgs,
-                   GridBackgroundTapedArgs, GridBackgroundTvArgs, GridRenderBackwardArgs, GridRenderTapedArgs, check)
+                   GridBackgroundTapedArgs, GridBackgroundTvArgs, GridRenderBackwardArgs, GridRenderBackwardLossesArgs,
+                   GridRenderTapedArgs, check)
 from .grid import Rays
 from .grid_background import BackgroundGrid
 from .grid_train import GridTrainer
@@ -92,6 +95,26 @@ class BackgroundTrainer:
         add the gradients of ``mean((rgb - rgb_gt) ** 2)`` to ``grad_density``, ``grad_sh`` and ``grad_background``, marking
         what was touched in ``mask`` and ``mask_background``. Five launches on one stream, no host wait: the taped foreground
         (brightness 0), the taped background pass, the foreground's backward from the combined tape, the background's."""
+        return self._forward_backward(rays, rgb_gt, None, return_log_transmit)
+
+    def volume_render_fused(self, rays: Rays, rgb_gt: torch.Tensor, randomize: bool = False, beta_loss: float = 0.0,
+                            sparsity_loss: float = 0.0, return_log_transmit: bool = False):
+        """svox2's ``grid.volume_render_fused`` with its two regularisers (``GridTrainer.volume_render_fused`` states them):
+        the launches of :meth:`forward_backward`, with ``nerf_grid_render_backward_losses`` as the foreground's backward and
+        the foreground's own ``log_transmit`` (before the background pass) as its ``T_in``, as in svox2. ``beta_loss`` is
+        divided by the number of rays; ``sparsity_loss`` is passed as given and is applied to FOREGROUND samples only: svox2
+        also applies it to the sigma samples of the background layers, which is not built
+        (``nerf_grid_background_backward`` refuses it). ``grad_background`` does not depend on either weight.
+        ``randomize=True`` is refused."""
+        for name, v in (("beta_loss", beta_loss), ("sparsity_loss", sparsity_loss)):
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{name} = {v} must be finite and >= 0")
+        if randomize:
+            raise NotImplementedError("randomize is not built")
+        return self._forward_backward(rays, rgb_gt, (float(beta_loss), float(sparsity_loss)), return_log_transmit)
+
+    def _forward_backward(self, rays, rgb_gt, losses, return_log_transmit):
+        """``losses``: ``None`` (the foreground's backward is ``nerf_grid_render_backward``) or ``(lambda_beta, sparsity_loss)``"""
         g = self.grid
         h = self._sync()
         opt = g.opt._to_c(False)
@@ -131,7 +154,12 @@ class BackgroundTrainer:
         r.origins, r.dirs, r.n_rays, r.grad_rgb, r.tape = o.data_ptr(), d.data_ptr(), n, grad_rgb.data_ptr(), tape.data_ptr()
         r.grad_density, r.grad_sh, r.mask = self.grad_density.data_ptr(), self.grad_sh.data_ptr(), self.mask.data_ptr()
         r.use_skip, r.stream = 1, stream
-        check(lib.nerf_grid_render_backward(h, C.byref(fg_opt), C.byref(r)))
+        if losses is None:
+            check(lib.nerf_grid_render_backward(h, C.byref(fg_opt), C.byref(r)))
+        else:
+            ls = GridRenderBackwardLossesArgs()
+            ls.beta_loss, ls.sparsity_loss, ls.log_transmit = losses[0] / n, losses[1], logt_fg.data_ptr()
+            check(lib.nerf_grid_render_backward_losses(h, C.byref(fg_opt), C.byref(r), C.byref(ls)))
         w = GridBackgroundBackwardArgs()
         w.origins, w.dirs, w.n_rays, w.grad_rgb = o.data_ptr(), d.data_ptr(), n, grad_rgb.data_ptr()
         w.log_transmit, w.tape_background = logt_fg.data_ptr(), tape_bg.data_ptr()
@@ -140,8 +168,8 @@ class BackgroundTrainer:
         return (rgb, logt) if return_log_transmit else rgb
 
     def add_tv_grad(self, target: str = "density", scaling: float = 1.0, scaling_density: float = None, sparse_frac: float = 0.01,
-                    start: int = None, start_dim: int = 0, end_dim: int = None):
-        """``"density"`` / ``"sh"``: ``GridTrainer.add_tv_grad`` on the foreground tables. ``"background"``: svox2's
+                    start: int = None, start_dim: int = 0, end_dim: int = None, ignore_edge: bool = False):
+        """``"density"`` / ``"sh"``: ``GridTrainer.add_tv_grad`` on the foreground tables (``ignore_edge`` included). ``"background"``: svox2's
         ``inplace_tv_background_grad`` over ``max(1, int(sparse_frac * 2R R L))`` cells of the ``[2R, R, L]`` volume starting at
         cell ``start`` (C order, wrapping past the last; drawn from ``self.generator`` when ``None``), with ``scaling`` for the
         colours and ``scaling_density`` (default: ``scaling``) for sigma; the kernel receives each divided by the count.
@@ -150,9 +178,11 @@ class BackgroundTrainer:
         if target in ("density", "sh"):
             if scaling_density is not None:
                 raise ValueError("scaling_density belongs to target 'background'")
-            return self._fg.add_tv_grad(target, scaling, sparse_frac, start, start_dim, end_dim)
+            return self._fg.add_tv_grad(target, scaling, sparse_frac, start, start_dim, end_dim, ignore_edge)
         if target != "background":
             raise ValueError(f"target {target!r}: 'density', 'sh' or 'background'")
+        if ignore_edge:
+            raise ValueError("ignore_edge belongs to the targets 'density' and 'sh'")
         if start_dim != 0 or end_dim is not None:
             raise ValueError("start_dim / end_dim belong to the targets 'density' and 'sh'")
         if not 0.0 < sparse_frac <= 1.0:
@@ -194,15 +224,20 @@ class BackgroundTrainer:
     def train_step(self, rays: Rays, rgb_gt: torch.Tensor, lr_sigma: float = 30.0, lr_sh: float = 1e-2, lr_sigma_bg: float = 3.0,
                    lr_color_bg: float = 0.1, beta: float = 0.95, epsilon: float = 1e-8, optim: str = "rmsprop",
                    lambda_tv: float = 0.0, lambda_tv_sh: float = 0.0, lambda_tv_background_sigma: float = 0.0,
-                   lambda_tv_background_color: float = 0.0, tv_sparsity: float = 0.01, tv_background_sparsity: float = 0.01):
-        """``zero_grad``, ``forward_backward``, the TV gradients whose weight is not zero, ``step``. Returns
-        ``{"mse", "psnr"}`` of the batch before the step (reading them waits for the device)."""
+                   lambda_tv_background_color: float = 0.0, tv_sparsity: float = 0.01, tv_background_sparsity: float = 0.01,
+                   lambda_beta: float = 0.0, lambda_sparsity: float = 0.0, tv_sh_ignore_edge: bool = False):
+        """``zero_grad``, ``forward_backward`` (``volume_render_fused`` where ``lambda_beta`` or ``lambda_sparsity`` is not
+        zero), the TV gradients whose weight is not zero, ``step``. ``tv_sh_ignore_edge=True`` is what svox2's colour TV does.
+        Returns ``{"mse", "psnr"}`` of the batch before the step (reading them waits for the device)."""
         self.zero_grad()
-        rgb = self.forward_backward(rays, rgb_gt)
+        if lambda_beta or lambda_sparsity:
+            rgb = self.volume_render_fused(rays, rgb_gt, beta_loss=lambda_beta, sparsity_loss=lambda_sparsity)
+        else:
+            rgb = self.forward_backward(rays, rgb_gt)
         if lambda_tv:
             self.add_tv_grad("density", lambda_tv, sparse_frac=tv_sparsity)
         if lambda_tv_sh:
-            self.add_tv_grad("sh", lambda_tv_sh, sparse_frac=tv_sparsity)
+            self.add_tv_grad("sh", lambda_tv_sh, sparse_frac=tv_sparsity, ignore_edge=tv_sh_ignore_edge)
         if lambda_tv_background_sigma or lambda_tv_background_color:
             self.add_tv_grad("background", lambda_tv_background_color, lambda_tv_background_sigma, tv_background_sparsity)
         self.step(lr_sigma, lr_sh, lr_sigma_bg, lr_color_bg, beta, epsilon, optim)

@@ -5,9 +5,11 @@ csrc/grid_train_kernels.hip; the semantics of every call are stated in include/n
 training". It is the counterpart of svox2's training loop under names of its own::
 
     svox2                                              here
-    grid.volume_render_fused(rays, rgb_gt, ...)        trainer.forward_backward(rays, rgb_gt)
+    grid.volume_render_fused(rays, rgb_gt)             trainer.forward_backward(rays, rgb_gt)
+    grid.volume_render_fused(rays, rgb_gt,             trainer.volume_render_fused(rays, rgb_gt,
+        beta_loss=..., sparsity_loss=...)                  beta_loss=..., sparsity_loss=...)
     grid.inplace_tv_grad(grid.density_data.grad, ...)  trainer.add_tv_grad("density", ...)
-    grid.inplace_tv_color_grad(grid.sh_data.grad, ...) trainer.add_tv_grad("sh", ...)
+    grid.inplace_tv_color_grad(grid.sh_data.grad, ...) trainer.add_tv_grad("sh", ..., ignore_edge=True)
     grid.optim_density_step / grid.optim_sh_step       trainer.step(lr_sigma, lr_sh, ...)
     grid.resample(reso, ...)                           trainer.resample(reso, ...)      (grid_resample.py)
     (nothing)                                          trainer.remove_floaters(...)     (grid_components.py)
@@ -107,13 +109,33 @@ class GridTrainer:
     def forward_backward(self, rays: Rays, rgb_gt: torch.Tensor, beta_loss: float = 0.0, sparsity_loss: float = 0.0,
                          randomize: bool = False, return_log_transmit: bool = False):
         """Render ``rays`` (``rgb_out [N, 3]``, bit-identical to ``grid.volume_render(rays)``) and add the gradients of
-        ``mean((rgb_out - rgb_gt) ** 2)`` to ``grad_density`` / ``grad_sh``, marking the touched rows in ``mask``."""
+        ``mean((rgb_out - rgb_gt) ** 2)`` to ``grad_density`` / ``grad_sh``, marking the touched rows in ``mask``.
+        ``beta_loss`` and ``sparsity_loss`` are refused here: :meth:`volume_render_fused` has them."""
+        if beta_loss:
+            raise NotImplementedError("beta_loss is not built in forward_backward: use volume_render_fused")
+        if sparsity_loss:
+            raise NotImplementedError("sparsity_loss is not built in forward_backward: use volume_render_fused")
+        return self._fused(rays, rgb_gt, 0.0, 0.0, randomize, return_log_transmit, "nerf_grid_fused_backward")
+
+    def volume_render_fused(self, rays: Rays, rgb_gt: torch.Tensor, randomize: bool = False, beta_loss: float = 0.0,
+                            sparsity_loss: float = 0.0, return_log_transmit: bool = False):
+        """svox2's ``grid.volume_render_fused``: :meth:`forward_backward` plus the two regularisers of its published
+        configurations, folded into the density gradient of the same march. ``beta_loss`` is ``opt.py``'s ``lambda_beta``:
+        the kernel receives it divided by the number of rays, as svox2's does, and adds the gradient of
+        ``(beta_loss / N) * sum_ray [log_T + log(1 - exp(log_T) + 1e-3)]``. ``sparsity_loss`` is ``lambda_sparsity``, passed as
+        given: the gradient of ``sparsity_loss * sum over shaded samples of log(1 + 2 sigma ** 2)``. Both are finite and
+        ``>= 0``; ``rgb_out``, ``grad_sh`` and ``mask`` do not depend on them. ``randomize=True`` is refused."""
+        for name, v in (("beta_loss", beta_loss), ("sparsity_loss", sparsity_loss)):
+            if not (math.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{name} = {v} must be finite and >= 0")
+        if randomize:
+            raise NotImplementedError("randomize is not built")
+        return self._fused(rays, rgb_gt, float(beta_loss), float(sparsity_loss), False, return_log_transmit,
+                           "nerf_grid_fused_backward_losses")
+
+    def _fused(self, rays, rgb_gt, lambda_beta, sparsity_loss, randomize, return_log_transmit, entry):
         g = self.grid
         self._check_capacity()
-        if beta_loss:
-            raise NotImplementedError("beta_loss is not built")
-        if sparsity_loss:
-            raise NotImplementedError("sparsity_loss is not built")
         opt = g.opt._to_c(randomize)
         o = g._rays_arg(rays.origins, "rays.origins")
         d = g._rays_arg(rays.dirs, "rays.dirs", o.shape[0])
@@ -133,17 +155,21 @@ class GridTrainer:
         a.rgb_out = rgb.data_ptr()
         a.log_transmit = 0 if logt is None else logt.data_ptr()
         a.grad_density, a.grad_sh, a.mask = self.grad_density.data_ptr(), self.grad_sh.data_ptr(), self.mask.data_ptr()
+        a.beta_loss, a.sparsity_loss = lambda_beta / max(n, 1), sparsity_loss      # (svox2 divides lambda_beta by the rays too)
         a.use_skip = 1
         a.stream = self.ctx.stream().value
-        check(self.ctx.lib.nerf_grid_fused_backward(h, C.byref(opt), C.byref(a)))
+        check(getattr(self.ctx.lib, entry)(h, C.byref(opt), C.byref(a)))
         return (rgb, logt) if return_log_transmit else rgb
 
     def add_tv_grad(self, target: str = "density", scaling: float = 1.0, sparse_frac: float = 0.01, start: int = None,
-                    start_dim: int = 0, end_dim: int = None):
+                    start_dim: int = 0, end_dim: int = None, ignore_edge: bool = False):
         """Add the gradient of svox2's total-variation loss over ``max(1, int(sparse_frac * X Y Z))`` nodes starting at node
         ``start`` (C order, wrapping past the last; drawn from ``self.generator`` when ``None``) to the gradient of the
         ``"density"`` or the ``"sh"`` table, columns ``[start_dim, end_dim)``. The kernel receives
-        ``scaling / count`` as svox2's does. Returns ``(start, count)``."""
+        ``scaling / count`` as svox2's does. ``ignore_edge=True`` is the rule svox2's ``inplace_tv_color_grad`` always runs
+        with: an empty or out-of-range neighbour takes the cell's own value (no pull towards 0 at the shell of a sparse
+        grid), and the cell whose link is row 0 is left out (include/nerf_mi355x.h, ``nerf_grid_tv_grad_edge``). Returns
+        ``(start, count)``."""
         g = self.grid
         self._check_capacity()
         if target not in ("density", "sh"):
@@ -165,10 +191,12 @@ class GridTrainer:
         a.target = NERF_GRID_TV_DENSITY if target == "density" else NERF_GRID_TV_SH
         a.start_dim, a.end_dim, a.start, a.count = start_dim, end_dim, start, count
         a.scale = float(scaling) / count
+        a.ignore_edge = 1 if ignore_edge else 0
         a.grad = (self.grad_density if target == "density" else self.grad_sh).data_ptr()
         a.mask = self.mask.data_ptr()
         a.stream = self.ctx.stream().value
-        check(self.ctx.lib.nerf_grid_tv_grad(g._handle(), C.byref(a)))
+        entry = self.ctx.lib.nerf_grid_tv_grad_edge if ignore_edge else self.ctx.lib.nerf_grid_tv_grad
+        check(entry(g._handle(), C.byref(a)))
         return start, count
 
     def _step_one(self, data, rms, grad, kind, beta, lr, eps, minval):
@@ -194,15 +222,20 @@ class GridTrainer:
 
     def train_step(self, rays: Rays, rgb_gt: torch.Tensor, lr_sigma: float = 30.0, lr_sh: float = 1e-2, beta: float = 0.95,
                    epsilon: float = 1e-8, optim: str = "rmsprop", lambda_tv: float = 0.0, lambda_tv_sh: float = 0.0,
-                   tv_sparsity: float = 0.01):
-        """``zero_grad``, ``forward_backward``, the TV gradients whose weight is not zero, ``step``. Returns
-        ``{"mse", "psnr"}`` of the batch before the step (reading them waits for the device)."""
+                   tv_sparsity: float = 0.01, lambda_beta: float = 0.0, lambda_sparsity: float = 0.0,
+                   tv_sh_ignore_edge: bool = False):
+        """``zero_grad``, ``forward_backward`` (``volume_render_fused`` where ``lambda_beta`` or ``lambda_sparsity`` is not
+        zero), the TV gradients whose weight is not zero, ``step``. ``tv_sh_ignore_edge=True`` is what svox2's colour TV does.
+        Returns ``{"mse", "psnr"}`` of the batch before the step (reading them waits for the device)."""
         self.zero_grad()
-        rgb = self.forward_backward(rays, rgb_gt)
+        if lambda_beta or lambda_sparsity:
+            rgb = self.volume_render_fused(rays, rgb_gt, beta_loss=lambda_beta, sparsity_loss=lambda_sparsity)
+        else:
+            rgb = self.forward_backward(rays, rgb_gt)
         if lambda_tv:
             self.add_tv_grad("density", lambda_tv, tv_sparsity)
         if lambda_tv_sh:
-            self.add_tv_grad("sh", lambda_tv_sh, tv_sparsity)
+            self.add_tv_grad("sh", lambda_tv_sh, tv_sparsity, ignore_edge=tv_sh_ignore_edge)
         self.step(lr_sigma, lr_sh, beta, epsilon, optim)
         gt = rgb_gt.detach().to(device=rgb.device, dtype=torch.float32)
         mse = float(((rgb - gt) ** 2).mean()) if rgb.numel() else float("nan")
