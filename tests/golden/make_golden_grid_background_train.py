@@ -43,7 +43,6 @@ import make_golden_grid as MG  # noqa: E402
 import grid_background_oracle as BO  # noqa: E402
 import grid_background_train_oracle as BT  # noqa: E402
 import grid_oracle as GO  # noqa: E402
-import grid_train_oracle as GT  # noqa: E402
 
 svox2, ref_utils = MB.svox2, MB.ref_utils
 F = np.float32
@@ -104,11 +103,11 @@ def borderline(grid, o, d):
     bad = np.zeros(o.shape[0], bool)
     lo, hi = -25.0, np.log(0.05) + 0.05
 
-    def shade(rays, lk, wa, wb, raw, weight, log_t):
+    def shade(rays, lk, wa, wb, sigma, raw, weight, log_t):
         bad[rays[(log_t >= lo) & (log_t <= hi)]] = True
 
     for step in (0.5, 0.3):
-        GT._march(grid, o, d, step, 0.0, 0.0, 0.0, None, shade=shade)
+        GO.march_colour(grid, o, d, step, 0.0, 0.0, shade=shade)
     og, dg, _, ds, _, _, ok = GO.ray_setup(grid, o, d)
     su = BO.setup(np.where(ok[:, None], og, 0), np.where(ok[:, None], dg, 1), np.where(ok, ds, 1), RESO, np.float64)
     all_radii = np.unique(np.concatenate([BO.radii(nl, st) for nl, st, _, _ in SETTINGS]))
@@ -260,7 +259,7 @@ def main():
                   f"rows != 0: {int((a64.reshape(a64.shape[0], -1) != 0).any(-1).sum())} of {a64.shape[0]}")
         # the restatement's view of the same setting: the kernels' stop rule in the foreground, and the coverage
         res = BT.forward_backward(grid, bg, o, d, gt, step, 0.0, stop, bright)
-        fg_rgb, fg_logt, (_, _, _, tot) = GT._march(grid, o, d, step, 0.0, stop, 0.0, None)
+        fg_rgb, fg_logt, (_, _, _, tot), _ = GO.march_colour(grid, o, d, step, 0.0, stop)
         st = BT.taped(og, dg, ds, ok, RESO, bg, fg_rgb, fg_logt, tot, step, stop, bright, return_stats=True)[4]
         st64 = BT.taped(og, dg, ds, ok, RESO, bg, fg_rgb, fg_logt, tot, step, stop, bright, T=np.float64, return_stats=True)[4]
         assert (st["shaded"] == st64["shaded"]).all() and (st["stopped"] == st64["stopped"]).all(), "a ray stops in one precision only"

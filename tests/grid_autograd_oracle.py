@@ -1,10 +1,12 @@
 """numpy fp32 restatement of the sparse voxel grid's gradients for autograd (include/nerf_mi355x.h, "Sparse voxel grid:
 gradients for autograd"): the taped render, the render backward with a cotangent supplied from outside, and the transpose of
 the sampler - every operation a separate fp32 rounding in the order the header states, `remaining` in fp64. It builds on
-grid_train_oracle.py's march (same grid dict) and, like it, is a test oracle: slow and simple. Sums into a gradient row are
+grid_oracle.march_colour and grid_train_oracle.march_colour_bwd (same grid dict) and, like them, is a test oracle: slow and simple. Sums into a gradient row are
 taken in sample order (the kernels' atomics take them in any order), so gradients agree with the kernels to rounding of those
 sums.
 """
+import functools
+
 import numpy as np
 
 import grid_oracle as GO
@@ -16,7 +18,7 @@ F = GO.F
 def render_taped(grid, origins, dirs, step_size=0.5, sigma_thresh=1e-10, stop_thresh=1e-7, background_brightness=1.0,
                  near_clip=0.0, skip=None):
     """rgb [N, 3] fp32 (the render's), log_transmit [N], tape [N, 3] fp64"""
-    rgb, log_t, (_, _, _, tape) = GT._march(grid, origins, dirs, step_size, sigma_thresh, stop_thresh, near_clip, skip)
+    rgb, log_t, (_, _, _, tape), _ = GO.march_colour(grid, origins, dirs, step_size, sigma_thresh, stop_thresh, near_clip, skip)
     bg = np.exp(log_t).astype(F)
     rgb = (rgb + (bg * F(background_brightness))[:, None]).astype(F)
     tape = tape + (bg.astype(np.float64) * np.float64(F(background_brightness)))[:, None]
@@ -26,42 +28,16 @@ def render_taped(grid, origins, dirs, step_size=0.5, sigma_thresh=1e-10, stop_th
 def render_backward(grid, origins, dirs, grad_rgb, tape, step_size=0.5, sigma_thresh=1e-10, stop_thresh=1e-7,
                     near_clip=0.0, skip=None, grad_density=None, grad_sh=None, mask=None):
     """grad_density [C, 1], grad_sh [C, 3 B], mask [C] uint8 of ``sum(grad_rgb * rgb)``; added to when passed in"""
-    cap, cols = grid["density_data"].shape[0], grid["sh_data"].shape[1]
-    B = cols // 3
-    gd = np.zeros((cap, 1), dtype=F) if grad_density is None else grad_density
-    gs = np.zeros((cap, cols), dtype=F) if grad_sh is None else grad_sh
-    mk = np.zeros(cap, dtype=np.uint8) if mask is None else mask
+    gd, gs, mk = GT.grad_tables(grid, grad_density, grad_sh, mask)
     gc = np.asarray(grad_rgb, F)
-    remaining = np.array(tape, dtype=np.float64)      # (a copy: reduced below)
     if gc.shape[0] == 0:
         return gd, gs, mk
-    # Y and delta_scale depend on the rays only
-    o, g, view, delta_scale, tmin, tmax, ok = GO.ray_setup(grid, origins, dirs, near_clip)
-    Y = GO.sh_bases(B, np.where(ok[:, None], view, F(0.0)).astype(F))
-    step_ds = (F(step_size) * delta_scale).astype(F)
-
-    def shade(rays, lk, wa, wb, raw, weight, log_t_after):
-        col = np.maximum(raw, F(0.0))
-        gr = gc[rays]
-        dot = (((col[:, 0] * gr[:, 0]).astype(F) + (col[:, 1] * gr[:, 1]).astype(F)).astype(F) + (col[:, 2] * gr[:, 2]).astype(F)).astype(F)
-        remaining[rays] -= weight[:, None].astype(np.float64) * col.astype(np.float64)
-        accum = (remaining[rays] * gr.astype(np.float64)).sum(-1).astype(F)
-        d_sigma = (step_ds[rays] * ((np.exp(log_t_after).astype(F) * dot).astype(F) - accum).astype(F)).astype(F)
-        wy = (weight[:, None] * Y[rays]).astype(F)
-        d_coef = np.where(raw[:, :, None] >= 0, (wy[:, None, :] * gr[:, :, None]).astype(F), F(0.0)).astype(F).reshape(-1, 3 * B)
-        for c in range(8):
-            wx = wb[:, 0] if c & 4 else wa[:, 0]
-            wyy = wb[:, 1] if c & 2 else wa[:, 1]
-            wz = wb[:, 2] if c & 1 else wa[:, 2]
-            w8 = ((wx * wyy).astype(F) * wz).astype(F)
-            kept = (lk[c] >= 0) & (lk[c] < cap)
-            rows = lk[c][kept]
-            np.add.at(gd[:, 0], rows, (w8 * d_sigma).astype(F)[kept])
-            np.add.at(gs, rows, (w8[:, None] * d_coef).astype(F)[kept])
-            mk[rows] = 1
-
+    Y, delta_scale = GO.view_bases(grid, origins, dirs, near_clip)
+    # (remaining: a copy of the tape, reduced sample by sample)
+    shade = functools.partial(GT.march_colour_bwd, gc=gc, remaining=np.array(tape, dtype=np.float64), Y=Y,
+                              step_ds=(F(step_size) * delta_scale).astype(F), grad_density=gd, grad_sh=gs, mask=mk)
     with np.errstate(over="ignore", invalid="ignore"):
-        GT._march(grid, origins, dirs, step_size, sigma_thresh, stop_thresh, near_clip, skip, shade=shade)
+        GO.march_colour(grid, origins, dirs, step_size, sigma_thresh, stop_thresh, near_clip, skip, shade=shade)
     return gd, gs, mk
 
 

@@ -1,7 +1,9 @@
 """numpy restatement of the background pass (include/nerf_mi355x.h, "Sparse voxel grid: background layers").
 
 Stage by stage what csrc/grid_background_kernels.hip computes - the sphere set-up, the far hit of a radius, the texel
-coordinates, the wrapped fetch with z, y, x interpolation, the compositing with its edge rules - in the dtype ``T``:
+coordinates, the wrapped fetch with z, y, x interpolation, the compositing with its edge rules (``march``, the one
+loop over the spheres, with a per-sphere ``shade`` hook: ``background_pass`` here, the taped pass and the backward of
+grid_background_train_oracle.py) - in the dtype ``T``:
 ``np.float32`` with every operation a separate rounding (the kernel's arithmetic), or ``np.float64`` (the same formulas,
 exact enough to measure the fp32 statement against). The radii and the inputs are the fp32 values in both. It starts where the
 header starts: from the grid-coordinate origin ``o``, the unit grid direction ``d``, ``delta_scale`` and ``ok`` of the
@@ -115,60 +117,68 @@ def fetch(bg, l, w, T=F):
     return _lerp(v0, v1, w[:, 0:1]).astype(T)
 
 
-def composite_step(state, taken, invr, v, stop_thresh, T=F):
-    """One step of the loop on ``state`` = dict(out [n, 3], log_t, invr_last, live [n] bool), in place."""
-    live = state["live"] & taken
-    sigma = v[:, 3]
-    shade = live & (sigma > 0)
-    with np.errstate(all="ignore"):
-        p = ((state["invr_last"] - invr) * state["world_step"]) * sigma
-        weight = np.exp(state["log_t"]).astype(T) * (T(1.0) - np.exp(-p).astype(T))
-        new_log_t = state["log_t"] - p
-        col = np.maximum((v[:, :3] * T(SH_C0)) + T(0.5), T(0.0))
-        new_out = state["out"] + weight[:, None] * col
-        stop = shade & (np.exp(new_log_t).astype(T) < T(F(stop_thresh)))
-    state["out"] = np.where(shade[:, None], new_out, state["out"]).astype(T)
-    state["log_t"] = np.where(shade, new_log_t, state["log_t"]).astype(T)
-    state["invr_last"] = np.where(live & ~stop, invr, state["invr_last"]).astype(T)
-    state["live"] = state["live"] & ~stop
-    return shade, stop
+def march(o, d, delta_scale, ok, reso, bg, log_in, step_size, stop_thresh, T, shade):
+    """The one loop over the spheres, with its edge rules, for the rays with ``run`` = not left alone and a finite set-up, from
+    ``log_in`` (in ``T``). ``shade(idx, l, w, v, dstep, weight, log_t_after)`` is called once per sphere with the rays shaded
+    there. Returns (run, left_alone, final log_t, dict(stopped [n] bool, shaded [n] int))."""
+    nl, R = bg["data"].shape[1], bg["links"].shape[1]
+    ok = np.asarray(ok, bool)
+    with np.errstate(invalid="ignore"):
+        left_alone = log_in < T(-25.0)
+    run = ~left_alone & ok
+    su = setup(np.where(ok[:, None], o, 0.0), np.where(ok[:, None], d, 1.0), np.where(ok, delta_scale, 1.0), reso, T)
+    log_t = log_in.copy()
+    invr_last = (T(1.0) / su["inner"]).astype(T)
+    live = run.copy()
+    stats = dict(stopped=np.zeros(log_in.shape[0], bool), shaded=np.zeros(log_in.shape[0], np.int64))
+    for r in radii(nl, step_size):
+        taken, _, invr, u = hit(su, r, T)
+        x, y, z = texel_coords(u, invr, R, nl, T)
+        l, w = cell(x, y, z, R, nl, T)
+        v = fetch(bg, l, w, T)
+        cur = live & taken
+        sh = cur & (v[:, 3] > 0)
+        with np.errstate(all="ignore"):
+            dstep = ((invr_last - invr) * su["world_step"]).astype(T)
+            p = (dstep * v[:, 3]).astype(T)
+            weight = (np.exp(log_t).astype(T) * (T(1.0) - np.exp(-p).astype(T))).astype(T)
+            new_log = (log_t - p).astype(T)
+            stop = sh & (np.exp(new_log).astype(T) < T(F(stop_thresh)))
+        log_t = np.where(sh, new_log, log_t).astype(T)
+        idx = np.nonzero(sh)[0]
+        if idx.size:
+            shade(idx, l[idx], w[idx], v[idx], dstep[idx], weight[idx], log_t[idx])
+        stats["stopped"] |= stop
+        stats["shaded"] += sh
+        invr_last = np.where(cur & ~stop, invr, invr_last).astype(T)
+        live = live & ~stop
+    return run, left_alone, log_t, stats
 
 
 def background_pass(o, d, delta_scale, ok, reso, bg, rgb, log_transmit, step_size=0.5, stop_thresh=1e-7,
                     background_brightness=1.0, T=F, return_stats=False):
     """(rgb [n, 3], log_transmit [n]) in ``T`` after the pass over a foreground's fp32 ``rgb`` / ``log_transmit``.
     ``return_stats``: also dict(left_alone, brightness_only, stopped [n] bool, shaded [n] int, seam [n] int)."""
-    nl, R = bg["data"].shape[1], bg["links"].shape[1]
+    R = bg["links"].shape[1]
     rgb_in, log_in = np.asarray(rgb, F).astype(T), np.asarray(log_transmit, F).astype(T)
-    ok = np.asarray(ok, bool)
-    with np.errstate(invalid="ignore"):
-        left_alone = log_in < T(-25.0)
-    bright_only = ~left_alone & ~ok
-    run = ~left_alone & ok
-    su = setup(np.where(ok[:, None], o, 0.0), np.where(ok[:, None], d, 1.0), np.where(ok, delta_scale, 1.0), reso, T)
     n = rgb_in.shape[0]
-    state = dict(out=np.zeros((n, 3), T), log_t=log_in.copy(), invr_last=(T(1.0) / su["inner"]).astype(T), live=run.copy(),
-                 world_step=su["world_step"])
-    stopped = np.zeros(n, bool)
-    shaded = np.zeros(n, np.int64)
+    out = np.zeros((n, 3), T)
     seam = np.zeros(n, np.int64)
-    for r in radii(nl, step_size):
-        taken, _, invr, u = hit(su, r, T)
-        x, y, z = texel_coords(u, invr, R, nl, T)
-        l, w = cell(x, y, z, R, nl, T)
-        v = fetch(bg, l, w, T)
-        sh, st = composite_step(state, taken, invr, v, stop_thresh, T)
-        stopped |= st
-        shaded += sh
-        seam += sh & (l[:, 0] == 2 * R - 1)      # interpolated between the last and the first column
+
+    def shade(idx, l, w, v, dstep, weight, log_t):
+        col = np.maximum((v[:, :3] * T(SH_C0)) + T(0.5), T(0.0))
+        out[idx] = (out[idx] + weight[:, None] * col).astype(T)
+        seam[idx] += l[:, 0] == 2 * R - 1      # interpolated between the last and the first column
+
+    run, left_alone, log_t, stats = march(o, d, delta_scale, ok, reso, bg, log_in, step_size, stop_thresh, T, shade)
+    bright_only = ~left_alone & ~run
     with np.errstate(all="ignore"):
-        bterm = np.exp(state["log_t"]).astype(T) * T(F(background_brightness))
-        full = rgb_in + (state["out"] + bterm[:, None])
+        full = rgb_in + (out + (np.exp(log_t).astype(T) * T(F(background_brightness)))[:, None])
         only = rgb_in + (np.exp(log_in).astype(T) * T(F(background_brightness)))[:, None]
     rgb_out = np.where(run[:, None], full, np.where(bright_only[:, None], only, rgb_in)).astype(T)
-    log_out = np.where(run, state["log_t"], log_in).astype(T)
+    log_out = np.where(run, log_t, log_in).astype(T)
     if return_stats:
-        return rgb_out, log_out, dict(left_alone=left_alone, brightness_only=bright_only, stopped=stopped, shaded=shaded, seam=seam)
+        return rgb_out, log_out, dict(stats, left_alone=left_alone, brightness_only=bright_only, seam=seam)
     return rgb_out, log_out
 
 

@@ -2,13 +2,15 @@
 training"): the taped background pass, its backward, the total-variation gradient of the layers and their optimiser step, in
 the dtype ``T`` - ``np.float32`` with every operation a separate rounding in the order the header states (the kernels'
 arithmetic; ``remaining`` in fp64 as there), or ``np.float64`` (the same formulas, exact enough to compare with fp64
-autograd). It builds on grid_background_oracle.py (the march, stage by stage) and grid_train_oracle.py (the foreground) and,
-like them, is a test oracle: slow and simple. Sums into a gradient entry are taken in step order (the kernels' atomics take
+autograd). It builds on grid_background_oracle.py (the stages and ``march``, the one loop over the spheres: the taped
+pass and the backward are its ``shade`` hooks), on grid_autograd_oracle.py (the foreground: ``render_taped``, ``render_backward``)
+and on grid_train_oracle.py (``optim_step``) and, like them, is a test oracle: slow and simple. Sums into a gradient entry are taken in step order (the kernels' atomics take
 them in any order), so gradients agree with the kernels to rounding of those sums; the optimiser agrees bit for bit.
 A background is a dict: ``links`` int32 [2 R, R], ``data`` fp32 [capacity, L, 4].
 """
 import numpy as np
 
+import grid_autograd_oracle as GA
 import grid_background_oracle as BO
 import grid_oracle as GO
 import grid_train_oracle as GT
@@ -16,50 +18,6 @@ import grid_train_oracle as GT
 F = np.float32
 D = np.float64
 SH_C0 = BO.SH_C0
-
-
-def _march(o, d, delta_scale, ok, reso, bg, log_in, step_size, stop_thresh, T, shade):
-    """grid_background_oracle.background_pass's loop over the rays with ``run`` = not left alone and a finite set-up, from
-    ``log_in`` (in ``T``). ``shade(idx, l, w, v, dstep, weight, log_t_after)`` is called once per sphere with the rays shaded
-    there. Returns (run, left_alone, final log_t, stats)."""
-    nl, R = bg["data"].shape[1], bg["links"].shape[1]
-    ok = np.asarray(ok, bool)
-    with np.errstate(invalid="ignore"):
-        left_alone = log_in < T(-25.0)
-    run = ~left_alone & ok
-    su = BO.setup(np.where(ok[:, None], o, 0.0), np.where(ok[:, None], d, 1.0), np.where(ok, delta_scale, 1.0), reso, T)
-    n = log_in.shape[0]
-    log_t = log_in.copy()
-    invr_last = (T(1.0) / su["inner"]).astype(T)
-    live = run.copy()
-    stats = dict(stopped=np.zeros(n, bool), shaded=np.zeros(n, np.int64), seam_x=np.zeros(n, bool), seam_y=np.zeros(n, bool),
-                 clamped=np.zeros(n, bool))
-    for r in BO.radii(nl, step_size):
-        taken, _, invr, u = BO.hit(su, r, T)
-        x, y, z = BO.texel_coords(u, invr, R, nl, T)
-        l, w = BO.cell(x, y, z, R, nl, T)
-        v = BO.fetch(bg, l, w, T)
-        cur = live & taken
-        sh = cur & (v[:, 3] > 0)
-        with np.errstate(all="ignore"):
-            dstep = ((invr_last - invr) * su["world_step"]).astype(T)
-            p = (dstep * v[:, 3]).astype(T)
-            weight = (np.exp(log_t).astype(T) * (T(1.0) - np.exp(-p).astype(T))).astype(T)
-            new_log = (log_t - p).astype(T)
-            stop = sh & (np.exp(new_log).astype(T) < T(F(stop_thresh)))
-        log_t = np.where(sh, new_log, log_t).astype(T)
-        idx = np.nonzero(sh)[0]
-        if idx.size:
-            shade(idx, l[idx], w[idx], v[idx], dstep[idx], weight[idx], log_t[idx])
-            stats["shaded"][idx] += 1
-            stats["seam_x"][idx] |= l[idx, 0] == 2 * R - 1
-            stats["seam_y"][idx] |= l[idx, 1] == R - 1
-            with np.errstate(invalid="ignore"):
-                stats["clamped"][idx] |= (((v[idx, :3] * T(SH_C0)) + T(0.5)) < 0).any(-1)
-        stats["stopped"] |= stop
-        invr_last = np.where(cur & ~stop, invr, invr_last).astype(T)
-        live = live & ~stop
-    return run, left_alone, log_t, stats
 
 
 def taped(o, d, delta_scale, ok, reso, bg, rgb, log_transmit, tape, step_size=0.5, stop_thresh=1e-7, background_brightness=1.0,
@@ -70,13 +28,20 @@ def taped(o, d, delta_scale, ok, reso, bg, rgb, log_transmit, tape, step_size=0.
     n = rgb_in.shape[0]
     out = np.zeros((n, 3), T)
     tot = np.zeros((n, 3), D)
+    R = bg["links"].shape[1]
+    seen = dict(seam_x=np.zeros(n, bool), seam_y=np.zeros(n, bool), clamped=np.zeros(n, bool))
 
     def shade(idx, l, w, v, dstep, weight, log_t):
-        col = np.maximum((v[:, :3] * T(SH_C0)).astype(T) + T(0.5), T(0.0)).astype(T)
+        with np.errstate(invalid="ignore"):
+            raw = ((v[:, :3] * T(SH_C0)).astype(T) + T(0.5)).astype(T)
+            col = np.maximum(raw, T(0.0)).astype(T)
         out[idx] = (out[idx] + (weight[:, None] * col).astype(T)).astype(T)
         tot[idx] += weight[:, None].astype(D) * col.astype(D)
+        seen["seam_x"][idx] |= l[:, 0] == 2 * R - 1
+        seen["seam_y"][idx] |= l[:, 1] == R - 1
+        seen["clamped"][idx] |= (raw < 0).any(-1)
 
-    run, left_alone, log_t, stats = _march(o, d, delta_scale, ok, reso, bg, log_in, step_size, stop_thresh, T, shade)
+    run, left_alone, log_t, stats = BO.march(o, d, delta_scale, ok, reso, bg, log_in, step_size, stop_thresh, T, shade)
     bright = T(F(background_brightness))
     with np.errstate(all="ignore"):
         e_end, e_in = np.exp(log_t).astype(T), np.exp(log_in).astype(T)
@@ -89,7 +54,7 @@ def taped(o, d, delta_scale, ok, reso, bg, rgb, log_transmit, tape, step_size=0.
                   np.where(only_rays[:, None], (e_in.astype(D) * D(bright))[:, None], 0.0))
     tape_out = np.asarray(tape, D) + tb
     if return_stats:
-        stats.update(left_alone=left_alone, run=run)
+        stats.update(seen, left_alone=left_alone, run=run)
         return rgb_out, log_out, tape_out, tb, stats
     return rgb_out, log_out, tape_out, tb
 
@@ -136,7 +101,7 @@ def backward(o, d, delta_scale, ok, reso, bg, grad_rgb, log_transmit, tape_backg
                     np.add.at(gb, (lk[r], zz[r], c), add[r, c])
                     mk[lk[has], zz[has]] = 1
 
-    _march(o, d, delta_scale, ok, reso, bg, log_in, step_size, stop_thresh, T, shade)
+    BO.march(o, d, delta_scale, ok, reso, bg, log_in, step_size, stop_thresh, T, shade)
     return gb, mk
 
 
@@ -191,54 +156,12 @@ def optim_step(data, rms, grad, mask, kind, lr_sigma, lr_color, beta=0.95, eps=1
         rms[..., c] = rc.reshape(cap, L)
 
 
-def foreground_backward(grid, origins, dirs, grad_rgb, tape, step_size, sigma_thresh, stop_thresh, near_clip=0.0, skip=None,
-                        grad_density=None, grad_sh=None, mask=None):
-    """nerf_grid_render_backward (fp32): grid_train_oracle.fused's second march with a caller's cotangent and tape."""
-    cap, cols = grid["density_data"].shape[0], grid["sh_data"].shape[1]
-    B = cols // 3
-    gd = np.zeros((cap, 1), F) if grad_density is None else grad_density
-    gs = np.zeros((cap, cols), F) if grad_sh is None else grad_sh
-    mk = np.zeros(cap, np.uint8) if mask is None else mask
-    gc = np.asarray(grad_rgb, F)
-    remaining = np.array(tape, D)
-    _, _, _, delta_scale, _, _, _ = GO.ray_setup(grid, origins, dirs, near_clip)
-    step_ds = (F(step_size) * delta_scale).astype(F)
-    Y = [None]
-
-    def shade(rays, lk, wa, wb, raw, weight, log_t_after):
-        col = np.maximum(raw, F(0.0))
-        g = gc[rays]
-        dot = (((col[:, 0] * g[:, 0]).astype(F) + (col[:, 1] * g[:, 1]).astype(F)).astype(F) + (col[:, 2] * g[:, 2]).astype(F)).astype(F)
-        remaining[rays] -= weight[:, None].astype(D) * col.astype(D)
-        accum = (remaining[rays] * g.astype(D)).sum(-1).astype(F)
-        with np.errstate(all="ignore"):
-            d_sigma = (step_ds[rays] * ((np.exp(log_t_after).astype(F) * dot).astype(F) - accum).astype(F)).astype(F)
-        wy = (weight[:, None] * Y[0][rays]).astype(F)
-        d_coef = np.where(raw[:, :, None] >= 0, (wy[:, None, :] * g[:, :, None]).astype(F), F(0.0)).astype(F).reshape(-1, 3 * B)
-        for c in range(8):
-            wx = wb[:, 0] if c & 4 else wa[:, 0]
-            wyy = wb[:, 1] if c & 2 else wa[:, 1]
-            wz = wb[:, 2] if c & 1 else wa[:, 2]
-            w8 = ((wx * wyy).astype(F) * wz).astype(F)
-            kept = (lk[c] >= 0) & (lk[c] < cap)
-            rows = lk[c][kept]
-            np.add.at(gd[:, 0], rows, (w8 * d_sigma).astype(F)[kept])
-            np.add.at(gs, rows, (w8[:, None] * d_coef).astype(F)[kept])
-            mk[rows] = 1
-
-    args = (grid, origins, dirs, step_size, sigma_thresh, stop_thresh, near_clip, skip)
-    o, g, view, _, _, _, ok = GO.ray_setup(grid, origins, dirs, near_clip)
-    Y[0] = GO.sh_bases(B, np.where(ok[:, None], view, F(0.0)).astype(F))
-    GT._march(*args, shade=shade)
-    return gd, gs, mk
-
-
 def forward_backward(grid, bg, origins, dirs, rgb_gt, step_size=0.5, sigma_thresh=1e-10, stop_thresh=1e-7,
                      background_brightness=1.0, skip=None, grad_rgb=None, state=None):
     """BackgroundTrainer.forward_backward in fp32: the taped foreground (brightness 0), the taped background pass, the MSE
     cotangent (or ``grad_rgb``), the foreground's backward from the combined tape, the background's backward. Returns a dict:
     rgb, log_transmit, grad_density, grad_sh, mask, grad_background, mask_background (``state``: such a dict to add to)."""
-    fg_rgb, fg_logt, (_, _, _, tot) = GT._march(grid, origins, dirs, step_size, sigma_thresh, stop_thresh, 0.0, skip)
+    fg_rgb, fg_logt, tot = GA.render_taped(grid, origins, dirs, step_size, sigma_thresh, stop_thresh, background_brightness=0.0, skip=skip)
     og, dg, _, ds, _, _, ok = GO.ray_setup(grid, origins, dirs)
     reso = grid["links"].shape
     rgb, logt, tape, tb = taped(og, dg, ds, ok, reso, bg, fg_rgb, fg_logt, tot, step_size, stop_thresh, background_brightness)
@@ -246,8 +169,8 @@ def forward_backward(grid, bg, origins, dirs, rgb_gt, step_size=0.5, sigma_thres
     if grad_rgb is None:
         grad_rgb = ((rgb - np.asarray(rgb_gt, F)).astype(F) * (F(2.0) / (F(3.0) * F(n)))).astype(F)
     st = state or {}
-    gd, gs, mk = foreground_backward(grid, origins, dirs, grad_rgb, tape, step_size, sigma_thresh, stop_thresh, 0.0, skip,
-                                     st.get("grad_density"), st.get("grad_sh"), st.get("mask"))
+    gd, gs, mk = GA.render_backward(grid, origins, dirs, grad_rgb, tape, step_size, sigma_thresh, stop_thresh, 0.0, skip,
+                                    st.get("grad_density"), st.get("grad_sh"), st.get("mask"))
     gb, mb = backward(og, dg, ds, ok, reso, bg, grad_rgb, fg_logt, tb, step_size, stop_thresh, st.get("grad_background"),
                       st.get("mask_background"))
     return dict(rgb=rgb, log_transmit=logt, grad_density=gd, grad_sh=gs, mask=mk, grad_background=gb, mask_background=mb,

@@ -1,7 +1,8 @@
 """numpy restatement of the gradients of the sparse voxel grid's expected depth and log_transmit (include/nerf_mi355x.h,
 "Sparse voxel grid: gradients of depth and log_transmit for autograd"): the taped forward and the backward with a cotangent
-for each result, on the ray set-up of tests/grid_oracle.py and the sample lattice of tests/grid_depth_oracle.py (whose
-expected depth the taped forward here must reproduce bit for bit: tests/test_grid_depth_autograd_cpu.py).
+for each result, both callbacks of ``march`` of tests/grid_oracle.py (its ray set-up, its sample lattice, its ``sigma_at`` and
+``corner_weights``). The taped forward must reproduce the expected depth of tests/grid_depth_oracle.py bit for bit
+(tests/test_grid_depth_autograd_cpu.py).
 
 ``dtype=np.float32`` mirrors csrc/grid_depth_autograd_kernels.hip: every operation a separate fp32 rounding in the header's
 order, ``remaining`` in fp64. ``dtype=np.float64`` is the same statement on the same lattice - set-up, additions of ``t``,
@@ -17,60 +18,17 @@ import grid_oracle as GO
 F = np.float32
 
 
-def _rows(table, links, dtype):
-    """``table[links]`` in ``dtype``, zeros where a link is negative or >= capacity"""
-    ok = (links >= 0) & (links < table.shape[0])
-    out = np.zeros(links.shape[0], dtype=dtype)
-    out[ok] = table[links[ok], 0]
-    return out
-
-
-def _march(grid, origins, dirs, step_size, sigma_thresh, near_clip, skip, dtype, density, at):
-    """The lattice of grid_depth_oracle.depth: ``at(rays, t, lk, wa, wb, sigma)`` at the samples with sigma > sigma_thresh of
-    one pass (every ray at most once per pass, passes in march order); it returns the mask of the rays that stop."""
-    links = grid["links"]
-    step = F(step_size)
-    o, g, _, _, tmin, tmax, ok = GO.ray_setup(grid, origins, dirs, near_clip)
-    t = tmin.copy()
-    with np.errstate(invalid="ignore"):
-        skip_ok = (np.abs(o).max(-1) < GO.SKIP_MAX_T) & (np.abs(tmin) < GO.SKIP_MAX_T) & (np.abs(tmax) < GO.SKIP_MAX_T)
-        act = np.nonzero(ok & (tmin <= tmax))[0]
-    while act.size:
-        t_next = (t[act] + step).astype(F)
-        act, t_next = act[t_next > t[act]], t_next[t_next > t[act]]
-        if not act.size:
-            break
-        pos = (o[act] + t[act, None] * g[act]).astype(F)
-        l, wb = GO._cell(pos, links.shape)
-        wa = (F(1.0) - wb).astype(F)
-        sv = np.zeros(act.size, dtype=np.int64)
-        if skip is not None:
-            sv = np.where(skip_ok[act], skip[l[:, 0], l[:, 1], l[:, 2]].astype(np.int64), 0)
-        work = sv == 0
-        stopped = np.zeros(act.size, dtype=bool)
-        if work.any():
-            w_idx = np.nonzero(work)[0]
-            lk = [k[w_idx] for k in GO._corner_links(links, l)]
-            sigma = GO._trilerp([_rows(density, k, dtype)[:, None] for k in lk], wa[w_idx].astype(dtype), wb[w_idx].astype(dtype))[:, 0]
-            assert sigma.dtype == dtype
-            hit = sigma > dtype(F(sigma_thresh))
-            if hit.any():
-                h_idx = w_idx[hit]
-                done = at(act[h_idx], t[act[h_idx]], [k[hit] for k in lk], wa[h_idx], wb[h_idx], sigma[hit])
-                stopped[h_idx[done]] = True
-        t0 = t[act].copy()
-        t[act] = np.where(stopped, t[act], t_next)
-        reach = (sv - 1).astype(F) - F(0.0625)
-        going = ~work
-        while going.any():
-            cur = t[act]
-            going &= (cur - t0).astype(F) <= reach
-            nxt = (cur + step).astype(F)
-            going &= nxt > cur
-            t[act] = np.where(going, nxt, cur)
-        keep = ~stopped
-        keep &= t[act] <= tmax[act]
-        act = act[keep]
+def _shaded(at, density, sigma_thresh, dtype):
+    """the callback of grid_oracle.march that calls ``at(rays, t, lk, wa, wb, sigma)`` with the samples of a pass whose sigma (in
+    ``dtype``, of the table ``density``) exceeds ``sigma_thresh``; ``at`` returns the mask of the rays that stop"""
+    def of_pass(rays, t, lk, wa, wb):
+        sigma = GO.sigma_at(density, lk, wa, wb, dtype)
+        hit = sigma > dtype(F(sigma_thresh))
+        done = np.zeros(rays.size, dtype=bool)
+        if hit.any():
+            done[hit] = at(rays[hit], t[hit], [k[hit] for k in lk], wa[hit], wb[hit], sigma[hit])
+        return done
+    return of_pass
 
 
 class _Ray:
@@ -112,7 +70,7 @@ def _forward(grid, origins, dirs, step_size, sigma_thresh, stop_thresh, near_cli
         return done
 
     with np.errstate(over="ignore", invalid="ignore"):
-        _march(grid, origins, dirs, step_size, sigma_thresh, near_clip, skip, dtype, density, at)
+        GO.march(grid, origins, dirs, _shaded(at, density, sigma_thresh, dtype), step_size, near_clip, skip)
     return depth, log_t, tape, stopped
 
 
@@ -151,18 +109,13 @@ def depth_backward(grid, origins, dirs, grad_depth, grad_log_transmit, tape, ste
         lead = ((np.exp(log_t[rays]).astype(dtype) * tau).astype(dtype) * ray.world_step[rays]).astype(dtype)
         inner = (g_d[rays] * (lead - remaining[rays].astype(dtype)).astype(dtype)).astype(dtype)
         d_sigma = ((step_ds[rays] * inner).astype(dtype) - (g_t[rays] * step_ds[rays]).astype(dtype)).astype(dtype)
-        wa, wb = wa.astype(dtype), wb.astype(dtype)
-        for c in range(8):
-            wx = wb[:, 0] if c & 4 else wa[:, 0]
-            wy = wb[:, 1] if c & 2 else wa[:, 1]
-            wz = wb[:, 2] if c & 1 else wa[:, 2]
-            w8 = ((wx * wy).astype(dtype) * wz).astype(dtype)
+        for c, w8 in GO.corner_weights(wa, wb, dtype):
             kept = (lk[c] >= 0) & (lk[c] < gd.shape[0])
             np.add.at(gd[:, 0], lk[c][kept], (w8 * d_sigma).astype(dtype)[kept])
         return np.exp(log_t[rays]).astype(dtype) < dtype(F(stop_thresh))
 
     with np.errstate(over="ignore", invalid="ignore"):
-        _march(grid, origins, dirs, step_size, sigma_thresh, near_clip, skip, dtype, density, at)
+        GO.march(grid, origins, dirs, _shaded(at, density, sigma_thresh, dtype), step_size, near_clip, skip)
     return gd
 
 

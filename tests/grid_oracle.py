@@ -3,6 +3,9 @@
 It states what csrc/grid_kernels.hip computes - ray set-up, the sample lattice, trilinear interpolation in the order z, y, x,
 ``sigma_thresh``, ``stop_thresh`` with ``log_T = -1e3``, the background term, non-finite rays, the stall rule, the skip distances and the jump - with every
 operation a separate fp32 rounding, vectorised over rays. It is a test oracle (not part of the package): slow and simple.
+Every foreground oracle walks its rays in ``march`` (csrc/grid_device.h's ``grid_march``: the lattice exists here only) and
+interpolates with ``sigma_at`` and ``corner_weights``; ``march_colour`` is the colour accumulated along it, under ``render``
+here and under the training and autograd oracles (grid_train_oracle.py, grid_autograd_oracle.py, grid_train_losses_oracle.py).
 A grid is a dict: ``links`` int32 [X, Y, Z], ``density_data`` [C, 1], ``sh_data`` [C, 3 B], ``radius`` [3], ``center`` [3].
 """
 import numpy as np
@@ -42,11 +45,10 @@ def world2grid_consts(grid):
     return offset.astype(F), scaling.astype(F), gsz
 
 
-def _fetch(grid, links, table):
-    """rows of ``table`` at ``links`` (any negative link or one >= capacity: zeros)"""
-    cap = table.shape[0]
-    ok = (links >= 0) & (links < cap)
-    out = np.zeros((links.shape[0], table.shape[1]), dtype=F)
+def _fetch(table, links, dtype=F):
+    """rows of ``table`` at ``links`` in ``dtype`` (any negative link or one >= capacity: zeros)"""
+    ok = (links >= 0) & (links < table.shape[0])
+    out = np.zeros((links.shape[0], table.shape[1]), dtype=dtype)
     out[ok] = table[links[ok]]
     return out
 
@@ -78,6 +80,25 @@ def _trilerp(v, wa, wb):
     return c0 * wa[:, 0:1] + c1 * wb[:, 0:1]
 
 
+def sigma_at(table, lk, wa, wb, dtype=F):
+    """the density [n] in ``dtype`` interpolated from the density ``table`` [C, 1] (fp32, or fp64 for finite differences) at
+    the corner links ``lk`` with the fp32 weights"""
+    sigma = _trilerp([_fetch(table, k, dtype) for k in lk], wa.astype(dtype), wb.astype(dtype))[:, 0]
+    assert sigma.dtype == dtype
+    return sigma
+
+
+def corner_weights(wa, wb, dtype=F):
+    """(c, w8) with w8 the product (w_x * w_y) * w_z in ``dtype``, for the 8 corners in the order 000, 001, ..., 111 (x, y, z bits)"""
+    wa, wb = wa.astype(dtype), wb.astype(dtype)
+    for c in range(8):
+        wx = wb[:, 0] if c & 4 else wa[:, 0]
+        wy = wb[:, 1] if c & 2 else wa[:, 1]
+        wz = wb[:, 2] if c & 1 else wa[:, 2]
+        w8 = ((wx * wy).astype(dtype) * wz).astype(dtype)
+        yield c, w8
+
+
 def sample(grid, points, grid_coords=False, want_colors=True):
     links = grid["links"]
     p = np.asarray(points, dtype=F)
@@ -87,10 +108,10 @@ def sample(grid, points, grid_coords=False, want_colors=True):
     l, wb = _cell(p, links.shape)
     wa = (F(1.0) - wb).astype(F)
     lk = _corner_links(links, l)
-    dens = _trilerp([_fetch(grid, k, grid["density_data"]) for k in lk], wa, wb)
+    dens = _trilerp([_fetch(grid["density_data"], k) for k in lk], wa, wb)
     if not want_colors:
         return dens, np.zeros((0, grid["sh_data"].shape[1]), dtype=F)
-    return dens, _trilerp([_fetch(grid, k, grid["sh_data"]) for k in lk], wa, wb)
+    return dens, _trilerp([_fetch(grid["sh_data"], k) for k in lk], wa, wb)
 
 
 def skip_distances(links):
@@ -144,22 +165,19 @@ def ray_setup(grid, origins, dirs, near_clip=0.0):
     return o, g, view, delta_scale, tmin, tmax, ok
 
 
-def render(grid, origins, dirs, step_size=0.5, sigma_thresh=1e-10, stop_thresh=1e-7, background_brightness=1.0,
-           near_clip=0.0, skip=None, return_counts=False):
-    """rgb [N, 3], log_transmit [N] (and (samples whose links were loaded, samples shaded))."""
-    links, density, sh = grid["links"], grid["density_data"], grid["sh_data"]
-    B = sh.shape[1] // 3
+def march(grid, origins, dirs, at, step_size=0.5, near_clip=0.0, skip=None):
+    """grid_march of csrc/grid_device.h, the one sample lattice of the foreground oracles. ``at(rays, t, lk, wa, wb)`` is called
+    once per pass with the samples whose links are loaded - every sample the skip rule does not pass over; a ray at most once per
+    pass, passes in march order - ``lk`` the 8 corner-link arrays, ``wa`` / ``wb`` the fp32 weights. It applies its own density
+    threshold and returns the mask of the rays that end. Returns the rays that were marched [N] bool."""
+    links = grid["links"]
     step = F(step_size)
-    o, g, view, delta_scale, tmin, tmax, ok = ray_setup(grid, origins, dirs, near_clip)
-    Y = sh_bases(B, np.where(ok[:, None], view, F(0.0)).astype(F))
-    n = o.shape[0]
-    rgb = np.zeros((n, 3), dtype=F)
-    log_t = np.zeros(n, dtype=F)
+    o, g, _, _, tmin, tmax, ok = ray_setup(grid, origins, dirs, near_clip)
     t = tmin.copy()
-    visited = shaded = 0
     with np.errstate(invalid="ignore"):
         skip_ok = (np.abs(o).max(-1) < SKIP_MAX_T) & (np.abs(tmin) < SKIP_MAX_T) & (np.abs(tmax) < SKIP_MAX_T)
-        act = np.nonzero(ok & (tmin <= tmax))[0]
+        marched = ok & (tmin <= tmax)
+    act = np.nonzero(marched)[0]
     while act.size:
         # every pass advances t by at least one addition of step_size; a ray whose t no longer changes is left
         t_next = (t[act] + step).astype(F)
@@ -176,23 +194,8 @@ def render(grid, origins, dirs, step_size=0.5, sigma_thresh=1e-10, stop_thresh=1
         stopped = np.zeros(act.size, dtype=bool)
         if work.any():
             w_idx = np.nonzero(work)[0]
-            visited += w_idx.size      # samples whose links are loaded
             lk = [k[w_idx] for k in _corner_links(links, l)]
-            sigma = _trilerp([_fetch(grid, k, density) for k in lk], wa[w_idx], wb[w_idx])[:, 0]
-            hit = sigma > F(sigma_thresh)
-            if hit.any():
-                h_idx = w_idx[hit]
-                rays = act[h_idx]
-                shaded += rays.size
-                coef = _trilerp([_fetch(grid, k[hit], sh) for k in lk], wa[h_idx], wb[h_idx]).reshape(-1, 3, B)
-                col = np.maximum((Y[rays][:, None, :] * coef).astype(F).sum(-1, dtype=F) + F(0.5), F(0.0)).astype(F)
-                a = ((-step * sigma[hit]).astype(F) * delta_scale[rays]).astype(F)
-                weight = (np.exp(log_t[rays]).astype(F) * (F(1.0) - np.exp(a).astype(F))).astype(F)
-                rgb[rays] = (rgb[rays] + weight[:, None] * col).astype(F)
-                log_t[rays] = (log_t[rays] + a).astype(F)
-                done = np.exp(log_t[rays]).astype(F) < F(stop_thresh)
-                log_t[rays[done]] = F(-1e3)
-                stopped[h_idx[done]] = True
+            stopped[w_idx] = at(act[w_idx], t[act[w_idx]], lk, wa[w_idx], wb[w_idx])
         t0 = t[act].copy()
         t[act] = np.where(stopped, t[act], t_next)
         # a skipping ray also passes every later sample whose accumulated t is within sv - 1 - 1/16 of this one's
@@ -207,8 +210,63 @@ def render(grid, origins, dirs, step_size=0.5, sigma_thresh=1e-10, stop_thresh=1
         keep = ~stopped
         keep &= t[act] <= tmax[act]
         act = act[keep]
+    return marched
+
+
+def view_bases(grid, origins, dirs, near_clip=0.0):
+    """what a colour march needs of the rays alone: the SH bases Y [N, B] of the view direction (of the zero direction where
+    the set-up is not finite) and delta_scale [N]"""
+    _, _, view, delta_scale, _, _, ok = ray_setup(grid, origins, dirs, near_clip)
+    return sh_bases(grid["sh_data"].shape[1] // 3, np.where(ok[:, None], view, F(0.0)).astype(F)), delta_scale
+
+
+def march_colour(grid, origins, dirs, step_size=0.5, sigma_thresh=1e-10, stop_thresh=1e-7, near_clip=0.0, skip=None, shade=None):
+    """march_colour of csrc/grid_device.h on :func:`march`. Returns (rgb without the background term, log_transmit, (Y,
+    delta_scale, marched, the same colour summed in fp64), (samples whose links were loaded, samples shaded)).
+    ``shade(rays, lk, wa, wb, sigma, raw, weight, log_t_after)`` is called once per pass with the shaded samples of that pass."""
+    density, sh = grid["density_data"], grid["sh_data"]
+    B = sh.shape[1] // 3
+    step = F(step_size)
+    Y, delta_scale = view_bases(grid, origins, dirs, near_clip)
+    n = Y.shape[0]
+    rgb = np.zeros((n, 3), dtype=F)
+    tot = np.zeros((n, 3), dtype=np.float64)      # the colour once more, as the fp64 sum of its exact terms
+    log_t = np.zeros(n, dtype=F)
+    count = [0, 0]
+
+    def at(rays, t, lk, wa, wb):
+        count[0] += rays.size
+        sigma = sigma_at(density, lk, wa, wb)
+        hit = sigma > F(sigma_thresh)
+        done = np.zeros(rays.size, dtype=bool)
+        if hit.any():
+            rays, lk, wa, wb, sigma = rays[hit], [k[hit] for k in lk], wa[hit], wb[hit], sigma[hit]
+            count[1] += rays.size
+            coef = _trilerp([_fetch(sh, k) for k in lk], wa, wb).reshape(-1, 3, B)
+            raw = ((Y[rays][:, None, :] * coef).astype(F).sum(-1, dtype=F) + F(0.5)).astype(F)
+            col = np.maximum(raw, F(0.0))
+            a = ((-step * sigma).astype(F) * delta_scale[rays]).astype(F)
+            weight = (np.exp(log_t[rays]).astype(F) * (F(1.0) - np.exp(a).astype(F))).astype(F)
+            rgb[rays] = (rgb[rays] + weight[:, None] * col).astype(F)
+            tot[rays] += weight[:, None].astype(np.float64) * col.astype(np.float64)      # exact products
+            log_t[rays] = (log_t[rays] + a).astype(F)
+            if shade is not None:
+                shade(rays, lk, wa, wb, sigma, raw, weight, log_t[rays].copy())
+            end = np.exp(log_t[rays]).astype(F) < F(stop_thresh)
+            log_t[rays[end]] = F(-1e3)
+            done[hit] = end
+        return done
+
+    marched = march(grid, origins, dirs, at, step_size, near_clip, skip)
+    return rgb, log_t, (Y, delta_scale, marched, tot), tuple(count)
+
+
+def render(grid, origins, dirs, step_size=0.5, sigma_thresh=1e-10, stop_thresh=1e-7, background_brightness=1.0,
+           near_clip=0.0, skip=None, return_counts=False):
+    """rgb [N, 3], log_transmit [N] (and (samples whose links were loaded, samples shaded))."""
+    rgb, log_t, _, counts = march_colour(grid, origins, dirs, step_size, sigma_thresh, stop_thresh, near_clip, skip)
     rgb = (rgb + (np.exp(log_t).astype(F) * F(background_brightness))[:, None]).astype(F)
-    return (rgb, log_t, (visited, shaded)) if return_counts else (rgb, log_t)
+    return (rgb, log_t, counts) if return_counts else (rgb, log_t)
 
 
 def gen_rays(c2w, fx, fy, cx, cy, width, height):
