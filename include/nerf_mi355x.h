@@ -146,6 +146,16 @@ int nerf_set_view_fold(nerf_ctx* ctx, int on);
  * each point reads its own ray's row, the same values: an all-occupied grid still gives the dense render bit for bit. sigma is bit for bit the folded kernel's; the colours differ by the rounding of that term.
  * on (default) / off for the following launches of this context; every other launch is what it was. */
 int nerf_set_ray_view_bias(nerf_ctx* ctx, int on);
+/* Tile schedule of the inference MLP launches. A launch is one persistent workgroup per compute unit over equal tiles of 128
+ * points. NERF_TILES_STATIC: workgroup b runs tiles b, b + grid, ... - equal shares, and the launch ends with the slowest
+ * XCD (the eight dies hold clocks a few per cent apart under this load). NERF_TILES_CLAIMED (default): workgroups take
+ * batches of tiles from a counter in device memory, a decreasing sequence of sizes down to single tiles, so that all of them
+ * end within about one tile of each other. Which workgroup runs a tile changes no value: every output is bit for bit the
+ * same under both. Training passes and launches of one tile per workgroup or fewer are static always. For the following
+ * launches of this context. */
+#define NERF_TILES_STATIC 0
+#define NERF_TILES_CLAIMED 1
+int nerf_set_tile_schedule(nerf_ctx* ctx, int schedule);
 int nerf_view_fold_status(nerf_ctx* ctx, int slot, int* folded);
 /* NERF_PRECISION_F16X2 chooses a layer's per-point output scale from an a-priori bound (largest row sum of |W| x
  * largest |input| + largest |bias|). A bound 2^12 or more above a point's real outputs starts to cost low-order

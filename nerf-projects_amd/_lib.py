@@ -21,7 +21,7 @@ EXPORTS = (
     "nerf_get_precision", "nerf_precision_status", "nerf_get_adam_state", "nerf_set_adam_state",
     "nerf_shard_bounds", "nerf_render_shard", "nerf_precision_peek", "nerf_precision_check",
     "nerf_precision_detail", "nerf_profile_read_train", "nerf_set_render_precision",
-    "nerf_set_view_fold", "nerf_view_fold_status", "nerf_set_ray_view_bias",
+    "nerf_set_view_fold", "nerf_view_fold_status", "nerf_set_ray_view_bias", "nerf_set_tile_schedule",
     "nerf_pack_rays", "nerf_density_grid", "nerf_marching_cubes", "nerf_train_forward", "nerf_train_backward",
     "nerf_zero_grad", "nerf_adam_step", "nerf_occupancy_create", "nerf_occupancy_destroy", "nerf_occupancy_cells",
     "nerf_occupancy_stats", "nerf_render_rays_occ", "nerf_render_frame_occ",
@@ -47,6 +47,7 @@ NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
 NERF_GUARD_OFF, NERF_GUARD_REPORT, NERF_GUARD_FALLBACK = 0, 1, 2
 NERF_OCC_EVALUATE, NERF_OCC_EMPTY = 0, 1
+NERF_TILES_STATIC, NERF_TILES_CLAIMED = 0, 1
 NERF_GRID_TV_DENSITY, NERF_GRID_TV_SH = 0, 1
 NERF_GRID_OPTIM_RMSPROP, NERF_GRID_OPTIM_SGD = 0, 1
 NERF_GRID_DEPTH_EXPECTED, NERF_GRID_DEPTH_THRESHOLD, NERF_GRID_DEPTH_RAYLEN = 0, 1, 2
@@ -430,6 +431,8 @@ def load():
     lib.nerf_set_view_fold.argtypes = [vp, i32]
     lib.nerf_set_ray_view_bias.restype = i32
     lib.nerf_set_ray_view_bias.argtypes = [vp, i32]
+    lib.nerf_set_tile_schedule.restype = i32
+    lib.nerf_set_tile_schedule.argtypes = [vp, i32]
     lib.nerf_view_fold_status.restype = i32
     lib.nerf_view_fold_status.argtypes = [vp, i32, C.POINTER(i32)]
     lib.nerf_get_precision.restype = i32

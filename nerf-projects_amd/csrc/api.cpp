@@ -94,6 +94,26 @@ int run_mlp(nerf_ctx* c, MlpLaunch& a, const PackedNet& net_in, int mode, hipStr
         a.ray_bias = c->ray_bias;
         a.stream_ray = net.d_stream_ray;
     }
+    // The claimed tile schedule (tile_claim.h): the stream's pair of words. launch_mlp_h2 / launch_mlp drop it where a
+    // workgroup has one tile at the most.
+    a.tile_claim = nullptr;
+    if (c->tile_schedule == NERF_TILES_CLAIMED && !a.store) {
+        std::lock_guard<std::mutex> lock(c->claim_mutex);
+        for (const auto& w : c->claim_words)
+            if (w.first == s) a.tile_claim = w.second;
+        if (!a.tile_claim) {
+            // (a stream's first launch: rare, like a growing workspace)
+            unsigned* words = nullptr;
+            HIP_TRY(hipMalloc((void**)&words, 2 * sizeof(unsigned)));
+            const hipError_t e = hipMemset(words, 0, 2 * sizeof(unsigned));
+            if (e != hipSuccess) {
+                (void)hipFree(words);
+                HIP_TRY(e);
+            }
+            c->claim_words.emplace_back(s, words);
+            a.tile_claim = words;
+        }
+    }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->profiling) {
         for (hipEvent_t* e : {&e0, &e1}) {
@@ -380,6 +400,7 @@ void nerf_ctx_destroy(nerf_ctx* c) {
     if (c->tape_mem) (void)hipFree(c->tape_mem);
     if (c->frame_rays) (void)hipFree(c->frame_rays);
     if (c->ray_bias) (void)hipFree(c->ray_bias);
+    for (auto& w : c->claim_words) (void)hipFree(w.second);
     if (c->d_loose) (void)hipFree(c->d_loose);
     if (c->h_loose) (void)hipHostFree(c->h_loose);
     if (c->scratch_done) (void)hipEventDestroy(c->scratch_done);
@@ -432,6 +453,15 @@ int nerf_set_ray_view_bias(nerf_ctx* c, int on) {
         return NERF_E_INVALID;
     }
     c->ray_view_bias = on != 0;
+    return NERF_OK;
+}
+
+int nerf_set_tile_schedule(nerf_ctx* c, int schedule) {
+    if (!c || (schedule != NERF_TILES_STATIC && schedule != NERF_TILES_CLAIMED)) {
+        set_error("nerf_set_tile_schedule: invalid argument");
+        return NERF_E_INVALID;
+    }
+    c->tile_schedule = schedule;
     return NERF_OK;
 }
 

@@ -58,6 +58,12 @@ struct nerf_ctx {
     bool ray_view_bias = true;
     float* ray_bias = nullptr;
     size_t ray_bias_floats = 0;
+    // nerf_set_tile_schedule, and the words of the claimed schedule (MlpLaunch::tile_claim): one pair per stream this context
+    // has launched an inference pass on. Launches in one stream run one after the other and each leaves its pair zero, so they
+    // share it; launches on two streams may run side by side and must not. Allocated (and zeroed) when a stream is first seen.
+    int tile_schedule = NERF_TILES_CLAIMED;
+    std::mutex claim_mutex;
+    std::vector<std::pair<hipStream_t, unsigned*>> claim_words;
     // The scratch above is shared by every call on this context (nerf_render_rays, nerf_render_frame, nerf_train_step,
     // nerf_image_metrics). Calls are asynchronous, so two calls may only reuse it in stream order: ScratchScope
     // (below) serialises host threads with `scratch_mutex` and, when a call arrives on another stream than the one

@@ -33,6 +33,7 @@
 // dot products). Bound: fp32 MFMA, 64 cycles per v_mfma_f32_32x32x2_f32 per SIMD,
 // 157.3 TFLOP/s per chip.
 #include "mlp_inputs.h"
+#include "tile_claim.h"
 
 namespace nerf {
 
@@ -351,7 +352,31 @@ void nerf_mlp_kernel(const MlpLaunch a) {
     int64_t n_live = a.n_points;
     if constexpr (MODE == kInputRaysIndexed) n_live = __builtin_amdgcn_readfirstlane(*a.index_count);
     const int64_t n_tiles = (n_live + kPointsPerGroup - 1) / kPointsPerGroup;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    // The tile schedule, as in the fp16-pair kernels (mlp_kernel_h2_body.inc, tile_claim.h): static when a.tile_claim is
+    // nullptr and in the training pass; claimed otherwise - the first batch by position, the later ones from the launch's
+    // counter, one lane's returning atomic handed round through LDS behind a barrier, at a tile boundary.
+    __shared__ unsigned claim_lds;
+    int64_t tile = blockIdx.x, tile_end = n_tiles;
+    int tile_step = gridDim.x, claim_share = 0, claim_done = 0;
+    const bool claimed = !STORE && a.tile_claim != nullptr;
+    if (claimed) {
+        claim_share = (int)((n_tiles + gridDim.x - 1) / gridDim.x);
+        claim_done = tile_claim_batch(claim_share, 0);
+        tile = (int64_t)blockIdx.x * claim_done;
+        tile_end = tile + claim_done < n_tiles ? tile + claim_done : n_tiles;
+        tile_step = 1;
+    }
+    for (;; tile += tile_step) {
+    if (tile >= tile_end) {
+        if (!claimed) break;
+        const int size = tile_claim_batch(claim_share, claim_done);
+        if (threadIdx.x == 0) claim_lds = atomicAdd(a.tile_claim, (unsigned)size);
+        __syncthreads();
+        tile = (int64_t)gridDim.x * tile_claim_batch(claim_share, 0) + __builtin_amdgcn_readfirstlane(*(volatile unsigned*)&claim_lds);
+        if (tile >= n_tiles) break;      // the pool is dry: leave
+        tile_end = tile + size < n_tiles ? tile + size : n_tiles;
+        claim_done += size;
+    }
     pipe.c = 0;
     const int64_t tile0 = tile * kPointsPerGroup + wave * kPointsPerWave;
     const int64_t pt_raw = tile0 + (lane & 31);
@@ -470,6 +495,13 @@ void nerf_mlp_kernel(const MlpLaunch a) {
     }   // tile loop
     // the ring's trailing prefetches must land before this workgroup's LDS is released
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (claimed && threadIdx.x == 0) {
+        // the last workgroup out zeroes the counter and the count of leavers for the next launch in the stream
+        if (atomicAdd(a.tile_claim + 1, 1u) == gridDim.x - 1) {
+            __hip_atomic_store(a.tile_claim, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.tile_claim + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 // ---- fused backward-data pass (training) --------------------------------------------------
@@ -741,7 +773,8 @@ hipError_t launch_mlp_bwd(const MlpBwdLaunch& b, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_mlp(const MlpLaunch& a, int mode, hipStream_t s) {
+hipError_t launch_mlp(const MlpLaunch& a_in, int mode, hipStream_t s) {
+    MlpLaunch a = a_in;
     if (a.n_points <= 0) return hipSuccess;
     const int64_t tiles = (a.n_points + kPointsPerGroup - 1) / kPointsPerGroup;
     // persistent grid: the kernel's 112 KiB of LDS and 512 registers per lane admit exactly one
@@ -757,6 +790,7 @@ hipError_t launch_mlp(const MlpLaunch& a, int mode, hipStream_t s) {
         if (n_cu[dev] <= 0) n_cu[dev] = 256;
     }
     const dim3 grid((unsigned)(tiles < n_cu[dev] ? tiles : n_cu[dev])), block(256);
+    if (tiles <= n_cu[dev] || a.store) a.tile_claim = nullptr;      // one tile per workgroup at the most, or a training pass: static
     const size_t lds = kBiasLdsBytes + kRing * kChunkBytes;
     static bool raised[64][6] = {};
     if (mode < 0 || mode > 4) return hipErrorInvalidValue;

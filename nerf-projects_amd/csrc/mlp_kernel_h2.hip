@@ -30,6 +30,7 @@
 // the trunk output through W_v[:, :W] W_f, formed on the device - nerf_mlp_h2_fold_kernel below, refresh_kernels.hip): 66
 // chunks and 3 144 MFMAs per wave tile instead of 74 and 3 528.
 #include "mlp_pair_common.h"
+#include "tile_claim.h"
 
 namespace nerf {
 
@@ -396,7 +397,8 @@ void nerf_mlp_h2_fold_ray_kernel(const MlpLaunch a) {
 }
 
 
-hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
+hipError_t launch_mlp_h2(const MlpLaunch& a_in, int mode, hipStream_t s) {
+    MlpLaunch a = a_in;
     if (a.n_points <= 0) return hipSuccess;
     if (!a.stream_h2 || !a.descale || !a.gain) return hipErrorInvalidValue;
     const int64_t tiles = (a.n_points + kPointsPerGroup - 1) / kPointsPerGroup;
@@ -411,6 +413,7 @@ hipError_t launch_mlp_h2(const MlpLaunch& a, int mode, hipStream_t s) {
         if (n_cu[dev] <= 0) n_cu[dev] = 256;
     }
     const dim3 grid((unsigned)(tiles < n_cu[dev] ? tiles : n_cu[dev])), block(256);
+    if (tiles <= n_cu[dev] || a.store) a.tile_claim = nullptr;      // one tile per workgroup at the most, or a training pass: static
     const size_t lds = kRingH * kChunkBytes;   // + 20.5 KiB static (bias block, layer scales; + 4 KiB in the per-ray-bias kernel)
     static bool raised[64][5] = {};
     if (mode < 0 || mode > 4) return hipErrorInvalidValue;

@@ -57,7 +57,34 @@
     if (idle) n_live = 0;      // the launch belongs to this kernel's twin
     const int64_t n_tiles = (n_live + kPointsPerGroup - 1) / kPointsPerGroup;
     const int n_layers = (a.use_viewdirs && !fold) ? a.D + 1 : a.D;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    // The tile schedule. Static (a.tile_claim == nullptr; every STORE kernel): workgroup b runs tiles b, b + grid, ... Claimed
+    // (tile_claim.h): contiguous batches - the first by position, the later ones from the launch's counter, 15 to 35
+    // claims per launch, each in the open at a tile boundary: one lane's returning atomic, handed round through LDS behind
+    // one barrier. The bounds are wave-uniform and live in scalar registers. Tile order changes no value.
+    __shared__ unsigned claim_lds;
+    int64_t tile = blockIdx.x, tile_end = n_tiles;
+    int tile_step = gridDim.x, claim_share = 0, claim_done = 0;
+    bool claimed = false;
+    if constexpr (STORE == 0) claimed = a.tile_claim != nullptr && !idle;
+    if (claimed) {
+        claim_share = (int)((n_tiles + gridDim.x - 1) / gridDim.x);
+        claim_done = tile_claim_batch(claim_share, 0);
+        tile = (int64_t)blockIdx.x * claim_done;
+        tile_end = tile + claim_done < n_tiles ? tile + claim_done : n_tiles;
+        tile_step = 1;
+    }
+    for (;; tile += tile_step) {
+        if (tile >= tile_end) {
+            if (!claimed) break;
+            const int size = tile_claim_batch(claim_share, claim_done);
+            if (threadIdx.x == 0) claim_lds = atomicAdd(a.tile_claim, (unsigned)size);
+            __syncthreads();
+            tile = (int64_t)gridDim.x * tile_claim_batch(claim_share, 0) +
+                   __builtin_amdgcn_readfirstlane(__float_as_uint(lds_scalar((const float*)&claim_lds)));
+            if (tile >= n_tiles) break;      // the pool is dry: leave
+            tile_end = tile + size < n_tiles ? tile + size : n_tiles;
+            claim_done += size;
+        }
         pipe_tile_start(pipe);
         const int64_t tile0 = tile * kPointsPerGroup + wave * kPointsPerWave;
         const int64_t pt_raw = tile0 + (lane & 31);
@@ -339,6 +366,14 @@
         }
     }   // tile loop
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if (claimed && threadIdx.x == 0) {
+        // every workgroup of the launch passes here once, behind its last claim: the last one out zeroes the counter and the
+        // count of leavers for the next launch in the stream
+        if (atomicAdd(a.tile_claim + 1, 1u) == gridDim.x - 1) {
+            __hip_atomic_store(a.tile_claim, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.tile_claim + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
     if constexpr (STORE) {
         __syncthreads();
         flush_maxes(a.st.maxes, max_record, kBwdMaxSlots);

@@ -196,7 +196,11 @@ struct MlpLaunch {
     const float* descale;
     const float* gain;
     unsigned* loose;             // counter of (wave, layer) events where the a-priori output bound was >= 2^12 x too wide
-    unsigned long long* reserved;   // unused (was `stamps`). Without it the f16x2 frame rate left the parent's spread: 0.04 % ABOVE it, within noise; kept by the rule of that change (profiles/switch_removal_ab.md)
+    // The claimed tile schedule (tile_claim.h; inference kernels only): two words, [0] the launch's counter of claimed tiles,
+    // [1] the count of workgroups that have left. Both are zero when a launch starts and the last workgroup out leaves them
+    // zero, so launches in one stream reuse them without a memset; launches that may run side by side need words of their
+    // own (nerf_ctx::claim_words). nullptr: the static loop.
+    unsigned* tile_claim;
     const float* bias;
     int n_chunks;
     int n_bias_tiles;

@@ -48,6 +48,9 @@ class Context:
         default = os.environ.get("NERF_PRECISION")
         if default:
             self.set_precision(default)
+        schedule = os.environ.get("NERF_TILE_SCHEDULE")      # for A/B runs of unchanged programs
+        if schedule:
+            self.set_tile_schedule(schedule)
 
     PRECISIONS = {"f32": 0, "f16x2": 1}
 
@@ -73,6 +76,16 @@ class Context:
         """Whether folded renders of ray records with a multiple of 32 samples per ray take the view layer's gamma(dir) term
         per ray instead of per point (nerf_set_ray_view_bias). On by default; sigma is the same bits either way."""
         check(self.lib.nerf_set_ray_view_bias(self.handle, int(bool(on))))
+
+    TILE_SCHEDULES = {"static": _lib.NERF_TILES_STATIC, "claimed": _lib.NERF_TILES_CLAIMED}
+
+    def set_tile_schedule(self, name):
+        """How an inference MLP launch spreads its tiles over the compute units: "claimed" (default; workgroups take batches
+        from a counter, so that fast XCDs do not idle) or "static" (equal shares). The same bits either way
+        (nerf_set_tile_schedule)."""
+        if name not in self.TILE_SCHEDULES:
+            raise ValueError(f"tile schedule {name!r}: expected one of {sorted(self.TILE_SCHEDULES)}")
+        check(self.lib.nerf_set_tile_schedule(self.handle, self.TILE_SCHEDULES[name]))
 
     def view_fold_status(self, slot):
         """True if the next fp16-pair inference launch of the network in ``slot`` uses the view fold
