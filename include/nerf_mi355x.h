@@ -599,7 +599,33 @@ int nerf_marching_cubes(nerf_ctx* ctx, const nerf_mc_args* args);
  * and follow every call to a pinned host mirror; nerf_occupancy_stats waits for the device and reads them.
  * nerf_occupancy_create synchronises `stream` (it returns with the count of occupied cells known). reso[a] in [2, 1024].
  * A grid belongs to the context it was created on: use it with that context only, and destroy it before the context.
- * Training calls and nerf_render_shard take no grid. */
+ * The taped calls (nerf_train_forward / nerf_train_backward) and nerf_render_shard take no grid.
+ *
+ * Training with a grid: nerf_train_step_occ is nerf_train_step - the reference's loop body, nerf.ipynb:1258-1282 - with the
+ * network query of both passes replaced by the masked query above. Everything else is the dense step: sample_pdf on the
+ * (masked) coarse weights, both MSE terms, Adam, z_vals_fine_in, perturb, lindisp, white_bkgd; nerf_train_args is unchanged.
+ *   - Which samples are kept: the rule above, by the same device function - `outside` as the grid says, a non-finite
+ *     position kept, the last sample of every ray always kept.
+ *   - Skipped samples have a raw row of zeros, and their alpha is EXACTLY 0 even with sigma noise (noise0 / noise): the
+ *     noise is not applied to a skipped sample (relu(0 + noise) would be positive at half of all empty samples, and the
+ *     step would train against fog). Rendering calls keep their behaviour: there the caller's noise reaches every sample.
+ *   - Gradients: a skipped sample sends no gradient to any parameter; a kept sample sends exactly what the dense step
+ *     would send given the same raw everywhere. A cell wrongly called empty therefore receives no gradient until a
+ *     refresh finds density there.
+ *   - Statistics: both passes are counted in the grid's evaluated / total counters like rendering passes.
+ *   - slot_fine < 0 with N_importance > 0 (one network, two passes, gradients summed), networks without view directions
+ *     and networks narrower than 256 work as in nerf_train_step.
+ *   - Determinism: the same batch, grid and weights give the same bits in either arithmetic. In NERF_PRECISION_F32 a kept
+ *     point's forward values do not depend on where it stands in the list; in NERF_PRECISION_F16X2 the per-wavefront
+ *     input scale makes the last bits depend on which 32 kept points share a wavefront. A grid that keeps every
+ *     sample gives nerf_train_step's bits.
+ *   - The kept count of each pass crosses to the host (one stream synchronisation per pass): the backward and
+ *     weight-gradient launches are sized by it.
+ * A NULL grid or one of another context is NERF_E_INVALID.
+ * nerf_occupancy_refresh rebuilds the cells of an existing grid in place from new lattices / a new mask (threshold, dilate
+ * and outside as given): same handle, same bit table, the statistics counters untouched, the occupied count updated. Box and
+ * resolution must be the grid's own (NERF_E_INVALID otherwise). It synchronises `stream`; work on other streams that reads
+ * the grid must have finished. */
 #define NERF_OCC_EVALUATE 0       /* points outside the box are evaluated                                          */
 #define NERF_OCC_EMPTY 1          /* points outside the box are skipped                                            */
 typedef struct nerf_occupancy nerf_occupancy;
@@ -623,6 +649,8 @@ int nerf_occupancy_cells(const nerf_occupancy* occ, uint8_t* mask, int64_t* n_oc
 int nerf_occupancy_stats(nerf_occupancy* occ, int64_t* evaluated /*[host]*/, int64_t* total /*[host]*/, int reset);
 int nerf_render_rays_occ(nerf_ctx* ctx, const nerf_render_args* args, const nerf_occupancy* occ);
 int nerf_render_frame_occ(nerf_ctx* ctx, const nerf_frame_args* args, const nerf_occupancy* occ);
+int nerf_train_step_occ(nerf_ctx* ctx, const nerf_train_args* args, nerf_occupancy* occ);
+int nerf_occupancy_refresh(nerf_occupancy* occ, const nerf_occupancy_args* args);
 
 /* Sparse voxel grid ------------------------------------------------------------------------------
  * A Plenoxels grid (svox2.SparseGrid, forward side): X x Y x Z nodes, a density and 3 * basis_dim spherical-harmonic colour

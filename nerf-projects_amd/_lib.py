@@ -24,7 +24,7 @@ EXPORTS = (
     "nerf_set_view_fold", "nerf_view_fold_status", "nerf_set_ray_view_bias", "nerf_set_tile_schedule",
     "nerf_pack_rays", "nerf_density_grid", "nerf_marching_cubes", "nerf_train_forward", "nerf_train_backward",
     "nerf_zero_grad", "nerf_adam_step", "nerf_occupancy_create", "nerf_occupancy_destroy", "nerf_occupancy_cells",
-    "nerf_occupancy_stats", "nerf_render_rays_occ", "nerf_render_frame_occ",
+    "nerf_occupancy_stats", "nerf_render_rays_occ", "nerf_render_frame_occ", "nerf_train_step_occ", "nerf_occupancy_refresh",
     "nerf_grid_create", "nerf_grid_destroy", "nerf_grid_render_rays", "nerf_grid_render_image", "nerf_grid_gen_rays",
     "nerf_grid_sample", "nerf_grid_accelerate", "nerf_grid_drop_skip", "nerf_grid_has_skip", "nerf_grid_project_sh",
     "nerf_grid_fused_backward", "nerf_grid_tv_grad", "nerf_grid_optim_step",
@@ -461,6 +461,10 @@ def load():
     lib.nerf_occupancy_cells.argtypes = [vp, vp, C.POINTER(i64), vp]
     lib.nerf_occupancy_stats.restype = i32
     lib.nerf_occupancy_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), i32]
+    lib.nerf_train_step_occ.restype = i32
+    lib.nerf_train_step_occ.argtypes = [vp, C.POINTER(TrainArgs), vp]
+    lib.nerf_occupancy_refresh.restype = i32
+    lib.nerf_occupancy_refresh.argtypes = [vp, C.POINTER(OccupancyArgs)]
     lib.nerf_render_rays_occ.restype = i32
     lib.nerf_render_rays_occ.argtypes = [vp, C.POINTER(RenderArgs), vp]
     lib.nerf_render_frame_occ.restype = i32

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnerf_mi355x.so")
 SOURCES = ["api.cpp", "train_api.cpp", "pack_weights.cpp", "mlp_kernel.hip", "mlp_kernel_h2.hip", "mlp_bwd_kernel_h2.hip",
-           "ray_kernels.hip", "train_kernels.hip", "train_dw_kernel.hip", "refresh_kernels.hip", "mesh_kernels.hip", "occupancy_kernels.hip",
+           "ray_kernels.hip", "train_kernels.hip", "train_dw_kernel.hip", "refresh_kernels.hip", "mesh_kernels.hip", "occupancy_kernels.hip", "train_occ_kernels.hip",
            "grid_api.cpp", "grid_kernels.hip", "grid_train_api.cpp", "grid_train_kernels.hip", "grid_train_losses_kernels.hip",
            "grid_resample_api.cpp", "grid_resample_kernels.hip",
            "grid_components_api.cpp", "grid_components_kernels.hip",

@@ -1439,6 +1439,64 @@ int nerf_occupancy_create(nerf_ctx* c, const nerf_occupancy_args* a, nerf_occupa
     return NERF_OK;
 }
 
+int nerf_occupancy_refresh(nerf_occupancy* occ, const nerf_occupancy_args* a) {
+    if (!occ || !a) {
+        set_error("nerf_occupancy_refresh: NULL argument");
+        return NERF_E_INVALID;
+    }
+    OccGrid& g = occ->g;
+    for (int k = 0; k < 3; ++k)
+        if (a->reso[k] != g.nc[k] + 1 || (float)a->c1[k] != g.c1[k] || (float)a->c2[k] != g.c2[k]) {
+            set_error("nerf_occupancy_refresh: axis %d: the grid has %d nodes over [%g, %g], the arguments name %d over [%g, %g] "
+                      "(a refresh keeps box and resolution: create a new grid for another shape)", k, g.nc[k] + 1, g.c1[k],
+                      g.c2[k], a->reso[k], a->c1[k], a->c2[k]);
+            return NERF_E_INVALID;
+        }
+    if (a->n_lattices < 0 || a->n_lattices > 8 || (a->n_lattices > 0 && !a->sigma) || (a->n_lattices == 0 && !a->cell_mask)) {
+        set_error("nerf_occupancy_refresh: 1..8 sigma lattices or a cell mask are required (n_lattices = %d)", a->n_lattices);
+        return NERF_E_INVALID;
+    }
+    for (int l = 0; l < a->n_lattices; ++l)
+        if (!a->sigma[l]) {
+            set_error("nerf_occupancy_refresh: sigma[%d] is NULL", l);
+            return NERF_E_INVALID;
+        }
+    if (a->dilate < 0 || a->dilate > 1024 || (a->outside != NERF_OCC_EVALUATE && a->outside != NERF_OCC_EMPTY) ||
+        std::isnan(a->threshold)) {
+        set_error("nerf_occupancy_refresh: dilate = %d must be in [0, 1024], outside = %d a NERF_OCC_* value, threshold not NaN",
+                  a->dilate, a->outside);
+        return NERF_E_INVALID;
+    }
+    if (!occ->ctx || !occ->d_bits) {
+        set_error("nerf_occupancy_refresh: the grid has no context or no bit table");
+        return NERF_E_INVALID;
+    }
+    DeviceGuard dg(occ->ctx->device);
+    hipStream_t s = (hipStream_t)a->stream;
+    // (the bit table is rewritten in place: work of other streams that still reads it must have finished - the caller's
+    // business, as for every buffer handed to two streams; the context's own calls are ordered by its scratch scope)
+    ScratchScope scope(occ->ctx, s);
+    HIP_TRY(scope.status);
+    const size_t cells = (size_t)g.nc[0] * g.nc[1] * g.nc[2];
+    uint8_t* tmp = nullptr;
+    unsigned long long n_occ = 0;
+    unsigned long long* d_n = occ->d_stats + 2;
+    hipError_t e = hipMalloc((void**)&tmp, 2 * cells);
+    if (e == hipSuccess)
+        e = launch_occ_build(a->sigma, a->n_lattices, a->cell_mask, g.nc, a->threshold, a->dilate, tmp, tmp + cells, occ->d_bits,
+                             d_n, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&n_occ, d_n, sizeof(n_occ), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (tmp) (void)hipFree(tmp);
+    if (e != hipSuccess) {
+        set_error("nerf_occupancy_refresh: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? NERF_E_NOMEM : NERF_E_HIP;
+    }
+    g.outside_keep = a->outside == NERF_OCC_EVALUATE;
+    occ->n_occupied = (int64_t)n_occ;
+    return NERF_OK;
+}
+
 int nerf_occupancy_cells(const nerf_occupancy* occ, uint8_t* mask, int64_t* n_occupied, void* stream) {
     if (!occ) {
         set_error("nerf_occupancy_cells: NULL grid");

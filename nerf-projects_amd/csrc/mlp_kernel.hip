@@ -381,6 +381,7 @@ void nerf_mlp_kernel(const MlpLaunch a) {
     const int64_t tile0 = tile * kPointsPerGroup + wave * kPointsPerWave;
     const int64_t pt_raw = tile0 + (lane & 31);
     int64_t pt = pt_raw < n_live ? pt_raw : n_live - 1;   // clamp: padded lanes recompute the last point
+    const int64_t slot = pt;      // STORE: what the backward pass keeps goes to the tile slot - compact, in list order
     if constexpr (MODE == kInputRaysIndexed) pt = a.index[pt];      // the listed point replaces the slot: inputs, output row
     const bool live = pt_raw < n_live;
 
@@ -409,7 +410,7 @@ void nerf_mlp_kernel(const MlpLaunch a) {
         load_bias<8>(acc, bias_lds, is_feature ? 8 * a.D + 1 : 8 * i, h);
         // (training: tile kt of the previous layer's output - this chunk's B operand - goes to memory behind this chunk's
         // barrier)
-        const RowRef keep = STORE ? row_ref(a.st.h[i - 1], a.st.h_ld[i - 1], pt, h) : RowRef{nullptr, 0u};
+        const RowRef keep = STORE ? row_ref(a.st.h[i - 1], a.st.h_ld[i - 1], slot, h) : RowRef{nullptr, 0u};
 #pragma unroll
         for (int kt = 0; kt < 8; ++kt) {
             if constexpr (STORE)
@@ -433,7 +434,7 @@ void nerf_mlp_kernel(const MlpLaunch a) {
     }
     // without a view layer the last trunk output has no following chunks to ride behind
     if constexpr (STORE)
-        if (!a.use_viewdirs) store_tiles<8>(a.st.h[a.D - 1], a.st.h_ld[a.D - 1], hid, pt, h, live);
+        if (!a.use_viewdirs) store_tiles<8>(a.st.h[a.D - 1], a.st.h_ld[a.D - 1], hid, slot, h, live);
 
     unsigned bad;      // NaN / Inf inputs propagate as through F.relu (mlp_inputs.h, kBadXyz): raw inputs re-read here
     {
@@ -444,7 +445,7 @@ void nerf_mlp_kernel(const MlpLaunch a) {
     if (a.use_viewdirs) {
         // views_linears[0] on cat[feature, gamma(dir)] (nerf.py:93-98): 4 output tiles
         load_bias<4>(acc, bias_lds, 8 * a.D + 9, h);
-        const RowRef keep = STORE ? row_ref(a.st.feat, a.st.feat_ld, pt, h) : RowRef{nullptr, 0u};
+        const RowRef keep = STORE ? row_ref(a.st.feat, a.st.feat_ld, slot, h) : RowRef{nullptr, 0u};
 #pragma unroll
         for (int kp = 0; kp < 4; ++kp) {
             if constexpr (STORE)
@@ -457,7 +458,7 @@ void nerf_mlp_kernel(const MlpLaunch a) {
         }
         chunk_ktile4(pipe, cur, acc, dd);
         activate<4, true>(hid, acc);
-        if constexpr (STORE) store_tiles<4>(a.st.hv, a.st.hv_ld, hid, pt, h, live);
+        if constexpr (STORE) store_tiles<4>(a.st.hv, a.st.hv_ld, hid, slot, h, live);
         // rgb_linear (nerf.py:101): three output rows over the 128-wide view layer, as dot products
         const float* rb = bias_lds + (8 * a.D + 13) * 32;
         const float r0 = row_dot<4>(hid, bias_lds, 8 * a.D + 22, h) + rb[0];
@@ -792,21 +793,24 @@ hipError_t launch_mlp(const MlpLaunch& a_in, int mode, hipStream_t s) {
     const dim3 grid((unsigned)(tiles < n_cu[dev] ? tiles : n_cu[dev])), block(256);
     if (tiles <= n_cu[dev] || a.store) a.tile_claim = nullptr;      // one tile per workgroup at the most, or a training pass: static
     const size_t lds = kBiasLdsBytes + kRing * kChunkBytes;
-    static bool raised[64][6] = {};
+    static bool raised[64][7] = {};
     if (mode < 0 || mode > 4) return hipErrorInvalidValue;
-    if (mode == kInputRaysIndexed && (a.store || !a.index || !a.index_count)) return hipErrorInvalidValue;
-    if (a.store && (mode != kInputRays || a.n_points > (int64_t)1 << 22)) return hipErrorInvalidValue;   // training forward: ray records; 32-bit element offsets in store_tiles
+    if (mode == kInputRaysIndexed && (!a.index || !a.index_count)) return hipErrorInvalidValue;
+    // training forward: ray records (kInputRaysIndexed: the listed points, kept at the tile slots; n_points = the list's length);
+    // 32-bit element offsets in store_tiles
+    if (a.store && ((mode != kInputRays && mode != kInputRaysIndexed) || a.n_points > (int64_t)1 << 22)) return hipErrorInvalidValue;
     if (a.store) {   // the hooks inside the chunk loop are unconditional 16-byte stores (RowRef)
         bool rows_ok = !a.use_viewdirs || (training_rows_ok(a.st.feat, a.st.feat_ld) && training_rows_ok(a.st.hv, a.st.hv_ld));
         for (int i = 0; i < a.D; ++i) rows_ok = rows_ok && training_rows_ok(a.st.h[i], a.st.h_ld[i]);
         if (!rows_ok) return hipErrorInvalidValue;
     }
     typedef void (*kernel_t)(const MlpLaunch);
-    static const kernel_t table[6] = {nerf_mlp_kernel<kInputEmbedded>, nerf_mlp_kernel<kInputPoints>,
+    static const kernel_t table[7] = {nerf_mlp_kernel<kInputEmbedded>, nerf_mlp_kernel<kInputPoints>,
                                       nerf_mlp_kernel<kInputRays>, nerf_mlp_kernel<kInputRays, true>,
-                                      nerf_mlp_kernel<kInputLattice>, nerf_mlp_kernel<kInputRaysIndexed>};
+                                      nerf_mlp_kernel<kInputLattice>, nerf_mlp_kernel<kInputRaysIndexed>,
+                                      nerf_mlp_kernel<kInputRaysIndexed, true>};
     static_assert(kInputEmbedded == 0 && kInputPoints == 1 && kInputRays == 2 && kInputLattice == 3, "kernel table order");
-    const int which = a.store ? 3 : mode == kInputLattice ? 4 : mode == kInputRaysIndexed ? 5 : mode;
+    const int which = a.store ? (mode == kInputRaysIndexed ? 6 : 3) : mode == kInputLattice ? 4 : mode == kInputRaysIndexed ? 5 : mode;
     // 112 KiB of dynamic LDS is above the 64 KiB default cap: raise it once per device and kernel
     if (!raised[dev][which]) {
         e = hipFuncSetAttribute((const void*)table[which], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

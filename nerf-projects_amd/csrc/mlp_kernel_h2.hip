@@ -417,11 +417,12 @@ hipError_t launch_mlp_h2(const MlpLaunch& a_in, int mode, hipStream_t s) {
     const size_t lds = kRingH * kChunkBytes;   // + 20.5 KiB static (bias block, layer scales; + 4 KiB in the per-ray-bias kernel)
     static bool raised[64][5] = {};
     if (mode < 0 || mode > 4) return hipErrorInvalidValue;
-    if (mode == kInputRaysIndexed && (a.store || !a.index || !a.index_count)) return hipErrorInvalidValue;
+    if (mode == kInputRaysIndexed && (!a.index || !a.index_count)) return hipErrorInvalidValue;
     if (a.store) {
-        // training forward: ray records, a view-dependent network, buffers the one-instruction stores can address
-        // (16-byte aligned rows, byte offsets below 2^32)
-        if (mode != kInputRays) return hipErrorInvalidValue;
+        // training forward: ray records - every point, or (kInputRaysIndexed: the step with an occupancy grid) the listed ones,
+        // whose kept values go to the tile slots: n_points is then the list's length -, buffers the one-instruction stores
+        // can address (16-byte aligned rows, byte offsets below 2^32)
+        if (mode != kInputRays && mode != kInputRaysIndexed) return hipErrorInvalidValue;
         auto ok = [&](const float* b, int ld) {
             return b != nullptr && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(b) & 15) == 0 &&
                    (uint64_t)a.n_points * (uint64_t)ld * 4u < ((uint64_t)1 << 32);
@@ -433,16 +434,17 @@ hipError_t launch_mlp_h2(const MlpLaunch& a_in, int mode, hipStream_t s) {
         rows_ok = rows_ok && a.st.maxes && (a.st.mask_hv || !a.use_viewdirs) && (uint64_t)a.n_points * 32u < ((uint64_t)1 << 32);
         for (int i = 0; i < a.D; ++i) rows_ok = rows_ok && a.st.mask[i] && (reinterpret_cast<uintptr_t>(a.st.mask[i]) & 15) == 0;
         if (!rows_ok) return hipErrorInvalidValue;
-        static bool raised_store[64][2] = {};
-        const int blk = a.st.blocked ? 1 : 0;
-        if (!raised_store[dev][blk]) {
-            e = hipFuncSetAttribute(blk ? (const void*)nerf_mlp_h2_kernel<kInputRays, 2> : (const void*)nerf_mlp_h2_kernel<kInputRays, 1>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        static bool raised_store[64][4] = {};
+        const int blk = a.st.blocked ? 1 : 0, which = blk + (mode == kInputRaysIndexed ? 2 : 0);
+        typedef void (*kernel_t)(const MlpLaunch);
+        static const kernel_t store_table[4] = {nerf_mlp_h2_kernel<kInputRays, 1>, nerf_mlp_h2_kernel<kInputRays, 2>,
+                                                nerf_mlp_h2_kernel<kInputRaysIndexed, 1>, nerf_mlp_h2_kernel<kInputRaysIndexed, 2>};
+        if (!raised_store[dev][which]) {
+            e = hipFuncSetAttribute((const void*)store_table[which], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
-            raised_store[dev][blk] = true;
+            raised_store[dev][which] = true;
         }
-        if (blk) hipLaunchKernelGGL((nerf_mlp_h2_kernel<kInputRays, 2>), grid, block, lds, s, a);
-        else hipLaunchKernelGGL((nerf_mlp_h2_kernel<kInputRays, 1>), grid, block, lds, s, a);
+        hipLaunchKernelGGL(store_table[which], grid, block, lds, s, a);
         return hipGetLastError();
     }
     if (!raised[dev][mode]) {

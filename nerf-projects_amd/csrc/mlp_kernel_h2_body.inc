@@ -89,6 +89,7 @@
         const int64_t tile0 = tile * kPointsPerGroup + wave * kPointsPerWave;
         const int64_t pt_raw = tile0 + (lane & 31);
         int64_t pt = pt_raw < n_live ? pt_raw : n_live - 1;
+        const int64_t slot = pt;      // STORE: what the backward pass keeps goes to the tile slot - compact, in list order
         if constexpr (MODE == kInputRaysIndexed) pt = a.index[pt];      // the listed point replaces the slot: inputs, output row
         if constexpr (ray_bias && MODE == kInputRays) {
             // This wave's ray (a wave behind the batch's end: the last ray) -> its row of the table into the wave's slot, one
@@ -168,11 +169,11 @@
             if constexpr (STORE) {
                 pd.maskw = 0u;
                 pd.mask_base = wave_uniform(is_feature ? a.st.mask_hv : a.st.mask[l]);      // (feature_linear: not written)
-                pd.mask_off = 16u * (2u * (unsigned)pt + (unsigned)h);
+                pd.mask_off = 16u * (2u * (unsigned)slot + (unsigned)h);
                 pd.keep_base = (is_feature ? a.st.feat : a.st.h[l]) + (STORE == 2 ? 1024 : 0);      // (blocked: keep_pairs)
-                pd.keep_off = 4u * ((unsigned)pt * (unsigned)(is_feature ? a.st.feat_ld : a.st.h_ld[l]) + 4u * (unsigned)h);
+                pd.keep_off = 4u * ((unsigned)slot * (unsigned)(is_feature ? a.st.feat_ld : a.st.h_ld[l]) + 4u * (unsigned)h);
                 if constexpr (STORE == 2)      // blocked by 32 points: 32 KiB per group of a 256-wide buffer, 32 bytes per point of a piece
-                    pd.keep_off = ((unsigned)pt >> 5) * 32768u + ((unsigned)pt & 31u) * 32u + (unsigned)h * 16u;
+                    pd.keep_off = ((unsigned)slot >> 5) * 32768u + ((unsigned)slot & 31u) * 32u + (unsigned)h * 16u;
             }
         };
         // all 8 tiles of the pending layer are converted: its true output range
@@ -302,10 +303,10 @@
                 finish_views(y, accB, ray_bias ? lds_addr(ray_lds + wave * 256) + 64 * h : bias0 + 128 * (8 * a.D + 9),
                              lds_scalar(layer_tab + 4 * (a.D + 1)) * pow2f(-pd.t_out));
             if constexpr (STORE) {
-                const unsigned off = 4u * ((unsigned)pt * (unsigned)a.st.hv_ld + 4u * (unsigned)h);
+                const unsigned off = 4u * ((unsigned)slot * (unsigned)a.st.hv_ld + 4u * (unsigned)h);
                 keep_tiles4<0>(a.st.hv, off, y);
                 // the view layer's ReLU mask in the bit order of the trunk layers' (MlpStore::mask_hv, words 0 and 1)
-                const unsigned moff = 16u * (2u * (unsigned)pt + (unsigned)h);
+                const unsigned moff = 16u * (2u * (unsigned)slot + (unsigned)h);
                 const u32x4 rec = {relu_mask_word(y[0], y[1]), relu_mask_word(y[2], y[3]), 0u, 0u};
                 asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" : : "v"(moff), "v"(rec), "s"(a.st.mask_hv) : "memory");
             }

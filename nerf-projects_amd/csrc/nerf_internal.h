@@ -161,7 +161,8 @@ constexpr int kLooseBwdGuard = 1000;    // overshoot (in binades) from which a b
 // one float per point, relu(sigma), instead of the [n, out_ch] rows
 // kInputRaysIndexed: kInputRays over a compacted list - tile slot n evaluates point index[n] of the [rays, samples] grid, for
 // n < *index_count (a device-side count, read once at kernel start); inputs are read and the output row is written at the
-// listed point, every other row of `out` is left alone (occupancy_kernels.hip has zeroed it). Inference only.
+// listed point, every other row of `out` is left alone (occupancy_kernels.hip has zeroed it). With `store` (the training step
+// with a grid, train_api.cpp) what MlpStore names is written at the tile slot n: compact, in list order.
 enum MlpInputMode { kInputEmbedded = 0, kInputPoints = 1, kInputRays = 2, kInputLattice = 3, kInputRaysIndexed = 4 };
 
 // Training forward pass through the fused fp32 kernel: where the activations autograd would keep are written
@@ -614,6 +615,14 @@ hipError_t launch_occ_build(const float* const* sigma, int n_lattices, const uin
                             float threshold, int dilate, uint8_t* tmp0, uint8_t* tmp1, uint32_t* bits,
                             unsigned long long* n_occupied, hipStream_t s);
 hipError_t launch_occ_unpack(const uint32_t* bits, const int32_t nc[3], uint8_t* mask, hipStream_t s);
+// The training step with a grid (train_occ_kernels.hip). launch_embed_train over a list: slot n < M holds point index[n], its
+// rows are written at the slot; noise_out (optional, zeroed by the caller) receives noise_in at the listed points.
+hipError_t launch_occ_embed(const float* rays, int ray_ld, const float* z, const int* index, int64_t M, int S, int Lx, int Lv,
+                            float* x0, int ld0, float* x1, int ld1, float* vcat, int ldv, int voff, int pad,
+                            const float* noise_in, float* noise_out, hipStream_t s);
+// dst[n] = src[index[n]] / dst[index[n]] = src[n] for rows of C floats, n < M
+hipError_t launch_occ_gather_rows(const float* src, const int* index, int64_t M, int C, float* dst, hipStream_t s);
+hipError_t launch_occ_scatter_rows(const float* src, const int* index, int64_t M, int C, float* dst, hipStream_t s);
 
 void set_error(const char* fmt, ...);
 

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "compact_device.h"
 #include "ctx_internal.h"
 
 using namespace nerf;
@@ -214,6 +215,14 @@ struct Pass {              // one network evaluated at P = N*S points with every
     bool blocked = false;
     float* feat_blk = nullptr;
     int voff = 0;            // column of gamma(d) in vcat
+    // The step with an occupancy grid (nerf_train_step_occ): P is the number of KEPT points, index [P] their ids in the [N, S]
+    // grid (increasing), index_count the same number on the device. Everything above is compact, in list order; only the
+    // network's output and its gradient also exist per sample: raw_full / d_raw_full [N * S rows], where compositing, the loss
+    // and raw2outputs' backward run (skipped rows: zeros), and noise_masked [N * S], the pass's sigma noise at the kept samples.
+    const int* index = nullptr;
+    const int* index_count = nullptr;
+    float *raw_full = nullptr, *d_raw_full = nullptr, *noise_masked = nullptr;
+    const float* noise_in = nullptr;
 };
 
 size_t pass_floats(const PackedNet& net, int64_t P) {
@@ -384,6 +393,16 @@ hipError_t embed_inputs(Pass& ps, const float* rays, int ray_ld, float* z, int L
     for (int i = 1; i < a.D && first < 0; ++i)
         if ((net.skip_in_mask >> i) & 1) first = i;
     if (ps.blocked) first = -1;      // (blocked passes: the skip layers' gamma(x) IS layer 0's buffer, carve_pass)
+    if (ps.index) {      // the listed points' rows at the list slots, and the pass's noise at the listed points
+        hipError_t e = launch_occ_embed(rays, ray_ld, z, ps.index, ps.P, ps.S, Lx, Lv, ps.in[0], ps.in_ld[0],
+                                        first > 0 ? ps.in[first] : nullptr, first > 0 ? ps.in_ld[first] : 0, ps.vcat, ps.vcat_ld,
+                                        ps.voff, ps.blocked ? 1 : 0, ps.noise_in, ps.noise_in ? ps.noise_masked : nullptr, s);
+        for (int i = first + 1; first > 0 && i < a.D && e == hipSuccess; ++i)
+            if ((net.skip_in_mask >> i) & 1)
+                e = launch_occ_embed(rays, ray_ld, z, ps.index, ps.P, ps.S, Lx, 0, ps.in[i], ps.in_ld[i], nullptr, 0, nullptr, 0, 0,
+                                     0, nullptr, nullptr, s);
+        return e;
+    }
     hipError_t e = pro ? launch_train_prologue(rays, ray_ld, ps.N, ps.S, pro->lindisp, pro->t_rand, z, Lx, Lv, ps.in[0],
                                                ps.in_ld[0], first > 0 ? ps.in[first] : nullptr,
                                                first > 0 ? ps.in_ld[first] : 0, ps.vcat, ps.vcat_ld, ps.voff, pro->zero,
@@ -419,7 +438,10 @@ int forward_pass_fused(Pass& ps, const float* rays, int ray_ld, float* z, hipStr
     m.rays = rays;
     m.ray_ld = ray_ld;
     m.z_vals = z;
-    m.out = ps.raw;
+    m.out = ps.index ? ps.raw_full : ps.raw;      // (the output row is written at the listed point)
+    m.index = ps.index;
+    m.index_count = ps.index_count;
+    const int mode = ps.index ? kInputRaysIndexed : kInputRays;
     m.store = 1;
     for (int i = 0; i < a.D; ++i) {
         m.st.h[i] = ps.h[i];
@@ -449,7 +471,7 @@ int forward_pass_fused(Pass& ps, const float* rays, int ray_ld, float* z, hipStr
         for (int i = 0; i < a.D; ++i) m.st.mask[i] = ps.mask[i];
         m.st.mask_hv = ps.mask_hv;
         TrainTimer timer(ps.ctx, s, 0, ps.P);
-        HIP_TRY(launch_mlp_h2(m, kInputRays, s));
+        HIP_TRY(launch_mlp_h2(m, mode, s));
         return NERF_OK;
     }
     if (net.f32_dirty) {
@@ -457,7 +479,7 @@ int forward_pass_fused(Pass& ps, const float* rays, int ray_ld, float* z, hipStr
         if (rc != NERF_OK) return rc;
     }
     TrainTimer timer(ps.ctx, s, 0, ps.P);
-    HIP_TRY(launch_mlp(m, kInputRays, s));
+    HIP_TRY(launch_mlp(m, mode, s));
     return NERF_OK;
 }
 
@@ -497,6 +519,8 @@ int forward_pass(Pass& ps, const float* rays, int ray_ld, float* z, hipStream_t 
         GemmRows go{hl, hl_ld, wt + out.w_off, out.out, ps.raw, ps.C, ps.P, out.out, a.W, prm + out.b_off, 0, nullptr, 0, 0};
         HIP_TRY(launch_gemm_rows(go, s));                                                  // nerf.py:109
     }
+    // (with a grid the chain ran on the compact rows: its output goes to the listed points' rows)
+    if (ps.index) HIP_TRY(launch_occ_scatter_rows(ps.raw, ps.index, ps.P, ps.C, ps.raw_full, s));
     return NERF_OK;
 }
 
@@ -1148,19 +1172,46 @@ int ensure_tape(nerf_ctx* c, size_t bytes) {
     return NERF_OK;
 }
 
-}  // namespace
+// One pass of the step with an occupancy grid, up to the network's output: the list of kept points (classify, scan,
+// scatter: launch_occ_compact, which also zeroes the skipped rows of raw_full and counts the pass in the grid's statistics),
+// its length to the host - the one wait of the pass: every launch behind it is sized by the kept count, like a dense pass of
+// that many points -, then the encodings at the list slots and the forward pass over the list.
+int forward_pass_occ(Pass& ps, OccCompact& oc, const float* rays, int ray_ld, float* z, hipStream_t s) {
+    oc.z = z;
+    oc.S = ps.S;
+    oc.raw = ps.raw_full;
+    oc.C = ps.C;
+    HIP_TRY(launch_occ_compact(oc, s));
+    int kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, oc.count, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (ps.noise_in) HIP_TRY(hipMemsetAsync(ps.noise_masked, 0, (size_t)ps.N * ps.S * sizeof(float), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (kept < ps.N || kept > ps.N * ps.S) {      // (the last sample of every ray is always kept)
+        set_error("internal: the occupancy list of a training pass has %d entries for %lld rays x %d samples", kept,
+                  (long long)ps.N, ps.S);
+        return NERF_E_INVALID;
+    }
+    ps.P = kept;
+    ps.index = oc.index;
+    ps.index_count = oc.count;
+    return forward_pass(ps, rays, ray_ld, z, s);
+}
 
-extern "C" {
+// d raw of the kept points into list order, where the backward kernels read it
+int gather_d_raw(Pass& ps, hipStream_t s) {
+    HIP_TRY(launch_occ_gather_rows(ps.d_raw_full, ps.index, ps.P, ps.dC, ps.d_raw, s));
+    return NERF_OK;
+}
 
-int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
+int train_step(nerf_ctx* c, const nerf_train_args* r, nerf_occupancy* occ, const char* who) {
     if (!c || !r || !r->rays || !r->target || r->n_rays <= 0) {
-        set_error("nerf_train_step: invalid argument");
+        set_error("%s: invalid argument", who);
         return NERF_E_INVALID;
     }
     const StepInputs in{r->rays, r->n_rays, r->ray_stride, r->N_samples, r->N_importance, r->slot_coarse, r->slot_fine,
                         r->lindisp, r->white_bkgd, r->perturb, r->t_rand, r->u_rand, r->noise0, r->noise, r->z_vals_fine_in};
     PackedNet *ncp = nullptr, *nfp = nullptr;
-    int rc = check_step_inputs(c, in, "nerf_train_step", &ncp, &nfp);
+    int rc = check_step_inputs(c, in, who, &ncp, &nfp);
     if (rc != NERF_OK) return rc;
     const int64_t N = r->n_rays;
     const int Sc = r->N_samples, Si = r->N_importance, Sf = Sc + Si;
@@ -1183,8 +1234,17 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
     const int n_slices = kTnSlices;
     const size_t part_floats = tn_part_floats(nc);
     const size_t small = (size_t)N * (Sc * 2 + (Si ? Si + Sf * 2 : 0) + 24) + 8192;
+    // with a grid: the scratch of classify + compact (sized for the larger pass, reused in stream order) and per pass the
+    // per-sample raw / d raw (<= 32 + 32 floats per point budgeted as in pass_floats) and the masked noise
+    const size_t occ_pts = occ ? (size_t)(Si ? Pf : Pc) : 0, occ_nb = occ ? (size_t)compact_blocks((int64_t)occ_pts) : 0;
+    auto occ_pass_floats = [&](const PackedNet& net, int64_t P) { return (size_t)P * (2 * (size_t)(net.out_ch > 8 ? net.out_ch : 8) + 1) + 256; };
+    const size_t occ_floats = occ ? occ_nb * 32 + occ_nb + occ_pts + 4096 + occ_pass_floats(nc, Pc) + (Si ? occ_pass_floats(nf, Pf) : 0) : 1;
+    if (occ && (int64_t)occ_pts > 0x7fffffffLL) {
+        set_error("%s: n_rays * (N_samples + N_importance) must stay below 2^31 with an occupancy grid", who);
+        return NERF_E_INVALID;
+    }
     rc = ensure_workspace(c, arena_bytes({small, pass_floats(nc, Pc), Si ? pass_floats(nf, Pf) : 1, part_floats,
-                                          (size_t)n_slices * 512}) +
+                                          (size_t)n_slices * 512, occ_floats}) +
                                  (1 << 20));
     if (rc != NERF_OK) return rc;
     Arena ar(c->ws);
@@ -1216,7 +1276,71 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
     unsigned* ticket = zero_block + 2 * kBwdMaxSlots;
     float* rgb_last = Si ? rgb_f : rgb_c;
 
-    if (fused_glue) {
+    if (occ) {
+        // ---- the step with an occupancy grid (nerf_mi355x.h, "Occupancy grid"): the network runs over the kept
+        //      points of each pass, compositing / loss / raw2outputs' backward over every sample, the backward pass and the
+        //      weight gradients over the kept points again ----
+        OccCompact oc{};
+        oc.g = occ->g;
+        oc.rays = r->rays;
+        oc.ray_ld = r->ray_stride;
+        oc.N = N;
+        oc.keep_words = (unsigned long long*)ar.take(occ_nb * 32);
+        oc.block_counts = (int*)ar.take(occ_nb + 1);
+        oc.index = (int*)ar.take(occ_pts + 1);
+        oc.count = (int*)ar.take(64);
+        oc.stats = occ->d_stats;
+        // (one list buffer serves both passes in turn, so the coarse pass's list is copied aside before the fine pass's
+        // classification overwrites it: its backward pass runs after the fine forward pass)
+        int* index_c = Si ? (int*)ar.take((size_t)Pc + 1) : oc.index;
+        auto sparse_buffers = [&](Pass& ps, const float* noise) {
+            ps.raw_full = ar.take((size_t)ps.N * ps.S * ps.C);
+            ps.d_raw_full = ar.take((size_t)ps.N * ps.S * ps.dC);
+            ps.noise_in = noise;
+            ps.noise_masked = noise ? ar.take((size_t)ps.N * ps.S) : nullptr;
+        };
+        sparse_buffers(pc, r->noise0);
+        if (Si) sparse_buffers(pf, r->noise);
+        HIP_TRY(hipMemsetAsync(zero_block, 0, (2 * kBwdMaxSlots + 32) * sizeof(unsigned), s));
+        HIP_TRY(launch_stratified(r->rays, r->ray_stride, N, Sc, r->lindisp, r->perturb ? r->t_rand : nullptr, z_c, s));
+        if ((rc = forward_pass_occ(pc, oc, r->rays, r->ray_stride, z_c, s))) return rc;
+        if (Si) {
+            HIP_TRY(hipMemcpyAsync(index_c, oc.index, (size_t)pc.P * sizeof(int), hipMemcpyDeviceToDevice, s));
+            pc.index = index_c;
+            pc.index_count = nullptr;      // (the count word is the fine pass's from here on; the host has pc.P)
+            HIP_TRY(launch_train_mid(pc.raw_full, pc.C, z_c, r->rays + 3, r->ray_stride, pc.noise_masked, r->white_bkgd, N, Sc,
+                                     rgb_c, w_c, r->perturb ? r->u_rand : nullptr, Si, z_f, s));
+            if (r->z_vals_fine_in)
+                HIP_TRY(hipMemcpyAsync(z_f, r->z_vals_fine_in, (size_t)N * Sf * sizeof(float), hipMemcpyDeviceToDevice, s));
+            if ((rc = forward_pass_occ(pf, oc, r->rays, r->ray_stride, z_f, s))) return rc;
+        }
+        Pass& pl = Si ? pf : pc;
+        TrainEpilogue e{};
+        e.rays_d = r->rays + 3;
+        e.d_ld = r->ray_stride;
+        e.target = r->target;
+        e.N = N;
+        e.white_bkgd = r->white_bkgd;
+        e.raw_l = pl.raw_full; e.C_l = pl.C; e.z_l = Si ? z_f : z_c; e.noise_l = pl.noise_masked; e.S_l = Si ? Sf : Sc;
+        e.d_raw_l = pl.d_raw_full;
+        e.dC_l = pl.dC;
+        if (Si) {
+            e.raw_c = pc.raw_full; e.C_c = pc.C; e.z_c = z_c; e.noise_c = pc.noise_masked; e.S_c = Sc; e.d_raw_c = pc.d_raw_full;
+            e.dC_c = pc.dC; e.rgb_c = rgb_c;
+        }
+        e.out_rgb = r->rgb_map ? r->rgb_map : rgb_last;
+        e.out_rgb0 = Si ? r->rgb0 : nullptr;
+        e.part = loss_part;
+        e.ticket = ticket;
+        e.loss_dev = loss_dev;
+        e.out_loss = r->loss;
+        e.out_stats = r->stats;
+        HIP_TRY(launch_train_epilogue(e, s));
+        if ((rc = gather_d_raw(pc, s))) return rc;
+        if (Si && (rc = gather_d_raw(pf, s))) return rc;
+        if ((rc = backward_phase(pc, pf, Si, shared, sc, false, s))) return rc;
+        HIP_TRY(hipMemcpyAsync(occ->h_stats, occ->d_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    } else if (fused_glue) {
         // ---- forward (render(..., retraw=True, **render_kwargs_train), nerf.ipynb:1258), the small stages fused ----
         if ((rc = forward_phase(pc, pf, in, r->rays, r->noise0, z_c, w_c, rgb_c, z_f, zero_block, s))) return rc;
         // ---- raw2outputs of the last pass, loss = img2mse(rgb, target) [+ img2mse(rgb0, target)] (nerf.ipynb:1262-1272),
@@ -1290,7 +1414,7 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
     bool mirrored = false;
     if (r->apply_update) {
         if (r->step < 1) {
-            set_error("nerf_train_step: step must be the 1-based Adam step count");
+            set_error("%s: step must be the 1-based Adam step count", who);
             return NERF_E_INVALID;
         }
         PackedNet* both[2] = {&nc, &nf};
@@ -1299,11 +1423,29 @@ int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) {
     }
     if (!mirrored) HIP_TRY(mirror_loose(c, s));
     if (fell_back) {
-        set_error("nerf_train_step: the fp16-pair kernels' output-scale bound was loose in an earlier step (some activations "
-                  "kept fewer than 24 bits with these weights); training continues on the fp32 kernels");
+        set_error("%s: the fp16-pair kernels' output-scale bound was loose in an earlier step (some activations "
+                  "kept fewer than 24 bits with these weights); training continues on the fp32 kernels", who);
         return NERF_W_PRECISION_FALLBACK;
     }
     return NERF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nerf_train_step(nerf_ctx* c, const nerf_train_args* r) { return train_step(c, r, nullptr, "nerf_train_step"); }
+
+int nerf_train_step_occ(nerf_ctx* c, const nerf_train_args* r, nerf_occupancy* occ) {
+    if (!occ) {
+        set_error("nerf_train_step_occ: the occupancy grid is NULL (nerf_train_step is the step without one)");
+        return NERF_E_INVALID;
+    }
+    if (!c || occ->ctx != c) {
+        set_error("nerf_train_step_occ: the occupancy grid belongs to another context");
+        return NERF_E_INVALID;
+    }
+    return train_step(c, r, occ, "nerf_train_step_occ");
 }
 
 int nerf_train_forward(nerf_ctx* c, const nerf_train_forward_args* r) {

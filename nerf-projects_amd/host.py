@@ -1384,15 +1384,24 @@ def save_checkpoint(path, global_step, network_fn, network_fine, optimizer):
 def train_on_batch(H, W, K, batch_rays, target_s, optimizer, chunk=1024 * 32, ndc=True, near=0., far=1.,
                    use_viewdirs=False, network_fn=None, network_query_fn=None, N_samples=64, N_importance=0,
                    network_fine=None, perturb=0., raw_noise_std=0., white_bkgd=False, lindisp=False, pytest=False,
-                   apply_update=True, _packed_rays=None, _z_vals_fine=None, **unused):
+                   apply_update=True, _packed_rays=None, _z_vals_fine=None, occupancy=None, **unused):
     """One iteration of the reference's training loop body (nerf.ipynb:1258-1282) on the GPU:
     ``render(H, W, K, rays=batch_rays, retraw=True, **render_kwargs_train)``, ``img_loss =
     img2mse(rgb, target_s)`` (``+ img2mse(rgb0, target_s)``), ``loss.backward()``, ``optimizer.step()``.
     Pass the same ``render_kwargs_train`` (plus ``near``/``far``) as keyword arguments. Returns
-    ``{'loss','img_loss','psnr'[, 'img_loss0','psnr0'], 'rgb'[, 'rgb0']}`` (tensors on the device)."""
+    ``{'loss','img_loss','psnr'[, 'img_loss0','psnr0'], 'rgb'[, 'rgb0']}`` (tensors on the device).
+
+    ``occupancy`` (an :class:`OccupancyGrid`) runs the network of both passes only at the samples the grid keeps - the rule
+    of ``render_rays(..., occupancy=occ)`` - and sends gradients through those alone; a skipped sample's alpha is exactly 0
+    even with ``raw_noise_std > 0`` (include/nerf_mi355x.h, "Occupancy grid"). ``occ.stats()`` counts the step's passes."""
     if not isinstance(network_fn, NeRF) or (network_fine is not None and not isinstance(network_fine, NeRF)):
         raise TypeError("train_on_batch needs this package's NeRF models")
     ctx = network_fn.ctx
+    occ_handle = None
+    if occupancy is not None:
+        if not hasattr(occupancy, "_handle_for") or not hasattr(occupancy, "refresh"):
+            raise TypeError(f"train_on_batch: occupancy must be an OccupancyGrid, not {type(occupancy).__name__}")
+        occ_handle = occupancy._handle_for(ctx)
     if _packed_rays is not None:      # (tests: a ray record exactly as the reference's render() packed it, e.g. NDC-warped)
         packed = _dev(_packed_rays, ctx).contiguous()
     else:
@@ -1459,7 +1468,10 @@ def train_on_batch(H, W, K, batch_rays, target_s, optimizer, chunk=1024 * 32, nd
         keep.append(zin)
         a.z_vals_fine_in = zin.data_ptr()
     a.stream = ctx.stream().value
-    check(ctx.lib.nerf_train_step(ctx.handle, C.byref(a)))
+    if occ_handle is not None:
+        check(ctx.lib.nerf_train_step_occ(ctx.handle, C.byref(a), occ_handle))
+    else:
+        check(ctx.lib.nerf_train_step(ctx.handle, C.byref(a)))
     out = {'img_loss': stats[0], 'psnr': stats[3], 'rgb': rgb, 'loss': stats[2]}
     if Si > 0:
         out.update(img_loss0=stats[1], psnr0=stats[4], rgb0=rgb0)

@@ -4,7 +4,8 @@ An :class:`OccupancyGrid` is one bit per cell of the lattice ``density_grid`` ev
 ``reso - 1`` cells). ``render_rays(..., occupancy=occ)`` / ``render(..., occupancy=occ)`` (and ``render_path`` through
 ``render_kwargs_test["occupancy"]``) evaluate the network only at samples whose cell is occupied - plus the last sample
 of every ray, always - and write zeros to ``raw`` everywhere else; the semantics are stated in include/nerf_mi355x.h,
-"Occupancy grid". The grid is a snapshot of the networks it was built from: rebuild it after training steps.
+"Occupancy grid". ``train_on_batch(..., occupancy=occ)`` trains through the kept samples alone. The grid is a snapshot
+of the networks it was built from: :meth:`OccupancyGrid.refresh` re-evaluates it in place every so many training steps.
 """
 import ctypes as C
 
@@ -29,14 +30,7 @@ class OccupancyGrid:
         self.ctx = ctx
         self.c1, self.c2, self.reso = c1, c2, reso
         self.outside, self.threshold, self.dilate = outside, float(threshold), int(dilate)
-        a = OccupancyArgs()
-        a.c1[:], a.c2[:], a.reso[:] = c1, c2, reso
-        a.n_lattices = len(lattices)
-        ptrs = (C.c_void_p * max(len(lattices), 1))(*[t.data_ptr() for t in lattices])
-        a.sigma = C.cast(ptrs, C.POINTER(C.c_void_p))
-        a.cell_mask = 0 if cell_mask is None else cell_mask.data_ptr()
-        a.threshold, a.dilate, a.outside = self.threshold, self.dilate, _OUTSIDE[outside]
-        a.stream = ctx.stream().value
+        a, _keep = self._args(lattices, cell_mask)
         handle = C.c_void_p()
         self._handle = None
         check(ctx.lib.nerf_occupancy_create(ctx.handle, C.byref(a), C.byref(handle)))      # (synchronises the stream)
@@ -44,6 +38,36 @@ class OccupancyGrid:
         n = C.c_int64()
         check(ctx.lib.nerf_occupancy_cells(self._handle, None, C.byref(n), None))
         self.n_occupied = n.value
+
+    def _args(self, lattices, cell_mask):
+        a = OccupancyArgs()
+        a.c1[:], a.c2[:], a.reso[:] = self.c1, self.c2, self.reso
+        a.n_lattices = len(lattices)
+        ptrs = (C.c_void_p * max(len(lattices), 1))(*[t.data_ptr() for t in lattices])
+        a.sigma = C.cast(ptrs, C.POINTER(C.c_void_p))
+        a.cell_mask = 0 if cell_mask is None else cell_mask.data_ptr()
+        a.threshold, a.dilate, a.outside = self.threshold, self.dilate, _OUTSIDE[self.outside]
+        a.stream = self.ctx.stream().value
+        return a, ptrs
+
+    def refresh(self, networks):
+        """Re-evaluates the grid in place from the networks as they are now: ``density_grid`` of each on the grid's own
+        lattice, then the cells by the grid's own ``threshold`` / ``dilate`` / ``outside`` - afterwards ``cells()`` equals
+        those of a fresh :meth:`build` with the same arguments. The handle and the ``stats()`` counters survive;
+        ``n_occupied`` is updated. Returns ``self``."""
+        nets = [networks] if isinstance(networks, NeRF) else list(networks)
+        if not nets or not all(isinstance(n, NeRF) for n in nets):
+            raise TypeError("OccupancyGrid.refresh needs this package's NeRF (or a list of them)")
+        if any(n.ctx is not self.ctx for n in nets):
+            raise ValueError("OccupancyGrid.refresh: the networks live on another device than the grid")
+        with torch.no_grad():
+            lattices = [density_grid(n, self.c1, self.c2, self.reso) for n in nets]
+        a, _keep = self._args(lattices, None)
+        check(self.ctx.lib.nerf_occupancy_refresh(self._handle, C.byref(a)))      # (synchronises the stream)
+        n = C.c_int64()
+        check(self.ctx.lib.nerf_occupancy_cells(self._handle, None, C.byref(n), None))
+        self.n_occupied = n.value
+        return self
 
     def __del__(self):
         if getattr(self, "_handle", None) is not None:
