@@ -489,13 +489,12 @@ struct GradBatch {
 hipError_t launch_grad_batch(GradBatch& b, bool wide, float* part, size_t part_floats, float* dbp, size_t dbp_floats,
                              hipStream_t s, bool pair = false);
 hipError_t launch_grad_batch_narrow_pair(GradBatch& b, float* part, size_t part_floats, float* dbp, size_t dbp_floats, hipStream_t s);
-// a rider row (GradJob::y) needs the LDS-prefetch kernel; its sums are added up into (dW_row [n_end - n_begin], db_row)
+// a rider row (GradJob::y) of a pair batch; its sums are added up into (dW_row [n_end - n_begin], db_row)
 struct GradRider {
     int job;               // index in the batch
     float* dW; float* db;
     GradExps ex;
 };
-bool grad_pair_takes_riders();
 hipError_t launch_grad_batch_with_rider(GradBatch& b, const GradRider& r, float* part, size_t part_floats, float* dbp,
                                         size_t dbp_floats, hipStream_t s);
 hipError_t launch_embed_train(const float* rays, int ray_ld, const float* z, int64_t P, int S, int Lx, int Lv,

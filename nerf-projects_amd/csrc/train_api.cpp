@@ -37,14 +37,12 @@ int ensure_train_state(nerf_ctx* c, PackedNet& net) {
     return NERF_OK;
 }
 
-bool gemm_forward_requested();
-
 // The master parameters changed (first training call on a slot, optimiser step): everything derived from them is stale
 // and is rebuilt by whoever needs it next - the fp32 kernels' stream (refresh_f32), the fp16-pair kernel's equalised
 // stream (refresh_h2), the backward-data streams (refresh_bwd). Only the layer-by-layer forward GEMMs' W^T copies are
 // made here.
 int mark_params_changed(PackedNet& net, hipStream_t s, bool stepped) {
-    if (gemm_forward_requested() || net.arch.W != kWidth)      // W^T is the B operand of the layer-by-layer forward GEMMs only
+    if (net.arch.W != kWidth)      // W^T is the B operand of the layer-by-layer forward GEMMs only
         for (const LinearDesc& d : net.linears)
             HIP_TRY(launch_transpose(net.d_params + d.w_off, d.out, d.in, net.train.d_wt + d.w_off, s));
     if (stepped) {
@@ -213,6 +211,11 @@ struct Pass {              // one network evaluated at P = N*S points with every
     // h[i], feat_blk (the feature vector; vcat then holds gamma(d) alone, voff = 0), dz[i], g_a (d feature), g_hv. Only when every
     // producer and consumer is one of the fp16-pair kernels that know the layout (set_units).
     bool blocked = false;
+    // The route of the fused backward's weight gradients, decided once (set_units): the 256-column jobs on the fp16 pipe; all
+    // jobs in batched launches rather than one grad_linear per layer; the view layer's job on the fp16 pipe too (the size of
+    // the feature vector is known: the fp16-pair forward pass tracked it, kBwdMaxFeatValue); alpha_linear's one row riding in
+    // feature_linear's job (GradJob::y) rather than a launch of its own.
+    bool pair_dw = false, batched = false, feat_known = false, alpha_rides = false;
     float* feat_blk = nullptr;
     int voff = 0;            // column of gamma(d) in vcat
     // The step with an occupancy grid (nerf_train_step_occ): P is the number of KEPT points, index [P] their ids in the [N, S]
@@ -318,60 +321,41 @@ void carve_pass(Arena& ar, Pass& ps) {
     }
 }
 
-// The training forward pass. NERF_TRAIN_GEMM_FORWARD=1 in the environment (or a network the fused kernel's store
-// path does not cover) selects the layer-by-layer GEMM chain below; the default is ONE launch of the fused fp32
-// encode+MLP kernel (mlp_kernel.hip, STORE variant: weights streamed by LDS-DMA, activations chained in registers) that
+// The training forward pass. A network the fused kernel's store path does not cover (W != 256) runs the layer-by-layer
+// GEMM chain below; every other one ONE launch of the fused fp32 encode+MLP kernel (mlp_kernel.hip, STORE variant: weights streamed by LDS-DMA, activations chained in registers) that
 // also writes what autograd would keep - every trunk layer's post-ReLU output, the feature vector, the view layer's
 // output - into the same buffers the GEMM chain fills, so the backward pass below is unchanged. Same arithmetic class
 // (v_mfma_f32_32x32x2_f32, fp32 accumulate), a different order of the 256 products of a sum.
 // With the context in NERF_PRECISION_F16X2 (the default) that launch is the fp16-pair kernel's STORE variant
 // (mlp_kernel_h2.hip: the contractions at 3 fp16 MFMAs per term, results as close to fp64 as the fp32 chain's), on a stream
-// converted from the plain parameters; NERF_TRAIN_FORWARD=f32 keeps the fp32 kernel. The backward pass is fp32 either way.
-bool pair_forward_allowed() {
-    static const bool on = [] {
-        const char* e = getenv("NERF_TRAIN_FORWARD");
-        return !(e && (e[0] == 'f' || e[0] == 'F') && e[1] == '3');
+// converted from the plain parameters. The wide weight-gradient jobs follow the context's precision as well (the fp16 pipe:
+// train_dw_kernel.hip, grad_batch_pair_dma_kernel), and so does backward-data (mlp_bwd_kernel_h2.hip) when the forward pass
+// ran on the fp16-pair kernel.
+//
+// The environment switches of the step, read once per process. The first three keep one stage on its fp32 kernel while the
+// context stays in F16X2 (bench.py, bench_train.py, nerf_mi355x.h); the other three select the routes that
+// test_train_glue_is_bit_identical compares the shipped ones with.
+struct TrainSwitches {
+    bool pair_forward;      // NERF_TRAIN_FORWARD=f32 clears it: the forward pass on the fp32 kernel
+    bool pair_dw;           // NERF_TRAIN_DW=f32: the wide weight-gradient jobs on the fp32 kernel
+    bool pair_bwd;          // NERF_TRAIN_BWD=f32: backward-data on the fp32 kernel (on the same - equalised - transposed weights)
+    bool narrow_pair;       // NERF_TRAIN_NARROW=f32: the gamma(x) / gamma(d) columns' weight gradients of a blocked pass on the fp32 kernel
+    bool blocked;           // NERF_TRAIN_BLOCKED=0: the kept activations row-major (Pass::blocked)
+    // NERF_TRAIN_GLUE=legacy keeps the step's small stages as launches of their own (stratified depths, encodings, compositing,
+    // resampling, losses, compositing backward: the stage kernels of ray_kernels.hip / train_kernels.hip) instead of the fused
+    // launches, which call the same device functions and are bit-identical
+    bool glue_legacy;
+};
+bool env_f32(const char* e) { return e && (e[0] == 'f' || e[0] == 'F') && e[1] == '3'; }
+bool env_zero(const char* e) { return e && *e == '0'; }
+const TrainSwitches& switches() {
+    static const TrainSwitches sw = [] {
+        const char* glue = getenv("NERF_TRAIN_GLUE");
+        return TrainSwitches{!env_f32(getenv("NERF_TRAIN_FORWARD")), !env_f32(getenv("NERF_TRAIN_DW")),
+                             !env_f32(getenv("NERF_TRAIN_BWD")),     !env_f32(getenv("NERF_TRAIN_NARROW")),
+                             !env_zero(getenv("NERF_TRAIN_BLOCKED")), glue && (glue[0] == 'l' || glue[0] == 'L')};
     }();
-    return on;
-}
-
-// The wide weight-gradient jobs follow the context's precision as well: NERF_PRECISION_F16X2 runs them on the fp16 pipe
-// (train_dw_kernel.hip, grad_batch_pair_kernel); NERF_TRAIN_DW=f32 keeps the fp32 kernel.
-bool pair_dw_allowed() {
-    static const bool on = [] {
-        const char* e = getenv("NERF_TRAIN_DW");
-        return !(e && (e[0] == 'f' || e[0] == 'F') && e[1] == '3');
-    }();
-    return on;
-}
-
-// Backward-data follows too (mlp_bwd_kernel_h2.hip) when the forward pass ran on the fp16-pair kernel; NERF_TRAIN_BWD=f32
-// keeps the fp32 kernel (on the same - equalised - transposed weights).
-bool pair_bwd_allowed() {
-    static const bool on = [] {
-        const char* e = getenv("NERF_TRAIN_BWD");
-        return !(e && (e[0] == 'f' || e[0] == 'F') && e[1] == '3');
-    }();
-    return on;
-}
-
-// NERF_TRAIN_GLUE=legacy keeps the step's small stages as launches of their own (stratified depths, encodings, compositing,
-// resampling, losses, compositing backward: the stage kernels of ray_kernels.hip / train_kernels.hip) - the A/B switch of
-// the fused launches, which call the same device functions and are bit-identical (tests: test_train_glue_is_bit_identical)
-bool glue_legacy() {
-    static const bool on = [] {
-        const char* e = getenv("NERF_TRAIN_GLUE");
-        return e && (e[0] == 'l' || e[0] == 'L');
-    }();
-    return on;
-}
-
-bool gemm_forward_requested() {
-    static const bool on = [] {
-        const char* e = getenv("NERF_TRAIN_GEMM_FORWARD");
-        return e && *e && *e != '0';
-    }();
-    return on;
+    return sw;
 }
 
 // gamma(x) into layer 0's input and into every concat buffer, gamma(dir) into the view concat buffer: one launch for the
@@ -487,7 +471,7 @@ int forward_pass(Pass& ps, const float* rays, int ray_ld, float* z, hipStream_t 
     const PackedNet& net = *ps.net;
     const nerf_arch& a = net.arch;
     // (the fused kernels keep 256-wide rows: a narrower network, which they evaluate zero-padded, trains on the chain below)
-    if (!gemm_forward_requested() && ps.C == net.out_ch && a.D <= kMaxDepth && a.W == kWidth)
+    if (ps.C == net.out_ch && a.D <= kMaxDepth && a.W == kWidth)
         return forward_pass_fused(ps, rays, ray_ld, z, s, pro);
     const float* wt = net.train.d_wt;
     const float* prm = net.d_params;
@@ -577,133 +561,100 @@ int grad_linear(const PackedNet& net, const LinearDesc& d, const float* dY, int 
     return NERF_OK;
 }
 
-// The backward pass with the data gradients from ONE launch of nerf_mlp_bwd_kernel (mlp_kernel.hip): d raw -> the
-// gradient at every pre-activation, transposed weights streamed, the running gradient chained in registers, masks read
-// from the activations the forward pass kept. The weight gradients stay what they were: one gemm_tn per Linear
-// (dW = dZ^T X, slices summed in a fixed order), now all issued after that launch. NERF_TRAIN_GEMM_BACKWARD=1 keeps the
-// layer-by-layer chain below (also used for networks without view directions).
-bool gemm_backward_requested() {
-    static const bool on = [] {
-        const char* e = getenv("NERF_TRAIN_GEMM_BACKWARD");
-        return e && *e && *e != '0';
-    }();
-    return on;
-}
-
-int backward_pass_fused_noviews(Pass& ps, const TnScratch& sc, hipStream_t s);
-
-// NERF_TRAIN_NARROW=f32: the gamma(x) / gamma(d) columns' weight gradients of a blocked pass on the fp32 kernel (A/B)
-bool narrow_pair_wanted() {
-    static const bool on = [] {
-        const char* e = getenv("NERF_TRAIN_NARROW");
-        return !(e && (e[0] == 'f' || e[0] == 'F') && e[1] == '3');
-    }();
-    return on;
-}
-
-// The gamma columns' jobs on the fp16 pipe (grad_batch_narrow_pair_kernel). A workgroup is a slice (its four waves share its
-// points and add their sums up in LDS): as many as fill the chip's 256 workgroups once over all jobs
-int narrow_pair_batch(Pass& ps, const TnScratch& sc, GradBatch& narrow_pair, hipStream_t s) {
-    if (narrow_pair.n == 0) return NERF_OK;
-    int n_slices = 256 / narrow_pair.n;
-    const int64_t cap = (ps.P + 255) / 256;
-    if (n_slices > cap) n_slices = (int)cap;
-    if (n_slices < 1) n_slices = 1;
-    int64_t pps = (ps.P + n_slices - 1) / n_slices;
-    pps = (pps + 127) / 128 * 128;
-    narrow_pair.n_slices = n_slices;
-    narrow_pair.pts_per_slice = pps;
-    narrow_pair.P = ps.P;
-    narrow_pair.accumulate = sc.accumulate;
-    TrainTimer timer(ps.ctx, s, 3, ps.P);
-    HIP_TRY(launch_grad_batch_narrow_pair(narrow_pair, sc.part, sc.part_floats, sc.dbp, sc.dbp_floats, s));
-    return NERF_OK;
-}
-
-int backward_pass_fused(Pass& ps, const TnScratch& sc, hipStream_t s) {
+// The data gradients of the fused backward pass from ONE launch of nerf_mlp_bwd_kernel (mlp_kernel.hip; the fp16-pair one:
+// mlp_bwd_kernel_h2.hip, on the equalised transposed weights, the masks as bits): d raw -> the gradient at every
+// pre-activation, transposed weights streamed, the running gradient chained in registers, masks read from the activations
+// the forward pass kept. Without view directions (use_viewdirs=False: output_linear on the trunk, nerf.py:109) the head's
+// transpose is the chain's first chunk (the fp32 kernel: vector products).
+int backward_data(Pass& ps, hipStream_t s) {
     const PackedNet& net = *ps.net;
     const nerf_arch& a = net.arch;
-    if (!a.use_viewdirs) return backward_pass_fused_noviews(ps, sc, s);
-    const LinearDesc &views = net.linears[a.D], &feat = net.linears[a.D + 1], &alpha = net.linears[a.D + 2],
-                     &rgb = net.linears[a.D + 3];
-    float* d_feat = ps.g_a;      // [P, W]
-    const bool eq = ps.eq;
-    {
-        const int rc = refresh_bwd(const_cast<PackedNet&>(net), eq, ps.pair_backward, s);
-        if (rc != NERF_OK) return rc;
-    }
+    const int rc = refresh_bwd(const_cast<PackedNet&>(net), ps.eq, ps.pair_backward, s);
+    if (rc != NERF_OK) return rc;
     MlpBwdLaunch b{};
     b.stream = net.train.d_stream_bwd;
     b.n_chunks = net.train.n_chunks_bwd;
-    b.bias = eq ? net.d_bias_h2 : net.d_bias;      // (the rgb / alpha rows of the network the pass runs on)
+    b.bias = ps.eq ? net.d_bias_h2 : net.d_bias;      // (the rgb / alpha rows of the network the pass runs on)
     b.n_bias_tiles = net.n_bias_tiles;
     b.D = a.D;
     b.n_points = ps.P;
     b.d_raw = ps.d_raw;
     b.C = ps.C;
-    b.use_viewdirs = 1;
+    b.use_viewdirs = a.use_viewdirs ? 1 : 0;
     for (int i = 0; i < a.D; ++i) {
         b.fwd.h[i] = ps.h[i];
         b.fwd.h_ld[i] = ps.h_ld[i];
         b.out.h[i] = ps.dz[i];
         b.out.h_ld[i] = a.W;
     }
-    b.fwd.hv = ps.hv;
-    b.fwd.hv_ld = views.out;
-    b.out.hv = ps.g_hv;
-    b.out.hv_ld = views.out;
-    b.out.feat = d_feat;
-    b.out.feat_ld = a.W;
+    if (a.use_viewdirs) {
+        const int hv_ld = net.linears[a.D].out;
+        b.fwd.hv = ps.hv;
+        b.fwd.hv_ld = hv_ld;
+        b.out.hv = ps.g_hv;
+        b.out.hv_ld = hv_ld;
+        b.out.feat = ps.g_a;      // d feature, [P, W]
+        b.out.feat_ld = a.W;
+    } else {
+        b.d_raw_ld = ps.dC;
+    }
     b.out.blocked = ps.blocked ? 1 : 0;
     // (ps.maxes was zeroed before the forward pass, which - on the fp16-pair kernel - has entered the kept activations'
     // maxima and the feature vector's; the backward kernels add the gradients', the fp32 one the kept ones as well)
-    const bool pair_dw = ps.precision == NERF_PRECISION_F16X2 && pair_dw_allowed() && ps.maxes != nullptr;
-    if (pair_dw || ps.pair_backward) b.maxes = ps.maxes;
+    if (ps.pair_dw || ps.pair_backward) b.maxes = ps.maxes;
     if (ps.pair_backward) {
         b.stream_h2 = net.train.d_stream_bwd_h2;
         b.descale = net.train.d_descale_bwd;
         b.gain = net.train.d_gain_bwd;
         b.loose = ps.loose;
         for (int i = 0; i < a.D; ++i) b.fwd.mask[i] = ps.mask[i];
-        b.fwd.mask_hv = ps.mask_hv;
-        TrainTimer timer(ps.ctx, s, 1, ps.P);
-        HIP_TRY(launch_mlp_bwd_h2(b, s));
-    } else {
-        TrainTimer timer(ps.ctx, s, 1, ps.P);
-        HIP_TRY(launch_mlp_bwd(b, s));
+        if (a.use_viewdirs) b.fwd.mask_hv = ps.mask_hv;
     }
-    // the view layer's job can join the fp16-pair batch when the feature vector's size is known: the fp16-pair forward pass
-    // has tracked it (kBwdMaxFeatValue)
-    const bool feat_known = pair_dw && eq;
+    TrainTimer timer(ps.ctx, s, 1, ps.P);
+    HIP_TRY(ps.pair_backward ? launch_mlp_bwd_h2(b, s) : launch_mlp_bwd(b, s));
+    return NERF_OK;
+}
+
+// A batch's split into slices: as many as fill the chip's 256 workgroups once over all its jobs, of at least 256 points, each
+// a whole number of `quantum` points (kSlicePointQuantum; 128 for the narrow-pair kernel, whose four waves share a slice)
+void size_slices(GradBatch& b, int64_t P, int quantum, int accumulate) {
+    int n_slices = 256 / b.n;
+    const int64_t cap = (P + 255) / 256;
+    if (n_slices > cap) n_slices = (int)cap;
+    if (n_slices < 1) n_slices = 1;
+    const int64_t pps = (P + n_slices - 1) / n_slices;
+    b.n_slices = n_slices;
+    b.pts_per_slice = (pps + quantum - 1) / quantum * quantum;
+    b.P = P;
+    b.accumulate = accumulate;
+}
+
+// The gamma columns' jobs on the fp16 pipe (grad_batch_narrow_pair_kernel). A workgroup is a slice (its four waves share its
+// points and add their sums up in LDS)
+int narrow_pair_batch(Pass& ps, const TnScratch& sc, GradBatch& narrow_pair, hipStream_t s) {
+    if (narrow_pair.n == 0) return NERF_OK;
+    size_slices(narrow_pair, ps.P, 128, sc.accumulate);
+    TrainTimer timer(ps.ctx, s, 3, ps.P);
+    HIP_TRY(launch_grad_batch_narrow_pair(narrow_pair, sc.part, sc.part_floats, sc.dbp, sc.dbp_floats, s));
+    return NERF_OK;
+}
+
+static_assert(kMaxDepth <= kMaxGradJobs, "a trunk's layers are one batch of weight-gradient jobs");
+
+// The fused backward pass: backward_data, then the weight gradients (dW = dZ^T X, slices summed in a fixed order) by the
+// route set_units chose. Batched, every one of them takes two launches (+ their reductions): the 256-column blocks of all
+// layers, then the gamma(x) / gamma(d) columns. With J jobs in a launch a layer is cut into 256 / J slices instead of 256: J
+// times fewer partial sums to write and to add up (a layer's 256 partials were 67 MB, and the pass over them 12 % of the
+// step). The head's small Linears - rgb_linear, alpha_linear where it does not ride, output_linear - are launches of their own.
+// (pack_weights.cpp takes input_ch <= 63, input_ch_views <= 27 and D <= kMaxDepth: the gamma columns fit a narrow job's 64.)
+int backward_pass_fused(Pass& ps, const TnScratch& sc, hipStream_t s) {
+    const PackedNet& net = *ps.net;
+    const nerf_arch& a = net.arch;
+    const bool eq = ps.eq;
+    int rc;
+    if ((rc = backward_data(ps, s))) return rc;
     const float* hl = ps.h[a.D - 1];
     const int hl_ld = ps.h_ld[a.D - 1];
-    int rc;
-    if ((rc = grad_linear(net, rgb, ps.d_raw, ps.C, ps.hv, views.out, ps.P, sc, s, eq))) return rc;
-    const bool batched = gemm_tn_is_direct(a.W) && gemm_tn_is_direct(views.out) && a.input_ch <= 64 &&
-                         a.input_ch_views <= 64 && a.D + 1 <= kMaxGradJobs;
-    // alpha_linear reads what feature_linear reads (h_{D-1}, nerf.py:86,89): its one-row gradient rides in that job of the
-    // fp16-pair batch (GradJob::y) where the kernel that takes riders is in use; a launch of its own otherwise
-    static const bool rider_wanted = [] {      // NERF_TRAIN_DW_RIDER=0: A/B
-        const char* e = getenv("NERF_TRAIN_DW_RIDER");
-        return !(e && *e == '0');
-    }();
-    const bool alpha_rides = rider_wanted && batched && pair_dw && grad_pair_takes_riders() && a.D + 2 <= kMaxGradJobs &&
-                             hl_ld % 4 == 0;
-    if (ps.blocked && !(alpha_rides && batched && pair_dw && feat_known)) {
-        set_error("internal: the blocked activation layout was chosen for a pass whose weight gradients cannot read it");
-        return NERF_E_INVALID;
-    }
-    if (!alpha_rides && (rc = grad_linear(net, alpha, ps.d_raw + 3, ps.C, hl, hl_ld, ps.P, sc, s, eq))) return rc;
-    if (!batched) {
-        if ((rc = grad_linear(net, views, ps.g_hv, views.out, ps.vcat, ps.vcat_ld, ps.P, sc, s, eq))) return rc;
-        if ((rc = grad_linear(net, feat, d_feat, a.W, hl, hl_ld, ps.P, sc, s, eq))) return rc;
-        for (int i = a.D - 1; i >= 0; --i)
-            if ((rc = grad_linear(net, net.linears[i], ps.dz[i], a.W, ps.in[i], ps.in_ld[i], ps.P, sc, s, eq))) return rc;
-        return NERF_OK;
-    }
-    // Every other weight gradient in two launches (+ their reductions): the 256-column blocks of all layers, then the
-    // gamma(x) / gamma(d) columns. With J jobs in a launch a layer is cut into 256 / J slices instead of 256: J times
-    // fewer partial sums to write and to add up (a layer's 256 partials were 67 MB, and the pass over them 12 % of the step).
     float* grad = net.train.d_grad;
     // (pairs: the jobs whose operands the backward kernel has measured - d z_i / d feature against the kept h_{i-1}, the
     // view layer's against a bound of the feature vector - go to the fp16-pair kernel when the context's arithmetic is F16X2)
@@ -718,59 +669,68 @@ int backward_pass_fused(Pass& ps, const TnScratch& sc, hipStream_t s) {
         j.blocked = blocked;
         j.b_first = b_first;
     };
-    GradBatch& hidden = pair_dw ? pairs : wide;
-    auto mx = [&](int slot) -> const unsigned* { return pair_dw ? ps.maxes + slot : nullptr; };
-    if (ps.blocked) {
-        // every hidden-width operand blocked by 32 points, in a buffer of its own; the gamma(x) / gamma(d) columns' jobs read
-        // a blocked dY against a narrow row-major X (rows of 64, zero-padded) whose column 0 is column n_begin of the Linear's
-        // input: on the fp16 pipe too (grad_batch_narrow_pair_kernel), or - NERF_TRAIN_NARROW=f32 - on the fp32 one
-        GradBatch& nb = narrow_pair_wanted() ? narrow_pair : narrow;
-        const int np = narrow_pair_wanted() ? 1 : 0;
-        job(pairs, feat, d_feat, a.W, ps.h[a.D - 1], a.W, 0, a.W, true, mx(kBwdMaxFeat), mx(kBwdMaxKept + a.D - 1), 3, 0);
-        job(pairs, views, ps.g_hv, views.out, ps.feat_blk, a.W, 0, a.W, true, mx(kBwdMaxViews), mx(kBwdMaxFeatValue), 3, 0);
-        if (views.in > a.W)
-            job(nb, views, ps.g_hv, views.out, np ? ps.vcat : ps.vcat - a.W, ps.vcat_ld, a.W, views.in, false, mx(kBwdMaxViews),
-                mx(kBwdMaxGammaD), 1);
-        for (int i = a.D - 1; i >= 0; --i) {
-            const LinearDesc& d = net.linears[i];
-            if (d.in >= a.W) {
-                const int lead = d.in - a.W;                                           // cat[gamma(x), h] (nerf.py:79-80)
-                job(pairs, d, ps.dz[i], a.W, ps.h[i - 1], a.W, lead, d.in, true, mx(i), mx(kBwdMaxKept + i - 1), 3, lead);
-                if (lead > 0) job(nb, d, ps.dz[i], a.W, ps.in[i], ps.in_ld[i], 0, lead, false, mx(i), mx(kBwdMaxGammaX), 1);
-            } else {
-                job(nb, d, ps.dz[i], a.W, ps.in[i], ps.in_ld[i], 0, d.in, true, mx(i), mx(kBwdMaxGammaX), 1);   // layer 0: gamma(x) only
-            }
+    // A blocked pass keeps every hidden-width operand blocked by 32 points, in a buffer of its own; its gamma(x) / gamma(d)
+    // columns' jobs read a blocked dY against a narrow row-major X (rows of 64, zero-padded) whose column 0 is column n_begin
+    // of the Linear's input: on the fp16 pipe too (grad_batch_narrow_pair_kernel), or - NERF_TRAIN_NARROW=f32 - on the fp32
+    // one, which like a row-major pass's wants X's column 0 to be the Linear's and takes no maxima.
+    const bool np = ps.blocked && switches().narrow_pair;
+    GradBatch& hidden = ps.pair_dw ? pairs : wide;
+    GradBatch& gamma = np ? narrow_pair : narrow;
+    const int wide_blk = ps.blocked ? 3 : 0, gamma_blk = ps.blocked ? 1 : 0;
+    auto mx = [&](int slot) -> const unsigned* { return ps.pair_dw ? ps.maxes + slot : nullptr; };
+    auto gmx = [&](int slot) -> const unsigned* { return ps.blocked ? ps.maxes + slot : nullptr; };
+
+    // ---- the head ----
+    if (a.use_viewdirs) {
+        const LinearDesc &views = net.linears[a.D], &feat = net.linears[a.D + 1], &alpha = net.linears[a.D + 2],
+                         &rgb = net.linears[a.D + 3];
+        float* d_feat = ps.g_a;      // [P, W]
+        if ((rc = grad_linear(net, rgb, ps.d_raw, ps.C, ps.hv, views.out, ps.P, sc, s, eq))) return rc;
+        // alpha_linear reads what feature_linear reads (h_{D-1}, nerf.py:86,89): its one-row gradient rides in that job of the
+        // fp16-pair batch (GradJob::y); a launch of its own otherwise
+        if (!ps.alpha_rides && (rc = grad_linear(net, alpha, ps.d_raw + 3, ps.C, hl, hl_ld, ps.P, sc, s, eq))) return rc;
+        if (!ps.batched) {
+            if ((rc = grad_linear(net, views, ps.g_hv, views.out, ps.vcat, ps.vcat_ld, ps.P, sc, s, eq))) return rc;
+            if ((rc = grad_linear(net, feat, d_feat, a.W, hl, hl_ld, ps.P, sc, s, eq))) return rc;
+        } else {
+            job(hidden, feat, d_feat, a.W, hl, hl_ld, 0, a.W, true, mx(kBwdMaxFeat), mx(kBwdMaxKept + a.D - 1), wide_blk);
+            // cat[feature, gamma(d)] (nerf.py:93): the feature vector from its blocked buffer, or the front of vcat's rows
+            job(ps.feat_known ? pairs : wide, views, ps.g_hv, views.out, ps.blocked ? ps.feat_blk : ps.vcat,
+                ps.blocked ? a.W : ps.vcat_ld, 0, a.W, true, mx(kBwdMaxViews), mx(kBwdMaxFeatValue), wide_blk);
+            if (views.in > a.W)
+                job(gamma, views, ps.g_hv, views.out, np ? ps.vcat : ps.vcat + ps.voff - a.W, ps.vcat_ld, a.W, views.in, false,
+                    gmx(kBwdMaxViews), gmx(kBwdMaxGammaD), gamma_blk);
         }
     } else {
-    job(hidden, feat, d_feat, a.W, hl, hl_ld, 0, a.W, true, mx(kBwdMaxFeat), mx(kBwdMaxKept + a.D - 1));
-    job(feat_known ? pairs : wide, views, ps.g_hv, views.out, ps.vcat, ps.vcat_ld, 0, a.W, true, mx(kBwdMaxViews),
-        mx(kBwdMaxFeatValue));                                                        // cat[feature, gamma(d)] (nerf.py:93)
-    if (views.in > a.W) job(narrow, views, ps.g_hv, views.out, ps.vcat, ps.vcat_ld, a.W, views.in, false);
+        // output_linear as one small job; views_linears exists in the module (nerf/nerf.py:43) and is never evaluated: its
+        // gradient is zero
+        const LinearDesc &views = net.linears[a.D], &out = net.linears[a.D + 1];
+        if ((rc = grad_linear(net, out, ps.d_raw, ps.dC, hl, hl_ld, ps.P, sc, s, eq, ps.blocked))) return rc;
+        if (!sc.accumulate)
+            HIP_TRY(hipMemsetAsync(grad + views.w_off, 0, ((size_t)views.out * views.in + views.out) * sizeof(float), s));
+    }
+
+    // ---- the trunk ----
     for (int i = a.D - 1; i >= 0; --i) {
         const LinearDesc& d = net.linears[i];
-        if (d.in >= a.W) {
-            const int lead = d.in - a.W;                                               // cat[gamma(x), h] (nerf.py:79-80)
-            job(hidden, d, ps.dz[i], a.W, ps.in[i], ps.in_ld[i], lead, d.in, true, mx(i), mx(kBwdMaxKept + i - 1));
-            if (lead > 0) job(narrow, d, ps.dz[i], a.W, ps.in[i], ps.in_ld[i], 0, lead, false);
-        } else {
-            job(narrow, d, ps.dz[i], a.W, ps.in[i], ps.in_ld[i], 0, d.in, true);       // layer 0: gamma(x) only
+        if (!ps.batched) {
+            if ((rc = grad_linear(net, d, ps.dz[i], a.W, ps.in[i], ps.in_ld[i], ps.P, sc, s, eq))) return rc;
+            continue;
         }
-    }
+        // the gamma(x) columns: in front of h_{i-1} in a layer that reads cat[gamma(x), h] (nerf.py:79-80), all of layer 0's
+        const int lead = d.in >= a.W ? d.in - a.W : d.in;
+        if (d.in >= a.W)
+            job(hidden, d, ps.dz[i], a.W, ps.blocked ? ps.h[i - 1] : ps.in[i], ps.blocked ? a.W : ps.in_ld[i], lead, d.in, true,
+                mx(i), mx(kBwdMaxKept + i - 1), wide_blk, ps.blocked ? lead : 0);
+        if (lead > 0)
+            job(gamma, d, ps.dz[i], a.W, ps.in[i], ps.in_ld[i], 0, lead, d.in < a.W, gmx(i), gmx(kBwdMaxGammaX), gamma_blk);
     }
     for (GradBatch* b : {&pairs, &wide, &narrow}) {
         if (b->n == 0) continue;
-        int n_slices = 256 / b->n;
-        const int64_t cap = (ps.P + 255) / 256;
-        if (n_slices > cap) n_slices = (int)cap;
-        if (n_slices < 1) n_slices = 1;
-        int64_t pps = (ps.P + n_slices - 1) / n_slices;
-        pps = (pps + kSlicePointQuantum - 1) / kSlicePointQuantum * kSlicePointQuantum;
-        b->n_slices = n_slices;
-        b->pts_per_slice = pps;
-        b->P = ps.P;
-        b->accumulate = sc.accumulate;
+        size_slices(*b, ps.P, kSlicePointQuantum, sc.accumulate);
         TrainTimer timer(ps.ctx, s, b == &narrow ? 3 : 2, ps.P);
-        if (b == &pairs && alpha_rides) {      // (job 0 of the batch is feature_linear's)
+        if (b == &pairs && ps.alpha_rides) {      // (job 0 of the batch is feature_linear's)
+            const LinearDesc& alpha = net.linears[a.D + 2];
             b->job[0].y = ps.d_raw + 3;
             b->job[0].ldy = ps.C;
             const GradRider rider{0, grad + alpha.w_off, grad + alpha.b_off, grad_exps(net, a.D + 2, eq)};
@@ -782,121 +742,8 @@ int backward_pass_fused(Pass& ps, const TnScratch& sc, hipStream_t s) {
     return narrow_pair_batch(ps, sc, narrow_pair, s);
 }
 
-// Networks without view directions (use_viewdirs=False: output_linear on the trunk, nerf.py:109): the same fused fp32 launch
-// from d raw to every pre-activation gradient - the head's transpose as vector products inside the kernel - then the trunk's
-// weight gradients batched as above and output_linear's as one small job. views_linears exists in the module
-// (nerf/nerf.py:43) and is never evaluated: its gradient is zero.
-int backward_pass_fused_noviews(Pass& ps, const TnScratch& sc, hipStream_t s) {
-    const PackedNet& net = *ps.net;
-    const nerf_arch& a = net.arch;
-    const LinearDesc &views = net.linears[a.D], &out = net.linears[a.D + 1];
-    const bool eq = ps.eq;
-    {
-        const int rc = refresh_bwd(const_cast<PackedNet&>(net), eq, ps.pair_backward, s);
-        if (rc != NERF_OK) return rc;
-    }
-    MlpBwdLaunch b{};
-    b.stream = net.train.d_stream_bwd;
-    b.n_chunks = net.train.n_chunks_bwd;
-    b.bias = eq ? net.d_bias_h2 : net.d_bias;
-    b.n_bias_tiles = net.n_bias_tiles;
-    b.D = a.D;
-    b.n_points = ps.P;
-    b.d_raw = ps.d_raw;
-    b.C = ps.C;
-    b.d_raw_ld = ps.dC;
-    b.use_viewdirs = 0;
-    for (int i = 0; i < a.D; ++i) {
-        b.fwd.h[i] = ps.h[i];
-        b.fwd.h_ld[i] = ps.h_ld[i];
-        b.out.h[i] = ps.dz[i];
-        b.out.h_ld[i] = a.W;
-    }
-    b.out.blocked = ps.blocked ? 1 : 0;
-    const bool pair_dw = ps.precision == NERF_PRECISION_F16X2 && pair_dw_allowed() && ps.maxes != nullptr;
-    if (pair_dw || ps.pair_backward) b.maxes = ps.maxes;
-    if (ps.pair_backward) {
-        // the fp16-pair kernel on the equalised transposed weights: W_output^T is the chain's first chunk, the masks are bits
-        b.stream_h2 = net.train.d_stream_bwd_h2;
-        b.descale = net.train.d_descale_bwd;
-        b.gain = net.train.d_gain_bwd;
-        b.loose = ps.loose;
-        for (int i = 0; i < a.D; ++i) b.fwd.mask[i] = ps.mask[i];
-        TrainTimer timer(ps.ctx, s, 1, ps.P);
-        HIP_TRY(launch_mlp_bwd_h2(b, s));
-    } else {
-        TrainTimer timer(ps.ctx, s, 1, ps.P);
-        HIP_TRY(launch_mlp_bwd(b, s));
-    }
-    int rc;
-    if (ps.blocked && !(pair_dw && ps.pair_backward && a.input_ch <= 64 && a.D <= kMaxGradJobs && gemm_tn_is_small(out.out, a.W))) {
-        set_error("internal: the blocked activation layout was chosen for a pass whose weight gradients cannot read it");
-        return NERF_E_INVALID;
-    }
-    if ((rc = grad_linear(net, out, ps.d_raw, ps.dC, ps.h[a.D - 1], ps.h_ld[a.D - 1], ps.P, sc, s, eq, ps.blocked))) return rc;
-    if (!sc.accumulate)
-        HIP_TRY(hipMemsetAsync(net.train.d_grad + views.w_off, 0, ((size_t)views.out * views.in + views.out) * sizeof(float), s));
-    float* grad = net.train.d_grad;
-    GradBatch wide{}, narrow{}, pairs{}, narrow_pair{};
-    auto job = [&](GradBatch& bt, const LinearDesc& d, const float* dY, const float* X, int ldx, int n0, int n1, bool with_db,
-                   const unsigned* a_max = nullptr, const unsigned* b_max = nullptr, int blocked = 0, int b_first = 0) {
-        GradJob& j = bt.job[bt.n++];
-        j = GradJob{dY, a.W, X, ldx, d.out, n0, n1, grad + d.w_off, d.in, with_db ? grad + d.b_off : nullptr,
-                    nullptr, nullptr, a_max, b_max, grad_exps(net, (int)(&d - &net.linears[0]), eq)};
-        j.blocked = blocked;
-        j.b_first = b_first;
-    };
-    if (ps.blocked) {
-        // as backward_pass_fused: hidden-width operands blocked by 32 points, the gamma(x) columns' jobs a blocked dY against the
-        // narrow row-major gamma(x) (rows of 64, zero-padded)
-        GradBatch& nb = narrow_pair_wanted() ? narrow_pair : narrow;
-        for (int i = a.D - 1; i >= 0; --i) {
-            const LinearDesc& d = net.linears[i];
-            if (d.in >= a.W) {
-                const int lead = d.in - a.W;
-                job(pairs, d, ps.dz[i], ps.h[i - 1], a.W, lead, d.in, true, ps.maxes + i, ps.maxes + kBwdMaxKept + i - 1, 3, lead);
-                if (lead > 0) job(nb, d, ps.dz[i], ps.in[i], ps.in_ld[i], 0, lead, false, ps.maxes + i, ps.maxes + kBwdMaxGammaX, 1);
-            } else {
-                job(nb, d, ps.dz[i], ps.in[i], ps.in_ld[i], 0, d.in, true, ps.maxes + i, ps.maxes + kBwdMaxGammaX, 1);
-            }
-        }
-    } else if (a.input_ch > 64 || a.D > kMaxGradJobs) {
-        for (int i = a.D - 1; i >= 0; --i)
-            if ((rc = grad_linear(net, net.linears[i], ps.dz[i], a.W, ps.in[i], ps.in_ld[i], ps.P, sc, s, eq))) return rc;
-        return NERF_OK;
-    }
-    if (!ps.blocked) {
-    GradBatch& hidden = pair_dw ? pairs : wide;
-    for (int i = a.D - 1; i >= 0; --i) {
-        const LinearDesc& d = net.linears[i];
-        if (d.in >= a.W) {
-            const int lead = d.in - a.W;                                               // cat[gamma(x), h] (nerf.py:79-80)
-            job(hidden, d, ps.dz[i], ps.in[i], ps.in_ld[i], lead, d.in, true, pair_dw ? ps.maxes + i : nullptr,
-                pair_dw ? ps.maxes + kBwdMaxKept + i - 1 : nullptr);
-            if (lead > 0) job(narrow, d, ps.dz[i], ps.in[i], ps.in_ld[i], 0, lead, false);
-        } else {
-            job(narrow, d, ps.dz[i], ps.in[i], ps.in_ld[i], 0, d.in, true);            // layer 0: gamma(x) only
-        }
-    }
-    }
-    for (GradBatch* bt : {&pairs, &wide, &narrow}) {
-        if (bt->n == 0) continue;
-        int n_slices = 256 / bt->n;
-        const int64_t cap = (ps.P + 255) / 256;
-        if (n_slices > cap) n_slices = (int)cap;
-        if (n_slices < 1) n_slices = 1;
-        int64_t pps = (ps.P + n_slices - 1) / n_slices;
-        pps = (pps + kSlicePointQuantum - 1) / kSlicePointQuantum * kSlicePointQuantum;
-        bt->n_slices = n_slices;
-        bt->pts_per_slice = pps;
-        bt->P = ps.P;
-        bt->accumulate = sc.accumulate;
-        TrainTimer timer(ps.ctx, s, bt == &narrow ? 3 : 2, ps.P);
-        HIP_TRY(launch_grad_batch(*bt, bt != &narrow, sc.part, sc.part_floats, sc.dbp, sc.dbp_floats, s, bt == &pairs));
-    }
-    return narrow_pair_batch(ps, sc, narrow_pair, s);
-}
-
+// The layer-by-layer chain (one gemm_rows and one gemm_tn per Linear) for the passes init_pass keeps off the fused route: a
+// network without a backward stream (W != 256, api.cpp), a view-direction head of other than 4 channels
 int backward_pass(Pass& ps, const TnScratch& sc, hipStream_t s) {
     if (ps.fused_backward) return backward_pass_fused(ps, sc, s);
     const PackedNet& net = *ps.net;
@@ -959,35 +806,35 @@ int backward_pass(Pass& ps, const TnScratch& sc, hipStream_t s) {
 // end - the kept activations, the backward-data pass on the equalised transposed weights, the weight gradients, which
 // are brought back to the plain parameters' by exact powers of two where their slices are added up (GradJob::ex).
 void set_units(Pass& ps) {
-    const nerf_arch& a = ps.net->arch;
-    const bool fused_forward = !gemm_forward_requested() && a.D <= kMaxDepth && a.W == kWidth;
-    // (networks without view directions, round 4: the same three fp16-pair kernels, output_linear as one more chunk in both
-    // directions - when the whole pass can stay on them: a head of <= 8 channels and the fused backward stream, api.cpp)
-    static const bool noviews_pair = [] {      // NERF_TRAIN_NOVIEWS=f32: the fused fp32 kernels for them (A/B)
-        const char* e = getenv("NERF_TRAIN_NOVIEWS");
-        return !(e && (e[0] == 'f' || e[0] == 'F') && e[1] == '3');
-    }();
-    const bool arch_ok = a.use_viewdirs || (noviews_pair && ps.fused_backward && pair_bwd_allowed() && ps.net->out_ch <= 8 && a.D >= 2);
-    ps.eq = ps.precision == NERF_PRECISION_F16X2 && pair_forward_allowed() && fused_forward && arch_ok &&
+    const PackedNet& net = *ps.net;
+    const nerf_arch& a = net.arch;
+    const TrainSwitches& sw = switches();
+    const bool fused_forward = a.D <= kMaxDepth && a.W == kWidth;
+    // (networks without view directions: the same three fp16-pair kernels, output_linear as one more chunk in both directions
+    // - when the whole pass can stay on them: a head of <= 8 channels and the fused backward stream, api.cpp. The fused fp32
+    // kernels otherwise: NERF_PRECISION_F32, out_ch > 8, D < 2)
+    const bool arch_ok = a.use_viewdirs || (ps.fused_backward && sw.pair_bwd && net.out_ch <= 8 && a.D >= 2);
+    ps.eq = ps.precision == NERF_PRECISION_F16X2 && sw.pair_forward && fused_forward && arch_ok &&
             (uint64_t)ps.P * (uint64_t)(a.W + a.input_ch + 4) * 4u < ((uint64_t)1 << 32);
-    ps.pair_backward = ps.eq && ps.fused_backward && pair_bwd_allowed();
-    // Blocked by 32 points (MlpStore::blocked; NERF_TRAIN_BLOCKED=0: row-major, the A/B switch): when the three fp16-pair
-    // kernels run the pass and the weight gradients go through the batched launches that read the layout - the conditions
-    // backward_pass_fused puts on `batched`, `pair_dw`, `feat_known` and the alpha rider
-    static const bool blocked_wanted = [] {
-        const char* e = getenv("NERF_TRAIN_BLOCKED");
-        return !(e && *e == '0');
-    }();
-    static const bool rider_on = [] {
-        const char* e = getenv("NERF_TRAIN_DW_RIDER");
-        return !(e && *e == '0');
-    }();
-    const bool dw_reads_blocked =
-        a.use_viewdirs ? rider_on && grad_pair_takes_riders() && gemm_tn_is_direct(a.W / 2) && a.input_ch_views <= 64 &&
-                             a.D + 2 <= kMaxGradJobs && ps.net->out_ch == 4
-                       : a.D <= kMaxGradJobs && gemm_tn_is_small(ps.net->out_ch, a.W);      // (backward_pass_fused_noviews)
-    ps.blocked = blocked_wanted && ps.pair_backward && pair_dw_allowed() && gemm_tn_is_direct(a.W) && a.input_ch <= 64 &&
-                 dw_reads_blocked && (uint64_t)ps.P * 1024u < ((uint64_t)1 << 32);
+    ps.pair_backward = ps.eq && ps.fused_backward && sw.pair_bwd;
+    // The route of the fused backward's weight gradients (Pass::pair_dw ...; ps.maxes is never null: init_pass, carve_pass)
+    ps.pair_dw = ps.precision == NERF_PRECISION_F16X2 && sw.pair_dw;
+    ps.feat_known = ps.pair_dw && ps.eq;
+    bool reads_blocked;      // the weight gradients go through the launches that read the blocked layout
+    if (a.use_viewdirs) {
+        // one batch holds the trunk's D jobs and the two of the head (feature_linear, the view layer), and the rider's reduction
+        // one entry more: D = 11 batches with alpha_linear on its own, D = 12 launches layer by layer. (The rider's X, h_{D-1},
+        // is no concatenation's half - carve_pass gives it rows of W floats, 16-byte aligned with W a multiple of 128)
+        ps.batched = gemm_tn_is_direct(a.W) && gemm_tn_is_direct(net.linears[a.D].out) && a.D + 1 <= kMaxGradJobs;
+        ps.alpha_rides = ps.batched && ps.pair_dw && a.D + 2 <= kMaxGradJobs;
+        reads_blocked = ps.alpha_rides && ps.feat_known;
+    } else {
+        ps.batched = true;      // (the trunk's jobs alone: static_assert above)
+        ps.alpha_rides = false;
+        reads_blocked = ps.pair_dw && gemm_tn_is_direct(a.W) && gemm_tn_is_small(net.out_ch, a.W);
+    }
+    // Blocked by 32 points (MlpStore::blocked; NERF_TRAIN_BLOCKED=0: row-major): when the three fp16-pair kernels run the pass
+    ps.blocked = sw.blocked && ps.pair_backward && reads_blocked && (uint64_t)ps.P * 1024u < ((uint64_t)1 << 32);
 }
 
 // ---- the phases of a training iteration, shared by nerf_train_step and the taped route ---------------------------------
@@ -1071,7 +918,7 @@ void init_pass(Pass& ps, PackedNet& net, int64_t N, int S, int precision, nerf_c
     ps.N = N;
     ps.P = N * S;
     ps.S = S;
-    ps.fused_backward = !gemm_backward_requested() && net.train.d_stream_bwd != nullptr && (net.out_ch == 4 || !net.arch.use_viewdirs);
+    ps.fused_backward = net.train.d_stream_bwd != nullptr && (net.out_ch == 4 || !net.arch.use_viewdirs);
     ps.precision = precision;
     ps.ctx = c;
     ps.loose = c->d_loose + kLooseTrain;
@@ -1131,7 +978,7 @@ int adam_phase(nerf_ctx* c, PackedNet* const* nets, int n, float lr, float beta1
     }
     if (eq) {
         PackedNet* both[2] = {nets[0], n > 1 ? nets[1] : nets[0]};
-        if (!glue_legacy()) {
+        if (!switches().glue_legacy) {
             if ((rc = refresh_after_step(c, both, n, s, mirrored))) return rc;
         } else if ((rc = refresh_h2_many(both, n, s))) return rc;
     }
@@ -1261,7 +1108,7 @@ int train_step(nerf_ctx* c, const nerf_train_args* r, nerf_occupancy* occ, const
     float* loss_dev = ar.take(4);
     TnScratch sc{ar.take(part_floats), ar.take((size_t)n_slices * 512), n_slices, 0, 0, part_floats, (size_t)n_slices * 512};
 
-    const bool fused_glue = !glue_legacy();
+    const bool fused_glue = !switches().glue_legacy;
     // one block of words that the prologue zeroes: both passes' running maxima and the loss kernel's ticket
     unsigned* zero_block = (unsigned*)ar.take(2 * kBwdMaxSlots + 32);
     double* loss_part = (double*)ar.take((size_t)4 * N + 16);      // [2][N] per-ray sums of squares
@@ -1275,6 +1122,39 @@ int train_step(nerf_ctx* c, const nerf_train_args* r, nerf_occupancy* occ, const
     }
     unsigned* ticket = zero_block + 2 * kBwdMaxSlots;
     float* rgb_last = Si ? rgb_f : rgb_c;
+    // raw2outputs of the last pass, loss = img2mse(rgb, target) [+ img2mse(rgb0, target)] (nerf.ipynb:1262-1272), and the
+    // backward of both raw2outputs: one launch, over every sample. A pass says where its network's output, the gradient of it
+    // and its sigma noise lie per sample: the pass's own buffers, or - with a grid - the per-sample ones beside the compact rows
+    struct PerSample {
+        const float* raw;
+        float* d_raw;
+        const float* noise;
+    };
+    auto epilogue = [&](const PerSample& coarse, const PerSample& fine) {
+        const Pass& pl = Si ? pf : pc;
+        const PerSample& last = Si ? fine : coarse;
+        TrainEpilogue e{};
+        e.rays_d = r->rays + 3;
+        e.d_ld = r->ray_stride;
+        e.target = r->target;
+        e.N = N;
+        e.white_bkgd = r->white_bkgd;
+        e.raw_l = last.raw; e.C_l = pl.C; e.z_l = Si ? z_f : z_c; e.noise_l = last.noise; e.S_l = Si ? Sf : Sc;
+        e.d_raw_l = last.d_raw;
+        e.dC_l = pl.dC;
+        if (Si) {
+            e.raw_c = coarse.raw; e.C_c = pc.C; e.z_c = z_c; e.noise_c = coarse.noise; e.S_c = Sc; e.d_raw_c = coarse.d_raw;
+            e.dC_c = pc.dC; e.rgb_c = rgb_c;
+        }
+        e.out_rgb = r->rgb_map ? r->rgb_map : rgb_last;
+        e.out_rgb0 = Si ? r->rgb0 : nullptr;
+        e.part = loss_part;
+        e.ticket = ticket;
+        e.loss_dev = loss_dev;
+        e.out_loss = r->loss;
+        e.out_stats = r->stats;
+        return launch_train_epilogue(e, s);
+    };
 
     if (occ) {
         // ---- the step with an occupancy grid (nerf_mi355x.h, "Occupancy grid"): the network runs over the kept
@@ -1314,28 +1194,7 @@ int train_step(nerf_ctx* c, const nerf_train_args* r, nerf_occupancy* occ, const
                 HIP_TRY(hipMemcpyAsync(z_f, r->z_vals_fine_in, (size_t)N * Sf * sizeof(float), hipMemcpyDeviceToDevice, s));
             if ((rc = forward_pass_occ(pf, oc, r->rays, r->ray_stride, z_f, s))) return rc;
         }
-        Pass& pl = Si ? pf : pc;
-        TrainEpilogue e{};
-        e.rays_d = r->rays + 3;
-        e.d_ld = r->ray_stride;
-        e.target = r->target;
-        e.N = N;
-        e.white_bkgd = r->white_bkgd;
-        e.raw_l = pl.raw_full; e.C_l = pl.C; e.z_l = Si ? z_f : z_c; e.noise_l = pl.noise_masked; e.S_l = Si ? Sf : Sc;
-        e.d_raw_l = pl.d_raw_full;
-        e.dC_l = pl.dC;
-        if (Si) {
-            e.raw_c = pc.raw_full; e.C_c = pc.C; e.z_c = z_c; e.noise_c = pc.noise_masked; e.S_c = Sc; e.d_raw_c = pc.d_raw_full;
-            e.dC_c = pc.dC; e.rgb_c = rgb_c;
-        }
-        e.out_rgb = r->rgb_map ? r->rgb_map : rgb_last;
-        e.out_rgb0 = Si ? r->rgb0 : nullptr;
-        e.part = loss_part;
-        e.ticket = ticket;
-        e.loss_dev = loss_dev;
-        e.out_loss = r->loss;
-        e.out_stats = r->stats;
-        HIP_TRY(launch_train_epilogue(e, s));
+        HIP_TRY(epilogue({pc.raw_full, pc.d_raw_full, pc.noise_masked}, {pf.raw_full, pf.d_raw_full, pf.noise_masked}));
         if ((rc = gather_d_raw(pc, s))) return rc;
         if (Si && (rc = gather_d_raw(pf, s))) return rc;
         if ((rc = backward_phase(pc, pf, Si, shared, sc, false, s))) return rc;
@@ -1343,29 +1202,7 @@ int train_step(nerf_ctx* c, const nerf_train_args* r, nerf_occupancy* occ, const
     } else if (fused_glue) {
         // ---- forward (render(..., retraw=True, **render_kwargs_train), nerf.ipynb:1258), the small stages fused ----
         if ((rc = forward_phase(pc, pf, in, r->rays, r->noise0, z_c, w_c, rgb_c, z_f, zero_block, s))) return rc;
-        // ---- raw2outputs of the last pass, loss = img2mse(rgb, target) [+ img2mse(rgb0, target)] (nerf.ipynb:1262-1272),
-        //      and the backward of both raw2outputs: one launch ----
-        Pass& pl = Si ? pf : pc;
-        TrainEpilogue e{};
-        e.rays_d = r->rays + 3;
-        e.d_ld = r->ray_stride;
-        e.target = r->target;
-        e.N = N;
-        e.white_bkgd = r->white_bkgd;
-        e.raw_l = pl.raw; e.C_l = pl.C; e.z_l = Si ? z_f : z_c; e.noise_l = Si ? r->noise : r->noise0; e.S_l = Si ? Sf : Sc;
-        e.d_raw_l = pl.d_raw;
-        e.dC_l = pl.dC;
-        if (Si) {
-            e.raw_c = pc.raw; e.C_c = pc.C; e.z_c = z_c; e.noise_c = r->noise0; e.S_c = Sc; e.d_raw_c = pc.d_raw; e.dC_c = pc.dC; e.rgb_c = rgb_c;
-        }
-        e.out_rgb = r->rgb_map ? r->rgb_map : rgb_last;
-        e.out_rgb0 = Si ? r->rgb0 : nullptr;
-        e.part = loss_part;
-        e.ticket = ticket;
-        e.loss_dev = loss_dev;
-        e.out_loss = r->loss;
-        e.out_stats = r->stats;
-        HIP_TRY(launch_train_epilogue(e, s));
+        HIP_TRY(epilogue({pc.raw, pc.d_raw, r->noise0}, {pf.raw, pf.d_raw, r->noise}));
         // ---- backward ----
         if ((rc = backward_phase(pc, pf, Si, shared, sc, false, s))) return rc;
     } else {

@@ -548,29 +548,21 @@ __global__ __launch_bounds__(256) void gemm_tn_small4_kernel(GemmTN g) {
     }
 }
 
-// NERF_TRAIN_STAGED_DW=1 keeps the LDS-staged kernel for every layer (A/B and fallback)
-static bool staged_dw_requested() {
-    static const bool on = [] {
-        const char* e = getenv("NERF_TRAIN_STAGED_DW");
-        return e && *e && *e != '0';
-    }();
-    return on;
-}
-
 // workgroups per slice of the launch that does the bulk of a layer's dW (the caller sizes the number of slices with it)
 // the weighted-column-sum kernel wants many short slices (its only parallelism besides the columns)
 // (five to eight rows - an output_linear of more than four channels - only against an X the 16-byte kernel reads)
 bool gemm_tn_is_small(int Mo, int No) {
-    return (Mo <= 4 || (Mo <= 8 && (No == 256 || No == 128 || No == 64))) && !staged_dw_requested();
+    return Mo <= 4 || (Mo <= 8 && (No == 256 || No == 128 || No == 64));
 }
 
 int gemm_tn_col_blocks(int Mo, int No) {
     if (gemm_tn_is_small(Mo, No)) return (No + 255) / 256;
-    if (Mo % 128 == 0 && Mo <= 256 && !staged_dw_requested()) return 1;
+    if (gemm_tn_is_direct(Mo)) return 1;
     return (No + 127) / 128;
 }
 
-bool gemm_tn_is_direct(int Mo) { return Mo % 128 == 0 && Mo <= 256 && !staged_dw_requested(); }
+// (every other shape - W = 128's view layer, say - goes to the LDS-staged gemm_tn_kernel)
+bool gemm_tn_is_direct(int Mo) { return Mo % 128 == 0 && Mo <= 256; }
 
 // One Linear at a time (the layer-by-layer backward pass, the small layers, the staged fallback); the fused backward pass
 // batches its direct-eligible layers itself (train_api.cpp).

@@ -24,3 +24,18 @@ def test_no_switch_in_the_kernel_sources_and_none_through_the_build():
     headers = {os.path.join(CSRC, n) for n in os.listdir(CSRC) if n.endswith((".h", ".inc"))}
     assert headers and headers <= set(build.HEADERS)
     assert os.path.join(ROOT, "include", "nerf_mi355x.h") in build.HEADERS
+
+
+def test_the_library_reads_six_environment_switches_once_each():
+    """The run-time switches of the library are the three that bench.py, bench_train.py and the public header name and the
+    three reference routes of test_train_glue_is_bit_identical; each is read by one getenv call, and no getenv takes a name
+    that is not spelled out at the call."""
+    kept = {"NERF_TRAIN_FORWARD", "NERF_TRAIN_BWD", "NERF_TRAIN_DW", "NERF_TRAIN_GLUE", "NERF_TRAIN_BLOCKED", "NERF_TRAIN_NARROW"}
+    names, calls = [], 0
+    for name in sorted(os.listdir(CSRC)):
+        with open(os.path.join(CSRC, name)) as f:
+            text = f.read()
+        calls += len(re.findall(r"\bgetenv\s*\(", text))
+        names += re.findall(r"\bgetenv\s*\(\s*\"(NERF_[A-Za-z0-9_]*)\"\s*\)", text)
+    assert sorted(names) == sorted(kept), sorted(names)
+    assert calls == len(names), (calls, names)

@@ -1,5 +1,5 @@
 """Per-tensor gradient errors of the no-viewdirs training fixture (tests/golden/train_step_noviewdirs.npz): largest element error /
-tensor's largest entry, and norm error. Run with and without NERF_TRAIN_NOVIEWS=f32. tools/gpu: run on the box."""
+tensor's largest entry, and norm error. Run with and without the NERF_TRAIN_* switches. tools/gpu: run on the box."""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,7 +17,7 @@ kw = dict(network_fn=net_c, network_fine=net_f, N_samples=64, N_importance=128, 
 opt = N.Adam([net_c, net_f], lr=5e-4)
 ctx = N.get_context(); ctx.precision_detail(reset=True)
 out = N.train_on_batch(800, 800, None, (rays[:, 0:3], rays[:, 3:6]), torch.from_numpy(g["target"]).cuda(), opt, apply_update=False, **kw)
-print("env", os.environ.get("NERF_TRAIN_NOVIEWS"), "losses", float(out["img_loss"]) - float(g["img_loss"]), float(out["img_loss0"]) - float(g["img_loss0"]),
+print("env", {k: v for k, v in os.environ.items() if k.startswith("NERF_TRAIN_")}, "losses", float(out["img_loss"]) - float(g["img_loss"]), float(out["img_loss0"]) - float(g["img_loss0"]),
       "events", ctx.precision_detail())
 for tag, net in (("c", net_c), ("f", net_f)):
     for k, gr in net.grad_dict().items():
