@@ -1665,6 +1665,90 @@ int nerf_grid_background_backward(nerf_sparse_grid* grid, const nerf_grid_render
 int nerf_grid_background_tv_grad(nerf_sparse_grid* grid, const nerf_grid_background_tv_args* args);
 int nerf_grid_background_optim_step(nerf_ctx* ctx, const nerf_grid_background_optim_args* args);
 
+/* Sparse voxel grid: regularisers as values ---------------------------------------------------------
+ * The regularisers of the Plenoxels objective as numbers with exact gradients: what a torch.autograd.Function needs so that
+ * total variation and the sparsity term can be written into any loss (svox2's SparseGrid.tv() / tv_color(), and the function
+ * whose gradient the sparsity_loss of nerf_grid_fused_backward_losses adds). The sections on training keep adding the
+ * reference's gradients straight into a trainer's buffers; nothing there changes. All calls are stream-ordered, synchronise
+ * and allocate nothing and return a status with nerf_last_error(). The backward calls ACCUMULATE: the caller zeroes.
+ *
+ * nerf_grid_tv_value: the total variation of the density table (target NERF_GRID_TV_DENSITY, one column) or of columns
+ * [start_dim, end_dim) of the SH table (NERF_GRID_TV_SH; refused on a half-precision handle): svox2's tv_kernel. An item is
+ * (cell, column c), a cell is a node (x, y, z) of the lattice. fp32, each operation one rounded operation, in this order:
+ *   v0  = data[link(cell), c]  where the link is in [0, capacity), else 0
+ *   v_i = the same at the +x, +y, +z neighbour; a neighbour that is empty or lies outside the lattice reads `null`:
+ *         null = v0 with ignore_edge = 1 (its difference is 0), 0 with ignore_edge = 0
+ *   with ignore_edge = 1 a cell whose own link is exactly row 0 contributes nothing (the reference's literal `links == 0`,
+ *         as in nerf_grid_tv_grad_edge)
+ *   d_i  = (v_i - v0) * s_i           s = (X / 256, Y / 256, Z / 256)
+ *   term = sqrt(((1e-5 + dx dx) + dy dy) + dz dz)
+ * *value = fp32(sum of term over cells and columns / n), the sum and the division in fp64, rounded once. svox2 runs tv() with
+ * ignore_edge = 0 and tv_color() with 1. cells == NULL: the cells are the n = (X-1)(Y-1)(Z-1) nodes whose three forward
+ * neighbours are inside the lattice, in C order (the reference's tv()). cells != NULL: n = n_cells flat C-order node
+ * indices over X Y Z on the device, int32 or int64 (cells_int64), the stochastic form (svox2's _get_rand_cells): any node may
+ * appear, repeatedly, and counts as often as it appears; an entry outside [0, X Y Z) contributes 0, stays in the divisor and
+ * is never read through. n = 0 or start_dim == end_dim: *value = 0. The sum uses no float atomics: workgroup b adds the
+ * terms of items [256 b, 256 b + 256) in fp64 in a fixed order into partials[b], and one workgroup adds the partials in a
+ * fixed order: two calls on the same tables return the same bits. partials holds nerf_grid_tv_value_workspace(items)
+ * doubles, items = n * (end_dim - start_dim) (1 column for the density): ceil(items / 256), 0 for items <= 0. Indices are
+ * 64-bit throughout (2^30 nodes times 27 columns pass 2^32).
+ *
+ * nerf_grid_tv_value_backward adds to grad [capacity, columns of the table] the exact gradient of that value times the
+ * cotangent grad_value[0], which the kernel reads from device memory. Per item, with the forward's d_i and term:
+ *   w = grad_value[0] / fp32(n)
+ *   neighbour i, if it is a kept row:  grad[row_i, c] += w * ((s_i * d_i) / term)
+ *   the cell, if it is a kept row:     grad[row_0, c] += w * (-(((s_x dx) + (s_y dy)) + (s_z dz)) / term)
+ * each unless the value added is 0 (a zero term is not added: a plateau of equal values receives exactly nothing). Float
+ * atomics (one hardware add each): two calls agree to rounding of the sums. This is NOT svox2's
+ * _TotalVariationFunction.backward, which calls tv_grad with a fixed scale of 1 (it ignores the cotangent), with 1e-9 where
+ * the value has 1e-5, and with the rsqrt of the unscaled differences, which on a non-cubic lattice is the gradient of no
+ * function; under autograd the gradient has to be that of the value returned. nerf_grid_tv_grad / nerf_grid_tv_grad_edge
+ * keep the reference's literal rule.
+ *
+ * nerf_grid_sparsity_rays: sparsity[ray] = the sum of log1pf(2 (sigma sigma)) over the samples of the renderer's own march
+ * (the lattice, step_size, near_clip, skip rule and stall rule of nerf_grid_render_rays) with sigma > opt.sigma_thresh, added
+ * in fp32 in march order, up to and including the sample at which exp(log_T) < opt.stop_thresh ends the ray
+ * (log_T = log_T + (-step_size * sigma) * delta_scale at every such sample, as in the renderer). A ray that is not marched
+ * (a miss, a non-finite set-up) gives exactly 0. With skip data the result is bit-identical: a skipped sample has sigma = 0.
+ * sh_data is not read. nerf_grid_sparsity_backward marches every ray again with the same log_T recurrence and adds to
+ * grad_density the gradient of sum_ray grad_sparsity[ray] * sparsity[ray]: at every such sample
+ *   d_sigma = grad_sparsity[ray] * ((4 sigma) / (1 + 2 (sigma sigma)))
+ *   at each of the 8 corners whose link is kept:  v = ((w_x * w_y) * w_z) * d_sigma;  grad_density[row] += v  unless v == 0
+ * (the expression nerf_grid_fused_backward_losses adds with sparsity_loss in the place of the cotangent). Nothing is kept
+ * per ray between the two calls. At most 2^26 rays per call; n_rays = 0 does nothing. */
+typedef struct nerf_grid_tv_value_args {
+    size_t struct_size;
+    int32_t target;             /* NERF_GRID_TV_DENSITY / NERF_GRID_TV_SH                                            */
+    int32_t start_dim, end_dim; /* columns [start_dim, end_dim) of the table; the density has one: 0, 1              */
+    int32_t ignore_edge;        /* 0 / 1                                                                            */
+    const void* cells;          /* [dev] [n_cells] flat node indices, or NULL: every cell with three forward neighbours */
+    int32_t cells_int64;        /* 0: cells are int32, 1: int64                                                     */
+    int64_t n_cells;            /* with cells: in [0, 2^30]; ignored without                                        */
+    double* partials;           /* [dev] [nerf_grid_tv_value_workspace(items)] workspace          (the value only)    */
+    float* value;               /* [dev] [1] out                                                  (the value only)    */
+    const float* grad_value;    /* [dev] [1] d loss / d value                                     (the backward only) */
+    float* grad;                /* [dev] [capacity, columns of the table], added to               (the backward only) */
+    void* stream;
+} nerf_grid_tv_value_args;
+
+typedef struct nerf_grid_sparsity_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]                                                                */
+    const float* dirs;          /* [dev] [n_rays, 3], need not be unit                                              */
+    int64_t n_rays;             /* 0: nothing is done                                                               */
+    float* sparsity;            /* [dev] [n_rays] out                                             (the value only)    */
+    const float* grad_sparsity; /* [dev] [n_rays] d loss / d sparsity                             (the backward only) */
+    float* grad_density;        /* [dev] [capacity, 1], added to                                  (the backward only) */
+    int32_t use_skip;           /* 1: use the skip data if nerf_grid_accelerate made it                             */
+    void* stream;
+} nerf_grid_sparsity_args;
+
+int64_t nerf_grid_tv_value_workspace(int64_t items);
+int nerf_grid_tv_value(nerf_sparse_grid* grid, const nerf_grid_tv_value_args* args);
+int nerf_grid_tv_value_backward(nerf_sparse_grid* grid, const nerf_grid_tv_value_args* args);
+int nerf_grid_sparsity_rays(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_sparsity_args* args);
+int nerf_grid_sparsity_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_sparsity_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,8 @@ EXPORTS = (
     "nerf_grid_background_sparsify_plan", "nerf_grid_background_gather",
     "nerf_grid_background_rays_taped", "nerf_grid_background_backward", "nerf_grid_background_tv_grad",
     "nerf_grid_background_optim_step",
+    "nerf_grid_tv_value_workspace", "nerf_grid_tv_value", "nerf_grid_tv_value_backward",
+    "nerf_grid_sparsity_rays", "nerf_grid_sparsity_backward",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -341,6 +343,17 @@ class GridBackgroundOptimArgs(_Sized):
                 ("minval", C.c_float), ("stream", C.c_void_p)]
 
 
+class GridTvValueArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("target", C.c_int32), ("start_dim", C.c_int32), ("end_dim", C.c_int32),
+                ("ignore_edge", C.c_int32), ("cells", _FP), ("cells_int64", C.c_int32), ("n_cells", C.c_int64),
+                ("partials", _FP), ("value", _FP), ("grad_value", _FP), ("grad", _FP), ("stream", C.c_void_p)]
+
+
+class GridSparsityArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("sparsity", _FP),
+                ("grad_sparsity", _FP), ("grad_density", _FP), ("use_skip", C.c_int32), ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -577,6 +590,16 @@ def load():
     lib.nerf_grid_background_tv_grad.argtypes = [vp, C.POINTER(GridBackgroundTvArgs)]
     lib.nerf_grid_background_optim_step.restype = i32
     lib.nerf_grid_background_optim_step.argtypes = [vp, C.POINTER(GridBackgroundOptimArgs)]
+    lib.nerf_grid_tv_value_workspace.restype = i64
+    lib.nerf_grid_tv_value_workspace.argtypes = [i64]
+    lib.nerf_grid_tv_value.restype = i32
+    lib.nerf_grid_tv_value.argtypes = [vp, C.POINTER(GridTvValueArgs)]
+    lib.nerf_grid_tv_value_backward.restype = i32
+    lib.nerf_grid_tv_value_backward.argtypes = [vp, C.POINTER(GridTvValueArgs)]
+    lib.nerf_grid_sparsity_rays.restype = i32
+    lib.nerf_grid_sparsity_rays.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridSparsityArgs)]
+    lib.nerf_grid_sparsity_backward.restype = i32
+    lib.nerf_grid_sparsity_backward.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridSparsityArgs)]
     _lib = lib
     return lib
 

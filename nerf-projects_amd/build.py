@@ -22,6 +22,7 @@ SOURCES = ["api.cpp", "train_api.cpp", "pack_weights.cpp", "mlp_kernel.hip", "ml
            "grid_depth_api.cpp", "grid_depth_kernels.hip",
            "grid_autograd_api.cpp", "grid_autograd_kernels.hip",
            "grid_depth_autograd_api.cpp", "grid_depth_autograd_kernels.hip",
+           "grid_regularisers_api.cpp", "grid_regularisers_kernels.hip",
            "grid_floater_api.cpp", "grid_floater_kernels.hip",
            "grid_half_api.cpp", "grid_half_kernels.hip",
            "grid_background_api.cpp", "grid_background_kernels.hip",

@@ -6,6 +6,7 @@
 //   grid_components_api.cpp occupancy, labelling, volumes, keep mask, row copy
 //   grid_depth_api.cpp      expected depth, threshold depth, ray length
 //   grid_depth_autograd_api.cpp   taped expected depth, backward with cotangents for depth and log_transmit
+//   grid_regularisers_api.cpp     total variation and the sparsity term as values, and their backwards
 //   grid_half_api.cpp       half-precision colours: pack / unpack, create; render and sample are dispatched from grid_api.cpp
 //   grid_background_api.cpp background layers: attach / detach, the background pass, the two calls of the thinning
 //   grid_background_train_api.cpp   background layers, training: taped pass, backward, TV gradient, optimiser step
@@ -246,6 +247,37 @@ struct GridDepthBwd {
 
 hipError_t launch_grid_depth_taped(const GridDev& g, const GridRenderOpt& o, const GridDepthTaped& r, hipStream_t s);
 hipError_t launch_grid_depth_bwd(const GridDev& g, const GridRenderOpt& o, const GridDepthBwd& r, hipStream_t s);
+
+// ---- regularisers as values (grid_regularisers_kernels.hip) ----
+constexpr int kGridTvValueItems = 256;   // items (cell, column) per workgroup = per fp64 partial
+
+struct GridTvValue {
+    const float* data;                 // the table: [capacity, cols]
+    int32_t cols, start_dim, end_dim;
+    int32_t edge;                      // svox2's ignore_edge
+    const void* cells;                 // [count] flat node indices, or nullptr: the (X-1)(Y-1)(Z-1) cells in C order
+    int32_t cells_int64;
+    int64_t count;                     // cells of the call: the divisor
+    float axis_scale[3];               // reso / 256
+    double* partials;                  // forward: one per workgroup
+    float* value;                      // forward: [1]
+    const float* grad_value;           // backward: [1]
+    float* grad;                       // backward: [capacity, cols], added to
+};
+
+struct GridSparsity {
+    const float* origins;
+    const float* dirs;
+    int64_t n_rays;
+    float* sparsity;                   // forward: [n_rays]
+    const float* grad_sparsity;        // backward: [n_rays]
+    float* grad_density;               // backward: [capacity, 1], added to
+};
+
+hipError_t launch_grid_tv_value(const GridDev& g, const GridTvValue& a, hipStream_t s);
+hipError_t launch_grid_tv_value_bwd(const GridDev& g, const GridTvValue& a, hipStream_t s);
+hipError_t launch_grid_sparsity(const GridDev& g, const GridRenderOpt& o, const GridSparsity& r, hipStream_t s);
+hipError_t launch_grid_sparsity_bwd(const GridDev& g, const GridRenderOpt& o, const GridSparsity& r, hipStream_t s);
 
 // ---- argument checks (grid_api.cpp): NERF_OK, or NERF_E_INVALID with last_error set. None needs a device or reads a handle. ----
 void set_error(const char* fmt, ...);

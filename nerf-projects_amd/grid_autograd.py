@@ -15,6 +15,13 @@ include/nerf_mi355x.h, "Sparse voxel grid: gradients for autograd" and "Sparse v
 log_transmit for autograd". The forward keeps 24 bytes per ray (the tape; 8 for a depth) for the backward; the backward
 marches every ray once. The expected depth and ``log_transmit`` depend on ``density_data`` alone: ``sh_data`` gets no
 gradient from them.
+The regularisers of the Plenoxels objective are values too: ``tv()`` and ``tv_color()`` (svox2's, 0-dim, deterministic bits,
+differentiable in ``density_data`` / ``sh_data`` respectively, over every cell or over a tensor of ``cells``) and
+``sparsity_loss(rays)`` (per ray, differentiable in ``density_data``), in the kernels of csrc/grid_regularisers_kernels.hip
+(include/nerf_mi355x.h, "Sparse voxel grid: regularisers as values"); the beta term is a function of ``log_transmit``::
+
+    loss = mse + l_tv * m.tv() + l_tv_sh * m.tv_color() + l_s * m.sparsity_loss(rays).sum()
+
 Not built: gradients with respect to rays, points or the camera, of the threshold depth (piecewise constant) or the ray
 length, double backward, sparse gradient tensors.
 """
@@ -24,8 +31,8 @@ from dataclasses import replace
 import torch
 from torch.autograd.function import once_differentiable
 
-from ._lib import (NERF_GRID_DEPTH_EXPECTED, GridDepthBackwardArgs, GridDepthTapedArgs, GridRenderBackwardArgs,
-                   GridRenderTapedArgs, GridSampleBackwardArgs, check)
+from ._lib import (NERF_GRID_DEPTH_EXPECTED, NERF_GRID_TV_DENSITY, NERF_GRID_TV_SH, GridDepthBackwardArgs, GridDepthTapedArgs,
+                   GridRenderBackwardArgs, GridRenderTapedArgs, GridSampleBackwardArgs, GridSparsityArgs, GridTvValueArgs, check)
 from .grid import Camera, Rays, SparseGrid, _refuse_half
 
 __all__ = ["GridModule"]
@@ -184,6 +191,113 @@ class _Sample(torch.autograd.Function):
         return gd, gs, None, None, None, None      # (without want_colors sh_data takes no part: no gradient)
 
 
+def _cells_arg(cells, device):
+    """``cells`` as a contiguous 1-D int32 / int64 tensor on ``device`` (None stays None: the dense form)"""
+    if cells is None:
+        return None
+    if not torch.is_tensor(cells):
+        raise TypeError("cells must be a tensor")
+    if cells.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"cells must be int32 or int64, got {cells.dtype}")
+    if not cells.is_cuda:
+        raise RuntimeError("cells is on the CPU: GridModule has no CPU fallback")
+    if cells.dim() != 1:
+        raise ValueError(f"cells must be [M] flat node indices, got {tuple(cells.shape)}")
+    return cells.detach().to(device=device).contiguous()
+
+
+def _tv_args(g, target, start_dim, end_dim, ignore_edge, cells):
+    a = GridTvValueArgs()
+    a.target, a.start_dim, a.end_dim, a.ignore_edge = target, start_dim, end_dim, int(ignore_edge)
+    if cells is not None:
+        # (an empty tensor has no address: any non-NULL one says "a list", and none of its entries is read)
+        a.cells, a.cells_int64, a.n_cells = cells.data_ptr() or g.links.data_ptr(), int(cells.dtype == torch.int64), cells.shape[0]
+    a.stream = g.ctx.stream().value
+    return a
+
+
+def _tv_value(g, h, target, start_dim, end_dim, ignore_edge, cells):
+    """nerf_grid_tv_value: the 0-dim fp32 value; the partials are a workspace of this call"""
+    dev = g.ctx.device
+    n = cells.shape[0] if cells is not None else (g.links.shape[0] - 1) * (g.links.shape[1] - 1) * (g.links.shape[2] - 1)
+    work = torch.empty((int(g.ctx.lib.nerf_grid_tv_value_workspace(n * (end_dim - start_dim))),), device=dev, dtype=torch.float64)
+    value = torch.empty((), device=dev, dtype=torch.float32)
+    a = _tv_args(g, target, start_dim, end_dim, ignore_edge, cells)
+    a.partials, a.value = work.data_ptr(), value.data_ptr()
+    check(g.ctx.lib.nerf_grid_tv_value(h, C.byref(a)))
+    return value, n
+
+
+class _TotalVariation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, module, target, start_dim, end_dim, ignore_edge, cells):
+        g = module.grid
+        value, n = _tv_value(g, g._handle(), target, start_dim, end_dim, ignore_edge, cells)
+        ctx.save_for_backward(table)      # the parameter: torch refuses a backward after an in-place step
+        ctx.module, ctx.cells, ctx.call = module, cells, (target, start_dim, end_dim, ignore_edge)
+        ctx.items = n * (end_dim - start_dim)
+        return value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_value):
+        (table,) = ctx.saved_tensors
+        g = ctx.module.grid
+        if ctx.call[0] == NERF_GRID_TV_DENSITY:
+            h = _same_tables(ctx.module, table)
+        else:
+            h = _same_tables(ctx.module, g.density_data, table)
+        if ctx.items == 0:      # no cell or no column: the value is the constant 0
+            return None, None, None, None, None, None, None
+        grad = torch.zeros_like(table, memory_format=torch.contiguous_format)
+        grad_value = grad_value.to(dtype=torch.float32).contiguous()      # stays on the device: the kernel reads it
+        a = _tv_args(g, *ctx.call, ctx.cells)
+        a.grad_value, a.grad = grad_value.data_ptr(), grad.data_ptr()
+        check(g.ctx.lib.nerf_grid_tv_value_backward(h, C.byref(a)))
+        return grad, None, None, None, None, None, None
+
+
+def _sparsity_args(g, o, d):
+    a = GridSparsityArgs()
+    a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]
+    a.use_skip = 1
+    a.stream = g.ctx.stream().value
+    return a
+
+
+def _sparsity_rays(g, h, opt, o, d):
+    s = torch.empty((o.shape[0],), device=o.device, dtype=torch.float32)
+    a = _sparsity_args(g, o, d)
+    a.sparsity = s.data_ptr()
+    check(g.ctx.lib.nerf_grid_sparsity_rays(h, C.byref(opt._to_c()), C.byref(a)))
+    return s
+
+
+class _SparsityLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, density, module, o, d):
+        g = module.grid
+        opt = replace(g.opt)
+        s = _sparsity_rays(g, g._handle(), opt, o, d)
+        ctx.save_for_backward(density, o, d)      # nothing is kept per ray besides the rays themselves
+        ctx.module, ctx.opt = module, opt
+        return s
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_s):
+        density, o, d = ctx.saved_tensors
+        g = ctx.module.grid
+        h = _same_tables(ctx.module, density)
+        gd = torch.zeros_like(density, memory_format=torch.contiguous_format)
+        if o.shape[0]:
+            grad_s = grad_s.to(dtype=torch.float32).contiguous()      # (s.sum().backward() hands in a stride-0 expansion)
+            a = _sparsity_args(g, o, d)
+            a.grad_sparsity, a.grad_density = grad_s.data_ptr(), gd.data_ptr()
+            check(g.ctx.lib.nerf_grid_sparsity_backward(h, C.byref(ctx.opt._to_c()), C.byref(a)))
+        return gd, None, None, None
+
+
 class GridModule(torch.nn.Module):
     """``density_data`` and ``sh_data`` are ``nn.Parameter`` views of the grid's own tensors: the same storage and the same
     version counter, so an optimiser that steps them in place is seen by ``grid.volume_render_image`` at once - the grid's
@@ -279,6 +393,61 @@ class GridModule(torch.nn.Module):
         if not self._differentiate():
             return self.grid.sample(p, grid_coords=grid_coords, want_colors=want_colors)
         return _Sample.apply(self.density_data, self.sh_data, self, p, bool(grid_coords), bool(want_colors))
+
+    def _tv(self, target, start_dim, end_dim, ignore_edge, cells):
+        g = self.grid
+        param = self.density_data if target == NERF_GRID_TV_DENSITY else self.sh_data
+        _refuse_half(g, "GridModule.tv / tv_color")
+        self._check_bound()
+        cells = _cells_arg(cells, g.ctx.device)
+        if not (torch.is_grad_enabled() and param.requires_grad):
+            return _tv_value(g, g._handle(), target, start_dim, end_dim, ignore_edge, cells)[0]
+        return _TotalVariation.apply(param, self, target, start_dim, end_dim, ignore_edge, cells)
+
+    def tv(self, cells: torch.Tensor = None, logalpha: bool = False, logalpha_delta: float = 2.0, ndc_coeffs=(-1.0, -1.0)):
+        """svox2's ``SparseGrid.tv()``: the total variation of the densities, a 0-dim fp32 tensor, differentiable with respect
+        to ``density_data`` only - the mean over cells of ``sqrt(1e-5 + dx^2 + dy^2 + dz^2)`` of the forward differences
+        scaled by ``reso / 256``, an empty node counting as 0. ``cells=None``: every cell with three forward neighbours.
+        ``cells``: an int32 / int64 device tensor of flat C-order node indices (svox2's ``_get_rand_cells``), duplicates
+        counting as often as they appear, entries outside the lattice contributing 0; the divisor is ``len(cells)``. Two
+        calls return the same bits. The gradient is the exact gradient of this value times the cotangent, which is NOT what
+        svox2's ``_TotalVariationFunction.backward`` computes (include/nerf_mi355x.h, ``nerf_grid_tv_value_backward``).
+        ``ndc_coeffs`` is accepted and has no effect, as in svox2, whose NDC branch of ``calculate_ray_scale`` is commented
+        out; ``logalpha=True`` raises."""
+        if logalpha:
+            raise NotImplementedError("logalpha=True is not built: svox2 itself asserts 'No longer supported'")
+        return self._tv(NERF_GRID_TV_DENSITY, 0, 1, False, cells)
+
+    def tv_color(self, start_dim: int = 0, end_dim: int = None, cells: torch.Tensor = None, logalpha: bool = False,
+                 logalpha_delta: float = 2.0, ndc_coeffs=(-1.0, -1.0)):
+        """svox2's ``SparseGrid.tv_color()``: :meth:`tv` of columns ``[start_dim, end_dim)`` of ``sh_data`` (negative values
+        wrap as in svox2), summed over the columns, differentiable with respect to ``sh_data`` only, with svox2's
+        ``ignore_edge``: an empty or out-of-range neighbour takes the cell's own value, and the cell whose link is row 0 is
+        left out. ``start_dim == end_dim`` is the constant 0. ``ndc_coeffs`` is accepted and has no effect, as in svox2."""
+        if logalpha:
+            raise NotImplementedError("logalpha=True is not built: svox2 itself asserts 'No longer supported'")
+        cols = self.sh_data.shape[1]
+        end_dim = cols if end_dim is None else int(end_dim)
+        start_dim = int(start_dim)
+        end_dim = end_dim + cols if end_dim < 0 else end_dim
+        start_dim = start_dim + cols if start_dim < 0 else start_dim
+        if not 0 <= start_dim <= end_dim <= cols:
+            raise ValueError(f"columns [{start_dim}, {end_dim}) outside [0, {cols})")
+        return self._tv(NERF_GRID_TV_SH, start_dim, end_dim, True, cells)
+
+    def sparsity_loss(self, rays: Rays):
+        """``[N]``: per ray the sum of ``log(1 + 2 sigma^2)`` over the samples of the renderer's own march that it shades
+        (``sigma > sigma_thresh``, up to and including the sample at which ``stop_thresh`` ends the ray); exactly 0 for a ray
+        that is not marched. Differentiable with respect to ``density_data`` only. It is the function whose gradient
+        ``GridTrainer.volume_render_fused(..., sparsity_loss=l)`` adds: write ``l * m.sparsity_loss(rays).sum()``."""
+        g = self.grid
+        _refuse_half(g, "GridModule.sparsity_loss")
+        self._check_bound()
+        o = _points_arg(rays.origins, "rays.origins", g.ctx.device)
+        d = _points_arg(rays.dirs, "rays.dirs", g.ctx.device, o.shape[0])
+        if not (torch.is_grad_enabled() and self.density_data.requires_grad):
+            return _sparsity_rays(g, g._handle(), g.opt, o, d)
+        return _SparsityLoss.apply(self.density_data, self, o, d)
 
     def forward(self, rays: Rays):
         return self.volume_render(rays)
