@@ -1749,6 +1749,72 @@ int nerf_grid_tv_value_backward(nerf_sparse_grid* grid, const nerf_grid_tv_value
 int nerf_grid_sparsity_rays(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_sparsity_args* args);
 int nerf_grid_sparsity_backward(nerf_sparse_grid* grid, const nerf_grid_render_options* opt, const nerf_grid_sparsity_args* args);
 
+/* Sparse voxel grid: training data ------------------------------------------------------------------
+ * A batch of training rays made from the images as they were loaded. svox2's DatasetBase.gen_rays materialises origin,
+ * direction and colour of every pixel of every training image (36 B per ray) and shuffle_rays copies the whole set through a
+ * host permutation once per epoch. Here the training set stays on the device as uint8 images and [n_images, 12] poses, and one
+ * launch, one lane per ray, makes rows [begin, begin + n) of the epoch. The call is stateless, stream-ordered, allocates and
+ * synchronises nothing and returns a status with nerf_last_error(). n == 0 launches nothing.
+ *
+ * Domain. h = height / factor, w = width / factor (integer division), N = n_images * h * w. A ray's index is
+ * (image * h + y) * w + x, the reference's flattened rays_init. Output row k is the ray whose index is sigma(begin + k).
+ *
+ * sigma, by `order`. All arithmetic below is on unsigned 32-bit words (wrapping) unless it says 64-bit.
+ *   hash32(v):  v ^= v >> 16;  v *= 0x7feb352d;  v ^= v >> 15;  v *= 0x846ca68b;  v ^= v >> 16
+ *   round keys: klo = key & 0xffffffff, khi = key >> 32;  rk[r] = hash32(hash32(klo + r * 0x9e3779b9) ^ khi),  r = 0 .. 3
+ *   NERF_GRID_ORDER_IDENTITY   sigma(p) = p                                                       (begin + n <= N)
+ *   NERF_GRID_ORDER_PERMUTED   a bijection of [0, N)                                              (begin + n <= N)
+ *     bits = the smallest even number >= 2 with 2^bits >= N;  half = bits / 2;  mask = 2^half - 1
+ *     feistel(v), v < 2^bits:  L = v >> half, R = v & mask;  for r = 0 .. 3: (L, R) = (R, L ^ (hash32(R ^ rk[r]) & mask));
+ *                              the result is (L << half) | R  (64-bit)
+ *     sigma(p) = v = feistel(p); while v >= N: v = feistel(v)          (cycle walking)
+ *     feistel is a bijection of [0, 2^bits), so the walk from p < N follows p's cycle and comes back into [0, N) at the latest
+ *     at p itself: the loop ends, and sigma is a bijection of [0, N). 2^bits < 4 N, so a walk takes fewer than 4 steps on average.
+ *   NERF_GRID_ORDER_RANDOM     independent draws, the reference's randint branch           (begin + n <= 2^62, any begin >= 0)
+ *     plo = p & 0xffffffff, phi = p >> 32;  a = hash32(hash32(plo ^ rk[0]) ^ phi ^ rk[1]);  c = hash32(a ^ rk[2])
+ *     sigma(p) = ((a << 32) | c) mod N                                                          (64-bit)
+ *
+ * Intrinsics. s = 1.0 / ((double)height / h) in fp64; fx' = (float)(fx * s), likewise fy', cx', cy' (svox2's Intrin.scale, whose
+ * fp64 products PyTorch rounds to fp32 where they meet an fp32 tensor). Only the height enters s, as in the reference.
+ *
+ * Direction of pixel (x, y) of image i, fp32, every operation rounded separately, no fused multiply-add, true divisions:
+ *   u = ((x + 0.5) - cx') / fx',  v = ((y + 0.5) - cy') / fy',  m = sqrt((u u + v v) + 1)
+ *   (u, v, t) = (u / m, v / m, 1 / m)
+ *   dirs[r] = (c2w[i][4 r] u + c2w[i][4 r + 1] v) + c2w[i][4 r + 2] t          r = 0, 1, 2;  c2w row-major [3, 4], OpenCV convention
+ * origins[r] = c2w[i][4 r + 3], bit for bit.
+ *
+ * Colour of a full-resolution pixel, per channel c < 3, fp32: q_c = u8_c / 255 (a true division). With channels == 4 and
+ * white_bkgd: a = u8_3 / 255 and q_c = (q_c a) + (1 - a). With channels == 4 and no white_bkgd the alpha is dropped.
+ * factor == 1: rgb = q. factor > 1: the mean of q over rows [floor(y height / h), ceil((y + 1) height / h)) and columns
+ * [floor(x width / w), ceil((x + 1) width / w)) (integer arithmetic; torch's interpolate(mode="area"), sizes that factor does
+ * not divide included), summed in fp32 row by row, left to right, then divided by the number of pixels.
+ *
+ * Limits: 1 <= n_images <= 2^20, 1 <= height, width <= 2^15, channels 3 or 4, 1 <= factor <= min(height, width),
+ * 0 <= n <= 2^26, fx and fy positive and finite, cx and cy finite. images must be 4-byte aligned when channels == 4. */
+#define NERF_GRID_ORDER_IDENTITY 0
+#define NERF_GRID_ORDER_PERMUTED 1
+#define NERF_GRID_ORDER_RANDOM 2
+
+typedef struct nerf_grid_dataset_batch_args {
+    size_t struct_size;
+    const uint8_t* images;      /* [dev] [n_images, height, width, channels]                                        */
+    const float* c2w;           /* [dev] [n_images, 12]: rows 0..2 of the camera-to-world matrices                   */
+    int32_t n_images, height, width, channels;
+    double fx, fy, cx, cy;      /* of the full-resolution images                                                    */
+    int32_t white_bkgd;
+    int32_t factor;
+    int32_t order;              /* NERF_GRID_ORDER_*                                                                */
+    uint64_t key;               /* the epoch's key (unused by the identity order)                                   */
+    int64_t begin, n;           /* rows [begin, begin + n) of the epoch                                             */
+    float* origins;             /* [dev] [n, 3]                                                                     */
+    float* dirs;                /* [dev] [n, 3]                                                                     */
+    float* rgb;                 /* [dev] [n, 3]                                                                     */
+    int64_t* indices;           /* [dev] [n] the ray index of every row, or NULL                                    */
+    void* stream;
+} nerf_grid_dataset_batch_args;
+
+int nerf_grid_dataset_batch(nerf_ctx* ctx, const nerf_grid_dataset_batch_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,5 +36,9 @@ from .grid_components import (compute_all_advanced_metrics, compute_FDR, compute
 from . import grid_floater_views  # noqa: F401
 from .grid_floater_views import (component_view, floater_overlay_on_render, main_object_overlay, multi_object_overlay,  # noqa: F401
                                  project_floaters_to_view)
+from . import grid_dataset  # noqa: F401
+from .grid_dataset import GridDataset  # noqa: F401
+from . import grid_fit  # noqa: F401
+from .grid_fit import GridTrainConfig, expon_lr, train_grid  # noqa: F401
 
 __version__ = "0.1.0"

@@ -44,6 +44,7 @@ EXPORTS = (
     "nerf_grid_background_optim_step",
     "nerf_grid_tv_value_workspace", "nerf_grid_tv_value", "nerf_grid_tv_value_backward",
     "nerf_grid_sparsity_rays", "nerf_grid_sparsity_backward",
+    "nerf_grid_dataset_batch",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -55,6 +56,7 @@ NERF_GRID_OPTIM_RMSPROP, NERF_GRID_OPTIM_SGD = 0, 1
 NERF_GRID_DEPTH_EXPECTED, NERF_GRID_DEPTH_THRESHOLD, NERF_GRID_DEPTH_RAYLEN = 0, 1, 2
 NERF_GRID_FLOATER_COUNTER_INTS = 8192
 NERF_GRID_HALF_LANES_DEFAULT, NERF_GRID_HALF_LANES_SINGLE, NERF_GRID_HALF_LANES_PAIR = 0, 1, 2
+NERF_GRID_ORDER_IDENTITY, NERF_GRID_ORDER_PERMUTED, NERF_GRID_ORDER_RANDOM = 0, 1, 2
 
 
 class NerfArch(C.Structure):
@@ -354,6 +356,14 @@ class GridSparsityArgs(_Sized):
                 ("grad_sparsity", _FP), ("grad_density", _FP), ("use_skip", C.c_int32), ("stream", C.c_void_p)]
 
 
+class GridDatasetBatchArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("images", _FP), ("c2w", _FP), ("n_images", C.c_int32), ("height", C.c_int32),
+                ("width", C.c_int32), ("channels", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("white_bkgd", C.c_int32), ("factor", C.c_int32), ("order", C.c_int32), ("key", C.c_uint64),
+                ("begin", C.c_int64), ("n", C.c_int64), ("origins", _FP), ("dirs", _FP), ("rgb", _FP), ("indices", _FP),
+                ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -600,6 +610,8 @@ def load():
     lib.nerf_grid_sparsity_rays.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridSparsityArgs)]
     lib.nerf_grid_sparsity_backward.restype = i32
     lib.nerf_grid_sparsity_backward.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridSparsityArgs)]
+    lib.nerf_grid_dataset_batch.restype = i32
+    lib.nerf_grid_dataset_batch.argtypes = [vp, C.POINTER(GridDatasetBatchArgs)]
     _lib = lib
     return lib
 

@@ -10,6 +10,7 @@
 //   grid_half_api.cpp       half-precision colours: pack / unpack, create; render and sample are dispatched from grid_api.cpp
 //   grid_background_api.cpp background layers: attach / detach, the background pass, the two calls of the thinning
 //   grid_background_train_api.cpp   background layers, training: taped pass, backward, TV gradient, optimiser step
+//   grid_dataset_api.cpp    training data: a batch of rays from the resident images (takes a context, no grid)
 //   grid_*_kernels.hip      the kernels of each, on grid_device.h (sampling, rays) and compact_device.h (compaction)
 #pragma once
 #include <hip/hip_runtime.h>
