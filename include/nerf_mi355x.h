@@ -1440,6 +1440,90 @@ int nerf_grid_pack_half(nerf_ctx* ctx, const nerf_grid_pack_half_args* args);
 int nerf_grid_unpack_half(nerf_ctx* ctx, const uint16_t* sh_half, int64_t rows, int32_t basis_dim, float* sh_data, void* stream);
 int nerf_grid_create_half(nerf_ctx* ctx, const nerf_grid_half_desc* desc, nerf_sparse_grid** out);
 
+/* Sparse voxel grid: palette-quantised colours ------------------------------------------------------
+ * An inference-side grid whose colours are palette indices: for each SH basis function k the RGB triple of coefficients
+ * (sh[:, k], sh[:, B + k], sh[:, 2 B + k]) of all nodes is quantised to one of 2^bits fp16 colours, and a node stores a uint16
+ * index per function - PlenOctree's octree/compression.py on this project's grid. The first `retain` functions may stay as
+ * fp16 triples. Density, links and skip data are those of section "Sparse voxel grid".
+ *
+ * The quantiser. The reference calls a C extension of svox for this step whose source is not available, so the algorithm is
+ * defined here, and pinned by a numpy oracle kept with the tests (tests/grid_palette_oracle.py).
+ * Balanced median cut of order `bits` over colours [m, 3] fp32, 1 <= bits <= 16:
+ *   boxes      level 0 is one box holding all m members in row order. At each of `bits` levels a box j with n members
+ *              becomes box 2 j with its first n - n / 2 members and box 2 j + 1 with the remaining n / 2 (integer division),
+ *              after the reordering below: sizes and offsets are a pure function of (m, level, j).
+ *   axis       a box with n >= 2 is split on the axis with the largest max - min (both exact, the difference rounded to fp32);
+ *              ties go to the lowest axis. A box with n < 2 is not reordered.
+ *   reordering a stable sort of the box's members by the fp32 value on that axis, in the order of the sign-flipped bit
+ *              pattern: -0.0 sorts before +0.0, equal keys keep their current order.
+ *   palette    entry j < 2^bits is the mean of final box j: summed in fp64 from -0.0 (the identity of addition, so that a box
+ *              of -0.0 members keeps its sign), divided, rounded to fp32 and then to fp16 (to nearest even, clamped to
+ *              +-65504): with at most one member a box the entry is half(x), bit for bit. An empty box gives (0, 0, 0). The
+ *              order of the fp64 sum is the kernel's own
+ *              (fixed: the same bits on every run); it may differ from another implementation's in the last bit of the sum.
+ *   index      ids[i] is the final box of member i.
+ * Non-finite inputs are counted on the device and refused: *nonfinite receives the number of rows with a NaN or an infinity,
+ * and if it is not zero nothing is sorted, ids and palette are not written and the call returns NERF_E_INVALID. That count
+ * is the only value that comes back to the host; the call synchronises `stream` for it. The sort is hipCUB's stable
+ * DeviceRadixSort of (box << 32 | key, member), one per level; everything else is kernels of this library.
+ * nerf_grid_median_cut_workspace(m, bits) is the size in bytes of the workspace [dev] the call needs (256-byte aligned):
+ * about 32 m. It needs no device; negative (NERF_E_INVALID) for m outside [0, 2^31) or bits outside [1, 16].
+ *
+ * Layouts of a palette grid, Q = basis_dim - retain quantised functions, P = 2^bits:
+ *   quant_map      uint16 [capacity, Q]     node-major, rows not padded (18 / 8 / 2 bytes at Q = 9 / 4 / 1): the lanes that
+ *                                           walk a ray read all Q indices of one node, so these lie together. (The file's
+ *                                           quant_map is the transpose, [Q, capacity], compression.py's.)
+ *   quant_colors   half   [Q, P, 3]         as in the file
+ *   data_retained  half   [capacity, retain, 3]   (the file's is [retain, capacity, 3])
+ * nerf_grid_create_palette is nerf_grid_create with these tables in place of sh_data: the same link check, and the check that
+ * every index is < 2^bits (both on the device; it synchronises `stream`), the same borrowed-pointer rules, the same opaque
+ * handle, destroyed by nerf_grid_destroy. On such a handle
+ *   - nerf_grid_render_rays, nerf_grid_render_image (also with `counters`) and nerf_grid_sample read a coefficient (channel c,
+ *     function k) as half k < retain ? data_retained[node, k, c] : quant_colors[k - retain, quant_map[node, k - retain], c],
+ *     widened to fp32 when it is loaded; everything after that is the fp32 arithmetic of section "Sparse voxel grid" in the
+ *     same order and association, so the results are, bit for bit, those of a nerf_grid_create handle on the dequantised
+ *     table. Skip data changes nothing, as there.
+ *   - what reads links and density only and is not training works unchanged: accelerate / drop_skip / has_skip, depth rays
+ *     and image in all modes, components occupancy, floater heatmap, component view.
+ *   - every training, autograd, resampling and TV entry point returns NERF_E_INVALID and names the palette grid, before any
+ *     launch: nerf_grid_fused_backward(_losses), nerf_grid_render_rays_taped, nerf_grid_render_backward(_losses),
+ *     nerf_grid_sample_backward, nerf_grid_tv_grad(_edge), nerf_grid_tv_value(_backward), nerf_grid_sparsity_rays / _backward,
+ *     nerf_grid_depth_rays_taped, nerf_grid_depth_backward, nerf_grid_lattice_density, nerf_grid_gather; and
+ *     nerf_grid_set_background with a desc. */
+typedef struct nerf_grid_median_cut_args {
+    size_t struct_size;         /* sizeof(nerf_grid_median_cut_args), checked                                       */
+    int64_t m;                  /* colours, in [0, 2^31)                                                            */
+    int32_t bits;               /* in [1, 16]                                                                       */
+    const float* colors;        /* [dev] [m, 3]                 (may be NULL when m == 0)                           */
+    uint16_t* ids;              /* [dev] [m]                    (may be NULL when m == 0)                           */
+    uint16_t* palette;          /* [dev] [2^bits, 3] binary16 bit patterns                                          */
+    void* workspace;            /* [dev] workspace_bytes >= nerf_grid_median_cut_workspace(m, bits), 256-byte aligned */
+    int64_t workspace_bytes;
+    int64_t* nonfinite;         /* [host] out: rows with a non-finite component                                     */
+    void* stream;
+} nerf_grid_median_cut_args;
+
+typedef struct nerf_grid_palette_desc {
+    size_t struct_size;         /* sizeof(nerf_grid_palette_desc), checked                                          */
+    int32_t reso[3];            /* nodes per axis, each in [2, 1024]                                                */
+    int32_t basis_dim;          /* 1, 4 or 9                                                                        */
+    float radius[3];            /* > 0                                                                              */
+    float center[3];
+    int64_t capacity;           /* rows of density_data / quant_map / data_retained, >= 0                           */
+    int32_t bits;               /* in [1, 16]: 2^bits palette entries per function                                  */
+    int32_t retain;             /* in [0, basis_dim]: functions kept as fp16 triples                                */
+    const int32_t* links;       /* [dev] [X, Y, Z]                                                                  */
+    const float* density_data;  /* [dev] [capacity, 1]          (may be NULL when capacity == 0)                    */
+    const uint16_t* quant_map;      /* [dev] [capacity, basis_dim - retain]   (may be NULL when that is empty)      */
+    const uint16_t* quant_colors;   /* [dev] [basis_dim - retain, 2^bits, 3]  (may be NULL when retain == basis_dim) */
+    const uint16_t* data_retained;  /* [dev] [capacity, retain, 3]            (may be NULL when that is empty)      */
+    void* stream;
+} nerf_grid_palette_desc;
+
+int64_t nerf_grid_median_cut_workspace(int64_t m, int32_t bits);
+int nerf_grid_quantize_median_cut(nerf_ctx* ctx, const nerf_grid_median_cut_args* args);
+int nerf_grid_create_palette(nerf_ctx* ctx, const nerf_grid_palette_desc* desc, nerf_sparse_grid** out);
+
 /* Sparse voxel grid: background layers --------------------------------------------------------------
  * svox2's multi-sphere-image background (background_nlayers > 0), forward side: L = nlayers concentric spheres around the
  * grid's centre, radius 1 (the unit sphere of the normalised box) outwards to infinity, each an equirectangular image of

@@ -20,6 +20,8 @@ from . import grid  # noqa: F401
 from .grid import Camera, Rays, RenderOptions, SparseGrid  # noqa: F401
 from . import grid_half  # noqa: F401
 from .grid_half import HalfGrid  # noqa: F401
+from . import grid_palette  # noqa: F401
+from .grid_palette import PaletteGrid, quantize_median_cut  # noqa: F401
 from . import grid_background  # noqa: F401
 from .grid_background import BackgroundGrid, load_grid  # noqa: F401
 from . import grid_train  # noqa: F401

@@ -38,6 +38,7 @@ EXPORTS = (
     "nerf_grid_depth_rays_taped", "nerf_grid_depth_backward",
     "nerf_grid_floater_heatmap", "nerf_grid_component_view",
     "nerf_grid_half_row_halfs", "nerf_grid_pack_half", "nerf_grid_unpack_half", "nerf_grid_create_half",
+    "nerf_grid_median_cut_workspace", "nerf_grid_quantize_median_cut", "nerf_grid_create_palette",
     "nerf_grid_set_background", "nerf_grid_has_background", "nerf_grid_background_rays", "nerf_grid_background_image",
     "nerf_grid_background_sparsify_plan", "nerf_grid_background_gather",
     "nerf_grid_background_rays_taped", "nerf_grid_background_backward", "nerf_grid_background_tv_grad",
@@ -298,6 +299,18 @@ class GridHalfDesc(_Sized):
 class GridPackHalfArgs(_Sized):
     _fields_ = [("struct_size", C.c_size_t), ("basis_dim", C.c_int32), ("capacity", C.c_int64), ("row0", C.c_int64),
                 ("rows", C.c_int64), ("sh_data", _FP), ("sh_half", _FP), ("clamped", _FP), ("stream", C.c_void_p)]
+
+
+class GridMedianCutArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("m", C.c_int64), ("bits", C.c_int32), ("colors", _FP), ("ids", _FP),
+                ("palette", _FP), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("nonfinite", C.POINTER(C.c_int64)),
+                ("stream", C.c_void_p)]
+
+
+class GridPaletteDesc(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("reso", C.c_int32 * 3), ("basis_dim", C.c_int32), ("radius", C.c_float * 3),
+                ("center", C.c_float * 3), ("capacity", C.c_int64), ("bits", C.c_int32), ("retain", C.c_int32), ("links", _FP),
+                ("density_data", _FP), ("quant_map", _FP), ("quant_colors", _FP), ("data_retained", _FP), ("stream", C.c_void_p)]
 
 
 class GridBackgroundDesc(_Sized):
@@ -579,6 +592,12 @@ def load():
     lib.nerf_grid_unpack_half.argtypes = [vp, vp, i64, C.c_int32, vp, vp]
     lib.nerf_grid_create_half.restype = i32
     lib.nerf_grid_create_half.argtypes = [vp, C.POINTER(GridHalfDesc), C.POINTER(vp)]
+    lib.nerf_grid_median_cut_workspace.restype = i64
+    lib.nerf_grid_median_cut_workspace.argtypes = [i64, C.c_int32]
+    lib.nerf_grid_quantize_median_cut.restype = i32
+    lib.nerf_grid_quantize_median_cut.argtypes = [vp, C.POINTER(GridMedianCutArgs)]
+    lib.nerf_grid_create_palette.restype = i32
+    lib.nerf_grid_create_palette.argtypes = [vp, C.POINTER(GridPaletteDesc), C.POINTER(vp)]
     lib.nerf_grid_set_background.restype = i32
     lib.nerf_grid_set_background.argtypes = [vp, C.POINTER(GridBackgroundDesc)]
     lib.nerf_grid_has_background.restype = i32

@@ -25,6 +25,7 @@ SOURCES = ["api.cpp", "train_api.cpp", "pack_weights.cpp", "mlp_kernel.hip", "ml
            "grid_regularisers_api.cpp", "grid_regularisers_kernels.hip",
            "grid_floater_api.cpp", "grid_floater_kernels.hip",
            "grid_half_api.cpp", "grid_half_kernels.hip",
+           "grid_palette_api.cpp", "grid_palette_kernels.hip", "grid_median_cut_kernels.hip",
            "grid_background_api.cpp", "grid_background_kernels.hip",
            "grid_background_train_api.cpp", "grid_background_train_kernels.hip",
            "grid_dataset_api.cpp", "grid_dataset_kernels.hip"]

@@ -21,7 +21,15 @@ int nerf::require_grid(const char* fn, const nerf_sparse_grid* grid) {
     return NERF_E_INVALID;
 }
 
+int nerf::refuse_palette_grid(const char* fn, const nerf_sparse_grid* grid) {
+    if (!grid->palette) return NERF_OK;
+    set_error("%s: a palette grid (nerf_grid_create_palette) is for rendering and sampling: train, differentiate and resample "
+              "a grid of nerf_grid_create on the dequantised table", fn);
+    return NERF_E_INVALID;
+}
+
 int nerf::refuse_half_grid(const char* fn, const nerf_sparse_grid* grid) {
+    if (grid->palette) return refuse_palette_grid(fn, grid);
     if (!grid->half) return NERF_OK;
     set_error("%s: a half-precision grid (nerf_grid_create_half) has no fp32 SH table to read or write: widen it with "
               "nerf_grid_unpack_half and use a grid of nerf_grid_create", fn);
@@ -134,7 +142,9 @@ int render(const char* fn, nerf_sparse_grid* grid, const nerf_grid_camera* cam, 
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;
     DeviceGuard dg(grid->ctx->device);
-    if (grid->half)
+    if (grid->palette)
+        HIP_TRY(launch_grid_palette_render(g, grid->pal, o, r, (hipStream_t)a->stream));
+    else if (grid->half)
         HIP_TRY(launch_grid_half_render(g, o, r, grid->half_pair, (hipStream_t)a->stream));
     else
         HIP_TRY(launch_grid_render(g, o, r, (hipStream_t)a->stream));
@@ -235,7 +245,10 @@ int nerf_grid_sample(nerf_sparse_grid* grid, const nerf_grid_sample_args* a) {
         return NERF_E_INVALID;
     }
     DeviceGuard dg(grid->ctx->device);
-    if (grid->half)
+    if (grid->palette)
+        HIP_TRY(launch_grid_palette_sample(grid->g, grid->pal, a->points, a->n, a->grid_coords, a->want_colors, a->density, a->sh,
+                                           (hipStream_t)a->stream));
+    else if (grid->half)
         HIP_TRY(launch_grid_half_sample(grid->g, a->points, a->n, a->grid_coords, a->want_colors, a->density, a->sh,
                                         (hipStream_t)a->stream));
     else

@@ -100,6 +100,10 @@ int nerf_grid_set_background(nerf_sparse_grid* grid, const nerf_grid_background_
         set_error("%s: a half-precision grid (nerf_grid_create_half) takes no background: attach it to a grid of nerf_grid_create", fn);
         return NERF_E_INVALID;
     }
+    if (grid->palette) {
+        set_error("%s: a palette grid (nerf_grid_create_palette) takes no background: attach it to a grid of nerf_grid_create", fn);
+        return NERF_E_INVALID;
+    }
     DeviceGuard dg(grid->ctx->device);
     rc = check_grid_links(fn, d->links, (int64_t)2 * d->reso * d->reso, d->capacity, (hipStream_t)d->stream);
     if (rc != NERF_OK) return rc;

@@ -39,6 +39,8 @@ int nerf_grid_depth_rays_taped(nerf_sparse_grid* grid, const nerf_grid_render_op
         return NERF_E_INVALID;
     }
     if (a->n_rays == 0) return NERF_OK;
+    rc = refuse_palette_grid(fn, grid);      // (the first read of the handle)
+    if (rc != NERF_OK) return rc;
     GridDepthTaped r{a->origins, a->dirs, a->n_rays, a->depth, a->log_transmit, a->tape};
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;
@@ -70,6 +72,8 @@ int nerf_grid_depth_backward(nerf_sparse_grid* grid, const nerf_grid_render_opti
         return NERF_E_INVALID;
     }
     if (a->n_rays == 0) return NERF_OK;
+    rc = refuse_palette_grid(fn, grid);      // (the first read of the handle)
+    if (rc != NERF_OK) return rc;
     GridDepthBwd r{a->origins, a->dirs, a->n_rays, a->grad_depth, a->grad_log_transmit, a->tape, a->grad_density};
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;

@@ -8,6 +8,7 @@
 //   grid_depth_autograd_api.cpp   taped expected depth, backward with cotangents for depth and log_transmit
 //   grid_regularisers_api.cpp     total variation and the sparsity term as values, and their backwards
 //   grid_half_api.cpp       half-precision colours: pack / unpack, create; render and sample are dispatched from grid_api.cpp
+//   grid_palette_api.cpp    palette-quantised colours: the median cut, create; render and sample likewise
 //   grid_background_api.cpp background layers: attach / detach, the background pass, the two calls of the thinning
 //   grid_background_train_api.cpp   background layers, training: taped pass, backward, TV gradient, optimiser step
 //   grid_dataset_api.cpp    training data: a batch of rays from the resident images (takes a context, no grid)
@@ -284,8 +285,12 @@ hipError_t launch_grid_sparsity_bwd(const GridDev& g, const GridRenderOpt& o, co
 void set_error(const char* fmt, ...);
 int require_ctx(const char* fn, const nerf_ctx* c);                      // "NULL context"
 int require_grid(const char* fn, const nerf_sparse_grid* grid);          // "NULL grid"
-// for the entry points that read or write an fp32 SH table through the handle: a grid of nerf_grid_create_half is refused
+// for the entry points that read or write an fp32 SH table through the handle: a grid of nerf_grid_create_half or of
+// nerf_grid_create_palette is refused
 int refuse_half_grid(const char* fn, const nerf_sparse_grid* grid);
+// for every training, autograd, resampling and TV entry point, also those that read density only: a grid of
+// nerf_grid_create_palette is refused
+int refuse_palette_grid(const char* fn, const nerf_sparse_grid* grid);
 // the link check of nerf_grid_create / nerf_grid_create_half: synchronises `s`; NERF_E_INVALID for a link >= capacity
 int check_grid_links(const char* fn, const int32_t* links, int64_t n, int64_t capacity, hipStream_t s);
 // reso not NULL, every side in [2, 1024] (so that a cell exists on every axis), at most 2^30 nodes
@@ -346,6 +351,42 @@ hipError_t launch_grid_unpack_half(const uint16_t* sh_half, int64_t rows, int ba
 hipError_t launch_grid_half_render(const GridDev& g, const GridRenderOpt& o, const GridRender& r, bool pair, hipStream_t s);
 hipError_t launch_grid_half_sample(const GridDev& g, const float* points, int64_t n, int grid_coords, int want_colors,
                                    float* density, float* sh, hipStream_t s);
+
+// ---- palette-quantised colours (grid_palette_kernels.hip, grid_median_cut_kernels.hip) ----
+// The colour tables of a palette grid; Q = basis_dim - retain. Passed to the palette kernels beside GridDev, whose sh and
+// sh_half are nullptr on such a grid: GridDev, and with it the arguments of every other kernel, stays as it was.
+struct GridPalette {
+    const uint16_t* map;               // [capacity, Q] palette indices, node-major, rows not padded
+    const uint16_t* colors;            // [Q, entries, 3] fp16
+    const uint16_t* retained;          // [capacity, retain, 3] fp16
+    int32_t retain, entries;           // entries = 2^bits
+};
+
+struct GridMedianCut {
+    const float* colors;               // [m, 3]
+    int64_t m;
+    int32_t bits;
+    uint16_t* ids;                     // [m]
+    uint16_t* palette;                 // [2^bits, 3] fp16
+    void* workspace;
+};
+
+// byte offsets into the workspace of a median cut, and its size; needs no device
+struct GridMedianCutLayout {
+    size_t keys, perm, minmax, minmax_bytes, nonfinite, sort, sort_bytes, total;
+};
+void grid_median_cut_layout(int64_t m, int bits, GridMedianCutLayout* l);
+// fills the identity order and counts the rows with a non-finite component into workspace + l.nonfinite (uint64)
+hipError_t launch_grid_median_cut_count(const GridMedianCut& a, const GridMedianCutLayout& l, hipStream_t s);
+// the cut itself, after launch_grid_median_cut_count found nothing; hipErrorOutOfMemory if the sort wants more than l.sort_bytes
+hipError_t launch_grid_median_cut(const GridMedianCut& a, const GridMedianCutLayout& l, hipStream_t s);
+// the palette twins of launch_grid_render / launch_grid_sample: the results of the fp32 kernels on the dequantised table
+hipError_t launch_grid_palette_render(const GridDev& g, const GridPalette& p, const GridRenderOpt& o, const GridRender& r,
+                                      hipStream_t s);
+hipError_t launch_grid_palette_sample(const GridDev& g, const GridPalette& p, const float* points, int64_t n, int grid_coords,
+                                      int want_colors, float* density, float* sh, hipStream_t s);
+// *out (device) = 1 if any of the n indices is >= entries, else 0
+hipError_t launch_grid_palette_check(const uint16_t* map, int64_t n, int entries, int* out, hipStream_t s);
 
 // ---- background layers (grid_background_kernels.hip) ----
 struct GridBg {
@@ -433,4 +474,6 @@ struct nerf_sparse_grid {
     bool half = false;                 // made by nerf_grid_create_half: g.sh_half is the colour table, g.sh is nullptr
     bool half_pair = false;            // ... and it renders with two coefficients per lane
     nerf::GridBg bg{};                 // nerf_grid_set_background; bg.links == nullptr: none
+    bool palette = false;              // made by nerf_grid_create_palette: `pal` holds the colours, g.sh and g.sh_half are nullptr
+    nerf::GridPalette pal{};
 };

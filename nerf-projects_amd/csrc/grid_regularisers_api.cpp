@@ -43,6 +43,8 @@ int tv_value(const char* fn, bool backward, nerf_sparse_grid* grid, const nerf_g
         return NERF_E_INVALID;
     }
     // ---- from here on the handle is read ----
+    rc = refuse_palette_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
     if (a->target == NERF_GRID_TV_SH) {
         rc = refuse_half_grid(fn, grid);
         if (rc != NERF_OK) return rc;
@@ -99,6 +101,8 @@ int sparsity(const char* fn, bool backward, nerf_sparse_grid* grid, const nerf_g
         return NERF_E_INVALID;
     }
     if (a->n_rays == 0) return NERF_OK;
+    rc = refuse_palette_grid(fn, grid);      // (the first read of the handle)
+    if (rc != NERF_OK) return rc;
     GridSparsity r{a->origins, a->dirs, a->n_rays, a->sparsity, a->grad_sparsity, a->grad_density};
     GridDev g = grid->g;
     g.skip = a->use_skip ? grid->d_skip : nullptr;

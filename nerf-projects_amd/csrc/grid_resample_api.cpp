@@ -29,6 +29,8 @@ int nerf_grid_lattice_density(nerf_sparse_grid* grid, const nerf_grid_lattice_ar
     for (int k = 0; k < 3; ++k) l.size[k] = a->reso[k];
     l.density = a->density;
     // ---- from here on the handle is read ----
+    rc = refuse_palette_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
     GridDev g = grid->g;
     g.skip = nullptr;
     DeviceGuard dg(grid->ctx->device);

@@ -105,6 +105,8 @@ int tv_grad(const char* fn, bool edge_entry, nerf_sparse_grid* grid, const nerf_
         return NERF_E_INVALID;
     }
     // ---- from here on the handle is read ----
+    rc = refuse_palette_grid(fn, grid);
+    if (rc != NERF_OK) return rc;
     if (a->target == NERF_GRID_TV_SH) {
         rc = refuse_half_grid(fn, grid);
         if (rc != NERF_OK) return rc;

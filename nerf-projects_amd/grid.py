@@ -241,6 +241,8 @@ def _refuse_half(grid, who):
     ``NotImplementedError`` for a ``grid_background.BackgroundGrid`` where only a foreground is handled."""
     if getattr(grid, "is_half", False):
         raise TypeError(f"{who} reads or writes the fp32 SH table of a SparseGrid and a HalfGrid has none: pass grid.to_float()")
+    if getattr(grid, "is_palette", False):
+        raise TypeError(f"{who} reads or writes the fp32 SH table of a SparseGrid and a PaletteGrid has none: pass grid.to_float()")
     if getattr(grid, "use_background", False):
         raise NotImplementedError(f"{who} is built for the foreground only (training, resampling and pruning a background are "
                                   "not): pass grid.foreground(), the SparseGrid on the same tensors")
@@ -631,6 +633,12 @@ class SparseGrid:
         """``grid_half.HalfGrid.from_grid(self)``: the inference twin of this grid with its colours in fp16 on the device."""
         from .grid_half import HalfGrid
         return HalfGrid.from_grid(self, lanes=lanes)
+
+    def to_palette(self, bits=16, retain=0, sigma_thresh=None):
+        """``grid_palette.PaletteGrid.from_grid(self, ...)``: the inference twin of this grid with one palette index per node
+        and basis function in place of its colours."""
+        from .grid_palette import PaletteGrid
+        return PaletteGrid.from_grid(self, bits=bits, retain=retain, sigma_thresh=sigma_thresh)
 
     def accelerate(self):
         """Build the empty-space skip data on the device from the CURRENT links (a separate array; ``links`` is not written)."""

@@ -93,7 +93,7 @@ class BackgroundGrid(SparseGrid):
     def from_grid(cls, grid: SparseGrid, background_nlayers: int, background_reso: int = 256):
         """``grid`` with a fresh background (every texel has a row, all zeros): the foreground tensors are shared with
         ``grid``, ``opt`` is a copy."""
-        if not isinstance(grid, SparseGrid) or getattr(grid, "is_half", False):
+        if not isinstance(grid, SparseGrid) or getattr(grid, "is_half", False) or getattr(grid, "is_palette", False):
             raise TypeError("BackgroundGrid.from_grid needs a SparseGrid (fp32 colours)")
         L, R = _check_nlayers_reso(background_nlayers, background_reso)
         dev = grid.ctx.device
