@@ -1135,7 +1135,8 @@ int nerf_grid_gather(nerf_sparse_grid* grid, const nerf_grid_gather_args* args);
  * nerf_grid_copy_rows: the tables of a grid that keeps a subset of another grid's nodes on the same lattice. For every node
  * with new_links[node] in [0, new_rows) and old_links[node] in [0, old_rows): row new_links[node] of density / sh = row
  * old_links[node] of old_density / old_sh, copied as 32-bit words (every bit pattern survives, NaN payloads included).
- * src_row is a workspace of new_rows int32. new_rows = 0: nothing is done. */
+ * src_row is a workspace of new_rows int32. new_rows = 0: nothing is done. old_rows is the old grid's capacity, in [0, 2^31): it
+ * may exceed the nodes of the lattice (rows no link names); new_rows is at most old_rows and at most the nodes. */
 #define NERF_E_INTERNAL (-5)    /* a device-side consistency check failed   */
 
 typedef struct nerf_grid_occupancy_args {

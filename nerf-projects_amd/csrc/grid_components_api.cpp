@@ -149,9 +149,10 @@ int nerf_grid_copy_rows(nerf_ctx* c, const nerf_grid_copy_rows_args* a) {
         set_error("%s: cols = %d outside [1, 27]", fn, a->cols);
         return NERF_E_INVALID;
     }
-    if (a->old_rows < 0 || a->old_rows > n || a->new_rows < 0 || a->new_rows > a->old_rows) {
-        set_error("%s: old_rows = %lld must be in [0, %lld] and new_rows = %lld in [0, old_rows]", fn, (long long)a->old_rows,
-                  (long long)n, (long long)a->new_rows);
+    // old_rows is a grid's capacity, which may exceed the nodes of its lattice (rows no link names); new_rows numbers nodes
+    if (a->old_rows < 0 || a->old_rows > 0x7fffffffLL || a->new_rows < 0 || a->new_rows > a->old_rows || a->new_rows > n) {
+        set_error("%s: old_rows = %lld must be in [0, 2^31) and new_rows = %lld in [0, min(old_rows, %lld)]", fn,
+                  (long long)a->old_rows, (long long)a->new_rows, (long long)n);
         return NERF_E_INVALID;
     }
     if (a->new_rows == 0) return NERF_OK;

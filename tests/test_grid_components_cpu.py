@@ -273,8 +273,12 @@ def test_component_calls_refuse_bad_arguments_before_any_device_call():
     assert lib.nerf_grid_copy_rows(fake, C.byref(r)) == 0      # no rows: nothing is done
     r.old_rows, r.new_rows = 5, 6
     assert lib.nerf_grid_copy_rows(fake, C.byref(r)) == -1 and "new_rows" in err()
-    r.old_rows, r.new_rows = 65, 6
+    r.old_rows, r.new_rows = 1 << 31, 6      # a capacity may exceed the 64 nodes of the lattice, up to the ABI's 2^31 - 1 rows
     assert lib.nerf_grid_copy_rows(fake, C.byref(r)) == -1 and "old_rows" in err()
+    r.old_rows, r.new_rows = 100, 65          # ... the new rows, one per kept node, may not
+    assert lib.nerf_grid_copy_rows(fake, C.byref(r)) == -1 and "new_rows" in err()
+    r.old_rows, r.new_rows = (1 << 31) - 1, 6
+    assert lib.nerf_grid_copy_rows(fake, C.byref(r)) == -1 and "required" in err()
     r.old_rows = 10
     assert lib.nerf_grid_copy_rows(fake, C.byref(r)) == -1 and "required" in err()
     r.cols = 0

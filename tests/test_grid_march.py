@@ -6,72 +6,15 @@ import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from grid_size_edges_lib import N_RAYS, hand_made_grid, hand_made_rays
 
-RESO = 24
-N_RAYS = 67      # 2, 4 or 16 rays per wavefront at basis_dim 9, 4, 1: the last wavefront holds a partial set of groups
+pytestmark = pytest.mark.gpu      # (the hand-made grid and its rays: grid_size_edges_lib.py, shared with the size-edge tests)
 
 
 @pytest.fixture(scope="module")
 def N():
     import nerf_projects_amd as pkg
     return pkg
-
-
-def hand_made_grid(basis_dim):
-    """24^3 nodes around the origin (node i at (i - 11.5) / 12): a kept ball of radius 8 nodes, dense enough that a ray
-    through its middle stops at stop_thresh, and a kept slab two nodes thick on the upper x face, thin enough to see through.
-    Rows in random order; empty links are -1 or below."""
-    rng = np.random.default_rng(24 + basis_dim)
-    i, j, k = np.meshgrid(*(np.arange(RESO, dtype=np.float64),) * 3, indexing="ij")
-    r = np.sqrt((i - 11.5) ** 2 + (j - 11.5) ** 2 + (k - 11.5) ** 2)
-    ball = r <= 8.0
-    slab = np.zeros_like(ball)
-    slab[RESO - 2:, 4:20, 4:20] = True
-    kept = ball | slab
-    n = int(kept.sum())
-    links = np.where(rng.uniform(size=kept.shape) < 0.5, -1, -3).astype(np.int32)
-    rows = rng.permutation(n).astype(np.int32)
-    links[kept] = rows
-    density = np.zeros((n, 1), np.float32)
-    density[links[ball], 0] = (60.0 * (1.0 - r[ball] / 9.0)).astype(np.float32)      # 60 in the middle, 6.7 at the rim
-    density[links[slab & ~ball], 0] = 2.0
-    sh = (0.5 * rng.normal(size=(n, 3 * basis_dim))).astype(np.float32)
-    return links, density, sh
-
-
-def hand_made_rays():
-    """67 rays, directions not unit: 30 through the ball (9 of them along +x towards it, through the slab), 12 grazing it,
-    8 missing the box, 14 starting inside it, one zero direction, one NaN origin, one infinite origin."""
-    rng = np.random.default_rng(67)
-
-    def unit(v):
-        return v / np.linalg.norm(v, axis=-1, keepdims=True)
-
-    o, d = [], []
-    # through the ball: from a sphere of radius 2.5 towards a point within 0.2 of the centre
-    src = 2.5 * unit(rng.normal(size=(30, 3)))
-    src[:9] = [2.5, 0.0, 0.0] + 0.3 * rng.uniform(-1, 1, (9, 3))
-    o.append(src)
-    d.append(rng.uniform(-0.2, 0.2, (30, 3)) - src)
-    # grazing: past the centre at 0.6 .. 0.72 (the ball's rim is at 8 / 12)
-    src = 2.5 * unit(rng.normal(size=(12, 3)))
-    side = unit(np.cross(src, rng.normal(size=(12, 3))))
-    o.append(src)
-    d.append(side * rng.uniform(0.6, 0.72, (12, 1)) - src)
-    # missing the box: pointing away from it
-    src = 2.5 * unit(rng.normal(size=(8, 3)))
-    o.append(src)
-    d.append(src + 0.3 * rng.normal(size=(8, 3)))
-    # starting inside the box (most of them inside the ball)
-    o.append(rng.uniform(-0.9, 0.9, (14, 3)))
-    d.append(rng.normal(size=(14, 3)))
-    o, d = np.concatenate(o), np.concatenate(d)
-    d *= rng.uniform(0.25, 4.0, (len(d), 1))
-    o = np.concatenate([o, [[0.1, 0.2, 2.5], [np.nan, 0.0, 2.5], [np.inf, 0.0, 0.0]]])
-    d = np.concatenate([d, [[0.0, 0.0, 0.0], [0.0, 0.0, -1.0], [-1.0, 0.0, 0.0]]])
-    assert o.shape == (N_RAYS, 3) and d.shape == (N_RAYS, 3)
-    return o.astype(np.float32), d.astype(np.float32)
 
 
 def march_everything(N, grid, rays, gt):
