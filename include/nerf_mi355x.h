@@ -1900,6 +1900,79 @@ typedef struct nerf_grid_dataset_batch_args {
 
 int nerf_grid_dataset_batch(nerf_ctx* ctx, const nerf_grid_dataset_batch_args* args);
 
+/* Sparse voxel grid: surface meshes ----------------------------------------------------------------
+ * A coloured triangle mesh of a grid's density field, on the grid's own lattice: no volume is resampled or materialised. Both
+ * calls take a grid of nerf_grid_create, nerf_grid_create_half or nerf_grid_create_palette; background layers attached to it
+ * are not read (they have no surface).
+ *
+ * The node value, for both calls. With p = (i, j, k) a node and n its C-order index:
+ *     v(p) = density_data[links[n]]   where links[n] is in [0, capacity) and (mask == NULL or mask[n] != 0)
+ *     v(p) = 0                        elsewhere: an empty node (any negative link) and a masked-out node
+ * mask is [dev] uint8 [X, Y, Z]. Rows may be numbered in any order, two nodes may name one row, rows may be unreferenced.
+ *
+ * nerf_grid_marching_cubes: the isosurface v = iso. iso must be finite and > 0 (NERF_E_INVALID otherwise), so that an empty
+ * node is outside. Every convention is nerf_marching_cubes' ("Mesh extraction": inside iff v >= iso and a NaN outside; one
+ * welded vertex per crossing edge at t = (iso - a) / (b - a) in fp32, 0.5 when t is not finite; vertices in index coordinates
+ * ordered by edge key, triangles by cell and table order; no atomics; both output pointers NULL = count only; a capacity too
+ * small = NERF_E_INVALID, nothing written, the counts reported; `stream` is synchronised), and the result equals, in every bit
+ * and in order, nerf_marching_cubes on the volume V[n] = v(p) with the same iso: the same kernels run with another source of
+ * the node values. The passes read `links` as coalesced runs (and the mask's bytes beside them) and gather a density only
+ * where a link is kept. The scratch is the context's workspace as for nerf_marching_cubes (nerf_workspace_bytes includes it:
+ * 2 bytes per node and a few per 2048 nodes). A vertex in index coordinates x sits at the world position
+ * center - radius + (x + 0.5) * 2 radius / reso ("Sparse voxel grid", Geometry).
+ *
+ * nerf_grid_mesh_attributes: normals and colours at n points given in index (grid) coordinates - the vertices above, or any
+ * other points: a point cloud. A point's cell and weights are nerf_grid_sample's with grid_coords: x clamped to [0, reso - 1],
+ * l = min(int(x), reso - 2), w = x - l, and every interpolation below is its trilinear one (z, then y, then x, fp32, each
+ * operation rounded) over the 8 nodes of that cell. On a lattice edge all but two of the weights are zero, so a vertex needs
+ * no record of its edge.
+ *   Gradient. At a node q, G(q)_b = h_b (v(q + e_b) - v(q - e_b)) with a neighbour outside the lattice replaced by q itself,
+ *     h_b = 0.5 where both neighbours exist and 1 at a border node. g = the interpolation of G at the point (index units).
+ *   Normal. gw_b = g_b * scaling_b with scaling_b = reso_b / (2 radius_b) (the grid's own fp32 value), the gradient in world
+ *     units; normal = -gw / |gw|, (0, 0, 0) where |gw| is 0 or not finite. -grad sigma points out of the region v >= iso:
+ *     the side the triangles' right-hand normals face. |gw| is formed after dividing gw by its largest component.
+ *   SH row. S[c][k], c < 3, k < basis_dim, is the interpolation of the rows' coefficients (an empty node is 0; the mask does
+ *     not enter): bit for bit what nerf_grid_sample returns at the point, for each kind of grid from its own table.
+ *   Colour, per channel c: clamp(0.5 + sum_{k < K} S[c][k] Y_k(d), 0, 1), Y the renderer's SH basis, the sum in order of k.
+ *     NERF_GRID_MESH_COLOR_DC    K = 1 (Y_0 = 0.28209479177387814), no direction
+ *     NERF_GRID_MESH_COLOR_SH    K = basis_dim, d = -normal: the ray that meets the surface head-on. Where the normal is
+ *                                (0, 0, 0) the colour is NERF_GRID_MESH_COLOR_DC's.
+ *     NERF_GRID_MESH_COLOR_VIEW  K = basis_dim, d = view, a unit vector (|view|^2 within 1e-5 of 1), the same for all points
+ *     NERF_GRID_MESH_COLOR_NONE  no colours; `colors` must be NULL (and must not be with any other mode)
+ *   normals may be NULL (not wanted). Stream-ordered, nothing is synchronised, no workspace. n <= 2^26. */
+#define NERF_GRID_MESH_COLOR_NONE 0
+#define NERF_GRID_MESH_COLOR_DC 1
+#define NERF_GRID_MESH_COLOR_SH 2
+#define NERF_GRID_MESH_COLOR_VIEW 3
+
+typedef struct nerf_grid_mc_args {
+    size_t struct_size;
+    const uint8_t* mask;        /* [dev] [X, Y, Z] or NULL                                                          */
+    float iso;                  /* finite, > 0                                                                      */
+    float* vertices;            /* [dev] [vertex_capacity, 3] index coordinates, or NULL (count only)               */
+    int64_t vertex_capacity;
+    int64_t* triangles;         /* [dev] [triangle_capacity, 3] or NULL (count only)                                */
+    int64_t triangle_capacity;
+    int64_t* n_vertices;        /* [host] out                                                                       */
+    int64_t* n_triangles;       /* [host] out                                                                       */
+    void* stream;
+} nerf_grid_mc_args;
+
+typedef struct nerf_grid_mesh_attributes_args {
+    size_t struct_size;
+    const float* points;        /* [dev] [n, 3] index coordinates                                                   */
+    int64_t n;
+    const uint8_t* mask;        /* [dev] [X, Y, Z] or NULL: the mask of the extraction                              */
+    int32_t color_mode;         /* NERF_GRID_MESH_COLOR_*                                                           */
+    float view[3];              /* NERF_GRID_MESH_COLOR_VIEW: the unit direction                                    */
+    float* normals;             /* [dev] [n, 3] or NULL                                                             */
+    float* colors;              /* [dev] [n, 3] in [0, 1], or NULL with NERF_GRID_MESH_COLOR_NONE                   */
+    void* stream;
+} nerf_grid_mesh_attributes_args;
+
+int nerf_grid_marching_cubes(nerf_sparse_grid* grid, const nerf_grid_mc_args* args);
+int nerf_grid_mesh_attributes(nerf_sparse_grid* grid, const nerf_grid_mesh_attributes_args* args);
+
 #ifdef __cplusplus
 }
 #endif

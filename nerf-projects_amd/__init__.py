@@ -40,6 +40,8 @@ from .grid_floater_views import (component_view, floater_overlay_on_render, main
                                  project_floaters_to_view)
 from . import grid_dataset  # noqa: F401
 from .grid_dataset import GridDataset  # noqa: F401
+from . import grid_mesh  # noqa: F401
+from .grid_mesh import GridMesh, extract_mesh, mesh_attributes  # noqa: F401
 from . import grid_fit  # noqa: F401
 from .grid_fit import GridTrainConfig, expon_lr, train_grid  # noqa: F401
 

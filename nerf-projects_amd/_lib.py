@@ -46,6 +46,7 @@ EXPORTS = (
     "nerf_grid_tv_value_workspace", "nerf_grid_tv_value", "nerf_grid_tv_value_backward",
     "nerf_grid_sparsity_rays", "nerf_grid_sparsity_backward",
     "nerf_grid_dataset_batch",
+    "nerf_grid_marching_cubes", "nerf_grid_mesh_attributes",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -58,6 +59,7 @@ NERF_GRID_DEPTH_EXPECTED, NERF_GRID_DEPTH_THRESHOLD, NERF_GRID_DEPTH_RAYLEN = 0,
 NERF_GRID_FLOATER_COUNTER_INTS = 8192
 NERF_GRID_HALF_LANES_DEFAULT, NERF_GRID_HALF_LANES_SINGLE, NERF_GRID_HALF_LANES_PAIR = 0, 1, 2
 NERF_GRID_ORDER_IDENTITY, NERF_GRID_ORDER_PERMUTED, NERF_GRID_ORDER_RANDOM = 0, 1, 2
+NERF_GRID_MESH_COLOR_NONE, NERF_GRID_MESH_COLOR_DC, NERF_GRID_MESH_COLOR_SH, NERF_GRID_MESH_COLOR_VIEW = 0, 1, 2, 3
 
 
 class NerfArch(C.Structure):
@@ -377,6 +379,17 @@ class GridDatasetBatchArgs(_Sized):
                 ("stream", C.c_void_p)]
 
 
+class GridMcArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("mask", _FP), ("iso", C.c_float), ("vertices", _FP),
+                ("vertex_capacity", C.c_int64), ("triangles", _FP), ("triangle_capacity", C.c_int64),
+                ("n_vertices", C.POINTER(C.c_int64)), ("n_triangles", C.POINTER(C.c_int64)), ("stream", C.c_void_p)]
+
+
+class GridMeshAttributesArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("points", _FP), ("n", C.c_int64), ("mask", _FP), ("color_mode", C.c_int32),
+                ("view", C.c_float * 3), ("normals", _FP), ("colors", _FP), ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -631,6 +644,10 @@ def load():
     lib.nerf_grid_sparsity_backward.argtypes = [vp, C.POINTER(GridRenderOptions), C.POINTER(GridSparsityArgs)]
     lib.nerf_grid_dataset_batch.restype = i32
     lib.nerf_grid_dataset_batch.argtypes = [vp, C.POINTER(GridDatasetBatchArgs)]
+    lib.nerf_grid_marching_cubes.restype = i32
+    lib.nerf_grid_marching_cubes.argtypes = [vp, C.POINTER(GridMcArgs)]
+    lib.nerf_grid_mesh_attributes.restype = i32
+    lib.nerf_grid_mesh_attributes.argtypes = [vp, C.POINTER(GridMeshAttributesArgs)]
     _lib = lib
     return lib
 

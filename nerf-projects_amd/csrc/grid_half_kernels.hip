@@ -18,12 +18,10 @@
 //           (6 busy): 4 / 8 rays per wavefront, the same number of load instructions per lane and sample. The busy lane l
 //           reads word l of the row. basis_dim 1 has no pairs and renders with `single`.
 // As in grid_kernels.hip all control flow is uniform inside a group, no LDS, no scratch, 256-thread workgroups.
-#include "grid_device.h"
+#include "grid_fetch_device.h"      // widen
 
 namespace nerf {
 namespace {
-
-__device__ __forceinline__ float widen(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 
 // ---- pack / unpack ----------------------------------------------------------------------------------------------------------
 // one thread per slot of the packed rows (pad slots included: they are written as zero)

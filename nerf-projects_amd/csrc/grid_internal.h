@@ -12,6 +12,7 @@
 //   grid_background_api.cpp background layers: attach / detach, the background pass, the two calls of the thinning
 //   grid_background_train_api.cpp   background layers, training: taped pass, backward, TV gradient, optimiser step
 //   grid_dataset_api.cpp    training data: a batch of rays from the resident images (takes a context, no grid)
+//   grid_mesh_api.cpp       surface meshes: marching cubes on the grid's own lattice, normals and colours at points
 //   grid_*_kernels.hip      the kernels of each, on grid_device.h (sampling, rays) and compact_device.h (compaction)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -387,6 +388,22 @@ hipError_t launch_grid_palette_sample(const GridDev& g, const GridPalette& p, co
                                       int want_colors, float* density, float* sh, hipStream_t s);
 // *out (device) = 1 if any of the n indices is >= entries, else 0
 hipError_t launch_grid_palette_check(const uint16_t* map, int64_t n, int entries, int* out, hipStream_t s);
+
+// ---- surface meshes (grid_mesh_kernels.hip; the extraction itself is mesh_kernels.hip's, nerf_internal.h) ----
+struct GridMeshAttr {
+    const float* points;               // [n, 3] grid coordinates
+    int64_t n;
+    const uint8_t* mask;               // [X, Y, Z] or nullptr
+    int32_t color_mode;                // NERF_GRID_MESH_COLOR_*
+    float view[3];                     // unit direction of NERF_GRID_MESH_COLOR_VIEW
+    float* normals;                    // [n, 3] or nullptr
+    float* colors;                     // [n, 3]; nullptr iff color_mode is NERF_GRID_MESH_COLOR_NONE
+    int32_t half_channel, half_row;    // set by the launcher: the layout of a packed half row
+};
+
+// `p` is read on a palette grid only; half / palette say which colour table `g` carries
+hipError_t launch_grid_mesh_attributes(const GridDev& g, const GridPalette& p, bool half, bool palette, const GridMeshAttr& a,
+                                       hipStream_t s);
 
 // ---- background layers (grid_background_kernels.hip) ----
 struct GridBg {

@@ -11,6 +11,10 @@
 //                            through the per-point record of the first pass
 // The per-point record is 16 bits: the prefix (< 3 * kMcTile = 6144, 13 bits) << 3 | the crossing mask. The triangle table
 // is generated once on the host (build_tri_table) and copied to __constant__ memory.
+//
+// The kernels are templates over where a node's value comes from (McVolume, McGridVolume below): nerf_grid_marching_cubes
+// (include/nerf_mi355x.h, "Sparse voxel grid: surface meshes") runs the same passes on a sparse voxel grid's links and
+// density table, and so returns what nerf_marching_cubes returns on the densified volume, bit for bit and in order.
 #include <cstring>
 #include <mutex>
 
@@ -31,14 +35,64 @@ __constant__ int8_t c_edge_axis[12] = {0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2};
 __constant__ int8_t c_tri[256][16];               // up to 5 triangles as edge triples, -1 terminated
 __constant__ int8_t c_ntri[256];
 
+__device__ __forceinline__ bool mc_inside(float v, float iso) { return v >= iso; }      // NaN is outside
+
+// Where the node values come from. A source has X, Y, Z, iso, at(p) = the value of lattice point p (C order) and
+// load_run(p0, P, v) = the kMcPer values from p0 on (0 past the end). Every kernel below is written once over a source: the
+// passes, the records, the order and the arithmetic of a vertex are the same for all of them.
+//
+// a dense fp32 volume (nerf_marching_cubes)
 struct McVolume {
     const float* v;
     uint32_t X, Y, Z;
     float iso;
     int vec;            // 16-byte aligned: a thread's own 8 values come in two 16-byte loads
+
+    __device__ __forceinline__ float at(uint32_t p) const { return v[p]; }
+    // the thread's kMcPer values starting at lattice point p0 (vector loads when they all exist and the volume is aligned)
+    __device__ __forceinline__ void load_run(uint32_t p0, uint32_t P, float (&out)[kMcPer]) const {
+        if (vec && p0 + kMcPer <= P) {
+            const float4 a = *(const float4*)(v + p0);
+            const float4 b = *(const float4*)(v + p0 + 4);
+            out[0] = a.x; out[1] = a.y; out[2] = a.z; out[3] = a.w;
+            out[4] = b.x; out[5] = b.y; out[6] = b.z; out[7] = b.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < kMcPer; ++q) out[q] = p0 + q < P ? v[p0 + q] : 0.0f;
+        }
+    }
 };
 
-__device__ __forceinline__ bool mc_inside(float v, float iso) { return v >= iso; }      // NaN is outside
+// a sparse voxel grid (nerf_grid_marching_cubes): the density of the node's row where its link is kept and its mask byte is
+// not 0, else 0. Only `links` is streamed; a density is gathered where a link is kept, and no volume is written anywhere.
+struct McGridVolume {
+    const int32_t* links;
+    const float* density;
+    const uint8_t* mask;      // [X, Y, Z] or nullptr
+    int64_t capacity;
+    uint32_t X, Y, Z;
+    float iso;
+    int vec;            // links 16-byte aligned
+
+    __device__ __forceinline__ float value(int32_t link, uint32_t p) const {
+        if (link < 0 || (int64_t)link >= capacity) return 0.0f;
+        if (mask && !mask[p]) return 0.0f;
+        return density[link];
+    }
+    __device__ __forceinline__ float at(uint32_t p) const { return value(links[p], p); }
+    __device__ __forceinline__ void load_run(uint32_t p0, uint32_t P, float (&out)[kMcPer]) const {
+        if (vec && p0 + kMcPer <= P) {
+            const int4 a = *(const int4*)(links + p0);
+            const int4 b = *(const int4*)(links + p0 + 4);
+            const int32_t l[kMcPer] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+            for (int q = 0; q < kMcPer; ++q) out[q] = value(l[q], p0 + q);
+        } else {
+#pragma unroll
+            for (int q = 0; q < kMcPer; ++q) out[q] = p0 + q < P ? at(p0 + q) : 0.0f;
+        }
+    }
+};
 
 // exclusive prefix over the workgroup of one value per thread; *total = the sum
 template <class T>
@@ -59,35 +113,24 @@ __device__ __forceinline__ T block_exclusive_scan(T x, T* total) {
     return incl - x;
 }
 
-// the thread's kMcPer values starting at lattice point p0 (vector loads when they all exist and the volume is aligned)
-__device__ __forceinline__ void load_run(const McVolume& g, uint32_t p0, uint32_t P, float (&v)[kMcPer]) {
-    if (g.vec && p0 + kMcPer <= P) {
-        const float4 a = *(const float4*)(g.v + p0);
-        const float4 b = *(const float4*)(g.v + p0 + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-#pragma unroll
-        for (int q = 0; q < kMcPer; ++q) v[q] = p0 + q < P ? g.v[p0 + q] : 0.0f;
-    }
-}
-
 // crossing mask of lattice point p (value vp): bit a set iff the edge to p + e_a exists and its ends classify differently
-__device__ __forceinline__ unsigned edge_mask(const McVolume& g, uint32_t p, float vp) {
+template <class Vol>
+__device__ __forceinline__ unsigned edge_mask(const Vol& g, uint32_t p, float vp) {
     const uint32_t k = p % g.Z, ij = p / g.Z, j = ij % g.Y, i = ij / g.Y;
     const bool in = mc_inside(vp, g.iso);
     unsigned m = 0;
-    if (i + 1 < g.X && mc_inside(g.v[p + g.Y * g.Z], g.iso) != in) m |= 1u;
-    if (j + 1 < g.Y && mc_inside(g.v[p + g.Z], g.iso) != in) m |= 2u;
-    if (k + 1 < g.Z && mc_inside(g.v[p + 1], g.iso) != in) m |= 4u;
+    if (i + 1 < g.X && mc_inside(g.at(p + g.Y * g.Z), g.iso) != in) m |= 1u;
+    if (j + 1 < g.Y && mc_inside(g.at(p + g.Z), g.iso) != in) m |= 2u;
+    if (k + 1 < g.Z && mc_inside(g.at(p + 1), g.iso) != in) m |= 4u;
     return m;
 }
 
-__global__ __launch_bounds__(kMcThreads) void mc_edge_count_kernel(const McVolume g, uint16_t* rec, int* tile_count) {
+template <class Vol>
+__global__ __launch_bounds__(kMcThreads) void mc_edge_count_kernel(const Vol g, uint16_t* rec, int* tile_count) {
     const uint32_t P = g.X * g.Y * g.Z;
     const uint32_t p0 = blockIdx.x * kMcTile + threadIdx.x * kMcPer;
     float v[kMcPer];
-    load_run(g, p0, P, v);
+    g.load_run(p0, P, v);
     unsigned m[kMcPer];
     int n = 0;
 #pragma unroll
@@ -106,19 +149,21 @@ __global__ __launch_bounds__(kMcThreads) void mc_edge_count_kernel(const McVolum
 }
 
 // case index of cell c (C order over [X-1, Y-1, Z-1]) and the linear index of its corner 0
-__device__ __forceinline__ unsigned cell_case(const McVolume& g, uint32_t c, uint32_t* p_out) {
+template <class Vol>
+__device__ __forceinline__ unsigned cell_case(const Vol& g, uint32_t c, uint32_t* p_out) {
     const uint32_t Zc = g.Z - 1, Yc = g.Y - 1;
     const uint32_t ck = c % Zc, cij = c / Zc, cj = cij % Yc, ci = cij / Yc;
     const uint32_t p = (ci * g.Y + cj) * g.Z + ck, YZ = g.Y * g.Z;
     const uint32_t off[8] = {0u, 1u, g.Z, g.Z + 1u, YZ, YZ + 1u, YZ + g.Z, YZ + g.Z + 1u};
     unsigned cs = 0;
 #pragma unroll
-    for (int v = 0; v < 8; ++v) cs |= mc_inside(g.v[p + off[v]], g.iso) ? (1u << v) : 0u;
+    for (int v = 0; v < 8; ++v) cs |= mc_inside(g.at(p + off[v]), g.iso) ? (1u << v) : 0u;
     *p_out = p;
     return cs;
 }
 
-__global__ __launch_bounds__(kMcThreads) void mc_cell_count_kernel(const McVolume g, int* tile_count) {
+template <class Vol>
+__global__ __launch_bounds__(kMcThreads) void mc_cell_count_kernel(const Vol g, int* tile_count) {
     const uint32_t C = (g.X - 1) * (g.Y - 1) * (g.Z - 1);
     const uint32_t c0 = blockIdx.x * kMcTile + threadIdx.x * kMcPer;
     int n = 0;
@@ -156,12 +201,12 @@ __global__ __launch_bounds__(kMcThreads) void mc_scan_kernel(const ScanJob j) {
     if (threadIdx.x == 0) j.totals[b] = total;
 }
 
-__global__ __launch_bounds__(kMcThreads) void mc_vertex_kernel(const McVolume g, const uint16_t* rec, const int64_t* tile_off,
-                                                               float* out) {
+template <class Vol>
+__global__ __launch_bounds__(kMcThreads) void mc_vertex_kernel(const Vol g, const uint16_t* rec, const int64_t* tile_off, float* out) {
     const uint32_t P = g.X * g.Y * g.Z;
     const uint32_t p0 = blockIdx.x * kMcTile + threadIdx.x * kMcPer;
     float v[kMcPer];
-    load_run(g, p0, P, v);
+    g.load_run(p0, P, v);
     const int64_t base = tile_off[blockIdx.x];
     for (int q = 0; q < kMcPer; ++q) {
         const uint32_t p = p0 + q;
@@ -173,7 +218,7 @@ __global__ __launch_bounds__(kMcThreads) void mc_vertex_kernel(const McVolume g,
         const uint32_t stride[3] = {g.Y * g.Z, g.Z, 1u};
         for (int ax = 0; ax < 3; ++ax) {
             if (!((r >> ax) & 1u)) continue;
-            const float a = v[q], b = g.v[p + stride[ax]];
+            const float a = v[q], b = g.at(p + stride[ax]);
             float t = (g.iso - a) / (b - a);
             if (!(fabsf(t) <= 3.4028234663852886e38f)) t = 0.5f;      // a NaN or infinite end
             float xyz[3] = {(float)i, (float)j, (float)k};
@@ -186,7 +231,8 @@ __global__ __launch_bounds__(kMcThreads) void mc_vertex_kernel(const McVolume g,
     }
 }
 
-__global__ __launch_bounds__(kMcThreads) void mc_triangle_kernel(const McVolume g, const uint16_t* rec, const int64_t* vtile_off,
+template <class Vol>
+__global__ __launch_bounds__(kMcThreads) void mc_triangle_kernel(const Vol g, const uint16_t* rec, const int64_t* vtile_off,
                                                                  const int64_t* ttile_off, int64_t* out) {
     const uint32_t C = (g.X - 1) * (g.Y - 1) * (g.Z - 1);
     const uint32_t c0 = blockIdx.x * kMcTile + threadIdx.x * kMcPer;
@@ -376,17 +422,18 @@ size_t mc_scratch_bytes(const int32_t reso[3]) {
     return align256(P * 2) + align256(nv * 4) + align256(nt * 4) + align256(nv * 8) + align256(nt * 8) + align256(16);
 }
 
-hipError_t launch_mc_count(const McArgs& m, char* scratch, int64_t* totals_host, hipStream_t s) {
+namespace {
+
+template <class Vol>
+hipError_t mc_count(const Vol& g, const int32_t reso[3], char* scratch, int64_t* totals_host, hipStream_t s) {
     hipError_t e = upload_tri_table();
     if (e != hipSuccess) return e;
-    const McVolume g{m.volume, (uint32_t)m.reso[0], (uint32_t)m.reso[1], (uint32_t)m.reso[2], m.iso,
-                     (reinterpret_cast<uintptr_t>(m.volume) & 15) == 0 ? 1 : 0};
     const uint64_t P = (uint64_t)g.X * g.Y * g.Z, C = (uint64_t)(g.X - 1) * (g.Y - 1) * (g.Z - 1);
     const unsigned nv = (unsigned)((P + kMcTile - 1) / kMcTile), nt = (unsigned)((C + kMcTile - 1) / kMcTile);
-    McScratch w = mc_scratch(m.reso, scratch);
-    hipLaunchKernelGGL(mc_edge_count_kernel, dim3(nv), dim3(kMcThreads), 0, s, g, w.rec, w.vcount);
+    McScratch w = mc_scratch(reso, scratch);
+    hipLaunchKernelGGL(mc_edge_count_kernel<Vol>, dim3(nv), dim3(kMcThreads), 0, s, g, w.rec, w.vcount);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_cell_count_kernel, dim3(nt), dim3(kMcThreads), 0, s, g, w.tcount);
+    hipLaunchKernelGGL(mc_cell_count_kernel<Vol>, dim3(nt), dim3(kMcThreads), 0, s, g, w.tcount);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const ScanJob j{{w.vcount, w.tcount}, {w.voff, w.toff}, {(int)nv, (int)nt}, w.totals};
     hipLaunchKernelGGL(mc_scan_kernel, dim3(2), dim3(kMcThreads), 0, s, j);
@@ -395,17 +442,44 @@ hipError_t launch_mc_count(const McArgs& m, char* scratch, int64_t* totals_host,
     return hipStreamSynchronize(s);
 }
 
-hipError_t launch_mc_emit(const McArgs& m, char* scratch, hipStream_t s) {
-    const McVolume g{m.volume, (uint32_t)m.reso[0], (uint32_t)m.reso[1], (uint32_t)m.reso[2], m.iso,
-                     (reinterpret_cast<uintptr_t>(m.volume) & 15) == 0 ? 1 : 0};
+template <class Vol>
+hipError_t mc_emit(const Vol& g, const int32_t reso[3], char* scratch, float* vertices, int64_t* triangles, hipStream_t s) {
     const uint64_t P = (uint64_t)g.X * g.Y * g.Z, C = (uint64_t)(g.X - 1) * (g.Y - 1) * (g.Z - 1);
     const unsigned nv = (unsigned)((P + kMcTile - 1) / kMcTile), nt = (unsigned)((C + kMcTile - 1) / kMcTile);
-    McScratch w = mc_scratch(m.reso, scratch);
+    McScratch w = mc_scratch(reso, scratch);
     hipError_t e;
-    hipLaunchKernelGGL(mc_vertex_kernel, dim3(nv), dim3(kMcThreads), 0, s, g, w.rec, w.voff, m.vertices);
+    hipLaunchKernelGGL(mc_vertex_kernel<Vol>, dim3(nv), dim3(kMcThreads), 0, s, g, w.rec, w.voff, vertices);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(mc_triangle_kernel, dim3(nt), dim3(kMcThreads), 0, s, g, w.rec, w.voff, w.toff, m.triangles);
+    hipLaunchKernelGGL(mc_triangle_kernel<Vol>, dim3(nt), dim3(kMcThreads), 0, s, g, w.rec, w.voff, w.toff, triangles);
     return hipGetLastError();
+}
+
+McVolume dense_source(const McArgs& m) {
+    return McVolume{m.volume, (uint32_t)m.reso[0], (uint32_t)m.reso[1], (uint32_t)m.reso[2], m.iso,
+                    (reinterpret_cast<uintptr_t>(m.volume) & 15) == 0 ? 1 : 0};
+}
+
+McGridVolume grid_source(const McGridArgs& m) {
+    return McGridVolume{m.links, m.density, m.mask, m.capacity, (uint32_t)m.reso[0], (uint32_t)m.reso[1], (uint32_t)m.reso[2],
+                        m.iso, (reinterpret_cast<uintptr_t>(m.links) & 15) == 0 ? 1 : 0};
+}
+
+}  // namespace
+
+hipError_t launch_mc_count(const McArgs& m, char* scratch, int64_t* totals_host, hipStream_t s) {
+    return mc_count(dense_source(m), m.reso, scratch, totals_host, s);
+}
+
+hipError_t launch_mc_emit(const McArgs& m, char* scratch, hipStream_t s) {
+    return mc_emit(dense_source(m), m.reso, scratch, m.vertices, m.triangles, s);
+}
+
+hipError_t launch_grid_mc_count(const McGridArgs& m, char* scratch, int64_t* totals_host, hipStream_t s) {
+    return mc_count(grid_source(m), m.reso, scratch, totals_host, s);
+}
+
+hipError_t launch_grid_mc_emit(const McGridArgs& m, char* scratch, hipStream_t s) {
+    return mc_emit(grid_source(m), m.reso, scratch, m.vertices, m.triangles, s);
 }
 
 McScratch mc_scratch(const int32_t reso[3], char* base) {

@@ -582,6 +582,20 @@ McScratch mc_scratch(const int32_t reso[3], char* base);
 hipError_t launch_mc_count(const McArgs& m, char* scratch, int64_t* totals_host, hipStream_t s);
 // the emitting passes (after launch_mc_count on the same scratch)
 hipError_t launch_mc_emit(const McArgs& m, char* scratch, hipStream_t s);
+// the same passes with the node values of a sparse voxel grid (nerf_grid_marching_cubes): density[links[p]] where the link is
+// in [0, capacity) and the mask byte (if any) is not 0, else 0. Scratch as above.
+struct McGridArgs {
+    const int32_t* links;    // [X, Y, Z]
+    const float* density;    // [capacity, 1]
+    const uint8_t* mask;     // [X, Y, Z] or nullptr
+    int64_t capacity;
+    int32_t reso[3];
+    float iso;
+    float* vertices;
+    int64_t* triangles;
+};
+hipError_t launch_grid_mc_count(const McGridArgs& m, char* scratch, int64_t* totals_host, hipStream_t s);
+hipError_t launch_grid_mc_emit(const McGridArgs& m, char* scratch, hipStream_t s);
 
 // ---- occupancy grid (occupancy_kernels.hip) -----------------------------------------------------------
 // One bit per cell of the lattice's (X-1) x (Y-1) x (Z-1) cells, 32 cells along z per word: cell (i, j, k) is bit k & 31 of
