@@ -718,11 +718,27 @@ typedef struct nerf_grid_render_options {      /* svox2.RenderOptions as far as 
     int32_t randomize;          /* must be 0 (not built)                                                            */
 } nerf_grid_render_options;
 
-typedef struct nerf_grid_camera {              /* svox2.Camera without NDC. c2w is OpenCV: x right, y down, z forward  */
-    size_t struct_size;
+/* The NDC warp of forward-facing scenes (svox2.utils.convert_to_ndc with near = 1, then the normalisation that its two
+ * callers, Camera.gen_rays and LLFFDataset.gen_rays, apply). rays_to_ndc(cx, cy, o, d), fp32, every operation rounded on its
+ * own, true divisions, a correctly rounded root, in this order:
+ *     t  = (1 - o.z) / d.z
+ *     o  = o + t * d                                    (a product, then a sum: no fused multiply-add)
+ *     o' = (cx * (o.x / o.z),  cy * (o.y / o.z),  1 - 2 / o.z)
+ *     d' = (cx * (d.x / d.z - o.x / o.z),  cy * (d.y / d.z - o.y / o.z),  2 / o.z)
+ *     n  = sqrt(fma(d'.z, d'.z, fma(d'.y, d'.y, d'.x * d'.x)))          (the fma chain of torch.norm's vectorised CPU sum)
+ *     d' = d' / n
+ * (cx, cy) are the ndc_coeffs (2 fx / width, 2 fy / height of the full-resolution images). Non-finite results (d.z == 0,
+ * o.z == 0) are passed on as they come: every marching kernel treats a ray whose set-up is not finite as a miss. This is
+ * the warp of svox2's Python path, whose rays its checkpoints were trained on; its CUDA world2ndc (another order, an fma)
+ * is not built. Three callers: the camera below, nerf_grid_dataset_batch, and nerf_grid_rays_to_ndc for a caller's own rays. */
+typedef struct nerf_grid_camera {              /* svox2.Camera. c2w is OpenCV: x right, y down, z forward             */
+    size_t struct_size;         /* 104 (96 before ndc_coeffs was added: hosts built against that header are refused)  */
     float c2w[12];              /* [3, 4] row-major                                                                 */
     double fx, fy, cx, cy;      /* pixel (x, y) looks along ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1)           */
     int32_t width, height;
+    float ndc_coeffs[2];        /* both > 0 (and finite): the pixel's ray, rounded to fp32, goes through rays_to_ndc;
+                                   ndc_coeffs[0] <= 0 (a zeroed tail, svox2's (-1, -1)): no NDC. NaN, infinity, or a
+                                   positive [0] with [1] <= 0 is NERF_E_INVALID                                     */
 } nerf_grid_camera;
 
 typedef struct nerf_grid_render_args {
@@ -757,6 +773,22 @@ int nerf_grid_render_image(nerf_sparse_grid* grid, const nerf_grid_camera* cam, 
                            const nerf_grid_render_args* args);
 /* those rays themselves: origins, dirs [dev] [height * width, 3] */
 int nerf_grid_gen_rays(nerf_ctx* ctx, const nerf_grid_camera* cam, float* origins, float* dirs, void* stream);
+
+/* rays_to_ndc (above) on a caller's rays, one lane per ray: origins_out / dirs_out [dev] [n, 3] from origins / dirs [dev]
+ * [n, 3]. An output may be the very pointer of its input (each lane reads its ray before it writes it); any other overlap is
+ * not allowed. 0 <= n <= 2^26, ndc_coeffs both positive and finite. Stream-ordered, allocates and synchronises nothing. */
+typedef struct nerf_grid_rays_to_ndc_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n, 3]                                                                     */
+    const float* dirs;          /* [dev] [n, 3], dirs need not be unit                                              */
+    int64_t n;
+    float ndc_coeffs[2];
+    float* origins_out;         /* [dev] [n, 3]                                                                     */
+    float* dirs_out;            /* [dev] [n, 3], unit                                                               */
+    void* stream;
+} nerf_grid_rays_to_ndc_args;
+
+int nerf_grid_rays_to_ndc(nerf_ctx* ctx, const nerf_grid_rays_to_ndc_args* args);
 /* svox2 SparseGrid.sample: trilinear, border padding, align_corners = False */
 int nerf_grid_sample(nerf_sparse_grid* grid, const nerf_grid_sample_args* args);
 int nerf_grid_accelerate(nerf_sparse_grid* grid, void* stream);
@@ -1299,7 +1331,8 @@ int nerf_grid_depth_backward(nerf_sparse_grid* grid, const nerf_grid_render_opti
  * opt/util/floater_visualization.py computes in Python loops on the host. Both calls scan the label tensor, one thread per
  * node, and take the node's entry in a per-label table built by the caller: table[label] for 1 <= label <= n_labels, and 0
  * (ignore) for label 0, a label outside that range or an entry of 0. Both are stream-ordered, allocate and synchronise
- * nothing and return a status with nerf_last_error(). NDC cameras do not exist in nerf_grid_camera. At most 2^26 pixels.
+ * nothing and return a status with nerf_last_error(). A camera with ndc_coeffs is refused (NERF_E_INVALID): both calls project
+ * world points through a pinhole, which an NDC view is not. At most 2^26 pixels.
  *
  * The projection of node (i, j, k), fp32, every operation rounded separately, no fused multiply-add, per axis a:
  *   p_a = ((idx_a / reso_a) * 2 - 1) * radius_a + center_a
@@ -1598,7 +1631,8 @@ typedef struct nerf_grid_background_args {
     size_t struct_size;
     const float* origins;       /* [dev] [n_rays, 3]       (nerf_grid_background_rays only)                         */
     const float* dirs;          /* [dev] [n_rays, 3], need not be unit                                              */
-    int64_t n_rays;             /* nerf_grid_background_image: ignored, width * height rays in row-major order      */
+    int64_t n_rays;             /* nerf_grid_background_image: ignored, width * height rays in row-major order; an NDC
+                                   camera (ndc_coeffs > 0) is refused there: svox2 never combines the two          */
     float* rgb;                 /* [dev] [n_rays, 3] in / out                                                       */
     float* log_transmit;        /* [dev] [n_rays] in / out                                                          */
     void* stream;
@@ -1896,6 +1930,9 @@ typedef struct nerf_grid_dataset_batch_args {
     float* rgb;                 /* [dev] [n, 3]                                                                     */
     int64_t* indices;           /* [dev] [n] the ray index of every row, or NULL                                    */
     void* stream;
+    float ndc_coeffs[2];        /* both > 0 (and finite): origin and direction above go through rays_to_ndc ("Sparse
+                                   voxel grid", nerf_grid_camera), svox2's LLFFDataset.gen_rays; [0] <= 0 (a zeroed
+                                   tail): world rays. The struct is 8 bytes larger than before this field was added    */
 } nerf_grid_dataset_batch_args;
 
 int nerf_grid_dataset_batch(nerf_ctx* ctx, const nerf_grid_dataset_batch_args* args);

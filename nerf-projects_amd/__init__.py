@@ -17,7 +17,7 @@ from .batching import RayBatcher  # noqa: F401
 from .mesh import density_grid, marching_cubes, marching_cubes_volume, save_obj  # noqa: F401
 from .occupancy import OccupancyGrid  # noqa: F401
 from . import grid  # noqa: F401
-from .grid import Camera, Rays, RenderOptions, SparseGrid  # noqa: F401
+from .grid import Camera, NdcCamera, Rays, RenderOptions, SparseGrid, rays_to_ndc  # noqa: F401
 from . import grid_half  # noqa: F401
 from .grid_half import HalfGrid  # noqa: F401
 from . import grid_palette  # noqa: F401

@@ -45,7 +45,7 @@ EXPORTS = (
     "nerf_grid_background_optim_step",
     "nerf_grid_tv_value_workspace", "nerf_grid_tv_value", "nerf_grid_tv_value_backward",
     "nerf_grid_sparsity_rays", "nerf_grid_sparsity_backward",
-    "nerf_grid_dataset_batch",
+    "nerf_grid_dataset_batch", "nerf_grid_rays_to_ndc",
     "nerf_grid_marching_cubes", "nerf_grid_mesh_attributes",
 )
 NERF_E_INTERNAL = -5
@@ -168,7 +168,13 @@ class GridRenderOptions(_Sized):
 
 class GridCamera(_Sized):
     _fields_ = [("struct_size", C.c_size_t), ("c2w", C.c_float * 12), ("fx", C.c_double), ("fy", C.c_double),
-                ("cx", C.c_double), ("cy", C.c_double), ("width", C.c_int32), ("height", C.c_int32)]
+                ("cx", C.c_double), ("cy", C.c_double), ("width", C.c_int32), ("height", C.c_int32),
+                ("ndc_coeffs", C.c_float * 2)]
+
+
+class GridRaysToNdcArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n", C.c_int64), ("ndc_coeffs", C.c_float * 2),
+                ("origins_out", _FP), ("dirs_out", _FP), ("stream", C.c_void_p)]
 
 
 class GridRenderArgs(_Sized):
@@ -376,7 +382,7 @@ class GridDatasetBatchArgs(_Sized):
                 ("width", C.c_int32), ("channels", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
                 ("cy", C.c_double), ("white_bkgd", C.c_int32), ("factor", C.c_int32), ("order", C.c_int32), ("key", C.c_uint64),
                 ("begin", C.c_int64), ("n", C.c_int64), ("origins", _FP), ("dirs", _FP), ("rgb", _FP), ("indices", _FP),
-                ("stream", C.c_void_p)]
+                ("stream", C.c_void_p), ("ndc_coeffs", C.c_float * 2)]
 
 
 class GridMcArgs(_Sized):
@@ -528,6 +534,8 @@ def load():
     lib.nerf_grid_render_image.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(GridRenderOptions), C.POINTER(GridRenderArgs)]
     lib.nerf_grid_gen_rays.restype = i32
     lib.nerf_grid_gen_rays.argtypes = [vp, C.POINTER(GridCamera), vp, vp, vp]
+    lib.nerf_grid_rays_to_ndc.restype = i32
+    lib.nerf_grid_rays_to_ndc.argtypes = [vp, C.POINTER(GridRaysToNdcArgs)]
     lib.nerf_grid_sample.restype = i32
     lib.nerf_grid_sample.argtypes = [vp, C.POINTER(GridSampleArgs)]
     lib.nerf_grid_accelerate.restype = i32

@@ -89,6 +89,21 @@ int nerf::check_grid_options(const char* fn, const nerf_grid_render_options* o, 
     return NERF_OK;
 }
 
+int nerf::check_ndc_coeffs(const char* fn, const float c[2], bool* use) {
+    *use = c[0] > 0.0f;
+    if (!std::isfinite(c[0]) || !std::isfinite(c[1]) || (*use && !(c[1] > 0.0f))) {
+        set_error("%s: ndc_coeffs = (%g, %g) must be finite, and both positive (NDC) or the first <= 0 (no NDC)", fn, c[0], c[1]);
+        return NERF_E_INVALID;
+    }
+    return NERF_OK;
+}
+
+int nerf::refuse_ndc_camera(const char* fn, const GridCam& cam, const char* why) {
+    if (!(cam.ndc[0] > 0.0f)) return NERF_OK;
+    set_error("%s: an NDC camera (ndc_coeffs > 0) is refused: %s", fn, why);
+    return NERF_E_INVALID;
+}
+
 int nerf::check_grid_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out) {
     NERF_CHECK_STRUCT(fn, cam, nerf_grid_camera);
     if (cam->width < 1 || cam->height < 1 || (int64_t)cam->width * cam->height > kGridMaxItems || !(std::fabs(cam->fx) > 0.0) ||
@@ -98,6 +113,11 @@ int nerf::check_grid_camera(const char* fn, const nerf_grid_camera* cam, GridCam
                   cam->fy, cam->cx, cam->cy);
         return NERF_E_INVALID;
     }
+    bool ndc = false;
+    const int rc = check_ndc_coeffs(fn, cam->ndc_coeffs, &ndc);
+    if (rc != NERF_OK) return rc;
+    out->ndc[0] = ndc ? cam->ndc_coeffs[0] : 0.0f;
+    out->ndc[1] = ndc ? cam->ndc_coeffs[1] : 0.0f;
     for (int i = 0; i < 12; ++i) out->c2w[i] = (double)cam->c2w[i];
     out->fx = cam->fx;
     out->fy = cam->fy;
@@ -233,6 +253,30 @@ int nerf_grid_gen_rays(nerf_ctx* c, const nerf_grid_camera* cam, float* origins,
     if (rc != NERF_OK) return rc;
     DeviceGuard dg(c->device);
     HIP_TRY(launch_grid_gen_rays(gc, origins, dirs, (hipStream_t)stream));
+    return NERF_OK;
+}
+
+int nerf_grid_rays_to_ndc(nerf_ctx* c, const nerf_grid_rays_to_ndc_args* a) {
+    const char* fn = "nerf_grid_rays_to_ndc";
+    int rc = require_ctx(fn, c);
+    if (rc != NERF_OK) return rc;
+    NERF_CHECK_STRUCT(fn, a, nerf_grid_rays_to_ndc_args);
+    if (a->n < 0 || a->n > kGridMaxItems || (a->n > 0 && (!a->origins || !a->dirs || !a->origins_out || !a->dirs_out))) {
+        set_error("%s: n = %lld must be in [0, 2^26] and needs origins, dirs, origins_out and dirs_out", fn, (long long)a->n);
+        return NERF_E_INVALID;
+    }
+    bool ndc = false;
+    rc = check_ndc_coeffs(fn, a->ndc_coeffs, &ndc);
+    if (rc != NERF_OK) return rc;
+    if (!ndc) {
+        set_error("%s: ndc_coeffs = (%g, %g) must both be positive", fn, a->ndc_coeffs[0], a->ndc_coeffs[1]);
+        return NERF_E_INVALID;
+    }
+    if (a->n == 0) return NERF_OK;
+    // ---- from here on the context is read ----
+    DeviceGuard dg(c->device);
+    HIP_TRY(launch_grid_rays_to_ndc(a->origins, a->dirs, a->n, a->ndc_coeffs[0], a->ndc_coeffs[1], a->origins_out, a->dirs_out,
+                                    (hipStream_t)a->stream));
     return NERF_OK;
 }
 

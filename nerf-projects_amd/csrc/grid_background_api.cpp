@@ -47,6 +47,7 @@ int background(const char* fn, nerf_sparse_grid* grid, const nerf_grid_camera* c
     GridBgRender r{};
     if (cam) {
         rc = check_grid_camera(fn, cam, &r.cam);
+        if (rc == NERF_OK) rc = refuse_ndc_camera(fn, r.cam, "background layers are for unbounded scenes, which svox2 never combines with NDC");
         if (rc != NERF_OK) return rc;
         r.n_rays = (int64_t)cam->width * cam->height;
     } else {

@@ -48,6 +48,9 @@ int nerf_grid_dataset_batch(nerf_ctx* c, const nerf_grid_dataset_batch_args* a) 
         set_error("%s: fx = %g and fy = %g must be positive and finite, cx = %g and cy = %g finite", fn, a->fx, a->fy, a->cx, a->cy);
         return NERF_E_INVALID;
     }
+    bool ndc = false;
+    rc = check_ndc_coeffs(fn, a->ndc_coeffs, &ndc);
+    if (rc != NERF_OK) return rc;
     GridDatasetBatch b{};
     b.height = a->height;
     b.width = a->width;
@@ -100,6 +103,8 @@ int nerf_grid_dataset_batch(nerf_ctx* c, const nerf_grid_dataset_batch_args* a) 
     b.dirs = a->dirs;
     b.rgb = a->rgb;
     b.indices = a->indices;
+    b.ndc[0] = ndc ? a->ndc_coeffs[0] : 0.0f;
+    b.ndc[1] = ndc ? a->ndc_coeffs[1] : 0.0f;
     if (a->n == 0) return NERF_OK;
     // ---- from here on the context is read ----
     DeviceGuard dg(c->device);

@@ -33,6 +33,7 @@ struct GridDatasetBatch {
     float* dirs;
     float* rgb;
     int64_t* indices;                  // or nullptr
+    float ndc[2];                      // ndc_coeffs; ndc[0] <= 0: world rays
 };
 
 hipError_t launch_grid_dataset_batch(const GridDatasetBatch& b, hipStream_t s);

@@ -3,8 +3,9 @@
 // measurements: DESIGN.md section 7o.
 //
 // One lane per output row k: the ray index sigma(begin + k), its image / pixel, the direction of svox2's gen_rays in rounded
-// fp32 operations, the translation column as the origin, and the composited colour of the pixel (factor 1) or the mean over
-// its area window (factor > 1). The kernel is a gather: in the permuted and random orders neighbouring lanes read pixels of
+// fp32 operations, the translation column as the origin (both through rays_to_ndc of grid_device.h where the data set has
+// ndc_coeffs: a forward-facing scene), and the composited colour of the pixel (factor 1) or the mean over its area window
+// (factor > 1). The kernel is a gather: in the permuted and random orders neighbouring lanes read pixels of
 // different images, 3 or 4 bytes each (one 32-bit load with an alpha channel), and the twelve pose floats of their image; the
 // three [n, 3] outputs are stored row by row, so a wavefront writes 768 contiguous bytes per output. Row and pixel arithmetic
 // is int64_t (n_images * height * width may pass 2^31). No LDS, no scratch, no atomics, no inline assembly.
@@ -78,10 +79,18 @@ __global__ __launch_bounds__(kGridThreads) void grid_dataset_batch_kernel(GridDa
     const float m = sqrtf(add(add(mul(u, u), mul(v, v)), 1.0f));
     const float d0 = __fdiv_rn(u, m), d1 = __fdiv_rn(v, m), d2 = __fdiv_rn(1.0f, m);
     const float* pose = b.c2w + image * 12;
+    float o[3], d[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        b.dirs[k * 3 + r] = add(add(mul(pose[4 * r], d0), mul(pose[4 * r + 1], d1)), mul(pose[4 * r + 2], d2));
-        b.origins[k * 3 + r] = pose[4 * r + 3];
+        d[r] = add(add(mul(pose[4 * r], d0), mul(pose[4 * r + 1], d1)), mul(pose[4 * r + 2], d2));
+        o[r] = pose[4 * r + 3];
+    }
+    // svox2's LLFFDataset.gen_rays: the world ray through the NDC warp (grid_device.h); the same branch for every lane
+    if (b.ndc[0] > 0.0f) rays_to_ndc(b.ndc[0], b.ndc[1], o, d);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        b.dirs[k * 3 + r] = d[r];
+        b.origins[k * 3 + r] = o[r];
     }
 
     // colour: the mean over the pixel's area window (one pixel at factor 1: 0 + q and q / 1 are exact)

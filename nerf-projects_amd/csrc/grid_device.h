@@ -117,7 +117,35 @@ __device__ __forceinline__ void load_links(const GridDev& g, int base, int lk[8]
     }
 }
 
-// svox2 Camera.gen_rays without NDC: fp64, rounded to fp32 at the end
+// The NDC warp of forward-facing scenes: svox2.utils.convert_to_ndc with near = 1, then the normalisation of its two callers
+// (Camera.gen_rays, LLFFDataset.gen_rays). fp32, every operation rounded on its own and in the reference's order, so that
+// hipcc contracts nothing:
+//     t  = (1 - oz) / dz
+//     o += t * d                                   (a product and a sum, not an fma)
+//     o' = (cx * (ox / oz),  cy * (oy / oz),  1 - 2 / oz)
+//     d' = (cx * (dx / dz - ox / oz),  cy * (dy / dz - oy / oz),  2 / oz)
+//     n  = sqrt(fma(d'z, d'z, fma(d'y, d'y, d'x * d'x)))         (torch.norm's vectorised CPU sum of squares)
+//     d' = d' / n
+// Non-finite results (dz == 0, oz == 0) are passed on: setup_ray makes such a ray a miss.
+__device__ __forceinline__ void rays_to_ndc(float coeffx, float coeffy, float o[3], float d[3]) {
+    const float t = __fdiv_rn(sub(1.0f, o[2]), d[2]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = add(o[i], mul(t, d[i]));
+    const float ox = __fdiv_rn(o[0], o[2]), oy = __fdiv_rn(o[1], o[2]), two_oz = __fdiv_rn(2.0f, o[2]);
+    const float dx = mul(coeffx, sub(__fdiv_rn(d[0], d[2]), ox));
+    const float dy = mul(coeffy, sub(__fdiv_rn(d[1], d[2]), oy));
+    // sqrtf: the correctly rounded root (hipcc's default)
+    const float n = sqrtf(__fmaf_rn(two_oz, two_oz, __fmaf_rn(dy, dy, mul(dx, dx))));
+    o[0] = mul(coeffx, ox);
+    o[1] = mul(coeffy, oy);
+    o[2] = sub(1.0f, two_oz);
+    d[0] = __fdiv_rn(dx, n);
+    d[1] = __fdiv_rn(dy, n);
+    d[2] = __fdiv_rn(two_oz, n);
+}
+
+// svox2 Camera.gen_rays: fp64, rounded to fp32 at the end; then, for an NDC camera (c.ndc[0] > 0, the same for every lane),
+// rays_to_ndc on the rounded ray, as svox2's Python does
 __device__ __forceinline__ void camera_ray(const GridCam& c, int64_t pix, float o[3], float d[3]) {
     const int py = (int)(pix / c.width), px = (int)(pix % c.width);
     double xx = ((double)px + 0.5 - c.cx) / c.fx;
@@ -132,6 +160,7 @@ __device__ __forceinline__ void camera_ray(const GridCam& c, int64_t pix, float 
         d[i] = (float)(c.c2w[i * 4 + 0] * xx + c.c2w[i * 4 + 1] * yy + c.c2w[i * 4 + 2] * zz);
         o[i] = (float)c.c2w[i * 4 + 3];
     }
+    if (c.ndc[0] > 0.0f) rays_to_ndc(c.ndc[0], c.ndc[1], o, d);
 }
 
 // ---- ray set-up (svox2.py:662-693) ----

@@ -20,6 +20,7 @@ int check_view(const char* fn, const nerf_grid_camera* cam, const int32_t* label
     }
     GridCam gc{};
     int rc = check_grid_camera(fn, cam, &gc);
+    if (rc == NERF_OK) rc = refuse_ndc_camera(fn, gc, "the floater views project world points through a pinhole camera");
     if (rc != NERF_OK) return rc;
     if (!labels || !table) {
         set_error("%s: labels and table are required", fn);

@@ -12,6 +12,7 @@
 //   grid_background_api.cpp background layers: attach / detach, the background pass, the two calls of the thinning
 //   grid_background_train_api.cpp   background layers, training: taped pass, backward, TV gradient, optimiser step
 //   grid_dataset_api.cpp    training data: a batch of rays from the resident images (takes a context, no grid)
+//   grid_ndc_kernels.hip    the NDC warp on a caller's rays (its entry point, nerf_grid_rays_to_ndc, is in grid_api.cpp)
 //   grid_mesh_api.cpp       surface meshes: marching cubes on the grid's own lattice, normals and colours at points
 //   grid_*_kernels.hip      the kernels of each, on grid_device.h (sampling, rays) and compact_device.h (compaction)
 #pragma once
@@ -53,6 +54,7 @@ struct GridCam {
     double c2w[12];
     double fx, fy, cx, cy;
     int32_t width, height;
+    float ndc[2];                      // ndc_coeffs; ndc[0] <= 0: a plain pinhole camera (camera_ray, grid_device.h)
 };
 
 struct GridRender {
@@ -296,7 +298,11 @@ int refuse_palette_grid(const char* fn, const nerf_sparse_grid* grid);
 int check_grid_links(const char* fn, const int32_t* links, int64_t n, int64_t capacity, hipStream_t s);
 // reso not NULL, every side in [2, 1024] (so that a cell exists on every axis), at most 2^30 nodes
 int check_grid_reso(const char* fn, const int32_t* reso, int64_t* nodes);
-// a public camera (struct_size, size, intrinsics) / the public render options (struct_size, what is not built, ranges), converted
+// ndc_coeffs of a public struct: NERF_OK and *use = whether NDC is on ([0] > 0); NaN, infinity or [0] > 0 with [1] <= 0 refused
+int check_ndc_coeffs(const char* fn, const float ndc_coeffs[2], bool* use);
+// for the entry points in which an NDC camera has no meaning (`why` ends the message)
+int refuse_ndc_camera(const char* fn, const GridCam& cam, const char* why);
+// a public camera (struct_size, size, intrinsics, ndc_coeffs) / the public render options (struct_size, what is not built, ranges), converted
 int check_grid_camera(const char* fn, const nerf_grid_camera* cam, GridCam* out);
 int check_grid_options(const char* fn, const nerf_grid_render_options* o, GridRenderOpt* out);
 
@@ -322,6 +328,9 @@ inline int grid_world2grid(const char* fn, const float center[3], const float ra
 
 hipError_t launch_grid_render(const GridDev& g, const GridRenderOpt& o, const GridRender& r, hipStream_t s);
 hipError_t launch_grid_gen_rays(const GridCam& cam, float* origins, float* dirs, hipStream_t s);
+// rays_to_ndc (grid_device.h) on n rays, one lane each; an output may be its input
+hipError_t launch_grid_rays_to_ndc(const float* origins, const float* dirs, int64_t n, float coeffx, float coeffy,
+                                   float* origins_out, float* dirs_out, hipStream_t s);
 hipError_t launch_grid_sample(const GridDev& g, const float* points, int64_t n, int grid_coords, int want_colors,
                               float* density, float* sh, hipStream_t s);
 // skip [X * Y * Z] bytes: kGridSkipCap stream-ordered launches, no atomics

@@ -19,13 +19,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (GridCamera, GridDepthArgs, GridProjectArgs, GridRenderArgs, GridRenderOptions, GridSampleArgs, SparseGridDesc,
+from ._lib import (GridCamera, GridDepthArgs, GridProjectArgs, GridRaysToNdcArgs, GridRenderArgs, GridRenderOptions, GridSampleArgs, SparseGridDesc,
                    check)
 from .host import NeRF, get_context, get_embedder, run_network
 from .mesh import _axes, density_grid
 from .occupancy import OccupancyGrid
 
-__all__ = ["SparseGrid", "Rays", "Camera", "RenderOptions", "BASIS_TYPE_SH", "BASIS_TYPE_3D_TEXTURE", "BASIS_TYPE_MLP",
+__all__ = ["SparseGrid", "Rays", "Camera", "NdcCamera", "rays_to_ndc", "RenderOptions", "BASIS_TYPE_SH", "BASIS_TYPE_3D_TEXTURE", "BASIS_TYPE_MLP",
            "eval_sh_bases", "fibonacci_directions", "sh_projection_matrix"]
 
 BASIS_TYPE_SH = 1
@@ -170,7 +170,10 @@ class Camera:
 
     def _to_c(self):
         if self.using_ndc:
-            raise NotImplementedError("NDC cameras are not built")
+            raise NotImplementedError("NDC cameras are not built into Camera: use NdcCamera")
+        return self._pinhole_c()
+
+    def _pinhole_c(self):
         c = GridCamera()
         m = torch.as_tensor(self.c2w).detach().to(device="cpu", dtype=torch.float32)
         if m.dim() != 2 or m.shape[0] < 3 or m.shape[1] != 4:
@@ -190,6 +193,64 @@ class Camera:
         d = torch.empty((n, 3), device=ctx.device, dtype=torch.float32)
         check(ctx.lib.nerf_grid_gen_rays(ctx.handle, C.byref(c), o.data_ptr(), d.data_ptr(), ctx.stream()))
         return Rays(o, d)
+
+
+def _ndc_coeffs_arg(ndc_coeffs):
+    try:
+        vals = [float(v) for v in ndc_coeffs]
+    except (TypeError, ValueError):
+        raise ValueError(f"ndc_coeffs = {ndc_coeffs!r} must be two finite positive numbers") from None
+    if len(vals) != 2 or not all(np.isfinite(v) and v > 0.0 for v in vals):
+        raise ValueError(f"ndc_coeffs = {ndc_coeffs!r} must be two finite positive numbers")
+    return vals
+
+
+@dataclass
+class NdcCamera(Camera):
+    """A ``Camera`` of a forward-facing scene: svox2's ``Camera(..., ndc_coeffs=(2 fx / w, 2 fy / h))``. The same fields;
+    ``ndc_coeffs`` must be two finite positive numbers. Every pixel's ray, made as ``Camera``'s and rounded to fp32, goes
+    through ``rays_to_ndc`` on the device (svox2's ``convert_to_ndc`` and the normalisation after it, bit for bit), in
+    ``gen_rays`` and inside every image kernel alike. ``Camera`` itself keeps refusing ``ndc_coeffs``: the capability has
+    this name. The floater views and ``BackgroundGrid`` refuse it (they have no NDC form in svox2 either)."""
+
+    def __post_init__(self):
+        self.ndc_coeffs = tuple(_ndc_coeffs_arg(self.ndc_coeffs))
+
+    def _to_c(self):
+        c = self._pinhole_c()
+        c.ndc_coeffs[:] = _ndc_coeffs_arg(self.ndc_coeffs)      # (checked again: a dataclass field can be reassigned)
+        return c
+
+
+def rays_to_ndc(rays: Rays, ndc_coeffs) -> Rays:
+    """World rays -> the NDC rays svox2 trains and renders forward-facing scenes with: ``svox2.utils.convert_to_ndc`` with
+    ``near = 1`` and ``dirs /= |dirs|``, one HIP launch, one lane per ray (the device function ``NdcCamera`` and the LLFF
+    batches use; the sequence of operations is in include/nerf_mi355x.h). For callers who bring their own rays. A ray with
+    ``dirs.z == 0`` comes back non-finite and renders as a miss."""
+    coeffs = _ndc_coeffs_arg(ndc_coeffs)
+    arrs = []
+    for t, name in ((rays.origins, "rays.origins"), (rays.dirs, "rays.dirs")):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a tensor")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} is on the CPU: rays_to_ndc has no CPU fallback")
+        if t.dim() != 2 or t.shape[1] != 3 or (arrs and t.shape[0] != arrs[0].shape[0]):
+            raise ValueError(f"{name} must be [N, 3], got {tuple(t.shape)}")
+        arrs.append(t.detach().to(dtype=torch.float32).contiguous())
+    o, d = arrs
+    if o.device != d.device:
+        raise RuntimeError(f"rays.origins is on {o.device}, rays.dirs on {d.device}")
+    n = o.shape[0]
+    if n > (1 << 26):
+        raise ValueError(f"{n} rays: at most 2^26 per call")
+    ctx = get_context(o.device)
+    oo, dd = torch.empty_like(o), torch.empty_like(d)
+    a = GridRaysToNdcArgs()
+    a.origins, a.dirs, a.n = o.data_ptr(), d.data_ptr(), n
+    a.ndc_coeffs[:] = coeffs
+    a.origins_out, a.dirs_out, a.stream = oo.data_ptr(), dd.data_ptr(), ctx.stream().value
+    check(ctx.lib.nerf_grid_rays_to_ndc(ctx.handle, C.byref(a)))
+    return Rays(oo, dd)
 
 
 def _three(v, name):

@@ -21,7 +21,7 @@ import torch
 
 from ._lib import (GridBackgroundArgs, GridBackgroundDesc, GridBackgroundGatherArgs, GridBackgroundSparsifyArgs, GridRenderArgs,
                    check)
-from .grid import BASIS_TYPE_SH, SparseGrid
+from .grid import BASIS_TYPE_SH, NdcCamera, SparseGrid
 from .host import get_context
 
 __all__ = ["BackgroundGrid", "load_grid"]
@@ -199,6 +199,9 @@ class BackgroundGrid(SparseGrid):
         lib, stream = self.ctx.lib, self.ctx.stream().value
         a, b = GridRenderArgs(), GridBackgroundArgs()
         if cam is not None:
+            if isinstance(cam, NdcCamera):
+                raise NotImplementedError("background layers are for unbounded scenes: svox2 never combines them with NDC, and "
+                                          "an NdcCamera is refused")
             c = cam._to_c()
             n = cam.width * cam.height
         else:

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from ._lib import NERF_GRID_FLOATER_COUNTER_INTS, GridComponentViewArgs, GridFloaterHeatmapArgs, check
-from .grid import SparseGrid, _volume_arg
+from .grid import NdcCamera, SparseGrid, _volume_arg
 from .grid_components import component_volumes
 
 __all__ = ["project_floaters_to_view", "component_view", "multi_object_overlay", "main_object_overlay",
@@ -120,6 +120,14 @@ def _depth_arg(grid, camera, depth_map):
     return depth_map.detach().contiguous()
 
 
+def _pinhole(camera):
+    """The C camera; ``Camera`` refuses ``ndc_coeffs`` itself, an ``NdcCamera`` is refused here."""
+    if isinstance(camera, NdcCamera):
+        raise NotImplementedError("the floater views project world points through a pinhole camera: an NDC camera (NdcCamera) "
+                                  "has no such view")
+    return camera._to_c()
+
+
 def project_floaters_to_view(grid, fdr_results, camera, render_size=None, filter_occluded=True, min_density=0.1,
                              depth_map=None, return_counts=False):
     """float32 ``[H, W]`` device tensor: how many visible floater voxels project to every pixel of ``camera``, dilated by
@@ -134,7 +142,7 @@ def project_floaters_to_view(grid, fdr_results, camera, render_size=None, filter
     if labels is None or floater_ids.size == 0:
         return None
     ctx = grid.ctx
-    cam = camera._to_c()      # an NDC camera is refused here
+    cam = _pinhole(camera)
     H, W = (int(camera.height), int(camera.width)) if render_size is None else (int(render_size[0]), int(render_size[1]))
     with torch.no_grad():
         depth = _depth_arg(grid, camera, depth_map) if filter_occluded else None
@@ -159,7 +167,7 @@ def project_floaters_to_view(grid, fdr_results, camera, render_size=None, filter
 
 def _slots(grid, labels, h, camera, table):
     ctx = grid.ctx
-    cam = camera._to_c()
+    cam = _pinhole(camera)
     hw = (int(camera.height), int(camera.width))
     keys = torch.empty(hw, dtype=torch.int64, device=ctx.device)
     slots = torch.empty(hw, dtype=torch.int32, device=ctx.device)
