@@ -2010,6 +2010,124 @@ typedef struct nerf_grid_mesh_attributes_args {
 int nerf_grid_marching_cubes(nerf_sparse_grid* grid, const nerf_grid_mc_args* args);
 int nerf_grid_mesh_attributes(nerf_sparse_grid* grid, const nerf_grid_mesh_attributes_args* args);
 
+/* PlenOctree ----------------------------------------------------------------------------------------
+ * An octree of branching factor 2 in svox's N3Tree layout, rendered by a cell-to-cell march. All arrays are borrowed.
+ *   child  [dev] int32 [n, 2, 2, 2]     0: the cell is a leaf; else the child node's index minus this node's index (> 0)
+ *   data   [dev] fp32  [n, 2, 2, 2, D]  D = 3 B + 1, B in {1, 4, 9, 16, 25}: a row is [R coefficients (B), G (B), B (B), sigma]
+ * World to unit cube: x * invradius + offset. max_depth is the depth of the deepest node (the root has depth 0, at most 24);
+ * a descent looks at no more than max_depth + 1 nodes, whatever `child` holds. nerf_octree_create checks every entry of
+ * `child` on the device (0, or positive with node + entry < n; it synchronises `stream`), so that no descent leaves the arrays,
+ * and that child, data and - in the render calls - every ray and output array are device memory of the context's GPU
+ * (NERF_E_INVALID otherwise, before any launch).
+ *
+ * The march. svox is not part of the project this one was modelled on (it only calls into it), so the arithmetic is DEFINED
+ * here: it restates svox 0.2's published algorithm from memory, it is not verified against svox. Every product, sum and
+ * difference is one rounded fp32 operation in the order written; divisions are IEEE. min / max drop a NaN.
+ *     o = origin * invradius + offset
+ *     d = dir * invradius;  delta_scale = 1 / |d|  (|d| = sqrt((dx dx + dy dy) + dz dz));  d = d * delta_scale
+ *     inv[i] = 1 / (d[i] + 1e-9)
+ *     unit(p): t1 = -p[i] * inv[i];  t2 = t1 + inv[i];  tmin = max(0, min(t1, t2) over i);  tmax = min(1e9, max(t1, t2) over i)
+ *     (tmin, tmax) = unit(o);  if tmax < 0 or tmin > tmax: rgb = background_brightness, steps = 0
+ *     T = 1, t = tmin
+ *     while t < tmax:
+ *         p = clamp(o + t * d, 0, 1 - 1e-6)                   (1 - 1e-6: the fp32 difference of the fp32 constants)
+ *         cube = 1, node = 0; repeat: p = p * 2; (u, v, w) = floor(p); p = p - (u, v, w); cube = cube * 2      (all exact)
+ *                             until child[node][u][v][w] == 0 or max_depth + 1 nodes were looked at; else node += child[...]
+ *         (a, b) = unit(p);  delta = (b - a) / cube + step_size                           (the division is exact)
+ *         row = data[node][u][v][w];  sigma = row[D - 1]
+ *         if sigma > sigma_thresh:
+ *             att = exp((-delta * delta_scale) * sigma)
+ *             s_c = sum over i < B, in order of i, of Y_i(viewdir) * row[c B + i]          c < 3
+ *             rgb[c] = rgb[c] + (T * (1 - att)) * act(s_c);  T = T * att
+ *             if T <= stop_thresh: rgb = rgb * (1 / (1 - T)); the ray ends here, without the background term
+ *         if not (t + delta > t): leave the loop              (an origin so far away that the step is below one ulp of t)
+ *         t = t + delta
+ *     rgb[c] = rgb[c] + T * background_brightness
+ * steps = the leaves looked at (passes through the loop). viewdir is the caller's direction as given (svox expects it
+ * normalised); the image form makes its rays as nerf_grid_gen_rays does (unit directions), so nerf_octree_render_image equals
+ * nerf_octree_render_rays on those rays bit for bit. act = 1 / (1 + exp(-s)) (NERF_OCTREE_RGB_SIGMOID, svox's) or
+ * max(s + 0.5, 0) (NERF_OCTREE_RGB_RELU_HALF, svox2's colour model: what a tree built from a grid carries).
+ * Y_i: the real spherical harmonics of degree 0..4 with the constants, signs and expressions of the reference's
+ * plenoctree/nerf_sh/nerf/sh.py, each product and difference rounded, left to right, e.g. Y_12 = (C3[3] z) ((2 zz - 3 xx) - 3 yy).
+ * A ray with a non-finite origin or direction component, or whose delta_scale is not finite and positive (a zero or an
+ * overflowing direction), gets NaN in all channels and 0 steps. The loop ends after 65536 passes at the latest; the rays it
+ * ended that way are added to *capped where that is not NULL.
+ *
+ * nerf_octree_accelerate: a dense table of side 2^k, k = min(levels, max_depth), built by one kernel and owned by the tree: an
+ * entry holds the cell index and depth of the deepest cell of depth <= k that contains the table cell. Every later render starts
+ * its descents at the entry of floor(p 2^k) instead of the root; with q = p 2^d the position inside a cell of depth d is
+ * q - floor(q), which is the number the d exact doublings and subtractions of the plain descent give, so an accelerated render
+ * equals a plain one bit for bit, steps included. levels in [0, 8]; 0, or a root-only tree, leaves the tree without a table.
+ * Replacing or dropping a table waits for the device. nerf_octree_table_levels: k of the current table, 0 without one.
+ *
+ * nerf_octree_build_from_grid: svox2's SparseGrid.to_svox1 on the device, for a cubic fp32 grid (nerf_grid_create) of side
+ * R = 2^L, 1 <= L <= 10. Leaf cell (i, j, k) at depth L holds [sh_data row, density] of lattice node (i, j, k) where
+ * links >= 0 and zeros elsewhere; a cell above it has a child node exactly when a kept node lies under it, else it is a zero
+ * leaf; the root always exists. Nodes are numbered breadth first: the root, then the nodes of depth 1 in C order of their
+ * cell coordinates, then depth 2, ...: no atomics, two builds give the same bits. parent_depth[node] = (parent * 8 + u * 4 +
+ * v * 2 + w, depth) of the cell the node hangs in; (0, 0) for the root (svox's value as remembered, not verified).
+ * Two calls: with child == NULL the structure is planned into `workspace` (nerf_octree_build_workspace(R) bytes, 256-byte
+ * aligned) and *n_nodes is written after ONE wait for `stream`; then, with the same workspace and arrays of n_nodes nodes,
+ * the second call fills child, parent_depth and data, stream-ordered, waiting for nothing. The grid must not change between. */
+typedef struct nerf_octree nerf_octree;
+
+#define NERF_OCTREE_RGB_SIGMOID 0
+#define NERF_OCTREE_RGB_RELU_HALF 1
+#define NERF_OCTREE_MAX_DEPTH 24
+
+typedef struct nerf_octree_desc {
+    size_t struct_size;
+    int64_t n_nodes;            /* 1 .. 2^27                                                                        */
+    int32_t data_dim;           /* 3 B + 1: 4, 13, 28, 49 or 76                                                     */
+    int32_t max_depth;          /* 0 .. NERF_OCTREE_MAX_DEPTH                                                       */
+    int32_t rgb_activation;     /* NERF_OCTREE_RGB_*                                                                */
+    float invradius[3];         /* positive, finite                                                                 */
+    float offset[3];            /* finite                                                                           */
+    const int32_t* child;       /* [dev] [n_nodes, 2, 2, 2]                                                         */
+    const float* data;          /* [dev] [n_nodes, 2, 2, 2, data_dim]                                               */
+    void* stream;
+} nerf_octree_desc;
+
+typedef struct nerf_octree_render_options {
+    size_t struct_size;
+    float step_size;            /* > 0, finite; in units of the cube's side                                         */
+    float sigma_thresh;         /* not NaN                                                                          */
+    float stop_thresh;          /* not NaN                                                                          */
+    float background_brightness;/* finite                                                                           */
+} nerf_octree_render_options;
+
+typedef struct nerf_octree_render_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]; unused by nerf_octree_render_image                            */
+    const float* dirs;          /* [dev] [n_rays, 3]                                                                */
+    int64_t n_rays;             /* 0 .. 2^26                                                                        */
+    float* rgb;                 /* [dev] [n_rays, 3]                                                                */
+    int32_t* steps;             /* [dev] [n_rays] or NULL                                                           */
+    unsigned long long* capped; /* [dev] [1] added to, or NULL                                                      */
+    void* stream;
+} nerf_octree_render_args;
+
+typedef struct nerf_octree_build_args {
+    size_t struct_size;
+    void* workspace;            /* [dev] nerf_octree_build_workspace(R) bytes                                       */
+    int64_t workspace_bytes;
+    int64_t* n_nodes;           /* [host] out of the planning call, in of the filling call                          */
+    int32_t* child;             /* [dev] [n_nodes, 2, 2, 2], or NULL: plan                                          */
+    int32_t* parent_depth;      /* [dev] [n_nodes, 2]                                                               */
+    float* data;                /* [dev] [n_nodes, 2, 2, 2, 3 basis_dim + 1]                                        */
+    void* stream;
+} nerf_octree_build_args;
+
+int nerf_octree_create(nerf_ctx* ctx, const nerf_octree_desc* desc, nerf_octree** out);
+void nerf_octree_destroy(nerf_octree* tree);
+int nerf_octree_render_rays(nerf_octree* tree, const nerf_octree_render_options* opt, const nerf_octree_render_args* args);
+int nerf_octree_render_image(nerf_octree* tree, const nerf_grid_camera* cam, const nerf_octree_render_options* opt,
+                             const nerf_octree_render_args* args);
+int nerf_octree_accelerate(nerf_octree* tree, int32_t levels, void* stream);
+int nerf_octree_table_levels(const nerf_octree* tree);
+int64_t nerf_octree_build_workspace(int32_t reso);      /* bytes, or -1 where reso is no power of two in [2, 1024] */
+int nerf_octree_build_from_grid(nerf_sparse_grid* grid, const nerf_octree_build_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,5 +44,7 @@ from . import grid_mesh  # noqa: F401
 from .grid_mesh import GridMesh, extract_mesh, mesh_attributes  # noqa: F401
 from . import grid_fit  # noqa: F401
 from .grid_fit import GridTrainConfig, expon_lr, train_grid  # noqa: F401
+from . import octree  # noqa: F401
+from .octree import N3Tree  # noqa: F401
 
 __version__ = "0.1.0"

@@ -47,6 +47,8 @@ EXPORTS = (
     "nerf_grid_sparsity_rays", "nerf_grid_sparsity_backward",
     "nerf_grid_dataset_batch", "nerf_grid_rays_to_ndc",
     "nerf_grid_marching_cubes", "nerf_grid_mesh_attributes",
+    "nerf_octree_create", "nerf_octree_destroy", "nerf_octree_render_rays", "nerf_octree_render_image",
+    "nerf_octree_build_workspace", "nerf_octree_build_from_grid", "nerf_octree_accelerate", "nerf_octree_table_levels",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -60,6 +62,8 @@ NERF_GRID_FLOATER_COUNTER_INTS = 8192
 NERF_GRID_HALF_LANES_DEFAULT, NERF_GRID_HALF_LANES_SINGLE, NERF_GRID_HALF_LANES_PAIR = 0, 1, 2
 NERF_GRID_ORDER_IDENTITY, NERF_GRID_ORDER_PERMUTED, NERF_GRID_ORDER_RANDOM = 0, 1, 2
 NERF_GRID_MESH_COLOR_NONE, NERF_GRID_MESH_COLOR_DC, NERF_GRID_MESH_COLOR_SH, NERF_GRID_MESH_COLOR_VIEW = 0, 1, 2, 3
+NERF_OCTREE_RGB_SIGMOID, NERF_OCTREE_RGB_RELU_HALF = 0, 1
+NERF_OCTREE_MAX_DEPTH = 24
 
 
 class NerfArch(C.Structure):
@@ -396,6 +400,27 @@ class GridMeshAttributesArgs(_Sized):
                 ("view", C.c_float * 3), ("normals", _FP), ("colors", _FP), ("stream", C.c_void_p)]
 
 
+class OctreeDesc(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("n_nodes", C.c_int64), ("data_dim", C.c_int32), ("max_depth", C.c_int32),
+                ("rgb_activation", C.c_int32), ("invradius", C.c_float * 3), ("offset", C.c_float * 3), ("child", _FP),
+                ("data", _FP), ("stream", C.c_void_p)]
+
+
+class OctreeRenderOptions(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("step_size", C.c_float), ("sigma_thresh", C.c_float),
+                ("stop_thresh", C.c_float), ("background_brightness", C.c_float)]
+
+
+class OctreeRenderArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("rgb", _FP),
+                ("steps", _FP), ("capped", _FP), ("stream", C.c_void_p)]
+
+
+class OctreeBuildArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("workspace", _FP), ("workspace_bytes", C.c_int64),
+                ("n_nodes", C.POINTER(C.c_int64)), ("child", _FP), ("parent_depth", _FP), ("data", _FP), ("stream", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -656,6 +681,22 @@ def load():
     lib.nerf_grid_marching_cubes.argtypes = [vp, C.POINTER(GridMcArgs)]
     lib.nerf_grid_mesh_attributes.restype = i32
     lib.nerf_grid_mesh_attributes.argtypes = [vp, C.POINTER(GridMeshAttributesArgs)]
+    lib.nerf_octree_create.restype = i32
+    lib.nerf_octree_create.argtypes = [vp, C.POINTER(OctreeDesc), C.POINTER(vp)]
+    lib.nerf_octree_destroy.restype = None
+    lib.nerf_octree_destroy.argtypes = [vp]
+    lib.nerf_octree_render_rays.restype = i32
+    lib.nerf_octree_render_rays.argtypes = [vp, C.POINTER(OctreeRenderOptions), C.POINTER(OctreeRenderArgs)]
+    lib.nerf_octree_render_image.restype = i32
+    lib.nerf_octree_render_image.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(OctreeRenderOptions), C.POINTER(OctreeRenderArgs)]
+    lib.nerf_octree_accelerate.restype = i32
+    lib.nerf_octree_accelerate.argtypes = [vp, C.c_int32, vp]
+    lib.nerf_octree_table_levels.restype = i32
+    lib.nerf_octree_table_levels.argtypes = [vp]
+    lib.nerf_octree_build_workspace.restype = i64
+    lib.nerf_octree_build_workspace.argtypes = [C.c_int32]
+    lib.nerf_octree_build_from_grid.restype = i32
+    lib.nerf_octree_build_from_grid.argtypes = [vp, C.POINTER(OctreeBuildArgs)]
     _lib = lib
     return lib
 

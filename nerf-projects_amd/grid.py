@@ -768,7 +768,9 @@ class SparseGrid:
     inplace_tv_grad = _not_built("inplace_tv_grad", "grid training (total-variation loss)")
     optim_density_step = _not_built("optim_density_step", "grid training (optimiser)")
     optim_sh_step = _not_built("optim_sh_step", "grid training (optimiser)")
-    to_svox1 = _not_built("to_svox1", "conversion to an svox1 octree")
+    # (the conversion exists under a name of its own, like training: octree.N3Tree.from_grid(grid); this svox2-named method
+    # keeps raising, as the other svox2-named methods here do)
+    to_svox1 = _not_built("to_svox1", "the svox2-named conversion (octree.N3Tree.from_grid(grid) builds the octree)")
     del _not_built
 
     # ---- baking -----------------------------------------------------------------------------------------
