@@ -2068,7 +2068,34 @@ int nerf_grid_mesh_attributes(nerf_sparse_grid* grid, const nerf_grid_mesh_attri
  * v * 2 + w, depth) of the cell the node hangs in; (0, 0) for the root (svox's value as remembered, not verified).
  * Two calls: with child == NULL the structure is planned into `workspace` (nerf_octree_build_workspace(R) bytes, 256-byte
  * aligned) and *n_nodes is written after ONE wait for `stream`; then, with the same workspace and arrays of n_nodes nodes,
- * the second call fills child, parent_depth and data, stream-ordered, waiting for nothing. The grid must not change between. */
+ * the second call fills child, parent_depth and data, stream-ordered, waiting for nothing. The grid must not change between.
+ *
+ * PlenOctree: backward. nerf_octree_backward_rays / _image: the gradient of the march above with respect to the rows of
+ * `data`, added to grad_data [n, 2, 2, 2, D] (fp32). Like the march, this arithmetic is defined here. The geometry of a march
+ * (its leaves and their delta) depends on `child` and the ray alone, never on `data`, so a ray's colour is a smooth function
+ * of the rows of the leaves it crosses, with fixed lengths. For one valid ray, in the notation above:
+ *     the shaded leaves k = 1..m: those with sigma_k > sigma_thresh, in march order
+ *     len_k = delta_k * delta_scale;  att_k = exp(-len_k sigma_k);  T_k: the transmittance before leaf k
+ *     w_k = T_k (1 - att_k);  s_kc = sum_i Y_i row_k[c B + i];  col_kc = act(s_kc);  A_c = sum_k w_k col_kc
+ *     T_e: the final transmittance;  stopped: T_e <= stop_thresh ended the march;  scale = 1 / (1 - T_e) if stopped, else 1
+ *     U_c = A_c + (stopped ? 0 : T_e * background_brightness);  pre_kc = sum over j < k of w_j col_jc
+ *     g_c: the incoming gradient of rgb_c;  act' = col (1 - col) for the sigmoid, (s + 0.5 > 0) ? 1 : 0 for relu_half
+ *     d / d row_k[c B + i] += g_c * scale * w_k * act'(s_kc) * Y_i
+ *     d / d sigma_k        += sum_c g_c * (scale * len_k * (T_k att_k col_kc - (U_c - pre_kc - w_k col_kc))
+ *                                          + (stopped ? -A_c * scale^2 * len_k * T_e : 0))
+ * The set of shaded leaves and the stopping leaf are held fixed (the function is piecewise smooth). Leaves at or below
+ * sigma_thresh, leaves after the stop, rays that miss the cube and NaN rays get nothing. The call replays the march with
+ * the renderer's operations: `rgb`, where not NULL, receives nerf_octree_render_rays' bits, and a ray that reaches the cap
+ * of 65536 passes is added to *capped and contributes the gradient of the leaves it saw. The gradient itself is fp32
+ * arithmetic in no promised order: float atomics arrive in any order, two calls may differ in the last bits. Adds of exact
+ * zeros are skipped: a row no ray shaded is not touched.
+ * Exactly one of grad_rgb and rgb_gt is given (NERF_E_INVALID otherwise). With grad_rgb [n, 3], g = grad_rgb. With rgb_gt
+ * [n, 3], the fused clamped squared error: g_c = loss_scale * (clamp(rgb_c, 0, 1) - gt_c) where 0 <= rgb_c <= 1, else 0
+ * (torch.clamp's closed interval), and *loss += sum over rays and c of (clamp(rgb_c, 0, 1) - gt_c)^2 where loss is not
+ * NULL. A NaN ray adds nothing to either - a documented deviation: torch would give a NaN loss. loss_scale = 2 / (3 n)
+ * makes grad_data the gradient of the mean squared error, and *loss / (3 n) that error.
+ * The checks of the render calls (device memory of the context's GPU for every array given, n_rays <= 2^26, struct_size) come
+ * before any launch. The table of nerf_octree_accelerate is honoured as in the renderer. The call waits for nothing. */
 typedef struct nerf_octree nerf_octree;
 
 #define NERF_OCTREE_RGB_SIGMOID 0
@@ -2118,11 +2145,29 @@ typedef struct nerf_octree_build_args {
     void* stream;
 } nerf_octree_build_args;
 
+typedef struct nerf_octree_backward_args {
+    size_t struct_size;
+    const float* origins;       /* [dev] [n_rays, 3]; unused by nerf_octree_backward_image                          */
+    const float* dirs;          /* [dev] [n_rays, 3]                                                                */
+    int64_t n_rays;             /* 0 .. 2^26                                                                        */
+    const float* grad_rgb;      /* [dev] [n_rays, 3], or NULL: exactly one of grad_rgb and rgb_gt                   */
+    const float* rgb_gt;        /* [dev] [n_rays, 3], or NULL                                                       */
+    float loss_scale;           /* finite; used with rgb_gt                                                         */
+    float* grad_data;           /* [dev] [n_nodes, 2, 2, 2, data_dim], added to                                     */
+    float* loss;                /* [dev] [1] added to (with rgb_gt), or NULL                                        */
+    float* rgb;                 /* [dev] [n_rays, 3] out, or NULL                                                   */
+    unsigned long long* capped; /* [dev] [1] added to, or NULL                                                      */
+    void* stream;
+} nerf_octree_backward_args;
+
 int nerf_octree_create(nerf_ctx* ctx, const nerf_octree_desc* desc, nerf_octree** out);
 void nerf_octree_destroy(nerf_octree* tree);
 int nerf_octree_render_rays(nerf_octree* tree, const nerf_octree_render_options* opt, const nerf_octree_render_args* args);
 int nerf_octree_render_image(nerf_octree* tree, const nerf_grid_camera* cam, const nerf_octree_render_options* opt,
                              const nerf_octree_render_args* args);
+int nerf_octree_backward_rays(nerf_octree* tree, const nerf_octree_render_options* opt, const nerf_octree_backward_args* args);
+int nerf_octree_backward_image(nerf_octree* tree, const nerf_grid_camera* cam, const nerf_octree_render_options* opt,
+                               const nerf_octree_backward_args* args);
 int nerf_octree_accelerate(nerf_octree* tree, int32_t levels, void* stream);
 int nerf_octree_table_levels(const nerf_octree* tree);
 int64_t nerf_octree_build_workspace(int32_t reso);      /* bytes, or -1 where reso is no power of two in [2, 1024] */

@@ -46,5 +46,6 @@ from . import grid_fit  # noqa: F401
 from .grid_fit import GridTrainConfig, expon_lr, train_grid  # noqa: F401
 from . import octree  # noqa: F401
 from .octree import N3Tree  # noqa: F401
+from . import octree_optimize  # noqa: F401
 
 __version__ = "0.1.0"

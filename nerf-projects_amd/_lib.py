@@ -49,6 +49,7 @@ EXPORTS = (
     "nerf_grid_marching_cubes", "nerf_grid_mesh_attributes",
     "nerf_octree_create", "nerf_octree_destroy", "nerf_octree_render_rays", "nerf_octree_render_image",
     "nerf_octree_build_workspace", "nerf_octree_build_from_grid", "nerf_octree_accelerate", "nerf_octree_table_levels",
+    "nerf_octree_backward_rays", "nerf_octree_backward_image",
 )
 NERF_E_INTERNAL = -5
 NERF_W_PRECISION, NERF_W_PRECISION_FALLBACK = 1, 2
@@ -416,6 +417,12 @@ class OctreeRenderArgs(_Sized):
                 ("steps", _FP), ("capped", _FP), ("stream", C.c_void_p)]
 
 
+class OctreeBackwardArgs(_Sized):
+    _fields_ = [("struct_size", C.c_size_t), ("origins", _FP), ("dirs", _FP), ("n_rays", C.c_int64), ("grad_rgb", _FP),
+                ("rgb_gt", _FP), ("loss_scale", C.c_float), ("grad_data", _FP), ("loss", _FP), ("rgb", _FP), ("capped", _FP),
+                ("stream", C.c_void_p)]
+
+
 class OctreeBuildArgs(_Sized):
     _fields_ = [("struct_size", C.c_size_t), ("workspace", _FP), ("workspace_bytes", C.c_int64),
                 ("n_nodes", C.POINTER(C.c_int64)), ("child", _FP), ("parent_depth", _FP), ("data", _FP), ("stream", C.c_void_p)]
@@ -689,6 +696,10 @@ def load():
     lib.nerf_octree_render_rays.argtypes = [vp, C.POINTER(OctreeRenderOptions), C.POINTER(OctreeRenderArgs)]
     lib.nerf_octree_render_image.restype = i32
     lib.nerf_octree_render_image.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(OctreeRenderOptions), C.POINTER(OctreeRenderArgs)]
+    lib.nerf_octree_backward_rays.restype = i32
+    lib.nerf_octree_backward_rays.argtypes = [vp, C.POINTER(OctreeRenderOptions), C.POINTER(OctreeBackwardArgs)]
+    lib.nerf_octree_backward_image.restype = i32
+    lib.nerf_octree_backward_image.argtypes = [vp, C.POINTER(GridCamera), C.POINTER(OctreeRenderOptions), C.POINTER(OctreeBackwardArgs)]
     lib.nerf_octree_accelerate.restype = i32
     lib.nerf_octree_accelerate.argtypes = [vp, C.c_int32, vp]
     lib.nerf_octree_table_levels.restype = i32

@@ -31,7 +31,7 @@ SOURCES = ["api.cpp", "train_api.cpp", "pack_weights.cpp", "mlp_kernel.hip", "ml
            "grid_dataset_api.cpp", "grid_dataset_kernels.hip",
            "grid_mesh_api.cpp", "grid_mesh_kernels.hip",
            "grid_ndc_kernels.hip",
-           "octree_api.cpp", "octree_kernels.hip"]
+           "octree_api.cpp", "octree_kernels.hip", "octree_grad_kernels.hip"]
 # every header of csrc/ (a new one is a dependency of up_to_date() without being listed) and the public one
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(ROOT, "include", "nerf_mi355x.h")]
 FLAGS = [

@@ -88,6 +88,68 @@ int render(const char* fn, nerf_octree* tree, const nerf_grid_camera* cam, const
     return NERF_OK;
 }
 
+int backward(const char* fn, nerf_octree* tree, const nerf_grid_camera* cam, const nerf_octree_render_options* opt,
+             const nerf_octree_backward_args* a) {
+    if (!tree) {
+        set_error("%s: NULL tree", fn);
+        return NERF_E_INVALID;
+    }
+    NERF_CHECK_STRUCT(fn, a, nerf_octree_backward_args);
+    OctreeRenderOpt o{};
+    int rc = check_options(fn, opt, &o);
+    if (rc != NERF_OK) return rc;
+    OctreeBackward b{};
+    if (cam) {
+        rc = check_grid_camera(fn, cam, &b.cam);
+        if (rc == NERF_OK) rc = refuse_ndc_camera(fn, b.cam, "NDC is not built for the octree");
+        if (rc != NERF_OK) return rc;
+        b.n_rays = (int64_t)cam->width * cam->height;
+    } else {
+        if (a->n_rays < 0 || a->n_rays > kGridMaxItems || (a->n_rays > 0 && (!a->origins || !a->dirs))) {
+            set_error("%s: n_rays = %lld must be in [0, 2^26] and needs origins and dirs", fn, (long long)a->n_rays);
+            return NERF_E_INVALID;
+        }
+        b.origins = a->origins;
+        b.dirs = a->dirs;
+        b.n_rays = a->n_rays;
+    }
+    if ((a->grad_rgb != nullptr) == (a->rgb_gt != nullptr)) {
+        set_error("%s: exactly one of grad_rgb and rgb_gt is required", fn);
+        return NERF_E_INVALID;
+    }
+    if (!a->grad_data) {
+        set_error("%s: grad_data is NULL", fn);
+        return NERF_E_INVALID;
+    }
+    if (!std::isfinite(a->loss_scale)) {
+        set_error("%s: loss_scale = %g must be finite", fn, a->loss_scale);
+        return NERF_E_INVALID;
+    }
+    if (b.n_rays == 0) return NERF_OK;
+    DeviceGuard dg(tree->ctx->device);
+    const int dev = tree->ctx->device;
+    if (!cam) {
+        rc = require_device_array(fn, "origins", a->origins, dev);
+        if (rc == NERF_OK) rc = require_device_array(fn, "dirs", a->dirs, dev);
+        if (rc != NERF_OK) return rc;
+    }
+    rc = a->grad_rgb ? require_device_array(fn, "grad_rgb", a->grad_rgb, dev) : require_device_array(fn, "rgb_gt", a->rgb_gt, dev);
+    if (rc == NERF_OK) rc = require_device_array(fn, "grad_data", a->grad_data, dev);
+    if (rc == NERF_OK && a->loss) rc = require_device_array(fn, "loss", a->loss, dev);
+    if (rc == NERF_OK && a->rgb) rc = require_device_array(fn, "rgb", a->rgb, dev);
+    if (rc == NERF_OK && a->capped) rc = require_device_array(fn, "capped", a->capped, dev);
+    if (rc != NERF_OK) return rc;
+    b.grad_rgb = a->grad_rgb;
+    b.rgb_gt = a->rgb_gt;
+    b.loss_scale = a->loss_scale;
+    b.grad_data = a->grad_data;
+    b.loss = a->loss;
+    b.rgb = a->rgb;
+    b.capped = a->capped;
+    HIP_TRY(launch_octree_backward(tree->t, o, b, (hipStream_t)a->stream));
+    return NERF_OK;
+}
+
 int levels_of(int reso) {
     for (int l = 1; l <= 10; ++l)
         if (reso == 1 << l) return l;
@@ -229,6 +291,19 @@ int nerf_octree_render_image(nerf_octree* tree, const nerf_grid_camera* cam, con
         return NERF_E_INVALID;
     }
     return render("nerf_octree_render_image", tree, cam, opt, args);
+}
+
+int nerf_octree_backward_rays(nerf_octree* tree, const nerf_octree_render_options* opt, const nerf_octree_backward_args* args) {
+    return backward("nerf_octree_backward_rays", tree, nullptr, opt, args);
+}
+
+int nerf_octree_backward_image(nerf_octree* tree, const nerf_grid_camera* cam, const nerf_octree_render_options* opt,
+                               const nerf_octree_backward_args* args) {
+    if (!cam) {
+        set_error("nerf_octree_backward_image: nerf_grid_camera is NULL");
+        return NERF_E_INVALID;
+    }
+    return backward("nerf_octree_backward_image", tree, cam, opt, args);
 }
 
 int64_t nerf_octree_build_workspace(int32_t reso) {

@@ -32,6 +32,21 @@ struct OctreeRender {
     unsigned long long* capped;        // or nullptr
 };
 
+// the backward of a march ("PlenOctree: backward"): rays as OctreeRender's; exactly one of grad_rgb and rgb_gt
+struct OctreeBackward {
+    const float* origins;              // nullptr: the rays of `cam`
+    const float* dirs;
+    GridCam cam;
+    int64_t n_rays;
+    const float* grad_rgb;             // [n, 3], or nullptr: the fused loss form
+    const float* rgb_gt;               // [n, 3], or nullptr
+    float loss_scale;
+    float* grad_data;                  // [n_nodes, 8, D], added to
+    float* loss;                       // [1], added to, or nullptr
+    float* rgb;                        // [n, 3] out, or nullptr
+    unsigned long long* capped;        // or nullptr
+};
+
 // the workspace of a build from a grid of side 2^levels: byte offsets, needs no device. Level l (1 <= l < levels) has
 // (2^l)^3 cells; occ[l] says whether a kept node lies under a cell, rank[l] is its rank among the occupied cells of its level
 // (compact_device.h) or -1. counts[l] = occupied cells of level l = nodes of depth l; base[l] = index of the first of them.
@@ -58,6 +73,7 @@ struct OctreeBuild {
 // *out (device) = 1 if an entry of child is negative or points at or past n_nodes, else 0
 hipError_t launch_octree_check_child(const int32_t* child, int64_t n_nodes, int* out, hipStream_t s);
 hipError_t launch_octree_render(const OctreeDev& t, const OctreeRenderOpt& o, const OctreeRender& r, hipStream_t s);
+hipError_t launch_octree_backward(const OctreeDev& t, const OctreeRenderOpt& o, const OctreeBackward& b, hipStream_t s);
 // table[(x, y, z)] of side 2^levels, 1 <= levels <= max_depth: the deepest cell of depth <= levels that holds the table cell
 hipError_t launch_octree_table(const OctreeDev& t, int levels, int2* table, hipStream_t s);
 // pyramid, one compaction per level, the bases; ws + lay.base[levels] (int32) is the node count

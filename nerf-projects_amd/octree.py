@@ -2,7 +2,9 @@
 a sparse voxel grid (what svox2's ``to_svox1`` computes) and the renderer (``svox.VolumeRenderer.render_persp``), in HIP.
 
 The container (fields, file, checks) works on any device with torch ops; building and rendering run in the kernels of
-csrc/octree_kernels.hip and, as everywhere in this package, have no CPU or PyTorch fallback. The arithmetic of the march is
+csrc/octree_kernels.hip, the gradient with respect to ``data`` (``loss.backward()`` through a render, and the fused
+:meth:`N3Tree.mse_backward` that ``octree_optimize.optimize`` - ``plenoctree/octree/optimization.py``'s loop - steps with) in
+csrc/octree_grad_kernels.hip; as everywhere in this package they have no CPU or PyTorch fallback. The arithmetic of the march is
 defined in include/nerf_mi355x.h, "PlenOctree": svox itself is not part of the reference (it only calls into it), so what is
 said here about svox's arrays, defaults and march is restated from memory of svox 0.2 and not verified against it; the array
 names of the file are confirmed by the list ``plenoctree/octree/compression.py`` deletes, the channel order by
@@ -16,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import OctreeBuildArgs, OctreeDesc, OctreeRenderArgs, OctreeRenderOptions, check
+from ._lib import OctreeBackwardArgs, OctreeBuildArgs, OctreeDesc, OctreeRenderArgs, OctreeRenderOptions, check
 from .grid import Camera, Rays, _refuse_half
 from .host import get_context
 
@@ -82,7 +84,11 @@ class N3Tree:
     ``x * invradius + offset``), ``data_format`` ``"SH1" | "SH4" | "SH9" | "SH16" | "SH25"``, ``rgb_activation``
     ``"sigmoid"`` (svox) or ``"relu_half"`` (``max(0.5 + sum, 0)``: the colour model of a grid, see :meth:`from_grid`).
     ``max_depth`` is measured at construction (:func:`measure_depth`); the kernels bound every descent by it. Writing into
-    ``child`` afterwards is not supported: make a new tree."""
+    ``child`` afterwards is not supported: make a new tree.
+    ``data`` is the tree's one parameter (:meth:`parameters`, :meth:`requires_grad_`): once it requires grad, the renders
+    are differentiable with respect to it, and :meth:`mse_backward` is the fused clamped-MSE step of ``optimization.py``.
+    An optimizer must update ``data`` in place (torch's do): the kernels keep its address. Not built: gradients with respect
+    to rays, editing (``refine``, ``shrink_to_fit``, ``merge``), fp16 ``data``, NDC, ``extra_data``."""
 
     def __init__(self, child, data, parent_depth=None, invradius=0.5, offset=0.5, data_format="SH9", rgb_activation="sigmoid",
                  N=2, extra_data=None, ndc=None, depth_limit=10, geom_resize_fact=1.0, device=None, _max_depth=None):
@@ -155,6 +161,26 @@ class N3Tree:
         t._handle_ptr = t._ctx = t._capped = None
         return t
 
+    def clone(self, device=None):
+        """A tree with copies of the arrays (on ``device``, default: this tree's), detached from any graph; ``data`` requires
+        grad where this tree's does. What ``optimization.py`` keeps as its best tree."""
+        dev = self.device if device is None else torch.device(device)
+        t = object.__new__(N3Tree)
+        t.__dict__.update(self.__dict__)
+        t.child, t.data, t.parent_depth = (x.detach().to(dev, copy=True) for x in (self.child, self.data, self.parent_depth))
+        t.data.requires_grad_(self.data.requires_grad)
+        t.invradius, t.offset = self.invradius.clone(), self.offset.clone()
+        t._handle_ptr = t._ctx = t._capped = None
+        return t
+
+    def parameters(self):
+        """``[data]``: ``torch.optim.SGD(tree.parameters(), lr=1e7)`` as in ``optimization.py``."""
+        return [self.data]
+
+    def requires_grad_(self, flag=True):
+        self.data.requires_grad_(bool(flag))
+        return self
+
     def _not_built(name, what):      # noqa: N805
         def f(self, *a, **k):
             raise NotImplementedError(f"N3Tree.{name}: {what} is not built")
@@ -180,7 +206,7 @@ class N3Tree:
             "offset": self.offset.numpy(),
             "depth_limit": np.int64(self.depth_limit),
             "geom_resize_fact": np.float64(self.geom_resize_fact),
-            "data": self.data.cpu().numpy().astype(np.float16),
+            "data": self.data.detach().cpu().numpy().astype(np.float16),
             "data_format": self.data_format,
             "rgb_activation": self.rgb_activation,
         }
@@ -342,26 +368,47 @@ class N3Tree:
         if not t.is_cuda:
             raise RuntimeError(f"{name} is on the CPU: the octree renderer has no CPU fallback")
         if t.requires_grad:
-            raise NotImplementedError("gradients through an N3Tree are not built")
+            raise NotImplementedError("gradients with respect to rays are not built: an N3Tree's parameter is its data")
         if t.dim() != 2 or t.shape[1] != 3 or (n is not None and t.shape[0] != n):
             raise ValueError(f"{name} must be [N, 3], got {tuple(t.shape)}")
         return t.detach().to(device=ctx.device, dtype=torch.float32).contiguous()
 
-    def _render(self, cam, rays, opt, return_steps):
-        h = self._handle()
-        ctx = self._ctx
+    def _warn_capped(self, stacklevel):
         # the cap's counter as the previous call's copy left it on the host: reported without a wait
         seen = int(self._capped_host.item())
         if seen > self._capped_seen:
-            warnings.warn(f"{seen - self._capped_seen} rays ended at the cap of 65536 march passes", RuntimeWarning, stacklevel=3)
+            warnings.warn(f"{seen - self._capped_seen} rays ended at the cap of 65536 march passes", RuntimeWarning, stacklevel=stacklevel + 1)
             self._capped_seen = seen
+
+    @staticmethod
+    def _refuse_ray_grads(rays):
+        # (before anything needs a device: the refusal is the same on every tree)
+        for x in (rays.origins, rays.dirs):
+            if torch.is_tensor(x) and x.requires_grad:
+                raise NotImplementedError("gradients with respect to rays are not built: an N3Tree's parameter is its data")
+
+    def _render(self, cam, rays, opt, return_steps):
+        if cam is None:
+            self._refuse_ray_grads(rays)
+        self._handle()
+        ctx = self._ctx
+        self._warn_capped(3)
+        o = d = None
+        if cam is None:
+            o = self._rays_arg(rays.origins, "rays.origins", ctx)
+            d = self._rays_arg(rays.dirs, "rays.dirs", ctx, o.shape[0])
+        if self.data.requires_grad and torch.is_grad_enabled():
+            out = _RenderFunction.apply(self.data, self, cam, o, d, opt, return_steps)
+            return out if return_steps else out[0]
+        return self._launch_render(cam, o, d, opt, return_steps)
+
+    def _launch_render(self, cam, o, d, opt, return_steps):
+        h, ctx = self._handle_ptr, self._ctx
         a = OctreeRenderArgs()
         if cam is not None:
             c = cam._to_c()
             n = cam.width * cam.height
         else:
-            o = self._rays_arg(rays.origins, "rays.origins", ctx)
-            d = self._rays_arg(rays.dirs, "rays.dirs", ctx, o.shape[0])
             n = o.shape[0]
             a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), n
         rgb = torch.empty((n, 3), device=ctx.device, dtype=torch.float32)
@@ -377,10 +424,65 @@ class N3Tree:
         self._capped_host.copy_(self._capped, non_blocking=True)
         return (rgb, steps) if return_steps else rgb
 
+    def _launch_backward(self, cam, o, d, opt, grad_data, grad_rgb=None, rgb_gt=None, loss_scale=0.0, loss=None, rgb=None):
+        """One launch of csrc/octree_grad_kernels.hip: adds into ``grad_data``; every array is a checked device tensor."""
+        h, ctx = self._handle_ptr, self._ctx
+        a = OctreeBackwardArgs()
+        if cam is None:
+            a.origins, a.dirs, a.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]
+        a.grad_rgb = 0 if grad_rgb is None else grad_rgb.data_ptr()
+        a.rgb_gt = 0 if rgb_gt is None else rgb_gt.data_ptr()
+        a.loss_scale = float(loss_scale)
+        a.grad_data = grad_data.data_ptr()
+        a.loss = 0 if loss is None else loss.data_ptr()
+        a.rgb = 0 if rgb is None else rgb.data_ptr()
+        a.capped = self._capped.data_ptr()
+        a.stream = ctx.stream().value
+        if cam is not None:
+            c = cam._to_c()
+            check(ctx.lib.nerf_octree_backward_image(h, C.byref(c), C.byref(opt), C.byref(a)))
+        else:
+            check(ctx.lib.nerf_octree_backward_rays(h, C.byref(opt), C.byref(a)))
+        self._capped_host.copy_(self._capped, non_blocking=True)
+
+    def mse_backward(self, camera_or_rays, rgb_gt, step_size=1e-3, sigma_thresh=0.0, stop_thresh=0.0, background_brightness=1.0,
+                     fast=False):
+        """``mse = ((render.clamp(0, 1) - rgb_gt) ** 2).mean(); mse.backward()`` in one launch: renders ``camera_or_rays`` (a
+        :class:`Camera` or :class:`Rays`), adds the gradient of ``mse`` into ``tree.data.grad`` (zeros are allocated where
+        that is ``None``) and returns ``mse`` as a 0-dim device tensor, without a wait. ``rgb_gt``: ``[H, W, 3]`` or
+        ``[N, 3]`` on the device. A NaN ray adds nothing to either (torch would give a NaN loss)."""
+        opt = self._options(step_size, sigma_thresh, stop_thresh, background_brightness, fast)
+        if not isinstance(camera_or_rays, Camera):
+            self._refuse_ray_grads(camera_or_rays)
+        self._handle()
+        ctx = self._ctx
+        self._warn_capped(2)
+        cam = o = d = None
+        if isinstance(camera_or_rays, Camera):
+            cam = camera_or_rays
+            n = cam.width * cam.height
+        else:
+            o = self._rays_arg(camera_or_rays.origins, "rays.origins", ctx)
+            d = self._rays_arg(camera_or_rays.dirs, "rays.dirs", ctx, o.shape[0])
+            n = o.shape[0]
+        if not torch.is_tensor(rgb_gt) or not rgb_gt.is_cuda:
+            raise RuntimeError("rgb_gt must be a tensor on the tree's device: the octree's backward has no CPU fallback")
+        if rgb_gt.numel() != 3 * n or rgb_gt.shape[-1] != 3:
+            raise ValueError(f"rgb_gt must hold [{n}, 3] colours, got {tuple(rgb_gt.shape)}")
+        gt = rgb_gt.detach().to(device=ctx.device, dtype=torch.float32).reshape(n, 3).contiguous()
+        if self.data.grad is None:
+            self.data.grad = torch.zeros_like(self.data)
+        loss = torch.zeros(1, device=ctx.device, dtype=torch.float32)
+        if n:
+            self._launch_backward(cam, o, d, opt, self.data.grad, rgb_gt=gt, loss_scale=2.0 / (3 * n), loss=loss)
+        return loss[0] / max(3 * n, 1)
+
     def volume_render(self, rays: Rays, step_size=1e-3, sigma_thresh=0.0, stop_thresh=0.0, background_brightness=1.0,
                       fast=False, return_steps=False):
         """``[N, 3]`` colours of ``rays``; ``rays.dirs`` is used as given, as the march direction (any length) and as the
-        argument of the SH basis (svox expects it normalised). ``step_size`` is svox's default as remembered (the
+        argument of the SH basis (svox expects it normalised). Where ``tree.data`` requires grad and grad mode is on, the
+        colours - the same bits - carry the gradient with respect to ``data`` (steps carry none); rays that require grad
+        keep raising. ``step_size`` is svox's default as remembered (the
         reference's configs pass 1e-5); ``fast`` sets both thresholds to 1e-2. With ``return_steps`` also int32 ``[N]``, the
         leaves each ray visited."""
         return self._render(None, rays, self._options(step_size, sigma_thresh, stop_thresh, background_brightness, fast), return_steps)
@@ -399,3 +501,25 @@ class N3Tree:
         cam = Camera.from_nerf_pose(c2w, height, width, fx)
         cam.fy = None if fy is None else float(fy)
         return self.volume_render_image(cam, fast=fast, **options)
+
+
+class _RenderFunction(torch.autograd.Function):
+    """A render whose backward is nerf_octree_backward_rays / _image: the colours are the plain render's bits."""
+
+    @staticmethod
+    def forward(ctx, data, tree, cam, o, d, opt, return_steps):
+        out = tree._launch_render(cam, o, d, opt, return_steps)
+        ctx.tree, ctx.cam, ctx.o, ctx.d, ctx.opt = tree, cam, o, d, opt
+        if return_steps:
+            ctx.mark_non_differentiable(out[1])
+            return out
+        return (out,)
+
+    @staticmethod
+    def backward(ctx, grad_rgb, *_):
+        tree = ctx.tree
+        grad = torch.zeros_like(tree.data)
+        g = grad_rgb.detach().to(dtype=torch.float32).contiguous()
+        if g.shape[0]:
+            tree._launch_backward(ctx.cam, ctx.o, ctx.d, ctx.opt, grad, grad_rgb=g)
+        return grad, None, None, None, None, None, None
